@@ -3,7 +3,7 @@
 activity vectors (BASELINE.json metric; workload = configs[2]: batches of 1024 pairs x 7 framerate
 ratios, max_offset_samples = 6000, reference transform length N = 2^21).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path (ffs_align_batch: pass A -> mid -> pass C -> nominees -> exact
 re-evaluation -> max over ratios) over this rank's pairs -- by default eight 1024-pair batches
@@ -63,6 +63,10 @@ def parse():
     ap.add_argument("--reference-length", action="store_true",
                     help="force the reference's transform length N=2^ceil(log2(R+S)) instead of the shorter "
                          "alias-free length the lag window allows")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the records the timed path returned in its last step as "
+                         "DIR/<name>.npy (float64 / float32; rank 0's pairs; at most 64 MB in all, a fixed sample of pairs "
+                         "above that): for comparing two builds output for output on identical seeded inputs")
     return ap.parse_args()
 
 
@@ -198,6 +202,34 @@ def emit(result):
             pass
     print("# detail: " + full, flush=True)
     print(compact_record(result, written), flush=True)
+
+
+DUMP_LIMIT = 64 * 10 ** 6  # bytes: what --dump-outputs may write in all, .npy headers included
+
+
+def dump_outputs(out_dir, seeds, pres, cres, limit=DUMP_LIMIT):
+    """--dump-outputs: the records a caller of the timed path receives -- pres [pairs] (PAIR_RESULT_DTYPE), cres [pairs,
+    candidates] (CAND_RESULT_DTYPE) -- one float array per field, as <out_dir>/<name>.npy, with the seed of every pair
+    (pair_seed).  Integers go to float64, which holds them exactly.  Above `limit` bytes the same pairs are always kept:
+    a sample drawn by RandomState(0), in batch order.  Returns the number of pairs written."""
+    import numpy as np
+
+    arrays = {"pair_seed": np.asarray(seeds, dtype=np.float64)}
+    for f in pres.dtype.names:
+        arrays["pair_" + f] = pres[f].astype(np.float64)
+    for f in cres.dtype.names:
+        arrays["cand_" + f] = cres[f].astype(np.float32 if cres.dtype[f] == np.float32 else np.float64)
+    n = len(seeds)
+    per_pair = sum(a.nbytes for a in arrays.values()) / max(1, n)
+    room = limit - 1024 * len(arrays)  # per file, room for its .npy header (128 bytes for arrays of these shapes)
+    if n * per_pair > room:
+        keep = np.sort(np.random.RandomState(0).choice(n, int(room // per_pair), replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+        n = keep.size
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+    return n
 
 
 def fail_line(args, message, world=None):
@@ -1034,6 +1066,8 @@ def main():
     # generator's ground truth for all pairs
     pres = pair_out.cpu().numpy().view(_native.PAIR_RESULT_DTYPE)[:P].copy()
     cres = cand_out.cpu().numpy().view(_native.CAND_RESULT_DTYPE)[: P * n_cand].reshape(P, n_cand).copy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, seeds, pres, cres)
     golden = load_headline_golden() if args.duration == 7200.0 else {}
     g_total = g_ok = 0
     for i, s in enumerate(seeds):

@@ -270,8 +270,8 @@ class MaxScoreAligner(TransformerMixin):
     """aligners.py:89-167: the constructor contract of SURVEY 8b, ``fit`` re-done for the device -- all candidate
     substrings / pipelines of a call (one per framerate ratio) go through ONE batched solve --, the golden-section wrapper
     and the pick of the best candidate.  ONE implementation whether or not ffsubsync is importable (the same code runs in
-    the CPU tests against the unmodified ``try_sync``, tests/test_install_real_seam.py, and on the GPU box, where
-    ffsubsync is absent); only ``TransformerMixin`` and the exception class are the reference's own when it is there."""
+    the CPU tests against stand-in ffsubsync modules, tests/test_host_logic.py, and on the GPU box, where ffsubsync is
+    absent); only ``TransformerMixin`` and the exception class are the reference's own when it is there."""
 
     def __init__(self, base_aligner, srtin: Optional[str] = None, sample_rate=None, max_offset_seconds=None) -> None:
         have_window = sample_rate is not None and max_offset_seconds is not None
