@@ -72,6 +72,10 @@ EXPORTED_SYMBOLS = (
     "ffs_plan_runs_stats",
     "ffs_plan_profile",
     "ffs_plan_profile_read",
+    "ffs_split_plan_create",
+    "ffs_split_plan_destroy",
+    "ffs_split_plan_workspace_bytes",
+    "ffs_align_split_batch",
     "ffs_last_error",
     "ffs_version",
 )
@@ -233,6 +237,16 @@ def load():
         lib.ffs_plan_profile.argtypes = [c.c_void_p, c.c_int]
         lib.ffs_plan_profile_read.restype = c.c_int
         lib.ffs_plan_profile_read.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p]
+        lib.ffs_split_plan_create.restype = c.c_int
+        lib.ffs_split_plan_create.argtypes = [c.c_int, c.c_int, c.c_int64, c.c_int64, c.c_int64, c.POINTER(c.c_void_p)]
+        lib.ffs_split_plan_destroy.restype = c.c_int
+        lib.ffs_split_plan_destroy.argtypes = [c.c_void_p]
+        lib.ffs_split_plan_workspace_bytes.restype = c.c_int64
+        lib.ffs_split_plan_workspace_bytes.argtypes = [c.c_void_p]
+        lib.ffs_align_split_batch.restype = c.c_int
+        lib.ffs_align_split_batch.argtypes = [c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                                              c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64,
+                                              c.c_double, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
         lib.ffs_last_error.restype = c.c_char_p
         lib.ffs_last_error.argtypes = []
         lib.ffs_version.restype = c.c_int
@@ -744,6 +758,64 @@ def scatter_segments(labels, src_off, dst_start, seg_len, out_len: int):
                                       dst_start.ctypes.data, seg_len.ctypes.data, int(src_off.size), out.data_ptr(),
                                       int(out_len), current_stream_ptr(torch)))
     return out
+
+
+class SplitPlan:
+    """Owns one ``ffs_split_plan``: the workspace of the split-aware aligner (``split_align.py``) for
+    ``pairs_in_flight`` problems of up to ``max_samples`` subtitle samples, ``max_blocks`` blocks and ``max_lags`` = 2W
+    lags."""
+
+    def __init__(self, pairs_in_flight: int, max_blocks: int, max_lags: int, max_samples: int,
+                 device: Optional[int] = None) -> None:
+        torch = require_gpu()
+        self.lib = load()
+        self.device = torch.cuda.current_device() if device is None else int(device)
+        self.pairs_in_flight, self.max_blocks = int(pairs_in_flight), int(max_blocks)
+        self.max_lags, self.max_samples = int(max_lags), int(max_samples)
+        handle = ctypes.c_void_p()
+        check(self.lib.ffs_split_plan_create(self.device, self.pairs_in_flight, self.max_blocks, self.max_lags,
+                                             self.max_samples, ctypes.byref(handle)))
+        self.handle = handle
+
+    @property
+    def workspace_bytes(self) -> int:
+        return int(self.lib.ffs_split_plan_workspace_bytes(self.handle))
+
+    def fits(self, pairs_in_flight: int, max_blocks: int, max_lags: int, max_samples: int) -> bool:
+        return (self.pairs_in_flight >= pairs_in_flight and self.max_blocks >= max_blocks and self.max_lags >= max_lags
+                and self.max_samples >= max_samples)
+
+    def align(self, ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, block_samples: int,
+              max_offset_samples: int, split_penalty: float, offsets_out, scores_out, totals_out,
+              stream: Optional[int] = None) -> None:
+        """``ffs_align_split_batch`` on host descriptor arrays (one entry per pair) into int32 / float64 / float64 CUDA
+        tensors of n_pairs * max_b, n_pairs * max_b and n_pairs entries (asynchronous)."""
+        torch = require_gpu()
+        u64 = lambda a: np.ascontiguousarray(a, dtype=np.uint64)
+        i64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        rp, rl, rlo, rhi = u64(ref_ptr), i64(ref_len), f64(ref_lo), f64(ref_hi)
+        sp, sl, slo, shi = u64(sub_ptr), i64(sub_len), f64(sub_lo), f64(sub_hi)
+        n = rp.size
+        if not all(a.size == n for a in (rl, rlo, rhi, sp, sl, slo, shi)):
+            raise ValueError("one descriptor entry per pair")
+        st = current_stream_ptr(torch) if stream is None else stream
+        check(self.lib.ffs_align_split_batch(self.handle, n, rp.ctypes.data, rl.ctypes.data, rlo.ctypes.data,
+                                             rhi.ctypes.data, sp.ctypes.data, sl.ctypes.data, slo.ctypes.data,
+                                             shi.ctypes.data, int(block_samples), int(max_offset_samples),
+                                             float(split_penalty), offsets_out.data_ptr(), scores_out.data_ptr(),
+                                             totals_out.data_ptr(), st))
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            self.lib.ffs_split_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self) -> None:  # pragma: no cover - interpreter shutdown ordering
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Comm:

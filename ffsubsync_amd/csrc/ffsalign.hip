@@ -25,6 +25,7 @@
 #include "../../include/ffsubsync_amd.h"
 #include "ffs_kernels.h"
 #include "ffs_runs.h"
+#include "ffs_split.h"
 
 using namespace ffsa;
 
@@ -997,7 +998,7 @@ void fill_xform(XformDesc* x, const VecView* a, const VecView* b, const void* sa
 extern "C" {
 
 const char* ffs_last_error(void) { return g_err.c_str(); }
-int ffs_version(void) { return 300; }
+int ffs_version(void) { return 310; }
 
 int64_t ffs_fft_length(int64_t ref_len, int64_t sub_len) {
     if (ref_len <= 0 || sub_len <= 0) return 0;
@@ -2904,4 +2905,180 @@ int ffs_speech_bounds(const float* frames_dev, int64_t n_frames, int64_t* bounds
     return FFS_OK;
 }
 
+/* ---- split-aware alignment (csrc/ffs_split.h) ---------------------------------------------------------------- */
+
+struct ffs_split_plan {
+    int device;
+    int pairs_in_flight;
+    int64_t max_blocks, max_lags, max_samples;
+    int64_t lpad, pw_s, pw_r;  // padded lag row, prefix words per vector
+    void* work;
+    int64_t work_bytes;
+    ffsa::SplitWs ws;
+    int32_t* pre;              // [slot][pw_s + pw_r]
+    ffsa::SplitDesc* dev_desc; // [pairs_in_flight]
+    ffsa::SplitDesc* host_desc; // pinned staging of the same
+    hipEvent_t desc_free;      // the last descriptor upload has left the staging buffer
+    hipEvent_t done;           // the plan's last call has finished with the workspace
+};
+
+namespace {
+int64_t split_align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
+}  // namespace
+
+int ffs_split_plan_create(int device, int pairs_in_flight, int64_t max_blocks, int64_t max_lags, int64_t max_samples,
+                          ffs_split_plan** out) {
+    if (!out) return fail(FFS_E_INVALID, "null output handle");
+    *out = nullptr;
+    if (pairs_in_flight < 1 || max_blocks < 1 || max_lags < 2 || max_lags > 262144 || max_samples < 1)
+        return fail(FFS_E_INVALID, "split plan: need pairs_in_flight >= 1, max_blocks >= 1, 2 <= max_lags <= 262144, "
+                                   "max_samples >= 1");
+    HIP_TRY(hipSetDevice(device));
+    ffs_split_plan* p = new (std::nothrow) ffs_split_plan();
+    if (!p) return fail(FFS_E_NOMEM, "split plan");
+    p->device = device;
+    p->pairs_in_flight = pairs_in_flight;
+    p->max_blocks = max_blocks;
+    p->max_lags = max_lags;
+    p->max_samples = max_samples;
+    p->lpad = split_align_up(max_lags, 64);
+    p->pw_s = max_samples / 32 + 2;
+    p->pw_r = (max_samples + max_lags / 2) / 32 + 2;
+    const int64_t counts_slot = split_align_up(max_blocks * p->lpad, 128);       // uint16
+    const int64_t stay_slot = split_align_up(max_blocks * (p->lpad / 64), 32);   // uint64
+    const int64_t v_slot = split_align_up(p->lpad, 32);                          // double
+    const int64_t arg_slot = split_align_up(max_blocks, 64);                     // int32
+    const int64_t pre_slot = split_align_up(p->pw_s + p->pw_r, 64);              // int32
+    const int64_t n = pairs_in_flight;
+    const int64_t b_counts = n * counts_slot * 2, b_stay = n * stay_slot * 8, b_v = n * v_slot * 8, b_arg = n * arg_slot * 4,
+                  b_pre = n * pre_slot * 4;
+    p->work_bytes = b_counts + b_stay + b_v + b_arg + b_pre;
+    if (hipMalloc(&p->work, p->work_bytes) != hipSuccess) {
+        delete p;
+        return fail(FFS_E_NOMEM, "split plan: %lld workspace bytes", (long long)(b_counts + b_stay + b_v + b_arg + b_pre));
+    }
+    char* w = (char*)p->work;
+    p->ws.counts = (uint16_t*)w;
+    p->ws.stay = (unsigned long long*)(w + b_counts);
+    p->ws.V = (double*)(w + b_counts + b_stay);
+    p->ws.arg = (int32_t*)(w + b_counts + b_stay + b_v);
+    p->pre = (int32_t*)(w + b_counts + b_stay + b_v + b_arg);
+    p->ws.counts_row = p->lpad;
+    p->ws.stay_row = p->lpad / 64;
+    p->ws.counts_slot = counts_slot;
+    p->ws.stay_slot = stay_slot;
+    p->ws.v_slot = v_slot;
+    p->ws.arg_slot = arg_slot;
+    const size_t desc_bytes = sizeof(ffsa::SplitDesc) * (size_t)pairs_in_flight;
+    if (hipMalloc((void**)&p->dev_desc, desc_bytes) != hipSuccess ||
+        hipHostMalloc((void**)&p->host_desc, desc_bytes, hipHostMallocDefault) != hipSuccess ||
+        hipEventCreateWithFlags(&p->desc_free, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&p->done, hipEventDisableTiming) != hipSuccess) {
+        ffs_split_plan_destroy(p);
+        return fail(FFS_E_HIP, "split plan: descriptor buffers / events");
+    }
+    *out = p;
+    return FFS_OK;
+}
+
+int ffs_split_plan_destroy(ffs_split_plan* plan) {
+    if (!plan) return FFS_OK;
+    (void)hipSetDevice(plan->device);
+    if (plan->done) {
+        (void)hipEventSynchronize(plan->done);
+        (void)hipEventDestroy(plan->done);
+    }
+    if (plan->desc_free) (void)hipEventDestroy(plan->desc_free);
+    if (plan->host_desc) (void)hipHostFree(plan->host_desc);
+    if (plan->dev_desc) (void)hipFree(plan->dev_desc);
+    if (plan->work) (void)hipFree(plan->work);
+    delete plan;
+    return FFS_OK;
+}
+
+int64_t ffs_split_plan_workspace_bytes(const ffs_split_plan* plan) { return plan ? plan->work_bytes : 0; }
+
+int ffs_align_split_batch(ffs_split_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
+                          const double* ref_lo, const double* ref_hi, const void* const* sub_ptr, const int64_t* sub_len,
+                          const double* sub_lo, const double* sub_hi, int64_t block_samples, int64_t max_offset_samples,
+                          double split_penalty, int32_t* block_offset_out_dev, double* block_score_out_dev,
+                          double* total_out_dev, void* hip_stream) {
+#pragma clang fp contract(off)
+    if (!plan) return fail(FFS_E_INVALID, "null split plan");
+    if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
+    if (n_pairs == 0) return FFS_OK;
+    if (!ref_ptr || !ref_len || !ref_lo || !ref_hi || !sub_ptr || !sub_len || !sub_lo || !sub_hi || !block_offset_out_dev ||
+        !block_score_out_dev || !total_out_dev)
+        return fail(FFS_E_INVALID, "null argument");
+    const int64_t K = block_samples, W = max_offset_samples;
+    if (K < 256 || K > ffsa::SPLIT_MAX_K || K % 32 != 0)
+        return fail(FFS_E_INVALID, "block_samples=%lld: need a multiple of 32 in [256, 32768]", (long long)K);
+    if (W < 1 || 2 * W > 262144) return fail(FFS_E_INVALID, "max_offset_samples=%lld: need 1 <= W, 2W <= 262144", (long long)W);
+    if (2 * W > plan->max_lags)
+        return fail(FFS_E_INVALID, "2 * max_offset_samples = %lld exceeds the plan's max_lags %lld", (long long)(2 * W),
+                    (long long)plan->max_lags);
+    if (!(split_penalty >= 0.0)) return fail(FFS_E_INVALID, "split_penalty must be >= 0 (not NaN)");
+    int64_t max_b = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+        if (ref_len[p] <= 0 || sub_len[p] <= 0)
+            return fail(FFS_E_EMPTY, "cannot align empty speech data (reference length=%lld, subtitle length=%lld)",
+                        (long long)(ref_len[p] > 0 ? ref_len[p] : 0), (long long)(sub_len[p] > 0 ? sub_len[p] : 0));
+        if (!ref_ptr[p] || !sub_ptr[p] || ((uintptr_t)ref_ptr[p] & 3) || ((uintptr_t)sub_ptr[p] & 3))
+            return fail(FFS_E_INVALID, "pair %d: null or misaligned vector", p);
+        if (sub_len[p] > plan->max_samples)
+            return fail(FFS_E_INVALID, "pair %d: subtitle length %lld exceeds the plan's max_samples %lld", p,
+                        (long long)sub_len[p], (long long)plan->max_samples);
+        const int64_t B = (sub_len[p] + K - 1) / K;
+        if (B > plan->max_blocks)
+            return fail(FFS_E_INVALID, "pair %d: %lld blocks exceed the plan's max_blocks %lld", p, (long long)B,
+                        (long long)plan->max_blocks);
+        if (!(std::isfinite(ref_lo[p]) && std::isfinite(ref_hi[p]) && std::isfinite(sub_lo[p]) && std::isfinite(sub_hi[p])))
+            return fail(FFS_E_INVALID, "pair %d: levels must be finite", p);
+        if (B > max_b) max_b = B;
+    }
+    HIP_TRY(hipSetDevice(plan->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    HIP_TRY(hipStreamWaitEvent(st, plan->done, 0));  // the previous call (any stream) is done with the workspace
+    const int64_t L = 2 * W;
+    const int n_tiles = (int)((L + ffsa::SPLIT_TILE - 1) / ffsa::SPLIT_TILE);
+    const int64_t pre_slot = split_align_up(plan->pw_s + plan->pw_r, 64);
+    for (int p0 = 0; p0 < n_pairs; p0 += plan->pairs_in_flight) {
+        const int np = std::min(plan->pairs_in_flight, n_pairs - p0);
+        HIP_TRY(hipEventSynchronize(plan->desc_free));  // the staging buffer's previous upload has been consumed
+        int64_t chunk_b = 0;
+        for (int i = 0; i < np; ++i) {
+            const int p = p0 + i;
+            ffsa::SplitDesc& d = plan->host_desc[i];
+            d.r = (const uint32_t*)ref_ptr[p];
+            d.s = (const uint32_t*)sub_ptr[p];
+            d.R = ref_len[p];
+            d.S = sub_len[p];
+            const double s0 = 2.0 * sub_lo[p] - 1.0, s1 = 2.0 * sub_hi[p] - 1.0;  // aligners.py:55-57
+            const double r0 = 2.0 * ref_lo[p] - 1.0, r1 = 2.0 * ref_hi[p] - 1.0;
+            d.c00 = s0 * r0;
+            d.c01 = s0 * r1;
+            d.c10 = s1 * r0;
+            d.c11 = s1 * r1;
+            d.pre_s = plan->pre + (int64_t)i * pre_slot;
+            d.pre_r = d.pre_s + plan->pw_s;
+            d.out_row = p;
+            chunk_b = std::max(chunk_b, (d.S + K - 1) / K);
+        }
+        HIP_TRY(hipMemcpyAsync(plan->dev_desc, plan->host_desc, sizeof(ffsa::SplitDesc) * np, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(plan->desc_free, st));
+        const int n_bgroups = (int)((chunk_b + ffsa::SPLIT_BPW - 1) / ffsa::SPLIT_BPW);
+        hipLaunchKernelGGL(ffsa::k_split_prefix, dim3(2 * np), dim3(ffsa::SPLIT_PREFIX_THREADS), 0, st, plan->dev_desc,
+                           (int64_t)W);
+        hipLaunchKernelGGL(ffsa::k_split_counts, dim3((unsigned)((int64_t)n_tiles * n_bgroups * np)),
+                           dim3(ffsa::SPLIT_CNT_THREADS), 0, st, plan->dev_desc, plan->ws, (int)K, (int64_t)W, n_tiles,
+                           n_bgroups);
+        hipLaunchKernelGGL(ffsa::k_split_dp, dim3(np), dim3(ffsa::SPLIT_DP_THREADS), 0, st, plan->dev_desc, plan->ws, (int)K,
+                           (int64_t)W, split_penalty, max_b, block_offset_out_dev, block_score_out_dev, total_out_dev);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(plan->done, st));
+    return FFS_OK;
+}
+
 }  // extern "C"
+

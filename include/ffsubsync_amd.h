@@ -384,6 +384,45 @@ int ffs_plan_profile(ffs_plan* plan, int enable);
  * launches[FFS_K_COUNT] (caller-zeroed or accumulating) and clears the recording. */
 int ffs_plan_profile_read(ffs_plan* plan, double* ms_total, int64_t* launches);
 
+/* ---- split-aware alignment: piecewise offsets for videos with breaks or cuts (csrc/ffs_split.h) ---------------
+ * Replaces: nothing in the reference -- its README names mid-video splits (ad breaks, recaps, cuts the subtitles do not
+ * share) as its one algorithmic limitation; FFTAligner finds one offset per file (aligners.py:45-80).  No upstream
+ * parity exists: the contract below is pinned against the numpy model tests/split_model.py, bit for bit.
+ *
+ * One problem = a two-level reference r (R samples, levels ref_lo/ref_hi) and a two-level subtitle vector s (S samples,
+ * e.g. the candidate at the chosen framerate ratio), both FFS_DTYPE_U1 in HBM (4-byte aligned).  Blocks of K =
+ * block_samples subtitle samples (a multiple of 32 in [256, 32768]); block b = [bK, min((b+1)K, S)), B = ceil(S/K).
+ * Lags d in [-W+1, W], W = max_offset_samples (1 <= W, 2W <= 262144): the reference's window without its short-input
+ * negative-slice quirk; subtitle sample i meets reference sample i+d.
+ * Block score m_b(d): over the samples i of block b with 0 <= i+d < R (others are absent, not zeros) count ov, n11, n1x
+ * (subtitle bit set), nx1 (reference bit set); n10 = n1x-n11, n01 = nx1-n11, n00 = ov-n11-n10-n01; with s0/s1/r0/r1 =
+ * 2*level-1 in fp64, m = ((n00*(s0*r0) + n01*(s0*r1)) + n10*(s1*r0)) + n11*(s1*r1), every operation rounded on its own
+ * (no fused multiply-add).
+ * DP: V_0 = m_0; for b >= 1: J = max_d V_{b-1}(d), a_{b-1} = the largest d attaining it, T = J - P,
+ * stay_b(d) = V_{b-1}(d) >= T, V_b(d) = (stay_b(d) ? V_{b-1}(d) : T) + m_b(d).  End lag = the largest d attaining
+ * max V_{B-1} (= total); backtrack o_{B-1} = end lag, o_{b-1} = stay_b(o_b) ? o_b : a_{b-1}.  P = split_penalty >= 0;
+ * +inf never splits (one piece at the windowed argmax of the whole-vector correlation).
+ *
+ * A plan owns the workspace for pairs_in_flight problems of up to max_samples subtitle samples, max_blocks blocks and
+ * max_lags = 2W lags: per pair max_blocks * max_lags * 2 bytes of uint16 counts (170 MB at 2 h, +-10 min, K = 1024) plus
+ * one stay bit per (block, lag) and one fp64 row of max_lags.  A plan serves one host thread at a time; successive calls
+ * (any streams) are ordered by the library. */
+typedef struct ffs_split_plan ffs_split_plan;
+int ffs_split_plan_create(int device, int pairs_in_flight, int64_t max_blocks, int64_t max_lags, int64_t max_samples,
+                          ffs_split_plan** out);
+int ffs_split_plan_destroy(ffs_split_plan* plan);
+int64_t ffs_split_plan_workspace_bytes(const ffs_split_plan* plan);
+/* Solve n_pairs problems (host arrays of n_pairs entries; ref_ptr / sub_ptr hold DEVICE pointers).  Outputs are
+ * caller-owned device buffers written in stream order on hip_stream: with max_b = max over the pairs of ceil(S/K),
+ * block_offset_out_dev[p * max_b + b] = o_b (int32 lag), block_score_out_dev[p * max_b + b] = m_b(o_b) (entries
+ * b >= B_p are written as 0), total_out_dev[p] = max V_{B-1}.  Pieces (maximal runs of equal o_b) are formed by the
+ * caller.  FFS_E_EMPTY for a vector of length 0. */
+int ffs_align_split_batch(ffs_split_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
+                          const double* ref_lo, const double* ref_hi, const void* const* sub_ptr, const int64_t* sub_len,
+                          const double* sub_lo, const double* sub_hi, int64_t block_samples, int64_t max_offset_samples,
+                          double split_penalty, int32_t* block_offset_out_dev, double* block_score_out_dev,
+                          double* total_out_dev, void* hip_stream);
+
 /* Thread-local description of the last error returned on this thread ("" if none). */
 const char* ffs_last_error(void);
 
