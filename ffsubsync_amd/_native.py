@@ -34,6 +34,16 @@ PAIR_RESULT_DTYPE = np.dtype(
     [("score", "<f8"), ("offset", "<i8"), ("best_cand", "<i4"), ("flags", "<i4")], align=True
 )
 assert CAND_RESULT_DTYPE.itemsize == 24 and PAIR_RESULT_DTYPE.itemsize == 24
+# ffs_quality_result (include/ffsubsync_amd.h; static size 160 bytes)
+QUALITY_MAX_PEAKS = 8
+QUALITY_FLAT = 1  # FFS_QUALITY_FLAT: every score of the lag set is equal (std = 0)
+QUALITY_EMPTY_WINDOW = 2  # FFS_QUALITY_EMPTY_WINDOW: the lag set is empty
+QUALITY_RESULT_DTYPE = np.dtype(
+    [("peak_score", "<f8", (QUALITY_MAX_PEAKS,)), ("peak_offset", "<i8", (QUALITY_MAX_PEAKS,)), ("mean", "<f8"),
+     ("std", "<f8"), ("n_lags", "<i8"), ("n_peaks", "<i4"), ("flags", "<i4")], align=True
+)
+QUALITY_RESULT_BYTES = 160
+assert QUALITY_RESULT_DTYPE.itemsize == QUALITY_RESULT_BYTES
 
 # every symbol include/ffsubsync_amd.h declares (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = (
@@ -76,6 +86,10 @@ EXPORTED_SYMBOLS = (
     "ffs_split_plan_destroy",
     "ffs_split_plan_workspace_bytes",
     "ffs_align_split_batch",
+    "ffs_quality_plan_create",
+    "ffs_quality_plan_destroy",
+    "ffs_quality_plan_workspace_bytes",
+    "ffs_align_quality_batch",
     "ffs_last_error",
     "ffs_version",
 )
@@ -247,6 +261,16 @@ def load():
         lib.ffs_align_split_batch.argtypes = [c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
                                               c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64,
                                               c.c_double, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
+        lib.ffs_quality_plan_create.restype = c.c_int
+        lib.ffs_quality_plan_create.argtypes = [c.c_int, c.c_int, c.c_int64, c.c_int64, c.POINTER(c.c_void_p)]
+        lib.ffs_quality_plan_destroy.restype = c.c_int
+        lib.ffs_quality_plan_destroy.argtypes = [c.c_void_p]
+        lib.ffs_quality_plan_workspace_bytes.restype = c.c_int64
+        lib.ffs_quality_plan_workspace_bytes.argtypes = [c.c_void_p]
+        lib.ffs_align_quality_batch.restype = c.c_int
+        lib.ffs_align_quality_batch.argtypes = [c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                                                c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int,
+                                                c.c_int64, c.c_void_p, c.c_void_p]
         lib.ffs_last_error.restype = c.c_char_p
         lib.ffs_last_error.argtypes = []
         lib.ffs_version.restype = c.c_int
@@ -810,6 +834,70 @@ class SplitPlan:
         if getattr(self, "handle", None):
             self.lib.ffs_split_plan_destroy(self.handle)
             self.handle = None
+
+    def __del__(self) -> None:  # pragma: no cover - interpreter shutdown ordering
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class QualityPlan:
+    """Owns one ``ffs_quality_plan``: the workspace of the alignment quality report (``quality.py``) for
+    ``pairs_in_flight`` problems of up to ``max_samples`` samples per vector and ``max_lags`` lags, plus (made on first
+    use) a bit buffer that boundary-list inputs are expanded into."""
+
+    def __init__(self, pairs_in_flight: int, max_lags: int, max_samples: int, device: Optional[int] = None) -> None:
+        torch = require_gpu()
+        self.lib = load()
+        self.device = torch.cuda.current_device() if device is None else int(device)
+        self.pairs_in_flight, self.max_lags, self.max_samples = int(pairs_in_flight), int(max_lags), int(max_samples)
+        self.scratch = None  # int32 CUDA tensor: FFS_DTYPE_U1 images of FFS_DTYPE_RUNS vectors
+        handle = ctypes.c_void_p()
+        check(self.lib.ffs_quality_plan_create(self.device, self.pairs_in_flight, self.max_lags, self.max_samples,
+                                               ctypes.byref(handle)))
+        self.handle = handle
+
+    @property
+    def workspace_bytes(self) -> int:
+        return int(self.lib.ffs_quality_plan_workspace_bytes(self.handle))
+
+    def fits(self, pairs_in_flight: int, max_lags: int, max_samples: int) -> bool:
+        return self.pairs_in_flight >= pairs_in_flight and self.max_lags >= max_lags and self.max_samples >= max_samples
+
+    def scratch_words(self, n_words: int):
+        """The plan's bit buffer, grown to at least ``n_words`` int32 words."""
+        torch = require_gpu()
+        if self.scratch is None or self.scratch.numel() < n_words:
+            self.scratch = torch.empty(int(n_words), dtype=torch.int32, device=torch.device("cuda", self.device))
+        return self.scratch
+
+    def report(self, ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, max_offset_samples,
+               top_k: int, exclusion_samples: int, out, stream: Optional[int] = None) -> None:
+        """``ffs_align_quality_batch`` on host descriptor arrays (one entry per pair) into a uint8 CUDA tensor of
+        n_pairs * 160 bytes (asynchronous).  ``max_offset_samples`` None = no window."""
+        torch = require_gpu()
+        u64 = lambda a: np.ascontiguousarray(a, dtype=np.uint64)
+        i64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        rp, rl, rlo, rhi = u64(ref_ptr), i64(ref_len), f64(ref_lo), f64(ref_hi)
+        sp, sl, slo, shi = u64(sub_ptr), i64(sub_len), f64(sub_lo), f64(sub_hi)
+        n = rp.size
+        if not all(a.size == n for a in (rl, rlo, rhi, sp, sl, slo, shi)):
+            raise ValueError("one descriptor entry per pair")
+        if out.numel() * out.element_size() < n * QUALITY_RESULT_BYTES:
+            raise ValueError("output buffer too small")
+        mo = -1 if max_offset_samples is None else int(max_offset_samples)
+        st = current_stream_ptr(torch) if stream is None else stream
+        check(self.lib.ffs_align_quality_batch(self.handle, n, rp.ctypes.data, rl.ctypes.data, rlo.ctypes.data,
+                                               rhi.ctypes.data, sp.ctypes.data, sl.ctypes.data, slo.ctypes.data,
+                                               shi.ctypes.data, mo, int(top_k), int(exclusion_samples), out.data_ptr(), st))
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            self.lib.ffs_quality_plan_destroy(self.handle)
+            self.handle = None
+        self.scratch = None
 
     def __del__(self) -> None:  # pragma: no cover - interpreter shutdown ordering
         try:

@@ -26,6 +26,7 @@
 #include "ffs_kernels.h"
 #include "ffs_runs.h"
 #include "ffs_split.h"
+#include "ffs_quality.h"
 
 using namespace ffsa;
 
@@ -998,7 +999,7 @@ void fill_xform(XformDesc* x, const VecView* a, const VecView* b, const void* sa
 extern "C" {
 
 const char* ffs_last_error(void) { return g_err.c_str(); }
-int ffs_version(void) { return 310; }
+int ffs_version(void) { return 320; }
 
 int64_t ffs_fft_length(int64_t ref_len, int64_t sub_len) {
     if (ref_len <= 0 || sub_len <= 0) return 0;
@@ -3080,5 +3081,186 @@ int ffs_align_split_batch(ffs_split_plan* plan, int n_pairs, const void* const* 
     return FFS_OK;
 }
 
-}  // extern "C"
+/* ---- alignment quality report (csrc/ffs_quality.h) ------------------------------------------------------------- */
 
+struct ffs_quality_plan {
+    int device;
+    int pairs_in_flight;
+    int64_t max_lags, max_samples;
+    int64_t lpad, pre_slot;     // padded curve row, prefix words per slot (both vectors)
+    void* work;
+    int64_t work_bytes;
+    uint32_t* curve;            // [slot][lpad]
+    double* sc;                 // [slot][lpad]
+    int32_t* pre;               // [slot][pre_slot]
+    void* dev_desc;             // SplitDesc[pairs_in_flight] (k_split_prefix), then QualDesc[pairs_in_flight]
+    void* host_desc;            // pinned staging of the same
+    hipEvent_t desc_free;       // the last descriptor upload has left the staging buffer
+    hipEvent_t done;            // the plan's last call has finished with the workspace
+};
+
+int ffs_quality_plan_create(int device, int pairs_in_flight, int64_t max_lags, int64_t max_samples, ffs_quality_plan** out) {
+    if (!out) return fail(FFS_E_INVALID, "null output handle");
+    *out = nullptr;
+    if (pairs_in_flight < 1 || max_lags < 1 || max_lags > (int64_t(1) << 31) || max_samples < 1 || max_samples >= (int64_t(1) << 30))
+        return fail(FFS_E_INVALID, "quality plan: need pairs_in_flight >= 1, 1 <= max_lags <= 2^31, 1 <= max_samples < 2^30");
+    HIP_TRY(hipSetDevice(device));
+    ffs_quality_plan* p = new (std::nothrow) ffs_quality_plan();
+    if (!p) return fail(FFS_E_NOMEM, "quality plan");
+    p->device = device;
+    p->pairs_in_flight = pairs_in_flight;
+    p->max_lags = max_lags;
+    p->max_samples = max_samples;
+    p->lpad = split_align_up(max_lags, 64);
+    p->pre_slot = split_align_up(2 * (max_samples / 32 + 2), 64);
+    const int64_t n = pairs_in_flight;
+    const int64_t b_curve = n * p->lpad * 4, b_sc = n * p->lpad * 8, b_pre = n * p->pre_slot * 4;
+    p->work_bytes = b_curve + b_sc + b_pre;
+    if (hipMalloc(&p->work, p->work_bytes) != hipSuccess) {
+        delete p;
+        return fail(FFS_E_NOMEM, "quality plan: %lld workspace bytes", (long long)(b_curve + b_sc + b_pre));
+    }
+    char* w = (char*)p->work;
+    p->sc = (double*)w;
+    p->curve = (uint32_t*)(w + b_sc);
+    p->pre = (int32_t*)(w + b_sc + b_curve);
+    const size_t desc_bytes = (sizeof(ffsa::SplitDesc) + sizeof(ffsa::QualDesc)) * (size_t)pairs_in_flight;
+    if (hipMalloc(&p->dev_desc, desc_bytes) != hipSuccess ||
+        hipHostMalloc(&p->host_desc, desc_bytes, hipHostMallocDefault) != hipSuccess ||
+        hipEventCreateWithFlags(&p->desc_free, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&p->done, hipEventDisableTiming) != hipSuccess) {
+        ffs_quality_plan_destroy(p);
+        return fail(FFS_E_HIP, "quality plan: descriptor buffers / events");
+    }
+    *out = p;
+    return FFS_OK;
+}
+
+int ffs_quality_plan_destroy(ffs_quality_plan* plan) {
+    if (!plan) return FFS_OK;
+    (void)hipSetDevice(plan->device);
+    if (plan->done) {
+        (void)hipEventSynchronize(plan->done);
+        (void)hipEventDestroy(plan->done);
+    }
+    if (plan->desc_free) (void)hipEventDestroy(plan->desc_free);
+    if (plan->host_desc) (void)hipHostFree(plan->host_desc);
+    if (plan->dev_desc) (void)hipFree(plan->dev_desc);
+    if (plan->work) (void)hipFree(plan->work);
+    delete plan;
+    return FFS_OK;
+}
+
+int64_t ffs_quality_plan_workspace_bytes(const ffs_quality_plan* plan) { return plan ? plan->work_bytes : 0; }
+
+int ffs_align_quality_batch(ffs_quality_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
+                            const double* ref_lo, const double* ref_hi, const void* const* sub_ptr, const int64_t* sub_len,
+                            const double* sub_lo, const double* sub_hi, int64_t max_offset_samples, int top_k,
+                            int64_t exclusion_samples, ffs_quality_result* out_dev, void* hip_stream) {
+    if (!plan) return fail(FFS_E_INVALID, "null quality plan");
+    if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
+    if (n_pairs == 0) return FFS_OK;
+    if (!ref_ptr || !ref_len || !ref_lo || !ref_hi || !sub_ptr || !sub_len || !sub_lo || !sub_hi || !out_dev)
+        return fail(FFS_E_INVALID, "null argument");
+    if (max_offset_samples < -1) return fail(FFS_E_INVALID, "max_offset_samples=%lld: need >= 0, or -1 for none", (long long)max_offset_samples);
+    if (top_k < 1 || top_k > ffsa::QUAL_MAX_PEAKS) return fail(FFS_E_INVALID, "top_k=%d outside [1, 8]", top_k);
+    if (exclusion_samples < 1) return fail(FFS_E_INVALID, "exclusion_samples=%lld: need >= 1", (long long)exclusion_samples);
+    if ((uintptr_t)out_dev & 7) return fail(FFS_E_INVALID, "misaligned output records");
+    int64_t max_sw = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+        if (ref_len[p] <= 0 || sub_len[p] <= 0)
+            return fail(FFS_E_EMPTY, "cannot align empty speech data (reference length=%lld, subtitle length=%lld)",
+                        (long long)(ref_len[p] > 0 ? ref_len[p] : 0), (long long)(sub_len[p] > 0 ? sub_len[p] : 0));
+        if (!ref_ptr[p] || !sub_ptr[p] || ((uintptr_t)ref_ptr[p] & 3) || ((uintptr_t)sub_ptr[p] & 3))
+            return fail(FFS_E_INVALID, "pair %d: null or misaligned vector", p);
+        if (ref_len[p] > plan->max_samples || sub_len[p] > plan->max_samples)
+            return fail(FFS_E_INVALID, "pair %d: lengths %lld / %lld exceed the plan's max_samples %lld", p,
+                        (long long)ref_len[p], (long long)sub_len[p], (long long)plan->max_samples);
+        if (!(std::isfinite(ref_lo[p]) && std::isfinite(ref_hi[p]) && std::isfinite(sub_lo[p]) && std::isfinite(sub_hi[p])))
+            return fail(FFS_E_INVALID, "pair %d: levels must be finite", p);
+        const int64_t n_ref = ffs_fft_length(ref_len[p], sub_len[p]);
+        int64_t wl = 0, wh = -1;
+        if (lag_window(ref_len[p], sub_len[p], n_ref, max_offset_samples, &wl, &wh) && wh - wl + 1 > plan->max_lags)
+            return fail(FFS_E_INVALID, "pair %d: %lld lags exceed the plan's max_lags %lld", p, (long long)(wh - wl + 1),
+                        (long long)plan->max_lags);
+        max_sw = std::max(max_sw, (sub_len[p] + 31) / 32);
+    }
+    HIP_TRY(hipSetDevice(plan->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    HIP_TRY(hipStreamWaitEvent(st, plan->done, 0));  // the previous call (any stream) is done with the workspace
+    ffsa::SplitDesc* hs = (ffsa::SplitDesc*)plan->host_desc;
+    ffsa::QualDesc* hq = (ffsa::QualDesc*)(hs + plan->pairs_in_flight);
+    const ffsa::SplitDesc* ds = (const ffsa::SplitDesc*)plan->dev_desc;
+    const ffsa::QualDesc* dq = (const ffsa::QualDesc*)(ds + plan->pairs_in_flight);
+    int n_sm = 0;
+    HIP_TRY(hipDeviceGetAttribute(&n_sm, hipDeviceAttributeMultiprocessorCount, plan->device));
+    for (int p0 = 0; p0 < n_pairs; p0 += plan->pairs_in_flight) {
+        const int np = std::min(plan->pairs_in_flight, n_pairs - p0);
+        HIP_TRY(hipEventSynchronize(plan->desc_free));  // the staging buffer's previous upload has been consumed
+        int64_t max_count = 0;
+        for (int i = 0; i < np; ++i) {
+            const int p = p0 + i;
+            const int64_t R = ref_len[p], S = sub_len[p];
+            ffsa::SplitDesc& sd = hs[i];
+            memset(&sd, 0, sizeof sd);
+            sd.r = (const uint32_t*)ref_ptr[p];
+            sd.s = (const uint32_t*)sub_ptr[p];
+            sd.R = R;
+            sd.S = S;
+            sd.pre_s = plan->pre + (int64_t)i * plan->pre_slot;
+            sd.pre_r = sd.pre_s + (S / 32 + 2);
+            sd.out_row = p;
+            ffsa::QualDesc& q = hq[i];
+            memset(&q, 0, sizeof q);
+            q.r = sd.r;
+            q.s = sd.s;
+            q.R = R;
+            q.S = S;
+            int64_t wl = 0, wh = -1;
+            if (lag_window(R, S, ffs_fft_length(R, S), max_offset_samples, &wl, &wh)) {
+                q.d_lo = wl;
+                q.n_lags = wh - wl + 1;
+                const int64_t clo = std::max(wl, 1 - S), chi = std::min(wh, R - 1);
+                q.c_lo = clo;
+                q.n_count = chi >= clo ? chi - clo + 1 : 0;
+            }
+            q.cd.R = (int32_t)R;
+            q.cd.S = (int32_t)S;
+            q.cd.s0 = mapped(sub_lo[p]);
+            q.cd.s1 = mapped(sub_hi[p]);
+            q.cd.r0 = mapped(ref_lo[p]);
+            q.cd.r1 = mapped(ref_hi[p]);
+            q.pre_r = sd.pre_r;
+            q.pre_s = sd.pre_s;
+            q.curve = plan->curve + (int64_t)i * plan->lpad;
+            q.sc = plan->sc + (int64_t)i * plan->lpad;
+            q.out_row = p;
+            max_count = std::max(max_count, q.n_count);
+        }
+        HIP_TRY(hipMemcpyAsync((void*)ds, hs, sizeof(ffsa::SplitDesc) * np, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync((void*)dq, hq, sizeof(ffsa::QualDesc) * np, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(plan->desc_free, st));
+        HIP_TRY(hipMemsetAsync(plan->curve, 0, (size_t)np * plan->lpad * 4, st));
+        // prefixes over every sample of both vectors (W beyond any length: k_split_prefix then covers all of r)
+        hipLaunchKernelGGL(ffsa::k_split_prefix, dim3(2 * np), dim3(ffsa::SPLIT_PREFIX_THREADS), 0, st, ds,
+                           (int64_t)(int64_t(1) << 40));
+        if (max_count > 0) {
+            // chunks of subtitle words: enough workgroups to fill the device (about 4 per CU), at least 64 words each so
+            // that the atomics stay a small fraction of the work, at most QUAL_MAX_CHUNK (LDS)
+            const int64_t n_tiles = (max_count + ffsa::QUAL_TILE - 1) / ffsa::QUAL_TILE;
+            const int64_t want = std::max<int64_t>(1, (int64_t)n_sm * 4);
+            int64_t cw = (np * n_tiles * max_sw + want - 1) / want;
+            cw = std::min<int64_t>(ffsa::QUAL_MAX_CHUNK, std::max<int64_t>(64, cw));
+            const int64_t n_chunks = (max_sw + cw - 1) / cw;
+            hipLaunchKernelGGL(ffsa::k_quality_counts, dim3((unsigned)(np * n_tiles * n_chunks)), dim3(ffsa::QUAL_CNT_THREADS),
+                               0, st, dq, (int)n_tiles, (int)n_chunks, (int)cw);
+        }
+        hipLaunchKernelGGL(ffsa::k_quality_peaks, dim3(np), dim3(ffsa::QUAL_PEAK_THREADS), 0, st, dq, top_k,
+                           exclusion_samples, (ffsa::QualResult*)out_dev);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(plan->done, st));
+    return FFS_OK;
+}
+
+}  // extern "C"

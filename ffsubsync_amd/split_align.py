@@ -204,12 +204,27 @@ def split_sync(problems, max_offset_seconds: float = 600, block_samples: int = D
     or a ``subtitle_raster.DeviceRaster``, the track the (start_us, end_us, is_metadata) triple of
     ``subtitle_raster.subtitle_records``.  Per problem: the framerate ratio from the existing seven-ratio batch solve over
     the same lag window, the winner rasterised on the device, the split DP, and every cue's output time."""
-    from . import batch as batch_mod
-    from .subtitle_raster import DeviceRaster, rasterize_candidates
-
     w = int(round(max_offset_seconds * sample_rate))
     validate_args(block_samples, w, split_penalty)
     ratios = list(candidate_ratios() if ratios is None else ratios)
+    db, best, pres = solve_ratios(problems, w, ratios, sample_rate)
+    results = split_align_batch(db.select_candidates(best), w, block_samples, split_penalty)
+    out = []
+    for p, ((_, (start_us, end_us, _meta)), res) in enumerate(zip(problems, results)):
+        ratio = ratios[int(best[p])]
+        cs, ce, which = map_cues(start_us, end_us, ratio, res.pieces, sample_rate)
+        out.append(SplitSyncResult(ratio, int(best[p]), int(pres[p]["offset"]), res.pieces, res.total, cs, ce, which))
+    return out
+
+
+def solve_ratios(problems, max_offset_samples: int, ratios: Sequence[float], sample_rate: int = SAMPLE_RATE):
+    """The existing seven-ratio batch solve of (reference, track) problems (see ``split_sync``): every track rasterised on
+    the device at each ratio, one ``BatchAligner`` solve over the lag window.  Returns (DeviceBatch, winning candidate
+    index per problem, the solve's ffs_pair_result records)."""
+    from . import batch as batch_mod
+    from .subtitle_raster import DeviceRaster, rasterize_candidates
+
+    w = int(max_offset_samples)
     refs = []
     for ref, track in problems:
         if len(track[0]) == 0:
@@ -237,10 +252,4 @@ def split_sync(problems, max_offset_seconds: float = 600, block_samples: int = D
     best = pres["best_cand"].astype(np.int64)
     if (best < 0).any():
         raise RuntimeError("no framerate ratio found an offset inside the window")
-    results = split_align_batch(db.select_candidates(best), w, block_samples, split_penalty)
-    out = []
-    for p, ((_, (start_us, end_us, _meta)), res) in enumerate(zip(problems, results)):
-        ratio = ratios[int(best[p])]
-        cs, ce, which = map_cues(start_us, end_us, ratio, res.pieces, sample_rate)
-        out.append(SplitSyncResult(ratio, int(best[p]), int(pres[p]["offset"]), res.pieces, res.total, cs, ce, which))
-    return out
+    return db, best, pres

@@ -423,6 +423,56 @@ int ffs_align_split_batch(ffs_split_plan* plan, int n_pairs, const void* const* 
                           double split_penalty, int32_t* block_offset_out_dev, double* block_score_out_dev,
                           double* total_out_dev, void* hip_stream);
 
+/* ---- alignment quality report: runner-up peaks and spread of the correlation curve (csrc/ffs_quality.h) ---------
+ * Replaces: nothing in the reference -- its only quality signal is the raw score at the winning lag (--min-score,
+ * ffsubsync.py:145-174), whose magnitude grows with the file's length and speech density.  The contract below is pinned
+ * against the numpy model tests/quality_model.py.
+ *
+ * One problem = a two-level reference r (R samples, levels ref_lo/ref_hi) and ONE two-level subtitle vector s (S
+ * samples), both FFS_DTYPE_U1 in HBM (4-byte aligned), and the lag window max_offset_samples W (>= 0, or -1 for none).
+ * Lag set: exactly the entries of the reference's masked `convolve` array that its argmax reads (aligners.py:31-48,
+ * Python slice semantics included): d in [-W+1, W] when R, S > W; all N = ffs_fft_length(R, S) entries without a
+ * window.  Score of lag d: over the samples i with 0 <= i+d < R, the counts ov, n11, n1x, nx1 scored by the arithmetic
+ * of ffs_pair_result.score (so peak 1 equals the solve's record bit for bit); exactly 0.0 where the overlap is empty.
+ * Peaks: peak 1 = the window maximum (largest lag on ties); peak k+1 = the maximum over the lags d with |d - d_j| >=
+ * exclusion_samples (E >= 1) for every earlier peak j, same tie rule; fewer than top_k (1..8) when no lag is eligible.
+ * Moments over the whole lag set (zero-overlap lags included): mean and population std (ddof = 0), two passes; when every
+ * score is equal, mean = that score and std = 0 exactly (FFS_QUALITY_FLAT).  An empty window gives n_lags = 0, no peak,
+ * and FFS_QUALITY_FLAT | FFS_QUALITY_EMPTY_WINDOW.
+ *
+ * A plan owns the workspace for pairs_in_flight problems of up to max_samples samples per vector and max_lags lags:
+ * per pair max_lags * 12 bytes (uint32 n11 curve + fp64 scores; 144 KB at +-60 s) plus the word prefix popcounts of both
+ * vectors.  Calls with more pairs run in sub-batches.  A plan serves one host thread at a time; successive calls (any
+ * streams) are ordered by the library. */
+#define FFS_QUALITY_FLAT 1         /* every score of the lag set is equal: std = 0 */
+#define FFS_QUALITY_EMPTY_WINDOW 2 /* the lag set is empty */
+
+typedef struct ffs_quality_result {
+    double peak_score[8];   /* peaks 0 .. n_peaks-1 (entries beyond: 0) */
+    int64_t peak_offset[8]; /* samples; subtitle shifted by +offset/sample_rate seconds */
+    double mean, std;       /* of the scores over the lag set */
+    int64_t n_lags;
+    int32_t n_peaks, flags; /* flags: FFS_QUALITY_* */
+} ffs_quality_result;
+#ifdef __cplusplus
+static_assert(sizeof(ffs_quality_result) == 160, "ffs_quality_result is 160 bytes");
+#else
+_Static_assert(sizeof(ffs_quality_result) == 160, "ffs_quality_result is 160 bytes");
+#endif
+
+typedef struct ffs_quality_plan ffs_quality_plan;
+int ffs_quality_plan_create(int device, int pairs_in_flight, int64_t max_lags, int64_t max_samples, ffs_quality_plan** out);
+int ffs_quality_plan_destroy(ffs_quality_plan* plan);
+int64_t ffs_quality_plan_workspace_bytes(const ffs_quality_plan* plan);
+/* Report n_pairs problems (host arrays of n_pairs entries; ref_ptr / sub_ptr hold DEVICE pointers) into out_dev[p]
+ * (caller-owned device array of n_pairs records, 8-byte aligned), in stream order on hip_stream.  FFS_E_EMPTY for a
+ * vector of length 0; FFS_E_INVALID for top_k outside [1, 8], exclusion_samples < 1, max_offset_samples < -1, or a
+ * problem beyond the plan's max_samples / max_lags. */
+int ffs_align_quality_batch(ffs_quality_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
+                            const double* ref_lo, const double* ref_hi, const void* const* sub_ptr, const int64_t* sub_len,
+                            const double* sub_lo, const double* sub_hi, int64_t max_offset_samples, int top_k,
+                            int64_t exclusion_samples, ffs_quality_result* out_dev, void* hip_stream);
+
 /* Thread-local description of the last error returned on this thread ("" if none). */
 const char* ffs_last_error(void);
 
