@@ -44,6 +44,16 @@ QUALITY_RESULT_DTYPE = np.dtype(
 )
 QUALITY_RESULT_BYTES = 160
 assert QUALITY_RESULT_DTYPE.itemsize == QUALITY_RESULT_BYTES
+# ffs_piece_report (include/ffsubsync_amd.h; static size 224 bytes)
+PIECE_OWN_NOT_PEAK = 4  # FFS_PIECE_OWN_NOT_PEAK: the piece's peak 1 is not at its own offset
+PIECE_REPORT_DTYPE = np.dtype(
+    [("first_block", "<i8"), ("end_block", "<i8"), ("start_sample", "<i8"), ("end_sample", "<i8"), ("offset", "<i8"),
+     ("own_score", "<f8"), ("prev_score", "<f8"), ("next_score", "<f8"), ("mean", "<f8"), ("std", "<f8"),
+     ("n_lags", "<i8"), ("peak_score", "<f8", (QUALITY_MAX_PEAKS,)), ("peak_offset", "<i8", (QUALITY_MAX_PEAKS,)),
+     ("n_peaks", "<i4"), ("flags", "<i4")], align=True
+)
+PIECE_REPORT_BYTES = 224
+assert PIECE_REPORT_DTYPE.itemsize == PIECE_REPORT_BYTES
 
 # every symbol include/ffsubsync_amd.h declares (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = (
@@ -86,6 +96,7 @@ EXPORTED_SYMBOLS = (
     "ffs_split_plan_destroy",
     "ffs_split_plan_workspace_bytes",
     "ffs_align_split_batch",
+    "ffs_align_split_report_batch",
     "ffs_quality_plan_create",
     "ffs_quality_plan_destroy",
     "ffs_quality_plan_workspace_bytes",
@@ -261,6 +272,11 @@ def load():
         lib.ffs_align_split_batch.argtypes = [c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
                                               c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64,
                                               c.c_double, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
+        lib.ffs_align_split_report_batch.restype = c.c_int
+        lib.ffs_align_split_report_batch.argtypes = [c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                                                     c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64,
+                                                     c.c_double, c.c_int, c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p,
+                                                     c.c_void_p, c.c_void_p, c.c_void_p]
         lib.ffs_quality_plan_create.restype = c.c_int
         lib.ffs_quality_plan_create.argtypes = [c.c_int, c.c_int, c.c_int64, c.c_int64, c.POINTER(c.c_void_p)]
         lib.ffs_quality_plan_destroy.restype = c.c_int
@@ -829,6 +845,30 @@ class SplitPlan:
                                              shi.ctypes.data, int(block_samples), int(max_offset_samples),
                                              float(split_penalty), offsets_out.data_ptr(), scores_out.data_ptr(),
                                              totals_out.data_ptr(), st))
+
+    def align_report(self, ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, block_samples: int,
+                     max_offset_samples: int, split_penalty: float, top_k: int, exclusion_samples: int, offsets_out,
+                     scores_out, totals_out, report_out, n_pieces_out, stream: Optional[int] = None) -> None:
+        """``ffs_align_split_report_batch``: ``align``'s outputs plus a uint8 CUDA tensor of n_pairs * max_b * 224 bytes
+        of piece reports and an int32 one of n_pairs piece counts (asynchronous)."""
+        torch = require_gpu()
+        u64 = lambda a: np.ascontiguousarray(a, dtype=np.uint64)
+        i64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        rp, rl, rlo, rhi = u64(ref_ptr), i64(ref_len), f64(ref_lo), f64(ref_hi)
+        sp, sl, slo, shi = u64(sub_ptr), i64(sub_len), f64(sub_lo), f64(sub_hi)
+        n = rp.size
+        if not all(a.size == n for a in (rl, rlo, rhi, sp, sl, slo, shi)):
+            raise ValueError("one descriptor entry per pair")
+        if n_pieces_out.numel() < n or report_out.numel() * report_out.element_size() < offsets_out.numel() * PIECE_REPORT_BYTES:
+            raise ValueError("output buffer too small")
+        st = current_stream_ptr(torch) if stream is None else stream
+        check(self.lib.ffs_align_split_report_batch(self.handle, n, rp.ctypes.data, rl.ctypes.data, rlo.ctypes.data,
+                                                    rhi.ctypes.data, sp.ctypes.data, sl.ctypes.data, slo.ctypes.data,
+                                                    shi.ctypes.data, int(block_samples), int(max_offset_samples),
+                                                    float(split_penalty), int(top_k), int(exclusion_samples),
+                                                    offsets_out.data_ptr(), scores_out.data_ptr(), totals_out.data_ptr(),
+                                                    report_out.data_ptr(), n_pieces_out.data_ptr(), st))
 
     def close(self) -> None:
         if getattr(self, "handle", None):

@@ -20,7 +20,9 @@
 //                     transpose so that each wave's adds cover 64 consecutive lags.
 //   k_quality_peaks   one workgroup per pair: scores of every lag into the workspace, their sum / min / max, the mean,
 //                     the centred sum of squares (second pass over the stored scores), then top_k rounds of a block
-//                     argmax over the lags at least E away from every earlier peak (largest lag on ties).
+//                     argmax over the lags at least E away from every earlier peak (largest lag on ties).  The moments
+//                     and the peak rounds are the device helpers quality_curve_moments / quality_curve_peaks, which the
+//                     split report (ffs_split_report.h) shares.
 #pragma once
 #include "ffs_kernels.h"
 #include "ffs_split.h"
@@ -140,18 +142,99 @@ FFS_DEV double quality_block_sum(double x, double* s_part) {
     return sum;
 }
 
-// one workgroup per pair: scores, moments and greedy peaks into the pair's ffs_quality_result
-__global__ void __launch_bounds__(QUAL_PEAK_THREADS) k_quality_peaks(const QualDesc* __restrict__ desc, int top_k,
-                                                                     int64_t exclusion, QualResult* __restrict__ out) {
+// min / max / fixed-order sum of the n scores first(j), then the centred sum of squares over again(j) (the same
+// scores, recomputed or read back): mean, population std and whether the curve is flat (every score equal: mean = that
+// score, std = 0).  Every thread of the workgroup calls it; the result is the same on every thread and every run.
+template <class F1, class F2>
+FFS_DEV void quality_curve_moments(int64_t n, F1 first, F2 again, double& mean, double& sd, bool& flat) {
 #pragma clang fp contract(off)
     constexpr int NW = QUAL_PEAK_THREADS / 64;
     __shared__ double s_part[NW];
+    __shared__ double s_mn[NW], s_mx[NW];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    double sum = 0.0, mn = INFINITY, mx = -INFINITY;
+    for (int64_t j = t; j < n; j += QUAL_PEAK_THREADS) {
+        const double v = first(j);
+        sum += v;
+        mn = fmin(mn, v);
+        mx = fmax(mx, v);
+    }
+    for (int s = 32; s >= 1; s >>= 1) {
+        mn = fmin(mn, __shfl_xor(mn, s, 64));
+        mx = fmax(mx, __shfl_xor(mx, s, 64));
+    }
+    if (lane == 0) {
+        s_mn[wave] = mn;
+        s_mx[wave] = mx;
+    }
+    const double total = quality_block_sum(sum, s_part);  // (its barriers publish s_mn / s_mx)
+    for (int w = 0; w < NW; ++w) {
+        mn = fmin(mn, s_mn[w]);
+        mx = fmax(mx, s_mx[w]);
+    }
+    flat = mn == mx;
+    mean = flat ? mx : total / (double)n;
+    double ss = 0.0;
+    if (!flat) {
+        for (int64_t j = t; j < n; j += QUAL_PEAK_THREADS) {
+            const double e = again(j) - mean;
+            ss += e * e;
+        }
+    }
+    const double css = quality_block_sum(ss, s_part);
+    sd = flat ? 0.0 : sqrt(css / (double)n);
+}
+
+// up to top_k greedy peaks of the n scores score(j): each round a block argmax (largest lag index on ties) over the lags
+// at least `exclusion` from every earlier peak.  Peak k's lag index and score land in s_peak[k] / s_pscore[k] (LDS);
+// returns the number of peaks (the same on every thread).
+template <class F>
+FFS_DEV int quality_curve_peaks(int64_t n, F score, int top_k, int64_t exclusion, int64_t* s_peak, double* s_pscore) {
+    constexpr int NW = QUAL_PEAK_THREADS / 64;
     __shared__ double s_v[NW];
     __shared__ int64_t s_j[NW];
-    __shared__ int64_t s_peak[QUAL_MAX_PEAKS];
-    __shared__ int s_found;
-    const QualDesc d = desc[blockIdx.x];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    int n_peaks = 0;
+    for (int k = 0; k < top_k; ++k) {
+        double best = -INFINITY;
+        int64_t bestj = -1;
+        for (int64_t j = t; j < n; j += QUAL_PEAK_THREADS) {
+            bool ok = true;
+            for (int p = 0; p < k; ++p) {
+                const int64_t dist = j - s_peak[p];
+                ok = ok && (dist >= exclusion || -dist >= exclusion);
+            }
+            if (ok) quality_max_pair(best, bestj, score(j), j);
+        }
+        for (int s = 32; s >= 1; s >>= 1) {
+            const double ov = __shfl_xor(best, s, 64);
+            const int64_t oj = __shfl_xor(bestj, s, 64);
+            quality_max_pair(best, bestj, ov, oj);
+        }
+        if (lane == 0) {
+            s_v[wave] = best;
+            s_j[wave] = bestj;
+        }
+        __syncthreads();
+        if (t == 0) {
+            for (int w = 1; w < NW; ++w) quality_max_pair(best, bestj, s_v[w], s_j[w]);
+            s_peak[k] = bestj;
+            s_pscore[k] = best;
+        }
+        __syncthreads();
+        if (s_peak[k] < 0) break;  // (uniform) no lag left outside the exclusion zones
+        n_peaks = k + 1;
+    }
+    return n_peaks;
+}
+
+// one workgroup per pair: scores, moments and greedy peaks into the pair's ffs_quality_result
+__global__ void __launch_bounds__(QUAL_PEAK_THREADS) k_quality_peaks(const QualDesc* __restrict__ desc, int top_k,
+                                                                     int64_t exclusion, QualResult* __restrict__ out) {
+    __shared__ int64_t s_peak[QUAL_MAX_PEAKS];
+    __shared__ double s_pscore[QUAL_MAX_PEAKS];
+    const QualDesc d = desc[blockIdx.x];
+    const int t = threadIdx.x;
     const int64_t n = d.n_lags;
     QualResult* rec = out + d.out_row;
     if (n <= 0) {  // (uniform) the reference's window is empty: no lag, no peak
@@ -168,78 +251,21 @@ __global__ void __launch_bounds__(QUAL_PEAK_THREADS) k_quality_peaks(const QualD
         }
         return;
     }
-    double sum = 0.0, mn = INFINITY, mx = -INFINITY;
-    for (int64_t j = t; j < n; j += QUAL_PEAK_THREADS) {
-        const double v = quality_score(d, j);
-        d.sc[j] = v;  // (read back below by this same thread only)
-        sum += v;
-        mn = fmin(mn, v);
-        mx = fmax(mx, v);
-    }
-    for (int s = 32; s >= 1; s >>= 1) {
-        mn = fmin(mn, __shfl_xor(mn, s, 64));
-        mx = fmax(mx, __shfl_xor(mx, s, 64));
-    }
-    __shared__ double s_mn[NW], s_mx[NW];
-    if (lane == 0) {
-        s_mn[wave] = mn;
-        s_mx[wave] = mx;
-    }
-    const double total = quality_block_sum(sum, s_part);  // (its barriers publish s_mn / s_mx)
-    for (int w = 0; w < NW; ++w) {
-        mn = fmin(mn, s_mn[w]);
-        mx = fmax(mx, s_mx[w]);
-    }
-    const bool flat = mn == mx;
-    const double mean = flat ? mx : total / (double)n;
-    double ss = 0.0;
-    if (!flat) {
-        for (int64_t j = t; j < n; j += QUAL_PEAK_THREADS) {
-            const double e = d.sc[j] - mean;
-            ss += e * e;
-        }
-    }
-    const double css = quality_block_sum(ss, s_part);
-    const double sd = flat ? 0.0 : sqrt(css / (double)n);
-    int n_peaks = 0;
-    for (int k = 0; k < top_k; ++k) {
-        double best = -INFINITY;
-        int64_t bestj = -1;
-        for (int64_t j = t; j < n; j += QUAL_PEAK_THREADS) {
-            bool ok = true;
-            for (int p = 0; p < k; ++p) {
-                const int64_t dist = j - s_peak[p];
-                ok = ok && (dist >= exclusion || -dist >= exclusion);
-            }
-            if (ok) quality_max_pair(best, bestj, d.sc[j], j);
-        }
-        for (int s = 32; s >= 1; s >>= 1) {
-            const double ov = __shfl_xor(best, s, 64);
-            const int64_t oj = __shfl_xor(bestj, s, 64);
-            quality_max_pair(best, bestj, ov, oj);
-        }
-        if (lane == 0) {
-            s_v[wave] = best;
-            s_j[wave] = bestj;
-        }
-        __syncthreads();
-        if (t == 0) {
-            for (int w = 1; w < NW; ++w) quality_max_pair(best, bestj, s_v[w], s_j[w]);
-            s_found = bestj >= 0;
-            if (bestj >= 0) {
-                s_peak[k] = bestj;
-                rec->peak_score[k] = best;
-                rec->peak_offset[k] = d.d_lo + bestj;
-            }
-        }
-        __syncthreads();
-        if (!s_found) break;  // (uniform) no lag left outside the exclusion zones
-        n_peaks = k + 1;
-    }
+    double mean, sd;
+    bool flat;
+    quality_curve_moments(
+        n,
+        [&](int64_t j) {
+            const double v = quality_score(d, j);
+            d.sc[j] = v;  // (read back below by this same thread only)
+            return v;
+        },
+        [&](int64_t j) { return d.sc[j]; }, mean, sd, flat);
+    const int n_peaks = quality_curve_peaks(n, [&](int64_t j) { return d.sc[j]; }, top_k, exclusion, s_peak, s_pscore);
     if (t == 0) {
-        for (int k = n_peaks; k < QUAL_MAX_PEAKS; ++k) {
-            rec->peak_score[k] = 0.0;
-            rec->peak_offset[k] = 0;
+        for (int k = 0; k < QUAL_MAX_PEAKS; ++k) {
+            rec->peak_score[k] = k < n_peaks ? s_pscore[k] : 0.0;
+            rec->peak_offset[k] = k < n_peaks ? d.d_lo + s_peak[k] : 0;
         }
         rec->mean = mean;
         rec->std = sd;

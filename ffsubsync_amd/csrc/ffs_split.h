@@ -159,9 +159,17 @@ __global__ void __launch_bounds__(SPLIT_CNT_THREADS) k_split_counts(const SplitD
     }
 }
 
+// ((n00*c00 + n01*c01) + n10*c10) + n11*c11 of the counts of an overlap of ov samples
+FFS_DEV double split_mix(const SplitDesc& d, int64_t ov, int64_t n11, int64_t n1x, int64_t nx1) {
+#pragma clang fp contract(off)
+    const int64_t n10 = n1x - n11, n01 = nx1 - n11, n00 = ov - n11 - n10 - n01;
+    // plain operators under the pragma: __dmul_rn / __dadd_rn are defined where contraction is on, and once inlined
+    // their products fuse with the sums (v_fmac_f64)
+    return (((double)n00 * d.c00 + (double)n01 * d.c01) + (double)n10 * d.c10) + (double)n11 * d.c11;
+}
+
 // m_b(d) of lag index j (d = j - W + 1): n11 from the counts, ov / n1x / nx1 from the prefix popcounts
 FFS_DEV double split_score(const SplitDesc& d, const uint16_t* counts_row, int64_t b, int64_t j, int K, int64_t W) {
-#pragma clang fp contract(off)
     const int64_t lag = j - (W - 1);
     const int64_t blo = b * K, bhi = (blo + K < d.S) ? blo + K : d.S;
     const int64_t a = blo > -lag ? blo : -lag;
@@ -173,10 +181,7 @@ FFS_DEV double split_score(const SplitDesc& d, const uint16_t* counts_row, int64
         n1x = split_prefix_at(d.pre_s, d.s, e) - split_prefix_at(d.pre_s, d.s, a);
         nx1 = split_prefix_at(d.pre_r, d.r, e + lag) - split_prefix_at(d.pre_r, d.r, a + lag);
     }
-    const int64_t n10 = n1x - n11, n01 = nx1 - n11, n00 = ov - n11 - n10 - n01;
-    // plain operators under the pragma: __dmul_rn / __dadd_rn are defined where contraction is on, and once inlined
-    // their products fuse with the sums (v_fmac_f64)
-    return (((double)n00 * d.c00 + (double)n01 * d.c01) + (double)n10 * d.c10) + (double)n11 * d.c11;
+    return split_mix(d, ov, n11, n1x, nx1);
 }
 
 // (value, lag index) maximum with the largest index on ties

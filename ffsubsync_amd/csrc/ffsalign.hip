@@ -27,6 +27,7 @@
 #include "ffs_runs.h"
 #include "ffs_split.h"
 #include "ffs_quality.h"
+#include "ffs_split_report.h"
 
 using namespace ffsa;
 
@@ -999,7 +1000,7 @@ void fill_xform(XformDesc* x, const VecView* a, const VecView* b, const void* sa
 extern "C" {
 
 const char* ffs_last_error(void) { return g_err.c_str(); }
-int ffs_version(void) { return 320; }
+int ffs_version(void) { return 330; }
 
 int64_t ffs_fft_length(int64_t ref_len, int64_t sub_len) {
     if (ref_len <= 0 || sub_len <= 0) return 0;
@@ -2919,6 +2920,8 @@ struct ffs_split_plan {
     int32_t* pre;              // [slot][pw_s + pw_r]
     ffsa::SplitDesc* dev_desc; // [pairs_in_flight]
     ffsa::SplitDesc* host_desc; // pinned staging of the same
+    uint32_t* curves;          // report calls only, made by the first: per-piece n11 rows, [slot][max_blocks][lpad]
+    int64_t curve_bytes;
     hipEvent_t desc_free;      // the last descriptor upload has left the staging buffer
     hipEvent_t done;           // the plan's last call has finished with the workspace
 };
@@ -2993,17 +2996,27 @@ int ffs_split_plan_destroy(ffs_split_plan* plan) {
     if (plan->host_desc) (void)hipHostFree(plan->host_desc);
     if (plan->dev_desc) (void)hipFree(plan->dev_desc);
     if (plan->work) (void)hipFree(plan->work);
+    if (plan->curves) (void)hipFree(plan->curves);
     delete plan;
     return FFS_OK;
 }
 
-int64_t ffs_split_plan_workspace_bytes(const ffs_split_plan* plan) { return plan ? plan->work_bytes : 0; }
+int64_t ffs_split_plan_workspace_bytes(const ffs_split_plan* plan) { return plan ? plan->work_bytes + plan->curve_bytes : 0; }
 
-int ffs_align_split_batch(ffs_split_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
-                          const double* ref_lo, const double* ref_hi, const void* const* sub_ptr, const int64_t* sub_len,
-                          const double* sub_lo, const double* sub_hi, int64_t block_samples, int64_t max_offset_samples,
-                          double split_penalty, int32_t* block_offset_out_dev, double* block_score_out_dev,
-                          double* total_out_dev, void* hip_stream) {
+namespace {
+struct SplitReportArgs {  // the per-piece report of ffs_align_split_report_batch
+    int top_k;
+    int64_t exclusion;
+    ffs_piece_report* out;
+    int32_t* n_pieces;
+};
+
+// ffs_align_split_batch, and with `rep` the piece reports after each sub-batch's DP
+int split_batch(ffs_split_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len, const double* ref_lo,
+                const double* ref_hi, const void* const* sub_ptr, const int64_t* sub_len, const double* sub_lo,
+                const double* sub_hi, int64_t block_samples, int64_t max_offset_samples, double split_penalty,
+                int32_t* block_offset_out_dev, double* block_score_out_dev, double* total_out_dev,
+                const SplitReportArgs* rep, void* hip_stream) {
 #pragma clang fp contract(off)
     if (!plan) return fail(FFS_E_INVALID, "null split plan");
     if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
@@ -3019,6 +3032,12 @@ int ffs_align_split_batch(ffs_split_plan* plan, int n_pairs, const void* const* 
         return fail(FFS_E_INVALID, "2 * max_offset_samples = %lld exceeds the plan's max_lags %lld", (long long)(2 * W),
                     (long long)plan->max_lags);
     if (!(split_penalty >= 0.0)) return fail(FFS_E_INVALID, "split_penalty must be >= 0 (not NaN)");
+    if (rep) {
+        if (rep->top_k < 1 || rep->top_k > ffsa::QUAL_MAX_PEAKS) return fail(FFS_E_INVALID, "top_k=%d outside [1, 8]", rep->top_k);
+        if (rep->exclusion < 1) return fail(FFS_E_INVALID, "exclusion_samples=%lld: need >= 1", (long long)rep->exclusion);
+        if (!rep->out || !rep->n_pieces) return fail(FFS_E_INVALID, "null argument");
+        if (((uintptr_t)rep->out & 7) || ((uintptr_t)rep->n_pieces & 3)) return fail(FFS_E_INVALID, "misaligned report outputs");
+    }
     int64_t max_b = 0;
     for (int p = 0; p < n_pairs; ++p) {
         if (ref_len[p] <= 0 || sub_len[p] <= 0)
@@ -3038,6 +3057,14 @@ int ffs_align_split_batch(ffs_split_plan* plan, int n_pairs, const void* const* 
         if (B > max_b) max_b = B;
     }
     HIP_TRY(hipSetDevice(plan->device));
+    if (rep && !plan->curves) {  // the first report call: one uint32 n11 row per (slot, block)
+        const int64_t bytes = (int64_t)plan->pairs_in_flight * plan->ws.counts_slot * 4;
+        if (hipMalloc((void**)&plan->curves, bytes) != hipSuccess) {
+            plan->curves = nullptr;
+            return fail(FFS_E_NOMEM, "split plan: %lld report workspace bytes", (long long)bytes);
+        }
+        plan->curve_bytes = bytes;
+    }
     hipStream_t st = (hipStream_t)hip_stream;
     HIP_TRY(hipStreamWaitEvent(st, plan->done, 0));  // the previous call (any stream) is done with the workspace
     const int64_t L = 2 * W;
@@ -3075,10 +3102,45 @@ int ffs_align_split_batch(ffs_split_plan* plan, int n_pairs, const void* const* 
                            n_bgroups);
         hipLaunchKernelGGL(ffsa::k_split_dp, dim3(np), dim3(ffsa::SPLIT_DP_THREADS), 0, st, plan->dev_desc, plan->ws, (int)K,
                            (int64_t)W, split_penalty, max_b, block_offset_out_dev, block_score_out_dev, total_out_dev);
+        if (rep) {
+            hipLaunchKernelGGL(ffsa::k_split_pieces, dim3(np), dim3(ffsa::PIECE_SCAN_THREADS), 0, st, plan->dev_desc, (int)K,
+                               max_b, block_offset_out_dev, (ffsa::PieceReport*)rep->out, rep->n_pieces);
+            const int n_sum_tiles = (int)((L + ffsa::PIECE_SUM_TILE - 1) / ffsa::PIECE_SUM_TILE);
+            hipLaunchKernelGGL(ffsa::k_split_piece_sums, dim3((unsigned)((int64_t)n_sum_tiles * np)),
+                               dim3(ffsa::PIECE_SUM_THREADS), 0, st, plan->dev_desc, plan->ws, plan->curves, (int)K,
+                               (int64_t)W, n_sum_tiles, max_b, (const int32_t*)block_offset_out_dev);
+            // one workgroup per possible piece (at most one per block); those past the pair's count return at once
+            hipLaunchKernelGGL(ffsa::k_split_piece_report, dim3((unsigned)(chunk_b * np)), dim3(ffsa::QUAL_PEAK_THREADS), 0,
+                               st, plan->dev_desc, plan->ws, (const uint32_t*)plan->curves, (int64_t)W, (int)chunk_b, max_b,
+                               rep->top_k, rep->exclusion, (const int32_t*)rep->n_pieces, (ffsa::PieceReport*)rep->out);
+        }
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(plan->done, st));
     return FFS_OK;
+}
+}  // namespace
+
+int ffs_align_split_batch(ffs_split_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
+                          const double* ref_lo, const double* ref_hi, const void* const* sub_ptr, const int64_t* sub_len,
+                          const double* sub_lo, const double* sub_hi, int64_t block_samples, int64_t max_offset_samples,
+                          double split_penalty, int32_t* block_offset_out_dev, double* block_score_out_dev,
+                          double* total_out_dev, void* hip_stream) {
+    return split_batch(plan, n_pairs, ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, block_samples,
+                       max_offset_samples, split_penalty, block_offset_out_dev, block_score_out_dev, total_out_dev, nullptr,
+                       hip_stream);
+}
+
+int ffs_align_split_report_batch(ffs_split_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
+                                 const double* ref_lo, const double* ref_hi, const void* const* sub_ptr,
+                                 const int64_t* sub_len, const double* sub_lo, const double* sub_hi, int64_t block_samples,
+                                 int64_t max_offset_samples, double split_penalty, int top_k, int64_t exclusion_samples,
+                                 int32_t* block_offset_out_dev, double* block_score_out_dev, double* total_out_dev,
+                                 ffs_piece_report* report_out_dev, int32_t* n_pieces_out_dev, void* hip_stream) {
+    const SplitReportArgs rep{top_k, exclusion_samples, report_out_dev, n_pieces_out_dev};
+    return split_batch(plan, n_pairs, ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, block_samples,
+                       max_offset_samples, split_penalty, block_offset_out_dev, block_score_out_dev, total_out_dev, &rep,
+                       hip_stream);
 }
 
 /* ---- alignment quality report (csrc/ffs_quality.h) ------------------------------------------------------------- */

@@ -108,18 +108,22 @@ def _check_batch(batch) -> None:
 _plan_cache: dict = {}
 
 
-def _get_plan(n_pairs: int, max_blocks: int, max_lags: int, max_samples: int, pairs_in_flight: Optional[int]):
+def _get_plan(n_pairs: int, max_blocks: int, max_lags: int, max_samples: int, pairs_in_flight: Optional[int],
+              report: bool = False):
+    """The cached plan of this device; report calls (``split_report``) get their own, sized for the per-piece n11 rows
+    the first report call adds (4 more bytes per block and lag)."""
     torch = _native.require_gpu()
     dev = torch.cuda.current_device()
     if pairs_in_flight is None:  # bound the workspace (~170 MB of counts per pair at 2 h, +-10 min, K = 1024) to ~12 GiB
-        per_pair = max_blocks * (max_lags + 64) * 2.2 + 1
+        per_pair = max_blocks * (max_lags + 64) * (6.2 if report else 2.2) + 1
         pairs_in_flight = int(max(1, min(n_pairs, 256, (12 << 30) // per_pair)))
-    plan = _plan_cache.get(dev)
+    key = (dev, "report") if report else dev
+    plan = _plan_cache.get(key)
     if plan is None or plan.handle is None or not plan.fits(pairs_in_flight, max_blocks, max_lags, max_samples):
         if plan is not None:
             plan.close()
         plan = _native.SplitPlan(pairs_in_flight, max_blocks, max_lags, max_samples, dev)
-        _plan_cache[dev] = plan
+        _plan_cache[key] = plan
     return plan
 
 
@@ -137,6 +141,13 @@ def split_align_batch(batch, max_offset_samples: int, block_samples: int = DEFAU
     splits.  Returns one ``SplitResult`` per pair."""
     validate_args(block_samples, max_offset_samples, split_penalty)
     _check_batch(batch)
+    return _solve(batch, max_offset_samples, block_samples, split_penalty, pairs_in_flight)[0]
+
+
+def _solve(batch, max_offset_samples, block_samples, split_penalty, pairs_in_flight, report=None):
+    """The device call behind ``split_align_batch`` (arguments checked); with ``report`` = (top_k, exclusion_samples)
+    ``ffs_align_split_report_batch``.  Returns (SplitResults, piece report records [n, max_b] or None, piece counts or
+    None)."""
     torch = _native.require_gpu()
     if batch.dtype == _native.FFS_DTYPE_U8:
         batch = batch.to_bits()
@@ -145,15 +156,23 @@ def split_align_batch(batch, max_offset_samples: int, block_samples: int = DEFAU
     ref_len, sub_len = batch.lens[:, 0].astype(np.int64), batch.lens[:, 1].astype(np.int64)
     n_blocks = (sub_len + k - 1) // k
     max_b = int(n_blocks.max())
-    plan = _get_plan(n, max_b, 2 * w, int(sub_len.max()), pairs_in_flight)
+    plan = _get_plan(n, max_b, 2 * w, int(sub_len.max()), pairs_in_flight, report is not None)
     base = np.uint64(batch.data.data_ptr())
     dev = batch.data.device
     offs_out = torch.empty(n * max_b, dtype=torch.int32, device=dev)
     scores_out = torch.empty(n * max_b, dtype=torch.float64, device=dev)
     totals_out = torch.empty(n, dtype=torch.float64, device=dev)
-    plan.align(base + batch.offs[:, 0].astype(np.uint64), ref_len, batch.lo[:, 0], batch.hi[:, 0],
-               base + batch.offs[:, 1].astype(np.uint64), sub_len, batch.lo[:, 1], batch.hi[:, 1], k, w,
-               float(split_penalty), offs_out, scores_out, totals_out)
+    args = (base + batch.offs[:, 0].astype(np.uint64), ref_len, batch.lo[:, 0], batch.hi[:, 0],
+            base + batch.offs[:, 1].astype(np.uint64), sub_len, batch.lo[:, 1], batch.hi[:, 1], k, w, float(split_penalty))
+    recs = counts = None
+    if report is None:
+        plan.align(*args, offs_out, scores_out, totals_out)
+    else:
+        rep_out = torch.empty(n * max_b * _native.PIECE_REPORT_BYTES, dtype=torch.uint8, device=dev)
+        n_out = torch.empty(n, dtype=torch.int32, device=dev)
+        plan.align_report(*args, int(report[0]), int(report[1]), offs_out, scores_out, totals_out, rep_out, n_out)
+        recs = rep_out.cpu().numpy().view(_native.PIECE_REPORT_DTYPE).reshape(n, max_b)
+        counts = n_out.cpu().numpy()
     offs_h = offs_out.cpu().numpy().reshape(n, max_b)
     scores_h = scores_out.cpu().numpy().reshape(n, max_b)
     totals_h = totals_out.cpu().numpy()
@@ -162,7 +181,7 @@ def split_align_batch(batch, max_offset_samples: int, block_samples: int = DEFAU
         nb = int(n_blocks[p])
         bo, bs = offs_h[p, :nb].copy(), scores_h[p, :nb].copy()
         out.append(SplitResult(pieces_from_blocks(bo, bs, k, int(sub_len[p])), float(totals_h[p]), bo, bs))
-    return out
+    return out, recs, counts
 
 
 def _scaled_us(us: int, ratio: float) -> int:

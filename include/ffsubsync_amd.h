@@ -473,6 +473,54 @@ int ffs_align_quality_batch(ffs_quality_plan* plan, int n_pairs, const void* con
                             const double* sub_lo, const double* sub_hi, int64_t max_offset_samples, int top_k,
                             int64_t exclusion_samples, ffs_quality_result* out_dev, void* hip_stream);
 
+/* ---- per-piece quality report of a split solve: break evidence (csrc/ffs_split_report.h) -------------------------
+ * Replaces: nothing in the reference.  The contract below is pinned against the numpy model tests/split_report_model.py.
+ *
+ * The split solve of ffs_align_split_batch (same arguments, same block_offset / block_score / total outputs bit for
+ * bit), then per pair its pieces -- maximal runs [f_i, e_i) of equal block offsets, subtitle samples
+ * [f_i K, min(e_i K, S)), offset o_i -- in report_out_dev[p * max_b + i] (max_b = the call's largest block count, as for
+ * the block outputs; records past the piece count are zero) and the piece count in n_pieces_out_dev[p].
+ * Piece curve c_i(d), d in [-W+1, W]: over the piece's samples j with 0 <= j+d < R, the counts ov, n1x, nx1 and
+ * n11 (the exact sum of the piece's block counts), scored ((n00*c00 + n01*c01) + n10*c10) + n11*c11 in fp64 with every
+ * operation rounded on its own (the block scores' arithmetic); exactly 0.0 where the overlap is empty.  Moments over the
+ * 2W lags (two passes, population std) and up to top_k greedy peaks with exclusion distance E, largest lag on ties, as
+ * ffs_quality_result (FFS_QUALITY_FLAT when every score is equal).  own_score = c_i(o_i); prev_score = c_i(o_{i-1}),
+ * next_score = c_i(o_{i+1}), NaN without that neighbour.  FFS_PIECE_OWN_NOT_PEAK: peak 1 is not at o_i.
+ *
+ * The first report call on a plan adds a workspace of one uint32 n11 row per block and lag (2x the block counts:
+ * max_blocks * max_lags * 4 bytes per pair in flight), counted by ffs_split_plan_workspace_bytes from then on; plans
+ * that never report keep the split workspace alone. */
+#define FFS_PIECE_OWN_NOT_PEAK 4   /* the piece's peak 1 is not at its own offset */
+
+typedef struct ffs_piece_report {
+    int64_t first_block, end_block;   /* blocks [first_block, end_block) */
+    int64_t start_sample, end_sample; /* subtitle samples [start_sample, end_sample) */
+    int64_t offset;                   /* the piece's offset o_i (samples) */
+    double own_score;                 /* c_i(o_i) */
+    double prev_score, next_score;    /* c_i(o_{i-1}), c_i(o_{i+1}); NaN without that neighbour */
+    double mean, std;                 /* of c_i over the 2W lags */
+    int64_t n_lags;                   /* 2W */
+    double peak_score[8];             /* peaks 0 .. n_peaks-1 (entries beyond: 0) */
+    int64_t peak_offset[8];           /* samples */
+    int32_t n_peaks, flags;           /* flags: FFS_QUALITY_FLAT, FFS_QUALITY_EMPTY_WINDOW, FFS_PIECE_OWN_NOT_PEAK */
+} ffs_piece_report;
+#ifdef __cplusplus
+static_assert(sizeof(ffs_piece_report) == 224, "ffs_piece_report is 224 bytes");
+#else
+_Static_assert(sizeof(ffs_piece_report) == 224, "ffs_piece_report is 224 bytes");
+#endif
+
+/* ffs_align_split_batch plus the piece reports, in one call on hip_stream.  report_out_dev: n_pairs * max_b records
+ * (8-byte aligned); n_pieces_out_dev: n_pairs int32.  FFS_E_INVALID / FFS_E_EMPTY as ffs_align_split_batch, and
+ * FFS_E_INVALID for top_k outside [1, 8], exclusion_samples < 1 or a null / misaligned report output; all before any
+ * launch. */
+int ffs_align_split_report_batch(ffs_split_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
+                                 const double* ref_lo, const double* ref_hi, const void* const* sub_ptr,
+                                 const int64_t* sub_len, const double* sub_lo, const double* sub_hi, int64_t block_samples,
+                                 int64_t max_offset_samples, double split_penalty, int top_k, int64_t exclusion_samples,
+                                 int32_t* block_offset_out_dev, double* block_score_out_dev, double* total_out_dev,
+                                 ffs_piece_report* report_out_dev, int32_t* n_pieces_out_dev, void* hip_stream);
+
 /* Thread-local description of the last error returned on this thread ("" if none). */
 const char* ffs_last_error(void);
 
