@@ -54,6 +54,18 @@ PIECE_REPORT_DTYPE = np.dtype(
 )
 PIECE_REPORT_BYTES = 224
 assert PIECE_REPORT_DTYPE.itemsize == PIECE_REPORT_BYTES
+# ffs_break_refine (include/ffsubsync_amd.h; static size 88 bytes)
+REFINE_MAX_RADIUS = 131072  # FFS_REFINE_MAX_RADIUS
+REFINE_CLIPPED = 1  # FFS_REFINE_CLIPPED: the window was narrowed by a neighbouring break's midpoint
+REFINE_AT_EDGE = 2  # FFS_REFINE_AT_EDGE: a cut sits at a window edge inside the file (the radius may be too small)
+REFINE_UNMATCHED = 4  # FFS_REFINE_UNMATCHED: t1 < t2
+BREAK_REFINE_DTYPE = np.dtype(
+    [("block", "<i8"), ("cut", "<i8"), ("lo", "<i8"), ("hi", "<i8"), ("t1", "<i8"), ("t2", "<i8"),
+     ("offset_prev", "<i8"), ("offset_next", "<i8"), ("coarse_score", "<f8"), ("refined_score", "<f8"),
+     ("flags", "<i4"), ("reserved", "<i4")], align=True
+)
+BREAK_REFINE_BYTES = 88
+assert BREAK_REFINE_DTYPE.itemsize == BREAK_REFINE_BYTES
 
 # every symbol include/ffsubsync_amd.h declares (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = (
@@ -97,6 +109,7 @@ EXPORTED_SYMBOLS = (
     "ffs_split_plan_workspace_bytes",
     "ffs_align_split_batch",
     "ffs_align_split_report_batch",
+    "ffs_split_refine_batch",
     "ffs_quality_plan_create",
     "ffs_quality_plan_destroy",
     "ffs_quality_plan_workspace_bytes",
@@ -277,6 +290,10 @@ def load():
                                                      c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64,
                                                      c.c_double, c.c_int, c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p,
                                                      c.c_void_p, c.c_void_p, c.c_void_p]
+        lib.ffs_split_refine_batch.restype = c.c_int
+        lib.ffs_split_refine_batch.argtypes = [c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                                               c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p,
+                                               c.c_int64, c.c_double, c.c_void_p, c.c_void_p, c.c_void_p]
         lib.ffs_quality_plan_create.restype = c.c_int
         lib.ffs_quality_plan_create.argtypes = [c.c_int, c.c_int, c.c_int64, c.c_int64, c.POINTER(c.c_void_p)]
         lib.ffs_quality_plan_destroy.restype = c.c_int
@@ -869,6 +886,30 @@ class SplitPlan:
                                                     float(split_penalty), int(top_k), int(exclusion_samples),
                                                     offsets_out.data_ptr(), scores_out.data_ptr(), totals_out.data_ptr(),
                                                     report_out.data_ptr(), n_pieces_out.data_ptr(), st))
+
+    def refine(self, ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, block_samples: int,
+               offsets, radius_samples: int, unmatched_margin: float, refine_out, n_breaks_out,
+               stream: Optional[int] = None) -> None:
+        """``ffs_split_refine_batch``: the int32 CUDA tensor of n_pairs * max_b block offsets (as ``align`` wrote them)
+        into a uint8 CUDA tensor of n_pairs * max_b * 88 bytes of break records and an int32 one of n_pairs break counts
+        (asynchronous); ``unmatched_margin`` NaN = a single cut."""
+        torch = require_gpu()
+        u64 = lambda a: np.ascontiguousarray(a, dtype=np.uint64)
+        i64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        rp, rl, rlo, rhi = u64(ref_ptr), i64(ref_len), f64(ref_lo), f64(ref_hi)
+        sp, sl, slo, shi = u64(sub_ptr), i64(sub_len), f64(sub_lo), f64(sub_hi)
+        n = rp.size
+        if not all(a.size == n for a in (rl, rlo, rhi, sp, sl, slo, shi)):
+            raise ValueError("one descriptor entry per pair")
+        if n_breaks_out.numel() < n or refine_out.numel() * refine_out.element_size() < offsets.numel() * BREAK_REFINE_BYTES:
+            raise ValueError("output buffer too small")
+        st = current_stream_ptr(torch) if stream is None else stream
+        check(self.lib.ffs_split_refine_batch(self.handle, n, rp.ctypes.data, rl.ctypes.data, rlo.ctypes.data,
+                                              rhi.ctypes.data, sp.ctypes.data, sl.ctypes.data, slo.ctypes.data,
+                                              shi.ctypes.data, int(block_samples), offsets.data_ptr(),
+                                              int(radius_samples), float(unmatched_margin), refine_out.data_ptr(),
+                                              n_breaks_out.data_ptr(), st))
 
     def close(self) -> None:
         if getattr(self, "handle", None):

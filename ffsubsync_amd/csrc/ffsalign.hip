@@ -28,6 +28,7 @@
 #include "ffs_split.h"
 #include "ffs_quality.h"
 #include "ffs_split_report.h"
+#include "ffs_split_refine.h"
 
 using namespace ffsa;
 
@@ -1000,7 +1001,7 @@ void fill_xform(XformDesc* x, const VecView* a, const VecView* b, const void* sa
 extern "C" {
 
 const char* ffs_last_error(void) { return g_err.c_str(); }
-int ffs_version(void) { return 330; }
+int ffs_version(void) { return 340; }
 
 int64_t ffs_fft_length(int64_t ref_len, int64_t sub_len) {
     if (ref_len <= 0 || sub_len <= 0) return 0;
@@ -2922,6 +2923,11 @@ struct ffs_split_plan {
     ffsa::SplitDesc* host_desc; // pinned staging of the same
     uint32_t* curves;          // report calls only, made by the first: per-piece n11 rows, [slot][max_blocks][lpad]
     int64_t curve_bytes;
+    ffsa::RefineDesc* refine_desc;       // refine calls only, made by the first: descriptors [pairs_in_flight] then
+    ffsa::RefineDesc* refine_host_desc;  // their pinned staging, and the null-score scratch [pairs_in_flight][4]
+    double* refine_scratch;
+    int64_t refine_bytes;
+    hipEvent_t refine_desc_free;
     hipEvent_t desc_free;      // the last descriptor upload has left the staging buffer
     hipEvent_t done;           // the plan's last call has finished with the workspace
 };
@@ -2997,11 +3003,16 @@ int ffs_split_plan_destroy(ffs_split_plan* plan) {
     if (plan->dev_desc) (void)hipFree(plan->dev_desc);
     if (plan->work) (void)hipFree(plan->work);
     if (plan->curves) (void)hipFree(plan->curves);
+    if (plan->refine_desc) (void)hipFree(plan->refine_desc);
+    if (plan->refine_host_desc) (void)hipHostFree(plan->refine_host_desc);
+    if (plan->refine_desc_free) (void)hipEventDestroy(plan->refine_desc_free);
     delete plan;
     return FFS_OK;
 }
 
-int64_t ffs_split_plan_workspace_bytes(const ffs_split_plan* plan) { return plan ? plan->work_bytes + plan->curve_bytes : 0; }
+int64_t ffs_split_plan_workspace_bytes(const ffs_split_plan* plan) {
+    return plan ? plan->work_bytes + plan->curve_bytes + plan->refine_bytes : 0;
+}
 
 namespace {
 struct SplitReportArgs {  // the per-piece report of ffs_align_split_report_batch
@@ -3141,6 +3152,105 @@ int ffs_align_split_report_batch(ffs_split_plan* plan, int n_pairs, const void* 
     return split_batch(plan, n_pairs, ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, block_samples,
                        max_offset_samples, split_penalty, block_offset_out_dev, block_score_out_dev, total_out_dev, &rep,
                        hip_stream);
+}
+
+/* ---- sample-exact break refinement (csrc/ffs_split_refine.h) -------------------------------------------------- */
+
+int ffs_split_refine_batch(ffs_split_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
+                           const double* ref_lo, const double* ref_hi, const void* const* sub_ptr, const int64_t* sub_len,
+                           const double* sub_lo, const double* sub_hi, int64_t block_samples,
+                           const int32_t* block_offset_dev, int64_t radius_samples, double unmatched_margin,
+                           ffs_break_refine* out_dev, int32_t* n_breaks_out_dev, void* hip_stream) {
+#pragma clang fp contract(off)
+    if (!plan) return fail(FFS_E_INVALID, "null split plan");
+    if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
+    if (n_pairs == 0) return FFS_OK;
+    if (!ref_ptr || !ref_len || !ref_lo || !ref_hi || !sub_ptr || !sub_len || !sub_lo || !sub_hi || !block_offset_dev ||
+        !out_dev || !n_breaks_out_dev)
+        return fail(FFS_E_INVALID, "null argument");
+    if (((uintptr_t)block_offset_dev & 3) || ((uintptr_t)out_dev & 7) || ((uintptr_t)n_breaks_out_dev & 3))
+        return fail(FFS_E_INVALID, "misaligned block offsets or refine outputs");
+    const int64_t K = block_samples, Rr = radius_samples;
+    if (K < 256 || K > ffsa::SPLIT_MAX_K || K % 32 != 0)
+        return fail(FFS_E_INVALID, "block_samples=%lld: need a multiple of 32 in [256, 32768]", (long long)K);
+    if (Rr < 1 || Rr > ffsa::REFINE_MAX_RADIUS)
+        return fail(FFS_E_INVALID, "radius_samples=%lld: need 1 <= radius <= %lld", (long long)Rr,
+                    (long long)ffsa::REFINE_MAX_RADIUS);
+    const bool single = std::isnan(unmatched_margin);
+    if (!single && !(unmatched_margin >= 0.0 && std::isfinite(unmatched_margin)))
+        return fail(FFS_E_INVALID, "unmatched_margin must be finite and >= 0, or NaN for a single cut");
+    int64_t max_b = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+        if (ref_len[p] <= 0 || sub_len[p] <= 0)
+            return fail(FFS_E_EMPTY, "cannot align empty speech data (reference length=%lld, subtitle length=%lld)",
+                        (long long)(ref_len[p] > 0 ? ref_len[p] : 0), (long long)(sub_len[p] > 0 ? sub_len[p] : 0));
+        if (!ref_ptr[p] || !sub_ptr[p] || ((uintptr_t)ref_ptr[p] & 3) || ((uintptr_t)sub_ptr[p] & 3))
+            return fail(FFS_E_INVALID, "pair %d: null or misaligned vector", p);
+        if (ref_len[p] > INT32_MAX / 2 || sub_len[p] > INT32_MAX / 2)
+            return fail(FFS_E_INVALID, "pair %d: vectors longer than 2^30 samples", p);
+        if (!(std::isfinite(ref_lo[p]) && std::isfinite(ref_hi[p]) && std::isfinite(sub_lo[p]) && std::isfinite(sub_hi[p])))
+            return fail(FFS_E_INVALID, "pair %d: levels must be finite", p);
+        max_b = std::max(max_b, (sub_len[p] + K - 1) / K);
+    }
+    HIP_TRY(hipSetDevice(plan->device));
+    const int pif = plan->pairs_in_flight;
+    if (!plan->refine_desc) {  // the first refine call: descriptors, their staging and the null-score scratch
+        const size_t desc_bytes = sizeof(ffsa::RefineDesc) * (size_t)pif, scratch_bytes = sizeof(double) * 4 * (size_t)pif;
+        void* dev = nullptr;
+        if (hipMalloc(&dev, desc_bytes + scratch_bytes) != hipSuccess) return fail(FFS_E_NOMEM, "split plan: refine workspace");
+        if (hipHostMalloc((void**)&plan->refine_host_desc, desc_bytes, hipHostMallocDefault) != hipSuccess ||
+            hipEventCreateWithFlags(&plan->refine_desc_free, hipEventDisableTiming) != hipSuccess) {
+            (void)hipFree(dev);
+            if (plan->refine_host_desc) (void)hipHostFree(plan->refine_host_desc);
+            plan->refine_host_desc = nullptr;
+            plan->refine_desc_free = nullptr;
+            return fail(FFS_E_HIP, "split plan: refine descriptor staging / event");
+        }
+        plan->refine_desc = (ffsa::RefineDesc*)dev;
+        plan->refine_scratch = (double*)((char*)dev + desc_bytes);
+        plan->refine_bytes = (int64_t)(desc_bytes + scratch_bytes);
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    HIP_TRY(hipStreamWaitEvent(st, plan->done, 0));  // the previous call (any stream) is done with the plan
+    for (int p0 = 0; p0 < n_pairs; p0 += pif) {
+        const int np = std::min(pif, n_pairs - p0);
+        HIP_TRY(hipEventSynchronize(plan->refine_desc_free));
+        int64_t chunk_b = 0;
+        for (int i = 0; i < np; ++i) {
+            const int p = p0 + i;
+            ffsa::RefineDesc& d = plan->refine_host_desc[i];
+            d.r = (const uint32_t*)ref_ptr[p];
+            d.s = (const uint32_t*)sub_ptr[p];
+            d.R = ref_len[p];
+            d.S = sub_len[p];
+            d.s0 = 2.0 * sub_lo[p] - 1.0;  // as split_batch
+            d.s1 = 2.0 * sub_hi[p] - 1.0;
+            d.r0 = 2.0 * ref_lo[p] - 1.0;
+            d.r1 = 2.0 * ref_hi[p] - 1.0;
+            d.c00 = d.s0 * d.r0;
+            d.c01 = d.s0 * d.r1;
+            d.c10 = d.s1 * d.r0;
+            d.c11 = d.s1 * d.r1;
+            d.pair_ws = plan->refine_scratch + 4 * (int64_t)i;
+            d.out_row = p;
+            chunk_b = std::max(chunk_b, (d.S + K - 1) / K);
+        }
+        HIP_TRY(hipMemcpyAsync(plan->refine_desc, plan->refine_host_desc, sizeof(ffsa::RefineDesc) * np,
+                               hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(plan->refine_desc_free, st));
+        hipLaunchKernelGGL(ffsa::k_refine_breaks, dim3(np), dim3(ffsa::REFINE_TABLE_THREADS), 0, st, plan->refine_desc,
+                           (int)K, max_b, Rr, unmatched_margin, block_offset_dev, (ffsa::BreakRefine*)out_dev,
+                           n_breaks_out_dev);
+        if (chunk_b > 1) {  // one workgroup per possible break (at most one per block after the first)
+            const int n_slots = (int)(chunk_b - 1);
+            hipLaunchKernelGGL(ffsa::k_refine_cut, dim3((unsigned)((int64_t)n_slots * np)), dim3(ffsa::REFINE_THREADS), 0,
+                               st, plan->refine_desc, n_slots, max_b, single, (const int32_t*)n_breaks_out_dev,
+                               (ffsa::BreakRefine*)out_dev);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(plan->done, st));
+    return FFS_OK;
 }
 
 /* ---- alignment quality report (csrc/ffs_quality.h) ------------------------------------------------------------- */

@@ -167,6 +167,13 @@ def checked_split_sync(problems, max_offset_seconds: float = 600, block_samples:
     - "single": some piece or break fails, but the whole-file quality report of the winning candidate passes
       ``quality.assess`` -- the cues scaled, then shifted by the single offset of the seven-ratio solve;
     - "untrusted": neither -- the input cue times, unmodified."""
+    return _checked_split_sync(problems, max_offset_seconds, block_samples, split_penalty, top_k, exclusion_samples,
+                               min_piece_psr, min_gain, min_psr, min_margin, sample_rate, ratios)[0]
+
+
+def _checked_split_sync(problems, max_offset_seconds, block_samples, split_penalty, top_k, exclusion_samples, min_piece_psr,
+                        min_gain, min_psr, min_margin, sample_rate, ratios):
+    """``checked_split_sync``'s work; returns (its results, the one-candidate DeviceBatch it solved, the SplitReports)."""
     w = int(round(max_offset_seconds * sample_rate))
     validate_args(block_samples, w, split_penalty, top_k, exclusion_samples)
     ratios = list(candidate_ratios() if ratios is None else ratios)
@@ -197,4 +204,4 @@ def checked_split_sync(problems, max_offset_seconds: float = 600, block_samples:
                 which = np.full(len(cs), -1, np.int64)
         out.append(CheckedSplitResult(decision, reasons, ratio, int(best[p]), g_off, rep.split.pieces, rep.pieces,
                                       break_support(rep.pieces, min_gain), q, cs, ce, which))
-    return out
+    return out, chosen, reps

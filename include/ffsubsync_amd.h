@@ -521,6 +521,57 @@ int ffs_align_split_report_batch(ffs_split_plan* plan, int n_pairs, const void* 
                                  int32_t* block_offset_out_dev, double* block_score_out_dev, double* total_out_dev,
                                  ffs_piece_report* report_out_dev, int32_t* n_pieces_out_dev, void* hip_stream);
 
+/* ---- sample-exact break refinement after a split solve (csrc/ffs_split_refine.h) ----------------------------------
+ * Replaces: nothing in the reference.  The contract below is pinned against the numpy model tests/split_refine_model.py.
+ *
+ * The split DP puts every break on a block boundary.  Per pair (the vectors as ffs_align_split_batch takes them, its
+ * block offsets o_b in block_offset_dev[p * max_b + b], max_b = the call's largest ceil(S/K)): breaks are the blocks f_j
+ * (j = 1..n) with o_{f_j} != o_{f_j - 1}, cut c_j = f_j K, between o_a = o_{f_j - 1} and o_b = o_{f_j}; c_0 = 0,
+ * c_{n+1} = S.  Window [L_j, U_j]: L_j = max(c_j - Rr, j == 1 ? 0 : floor((c_{j-1} + c_j) / 2)),
+ * U_j = min(c_j + Rr, j == n ? S : floor((c_j + c_{j+1}) / 2)), Rr = radius_samples in [1, FFS_REFINE_MAX_RADIUS].
+ * A(t) = the split's two-level score ((n00*c00 + n01*c01) + n10*c10) + n11*c11 of subtitle samples [L, t) at lag o_a,
+ * B(t) = that of [t, U) at lag o_b (samples whose partner lies outside the reference are absent).  Null score
+ * z_x = s~_x * rbar + beta * |s~_x|, s~_x = 2 lvl_s[x] - 1, rbar = ((R - P1) * r~_0 + P1 * r~_1) / R with P1 the
+ * reference's popcount and r~_y = 2 lvl_r[y] - 1; N(t) = n0 * z0 + n1 * z1 over [L, t).  F(t) = A(t) - N(t),
+ * G(t) = N(t) + B(t).  t2 = the smallest maximiser over [L, U] of G(t) + max_{L <= t' <= t} F(t'); t1 = the smallest
+ * maximiser of F on [L, t2].  beta = unmatched_margin >= 0 (finite), or NaN for a single cut: t1 = t2 = the smallest
+ * maximiser of A(t) + B(t).  Every value is fp64 with each operation rounded on its own.  Subtitle samples before t1
+ * keep o_a, samples in [t1, t2) match neither neighbour, samples from t2 on take o_b.
+ *
+ * Records: out_dev[p * max_b + j] for j < n (records past the count are zero), the count in n_breaks_out_dev[p].
+ * The call uses the split plan's pairs_in_flight for its sub-batches and none of its split workspace; the first refine
+ * call on a plan adds a few hundred bytes per pair in flight, counted by ffs_split_plan_workspace_bytes from then on. */
+#define FFS_REFINE_MAX_RADIUS 131072
+#define FFS_REFINE_CLIPPED 1   /* the window was narrowed by a neighbouring break's midpoint */
+#define FFS_REFINE_AT_EDGE 2   /* t1 = L > 0 or t2 = U < S: the radius may be too small */
+#define FFS_REFINE_UNMATCHED 4 /* t1 < t2 */
+
+typedef struct ffs_break_refine {
+    int64_t block, cut;               /* f_j and c_j = f_j K */
+    int64_t lo, hi;                   /* the window [L, U] */
+    int64_t t1, t2;                   /* the cut points, L <= t1 <= t2 <= U */
+    int64_t offset_prev, offset_next; /* o_a, o_b (samples) */
+    double coarse_score;              /* A(c) + B(c): the block cut's score */
+    double refined_score;             /* F(t1) + G(t2); A(t1) + B(t1) for a single cut */
+    int32_t flags, reserved;          /* flags: FFS_REFINE_*; reserved = 0 */
+} ffs_break_refine;
+#ifdef __cplusplus
+static_assert(sizeof(ffs_break_refine) == 88, "ffs_break_refine is 88 bytes");
+#else
+_Static_assert(sizeof(ffs_break_refine) == 88, "ffs_break_refine is 88 bytes");
+#endif
+
+/* Refine the breaks of n_pairs split solves on hip_stream (host arrays of n_pairs entries; ref_ptr / sub_ptr and
+ * block_offset_dev are DEVICE pointers).  out_dev: n_pairs * max_b records (8-byte aligned); n_breaks_out_dev: n_pairs
+ * int32.  FFS_E_INVALID / FFS_E_EMPTY as ffs_align_split_batch (no limit from the plan's sizes), and FFS_E_INVALID for a
+ * radius outside [1, FFS_REFINE_MAX_RADIUS], a negative or infinite margin, or a null / misaligned output; all before
+ * any launch, the outputs untouched. */
+int ffs_split_refine_batch(ffs_split_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
+                           const double* ref_lo, const double* ref_hi, const void* const* sub_ptr, const int64_t* sub_len,
+                           const double* sub_lo, const double* sub_hi, int64_t block_samples,
+                           const int32_t* block_offset_dev, int64_t radius_samples, double unmatched_margin,
+                           ffs_break_refine* out_dev, int32_t* n_breaks_out_dev, void* hip_stream);
+
 /* Thread-local description of the last error returned on this thread ("" if none). */
 const char* ffs_last_error(void);
 
