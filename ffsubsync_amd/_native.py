@@ -110,6 +110,10 @@ EXPORTED_SYMBOLS = (
     "ffs_align_split_batch",
     "ffs_align_split_report_batch",
     "ffs_split_refine_batch",
+    "ffs_split_range_plan_create",
+    "ffs_split_range_plan_destroy",
+    "ffs_split_range_plan_workspace_bytes",
+    "ffs_align_split_range_batch",
     "ffs_quality_plan_create",
     "ffs_quality_plan_destroy",
     "ffs_quality_plan_workspace_bytes",
@@ -294,6 +298,17 @@ def load():
         lib.ffs_split_refine_batch.argtypes = [c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
                                                c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p,
                                                c.c_int64, c.c_double, c.c_void_p, c.c_void_p, c.c_void_p]
+        lib.ffs_split_range_plan_create.restype = c.c_int
+        lib.ffs_split_range_plan_create.argtypes = [c.c_int, c.c_int, c.c_int64, c.c_int64, c.c_int64,
+                                                    c.POINTER(c.c_void_p)]
+        lib.ffs_split_range_plan_destroy.restype = c.c_int
+        lib.ffs_split_range_plan_destroy.argtypes = [c.c_void_p]
+        lib.ffs_split_range_plan_workspace_bytes.restype = c.c_int64
+        lib.ffs_split_range_plan_workspace_bytes.argtypes = [c.c_void_p]
+        lib.ffs_align_split_range_batch.restype = c.c_int
+        lib.ffs_align_split_range_batch.argtypes = [c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                                                    c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p,
+                                                    c.c_void_p, c.c_double, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
         lib.ffs_quality_plan_create.restype = c.c_int
         lib.ffs_quality_plan_create.argtypes = [c.c_int, c.c_int, c.c_int64, c.c_int64, c.POINTER(c.c_void_p)]
         lib.ffs_quality_plan_destroy.restype = c.c_int
@@ -914,6 +929,65 @@ class SplitPlan:
     def close(self) -> None:
         if getattr(self, "handle", None):
             self.lib.ffs_split_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self) -> None:  # pragma: no cover - interpreter shutdown ordering
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SplitRangePlan:
+    """Owns one ``ffs_split_range_plan``: the workspace of the lag-range split aligner (``cut_align.py``) for
+    ``pairs_in_flight`` problems of up to ``max_samples`` samples per vector, ``max_blocks`` blocks and ``max_lags``
+    lags."""
+
+    def __init__(self, pairs_in_flight: int, max_blocks: int, max_lags: int, max_samples: int,
+                 device: Optional[int] = None) -> None:
+        torch = require_gpu()
+        self.lib = load()
+        self.device = torch.cuda.current_device() if device is None else int(device)
+        self.pairs_in_flight, self.max_blocks = int(pairs_in_flight), int(max_blocks)
+        self.max_lags, self.max_samples = int(max_lags), int(max_samples)
+        handle = ctypes.c_void_p()
+        check(self.lib.ffs_split_range_plan_create(self.device, self.pairs_in_flight, self.max_blocks, self.max_lags,
+                                                   self.max_samples, ctypes.byref(handle)))
+        self.handle = handle
+
+    @property
+    def workspace_bytes(self) -> int:
+        return int(self.lib.ffs_split_range_plan_workspace_bytes(self.handle))
+
+    def fits(self, pairs_in_flight: int, max_blocks: int, max_lags: int, max_samples: int) -> bool:
+        return (self.pairs_in_flight >= pairs_in_flight and self.max_blocks >= max_blocks and self.max_lags >= max_lags
+                and self.max_samples >= max_samples)
+
+    def align(self, ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, block_samples: int, lag_lo,
+              lag_hi, split_penalty: float, offsets_out, scores_out, totals_out, stream: Optional[int] = None) -> None:
+        """``ffs_align_split_range_batch`` on host descriptor arrays (one entry per pair, ``lag_lo`` / ``lag_hi``
+        included) into int32 / float64 / float64 CUDA tensors of n_pairs * max_b, n_pairs * max_b and n_pairs entries
+        (asynchronous)."""
+        torch = require_gpu()
+        u64 = lambda a: np.ascontiguousarray(a, dtype=np.uint64)
+        i64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        rp, rl, rlo, rhi = u64(ref_ptr), i64(ref_len), f64(ref_lo), f64(ref_hi)
+        sp, sl, slo, shi = u64(sub_ptr), i64(sub_len), f64(sub_lo), f64(sub_hi)
+        llo, lhi = i64(lag_lo), i64(lag_hi)
+        n = rp.size
+        if not all(a.size == n for a in (rl, rlo, rhi, sp, sl, slo, shi, llo, lhi)):
+            raise ValueError("one descriptor entry per pair")
+        st = current_stream_ptr(torch) if stream is None else stream
+        check(self.lib.ffs_align_split_range_batch(self.handle, n, rp.ctypes.data, rl.ctypes.data, rlo.ctypes.data,
+                                                   rhi.ctypes.data, sp.ctypes.data, sl.ctypes.data, slo.ctypes.data,
+                                                   shi.ctypes.data, int(block_samples), llo.ctypes.data, lhi.ctypes.data,
+                                                   float(split_penalty), offsets_out.data_ptr(), scores_out.data_ptr(),
+                                                   totals_out.data_ptr(), st))
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            self.lib.ffs_split_range_plan_destroy(self.handle)
             self.handle = None
 
     def __del__(self) -> None:  # pragma: no cover - interpreter shutdown ordering

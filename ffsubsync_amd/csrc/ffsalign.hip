@@ -29,6 +29,7 @@
 #include "ffs_quality.h"
 #include "ffs_split_report.h"
 #include "ffs_split_refine.h"
+#include "ffs_split_range.h"
 
 using namespace ffsa;
 
@@ -1001,7 +1002,7 @@ void fill_xform(XformDesc* x, const VecView* a, const VecView* b, const void* sa
 extern "C" {
 
 const char* ffs_last_error(void) { return g_err.c_str(); }
-int ffs_version(void) { return 340; }
+int ffs_version(void) { return 350; }
 
 int64_t ffs_fft_length(int64_t ref_len, int64_t sub_len) {
     if (ref_len <= 0 || sub_len <= 0) return 0;
@@ -3247,6 +3248,194 @@ int ffs_split_refine_batch(ffs_split_plan* plan, int n_pairs, const void* const*
                                st, plan->refine_desc, n_slots, max_b, single, (const int32_t*)n_breaks_out_dev,
                                (ffsa::BreakRefine*)out_dev);
         }
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(plan->done, st));
+    return FFS_OK;
+}
+
+/* ---- split-aware alignment over a lag range (csrc/ffs_split_range.h) ------------------------------------------- */
+
+struct ffs_split_range_plan {
+    int device;
+    int pairs_in_flight;
+    int64_t max_blocks, max_lags, max_samples;
+    int64_t pw;                 // prefix words per vector
+    void* work;
+    int64_t work_bytes;
+    ffsa::RangeWs ws;
+    int32_t* pre;               // [slot][2 * pw]: s, then r
+    void* dev_desc;             // SplitDesc[pairs_in_flight], then RangeLag[pairs_in_flight]
+    void* host_desc;            // pinned staging of the same
+    hipEvent_t desc_free;       // the last descriptor upload has left the staging buffer
+    hipEvent_t done;            // the plan's last call has finished with the workspace
+};
+
+int ffs_split_range_plan_create(int device, int pairs_in_flight, int64_t max_blocks, int64_t max_lags, int64_t max_samples,
+                                ffs_split_range_plan** out) {
+    if (!out) return fail(FFS_E_INVALID, "null output handle");
+    *out = nullptr;
+    if (pairs_in_flight < 1 || pairs_in_flight > 65535 || max_blocks < 1 || max_lags < 1 || max_lags > INT32_MAX ||
+        max_samples < 1 || max_samples > INT32_MAX / 2)
+        return fail(FFS_E_INVALID, "split range plan: need 1 <= pairs_in_flight <= 65535, max_blocks >= 1, "
+                                   "1 <= max_lags <= 2^31 - 1, 1 <= max_samples <= 2^30 - 1");
+    HIP_TRY(hipSetDevice(device));
+    ffs_split_range_plan* p = new (std::nothrow) ffs_split_range_plan();
+    if (!p) return fail(FFS_E_NOMEM, "split range plan");
+    p->device = device;
+    p->pairs_in_flight = pairs_in_flight;
+    p->max_blocks = max_blocks;
+    p->max_lags = max_lags;
+    p->max_samples = max_samples;
+    p->pw = max_samples / 32 + 2;
+    const int64_t stay_row = (max_lags + 63) / 64;
+    const int64_t part_row = split_align_up((max_lags + ffsa::RANGE_TILE - 1) / ffsa::RANGE_TILE, 32);
+    const int64_t stay_slot = split_align_up(max_blocks * stay_row, 32);   // uint64
+    const int64_t v_slot = split_align_up(stay_row * 64, 32);             // double
+    const int64_t arg_slot = split_align_up(max_blocks, 64);               // int32
+    const int64_t pre_slot = split_align_up(2 * p->pw, 64);                // int32
+    const int64_t n = pairs_in_flight;
+    const int64_t b_stay = n * stay_slot * 8, b_v = n * v_slot * 8, b_pv = n * 2 * part_row * 8, b_pj = n * 2 * part_row * 4,
+                  b_arg = n * arg_slot * 4, b_pre = n * pre_slot * 4;
+    p->work_bytes = b_stay + b_v + b_pv + b_pj + b_arg + b_pre;
+    if (hipMalloc(&p->work, p->work_bytes) != hipSuccess) {
+        delete p;
+        return fail(FFS_E_NOMEM, "split range plan: %lld workspace bytes", (long long)(b_stay + b_v + b_pv + b_pj + b_arg + b_pre));
+    }
+    char* w = (char*)p->work;
+    p->ws.stay = (unsigned long long*)w;
+    p->ws.V = (double*)(w + b_stay);
+    p->ws.pv = (double*)(w + b_stay + b_v);
+    p->ws.pj = (int32_t*)(w + b_stay + b_v + b_pv);
+    p->ws.arg = (int32_t*)(w + b_stay + b_v + b_pv + b_pj);
+    p->pre = (int32_t*)(w + b_stay + b_v + b_pv + b_pj + b_arg);
+    p->ws.stay_row = stay_row;
+    p->ws.stay_slot = stay_slot;
+    p->ws.v_slot = v_slot;
+    p->ws.part_row = part_row;
+    p->ws.arg_slot = arg_slot;
+    const size_t desc_bytes = (sizeof(ffsa::SplitDesc) + sizeof(ffsa::RangeLag)) * (size_t)pairs_in_flight;
+    if (hipMalloc(&p->dev_desc, desc_bytes) != hipSuccess ||
+        hipHostMalloc(&p->host_desc, desc_bytes, hipHostMallocDefault) != hipSuccess ||
+        hipEventCreateWithFlags(&p->desc_free, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&p->done, hipEventDisableTiming) != hipSuccess) {
+        ffs_split_range_plan_destroy(p);
+        return fail(FFS_E_HIP, "split range plan: descriptor buffers / events");
+    }
+    *out = p;
+    return FFS_OK;
+}
+
+int ffs_split_range_plan_destroy(ffs_split_range_plan* plan) {
+    if (!plan) return FFS_OK;
+    (void)hipSetDevice(plan->device);
+    if (plan->done) {
+        (void)hipEventSynchronize(plan->done);
+        (void)hipEventDestroy(plan->done);
+    }
+    if (plan->desc_free) (void)hipEventDestroy(plan->desc_free);
+    if (plan->host_desc) (void)hipHostFree(plan->host_desc);
+    if (plan->dev_desc) (void)hipFree(plan->dev_desc);
+    if (plan->work) (void)hipFree(plan->work);
+    delete plan;
+    return FFS_OK;
+}
+
+int64_t ffs_split_range_plan_workspace_bytes(const ffs_split_range_plan* plan) { return plan ? plan->work_bytes : 0; }
+
+int ffs_align_split_range_batch(ffs_split_range_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
+                                const double* ref_lo, const double* ref_hi, const void* const* sub_ptr,
+                                const int64_t* sub_len, const double* sub_lo, const double* sub_hi, int64_t block_samples,
+                                const int64_t* lag_lo, const int64_t* lag_hi, double split_penalty,
+                                int32_t* block_offset_out_dev, double* block_score_out_dev, double* total_out_dev,
+                                void* hip_stream) {
+#pragma clang fp contract(off)
+    if (!plan) return fail(FFS_E_INVALID, "null split range plan");
+    if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
+    if (n_pairs == 0) return FFS_OK;
+    if (!ref_ptr || !ref_len || !ref_lo || !ref_hi || !sub_ptr || !sub_len || !sub_lo || !sub_hi || !lag_lo || !lag_hi ||
+        !block_offset_out_dev || !block_score_out_dev || !total_out_dev)
+        return fail(FFS_E_INVALID, "null argument");
+    if (((uintptr_t)block_offset_out_dev & 3) || ((uintptr_t)block_score_out_dev & 7) || ((uintptr_t)total_out_dev & 7))
+        return fail(FFS_E_INVALID, "misaligned outputs");
+    const int64_t K = block_samples;
+    if (K < 256 || K > ffsa::SPLIT_MAX_K || K % 32 != 0)
+        return fail(FFS_E_INVALID, "block_samples=%lld: need a multiple of 32 in [256, 32768]", (long long)K);
+    if (!(split_penalty >= 0.0)) return fail(FFS_E_INVALID, "split_penalty must be >= 0 (not NaN)");
+    int64_t max_b = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+        if (ref_len[p] <= 0 || sub_len[p] <= 0)
+            return fail(FFS_E_EMPTY, "cannot align empty speech data (reference length=%lld, subtitle length=%lld)",
+                        (long long)(ref_len[p] > 0 ? ref_len[p] : 0), (long long)(sub_len[p] > 0 ? sub_len[p] : 0));
+        if (!ref_ptr[p] || !sub_ptr[p] || ((uintptr_t)ref_ptr[p] & 3) || ((uintptr_t)sub_ptr[p] & 3))
+            return fail(FFS_E_INVALID, "pair %d: null or misaligned vector", p);
+        if (sub_len[p] > plan->max_samples || ref_len[p] > plan->max_samples)
+            return fail(FFS_E_INVALID, "pair %d: vector lengths %lld / %lld exceed the plan's max_samples %lld", p,
+                        (long long)ref_len[p], (long long)sub_len[p], (long long)plan->max_samples);
+        const int64_t B = (sub_len[p] + K - 1) / K;
+        if (B > plan->max_blocks)
+            return fail(FFS_E_INVALID, "pair %d: %lld blocks exceed the plan's max_blocks %lld", p, (long long)B,
+                        (long long)plan->max_blocks);
+        if (lag_lo[p] > lag_hi[p] || lag_lo[p] < -(int64_t)INT32_MAX || lag_hi[p] > INT32_MAX)
+            return fail(FFS_E_INVALID, "pair %d: lag range [%lld, %lld]: need -(2^31 - 1) <= lag_lo <= lag_hi <= 2^31 - 1", p,
+                        (long long)lag_lo[p], (long long)lag_hi[p]);
+        if (lag_hi[p] - lag_lo[p] + 1 > plan->max_lags)
+            return fail(FFS_E_INVALID, "pair %d: %lld lags exceed the plan's max_lags %lld", p,
+                        (long long)(lag_hi[p] - lag_lo[p] + 1), (long long)plan->max_lags);
+        if (!(std::isfinite(ref_lo[p]) && std::isfinite(ref_hi[p]) && std::isfinite(sub_lo[p]) && std::isfinite(sub_hi[p])))
+            return fail(FFS_E_INVALID, "pair %d: levels must be finite", p);
+        if (B > max_b) max_b = B;
+    }
+    HIP_TRY(hipSetDevice(plan->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    HIP_TRY(hipStreamWaitEvent(st, plan->done, 0));  // the previous call (any stream) is done with the workspace
+    const int64_t pre_slot = split_align_up(2 * plan->pw, 64);
+    const int pif = plan->pairs_in_flight;
+    ffsa::SplitDesc* hd = (ffsa::SplitDesc*)plan->host_desc;
+    ffsa::RangeLag* hl = (ffsa::RangeLag*)(hd + pif);
+    const ffsa::SplitDesc* dd = (const ffsa::SplitDesc*)plan->dev_desc;
+    const ffsa::RangeLag* dl = (const ffsa::RangeLag*)(dd + pif);
+    for (int p0 = 0; p0 < n_pairs; p0 += pif) {
+        const int np = std::min(pif, n_pairs - p0);
+        HIP_TRY(hipEventSynchronize(plan->desc_free));  // the staging buffer's previous upload has been consumed
+        int64_t chunk_b = 0, max_tiles = 0;
+        for (int i = 0; i < np; ++i) {
+            const int p = p0 + i;
+            ffsa::SplitDesc& d = hd[i];
+            d.r = (const uint32_t*)ref_ptr[p];
+            d.s = (const uint32_t*)sub_ptr[p];
+            d.R = ref_len[p];
+            d.S = sub_len[p];
+            const double s0 = 2.0 * sub_lo[p] - 1.0, s1 = 2.0 * sub_hi[p] - 1.0;  // as split_batch
+            const double r0 = 2.0 * ref_lo[p] - 1.0, r1 = 2.0 * ref_hi[p] - 1.0;
+            d.c00 = s0 * r0;
+            d.c01 = s0 * r1;
+            d.c10 = s1 * r0;
+            d.c11 = s1 * r1;
+            d.pre_s = plan->pre + (int64_t)i * pre_slot;
+            d.pre_r = d.pre_s + plan->pw;
+            d.out_row = p;
+            hl[i].lag_lo = lag_lo[p];
+            hl[i].L = lag_hi[p] - lag_lo[p] + 1;
+            chunk_b = std::max(chunk_b, (d.S + K - 1) / K);
+            max_tiles = std::max(max_tiles, (hl[i].L + ffsa::RANGE_TILE - 1) / ffsa::RANGE_TILE);
+        }
+        // one upload of both arrays (the RangeLag half is at a fixed offset: copy the whole used span)
+        HIP_TRY(hipMemcpyAsync(plan->dev_desc, plan->host_desc, sizeof(ffsa::SplitDesc) * pif + sizeof(ffsa::RangeLag) * np,
+                               hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(plan->desc_free, st));
+        // prefixes over every sample of both vectors (W = max_samples: min(R, S + W) = R)
+        hipLaunchKernelGGL(ffsa::k_split_prefix, dim3(2 * np), dim3(ffsa::SPLIT_PREFIX_THREADS), 0, st, dd,
+                           (int64_t)plan->max_samples);
+        for (int64_t b = 0; b < chunk_b; ++b)
+            hipLaunchKernelGGL(ffsa::k_range_step, dim3((unsigned)max_tiles, (unsigned)np), dim3(ffsa::RANGE_THREADS), 0, st,
+                               dd, dl, plan->ws, (int)K, b, split_penalty);
+        hipLaunchKernelGGL(ffsa::k_range_backtrack, dim3(np), dim3(ffsa::RANGE_THREADS), 0, st, dd, dl, plan->ws, (int)K,
+                           max_b, block_offset_out_dev, total_out_dev);
+        constexpr int waves = ffsa::RANGE_SCORE_THREADS / 64;
+        hipLaunchKernelGGL(ffsa::k_range_scores, dim3((unsigned)((max_b + waves - 1) / waves), (unsigned)np),
+                           dim3(ffsa::RANGE_SCORE_THREADS), 0, st, dd, dl, (int)K, max_b, block_offset_out_dev,
+                           block_score_out_dev);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(plan->done, st));

@@ -572,6 +572,36 @@ int ffs_split_refine_batch(ffs_split_plan* plan, int n_pairs, const void* const*
                            const int32_t* block_offset_dev, int64_t radius_samples, double unmatched_margin,
                            ffs_break_refine* out_dev, int32_t* n_breaks_out_dev, void* hip_stream);
 
+/* ---- split-aware alignment over any lag range: subtitles for another cut of the video (csrc/ffs_split_range.h) -----
+ * Replaces: nothing in the reference.  The contract below is pinned against the numpy model tests/cut_model.py.
+ *
+ * ffs_align_split_batch's contract (block counts with absent samples, the no-FMA fp64 score, the DP, its tie rules and
+ * backtrack, the output layout) with the lag set d in [lag_lo_p, lag_hi_p] per pair instead of [-W+1, W]: any
+ * lag_lo <= lag_hi inside the int32 range, not clipped to the overlap range [-(S-1), R-1]; lags without overlap score 0.
+ * At [-W+1, W] the records are bit-identical to ffs_align_split_batch's.
+ *
+ * One lag row is spread over many workgroups: one launch per block step covers every pair in flight, and block counts
+ * are computed inside the step, never stored.  A plan owns the workspace for pairs_in_flight (<= 65535) problems with up
+ * to max_samples samples in EITHER vector (<= 2^30 - 1), max_blocks blocks and max_lags lags (<= 2^31 - 1): per pair
+ * one stay bit per (block, lag) (127 MB at 2 h against 2 h over the full range, K = 1024), one fp64 row of max_lags,
+ * the word prefixes of both vectors and a few bytes per 2048 lags.  A plan serves one host thread at a time; successive
+ * calls (any streams) are ordered by the library. */
+typedef struct ffs_split_range_plan ffs_split_range_plan;
+int ffs_split_range_plan_create(int device, int pairs_in_flight, int64_t max_blocks, int64_t max_lags, int64_t max_samples,
+                                ffs_split_range_plan** out);
+int ffs_split_range_plan_destroy(ffs_split_range_plan* plan);
+int64_t ffs_split_range_plan_workspace_bytes(const ffs_split_range_plan* plan);
+/* ffs_align_split_batch with host arrays lag_lo / lag_hi (n_pairs entries) in place of max_offset_samples; the same
+ * outputs (block_offset_out_dev[p * max_b + b] = o_b as an int32 lag).  FFS_E_INVALID / FFS_E_EMPTY for the arguments
+ * ffs_align_split_batch refuses, a range with lag_lo > lag_hi, outside the int32 range or wider than max_lags, or a
+ * vector longer than max_samples; all before any launch, the outputs untouched. */
+int ffs_align_split_range_batch(ffs_split_range_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
+                                const double* ref_lo, const double* ref_hi, const void* const* sub_ptr,
+                                const int64_t* sub_len, const double* sub_lo, const double* sub_hi, int64_t block_samples,
+                                const int64_t* lag_lo, const int64_t* lag_hi, double split_penalty,
+                                int32_t* block_offset_out_dev, double* block_score_out_dev, double* total_out_dev,
+                                void* hip_stream);
+
 /* Thread-local description of the last error returned on this thread ("" if none). */
 const char* ffs_last_error(void);
 
