@@ -3,7 +3,7 @@
 activity vectors (BASELINE.json metric; workload = configs[2]: batches of 1024 pairs x 7 framerate
 ratios, max_offset_samples = 6000, reference transform length N = 2^21).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path (ffs_align_batch: pass A -> mid -> pass C -> nominees -> exact
 re-evaluation -> max over ratios) over this rank's pairs -- by default eight 1024-pair batches
@@ -12,9 +12,14 @@ resident in HBM (bit-packed, FFS_DTYPE_U1), plus the RCCL all-gather of the 24-b
 N > 1.  Pairs are sharded by rank, no data exchange during solves.  `--scaling weak` (default): every
 rank owns --pairs problems; `--scaling strong`: the same --pairs problems are split over the ranks
 (BASELINE configs[3]).  With --gpus N > 1 and no launcher in the environment the script starts itself
-under torch.distributed.run (one process per GPU).  Rank 0 prints the full record on a `# detail:` line (and writes
-bench_detail.json), then -- LAST -- one compact JSON line below 4 KB: the bench contract's fields, `roofline`,
-`cpu_baseline` and the scalars of the secondary legs (the driver parses the last line of an 8 KB tail).
+under torch.distributed.run (one process per GPU).
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the headline.  `--full` adds
+everything else the benchmark measures and checks, after the same timed steps: per-kernel tables and rooflines, the
+reference's goldens and the generator's ground truth, configs[3] scaling, the other paths, input formats and lag
+windows, the CPU baselines, the VAD and end-to-end figures.  Rank 0 prints the full record on a `# detail:` line (and
+writes bench_detail.json), then -- LAST -- one compact JSON line below 4 KB: the bench contract's fields, `roofline`,
+`cpu_baseline` and the scalars of the secondary legs (a reader of the output may keep only an 8 KB tail).
 """
 import argparse
 import json
@@ -45,16 +50,21 @@ def parse():
                          "above 1 the per-kernel table and the roofline record are omitted (concurrent kernels share the chip)")
     ap.add_argument("--input-format", choices=("bits", "bytes"), default="bits",
                     help="bits = FFS_DTYPE_U1 (native), bytes = FFS_DTYPE_U8")
-    ap.add_argument("--cpu-pairs", type=int, default=16, help="pairs timed on the CPU oracle (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, measure and check everything beyond the headline (per-kernel tables, "
+                         "rooflines, goldens, scaling, secondary legs, CPU baselines, VAD, end to end); a plain run only "
+                         "sets up, warms up, times the steps, dumps and prints the line")
+    ap.add_argument("--cpu-pairs", type=int, default=16, help="with --full: pairs timed on the CPU oracle (0 = skip)")
     ap.add_argument("--algorithm", choices=("auto", "fft", "runs"), default="auto",
                     help="auto (library default): run-boundary path for bit-packed vectors with short boundary lists, "
                          "transforms otherwise; fft: transforms only; runs: run-boundary path without the budget")
-    ap.add_argument("--no-profile", action="store_true", help="skip per-kernel HIP-event timing")
-    ap.add_argument("--no-vad", action="store_true", help="skip the VAD frame-energy sweep figures")
+    ap.add_argument("--no-profile", action="store_true",
+                    help="skip per-kernel HIP-event timing (recorded in the timed steps of every run, read with --full)")
+    ap.add_argument("--no-vad", action="store_true", help="with --full: skip the VAD frame-energy sweep figures")
     ap.add_argument("--e2e-files", type=int, default=32,
-                    help="files in the end-to-end PCM -> VAD -> rasterise -> align figure (0 = skip)")
+                    help="with --full: files in the end-to-end PCM -> VAD -> rasterise -> align figure (0 = skip)")
     ap.add_argument("--skip-secondary", action="store_true",
-                    help="headline measurement only (used by the rocprofv3 / PMC runs)")
+                    help="with --full: the headline's own tables and checks only (used by the rocprofv3 runs)")
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl",
                     help="torch.distributed backend for N > 1.  nccl (= RCCL, the default): one rank per GPU.  gloo: the "
                          "ranks may share GPUs (rank r runs on device r mod device_count) and the 24-byte records are "
@@ -95,6 +105,8 @@ def compact_record(result, detail_path=None):
     cfg = result.get("config", {})
     out = {k: _num(result.get(k)) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
                                             "higher_is_better", "scaling", "vs_baseline", "dtype", "data")}
+    if "full" in result:
+        out["full"] = result["full"]
     if "error" in result:
         out["error"] = str(result["error"])[:300]
     out["config"] = {k: cfg.get(k) for k in ("workload", "algorithm", "path", "pairs_per_gpu", "pairs_in_flight", "n_fft_reference",
@@ -900,6 +912,8 @@ def main():
     cand_out = torch.empty(max(P, 1) * n_cand * 24, dtype=torch.uint8, device="cuda")
     pair_out = torch.zeros(per * 24, dtype=torch.uint8, device="cuda")
     gathered = torch.empty(world * per * 24, dtype=torch.uint8, device="cuda") if use_dist else None
+    # per-kernel HIP events are recorded in the timed steps of a plain run too, so that it times exactly the steps a
+    # --full run times; only --full reads them into the kernel tables and rooflines
     profile = not args.no_profile and args.streams == 1
     gather_impl = None
     comm = None
@@ -1061,35 +1075,36 @@ def main():
     head_info = dict(info_now)
     by_runs = head_info["path"] != "transforms"
 
-    # correctness of what was timed: every pair the reference-generated goldens cover (bench seeds 0..255,
-    # tests/golden/headline_golden.json = the UNMODIFIED reference's (ratio, offset, score)), plus the
-    # generator's ground truth for all pairs
     pres = pair_out.cpu().numpy().view(_native.PAIR_RESULT_DTYPE)[:P].copy()
     cres = cand_out.cpu().numpy().view(_native.CAND_RESULT_DTYPE)[: P * n_cand].reshape(P, n_cand).copy()
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, seeds, pres, cres)
-    golden = load_headline_golden() if args.duration == 7200.0 else {}
-    g_total = g_ok = 0
-    for i, s in enumerate(seeds):
-        g = golden.get(s)
-        if g is None:
-            continue
-        g_total += 1
-        sc = float(g["score"])
-        gaps = g.get("per_candidate_top2_gap", [0.0] * n_cand)
-        g_ok += int(int(pres[i]["best_cand"]) == g["index"] and int(pres[i]["offset"]) == g["offset"]
-                    and abs(float(pres[i]["score"]) - sc) <= 1e-5 * abs(sc)
-                    and all((int(cres[i, j]["offset"]) == off or gaps[j] <= 0.5)
-                            and abs(float(cres[i, j]["score"]) - float(csc)) <= 1e-5 * abs(float(csc))
-                            for j, (csc, off) in enumerate(g["per_candidate"])))
-    truth_ok = sum(
-        int(pres[i]["best_cand"] == sp.true_ratio_index and abs(int(pres[i]["offset"]) - sp.true_offset_samples) <= 30)
-        for i, sp in enumerate(specs)
-    )
-    ambiguous = int(((cres["flags"] & 2) != 0).sum())
-    # health of the fp32 transform chain itself (the exact re-evaluation would mask a damaged one as long
-    # as the true peak still gets nominated): fp32 value of every winning lag vs its exact score
-    fp32_err = float(np.abs(cres["score_f32"].astype(np.float64) - cres["score"]).max()) if P else 0.0
+    if args.full:
+        # correctness of what was timed: every pair the reference-generated goldens cover (bench seeds 0..255,
+        # tests/golden/headline_golden.json = the UNMODIFIED reference's (ratio, offset, score)), plus the
+        # generator's ground truth for all pairs
+        golden = load_headline_golden() if args.duration == 7200.0 else {}
+        g_total = g_ok = 0
+        for i, s in enumerate(seeds):
+            g = golden.get(s)
+            if g is None:
+                continue
+            g_total += 1
+            sc = float(g["score"])
+            gaps = g.get("per_candidate_top2_gap", [0.0] * n_cand)
+            g_ok += int(int(pres[i]["best_cand"]) == g["index"] and int(pres[i]["offset"]) == g["offset"]
+                        and abs(float(pres[i]["score"]) - sc) <= 1e-5 * abs(sc)
+                        and all((int(cres[i, j]["offset"]) == off or gaps[j] <= 0.5)
+                                and abs(float(cres[i, j]["score"]) - float(csc)) <= 1e-5 * abs(float(csc))
+                                for j, (csc, off) in enumerate(g["per_candidate"])))
+        truth_ok = sum(
+            int(pres[i]["best_cand"] == sp.true_ratio_index and abs(int(pres[i]["offset"]) - sp.true_offset_samples) <= 30)
+            for i, sp in enumerate(specs)
+        )
+        ambiguous = int(((cres["flags"] & 2) != 0).sum())
+        # health of the fp32 transform chain itself (the exact re-evaluation would mask a damaged one as long
+        # as the true peak still gets nominated): fp32 value of every winning lag vs its exact score
+        fp32_err = float(np.abs(cres["score_f32"].astype(np.float64) - cres["score"]).max()) if P else 0.0
 
     total_pairs = args.pairs if strong else world * args.pairs
     solves_per_s = total_pairs * args.steps / elapsed
@@ -1136,21 +1151,24 @@ def main():
             "ranks_seen": ranks_seen,  # [rank, device, host] of every rank, all-gathered
             "devices_used": len({(x[2], x[1]) for x in ranks_seen}) if use_dist else 1,
         },
-        "offset_match": {"pairs_matching_reference_golden": "%d/%d" % (g_ok, g_total),
-                         "golden": "tests/golden/headline_golden.json (unmodified reference, bench seeds 0..1023): winning index and "
-                                   "offset bit-identical, all 7 per-candidate scores within 1e-5, per-candidate offsets "
-                                   "bit-identical wherever the reference's own top-2 gap exceeds 0.5 (exact ties on the "
-                                   "plateaus of wrong-ratio candidates are decided by its fp64 rounding noise)",
-                         "pairs_matching_ground_truth": truth_ok, "pairs": P, "ambiguous_flags": ambiguous,
-                         "max_abs_fp32_error_at_winning_lags": fp32_err},
-        "normaliser": {
+        "full": bool(args.full),
+    }
+    if args.full:
+        result["offset_match"] = {
+            "pairs_matching_reference_golden": "%d/%d" % (g_ok, g_total),
+            "golden": "tests/golden/headline_golden.json (unmodified reference, bench seeds 0..1023): winning index and "
+                      "offset bit-identical, all 7 per-candidate scores within 1e-5, per-candidate offsets "
+                      "bit-identical wherever the reference's own top-2 gap exceeds 0.5 (exact ties on the "
+                      "plateaus of wrong-ratio candidates are decided by its fp64 rounding noise)",
+            "pairs_matching_ground_truth": truth_ok, "pairs": P, "ambiguous_flags": ambiguous,
+            "max_abs_fp32_error_at_winning_lags": fp32_err}
+        result["normaliser"] = {
             "what": "SURVEY 8(d): the reference's 168*N bytes per seven-ratio solve (N = 2^21) x solves/s -- measures "
                     "algorithmic saving, not HBM efficiency (the device moves fewer bytes: see roofline)",
             "bytes_per_solve": 168 * n_ref,
             "GBps": solves_per_s * 168 * n_ref / 1e9,
             "frac_of_8TBps_per_gpu": solves_per_s * 168 * n_ref / (HBM_PEAK * world),
-        },
-    }
+        }
 
     def roofline_of(per_kernel, pairs, steps, n_fft, seg_mode, cands=n_cand):
         """`roofline` object for the kernel that takes the most time among those that move bytes through HBM."""
@@ -1246,7 +1264,7 @@ def main():
             out["lds_conflict_frac"] = lj.get("lds_bank_conflict_per_pair", 0.0) / lj["lds_idx_active_per_pair"]
         return out
 
-    if profile and rank == 0:
+    if args.full and profile and rank == 0:
         per_kernel = kernel_table(ktimes, args.steps, n_dev, seg_mode)
         result["kernels"] = per_kernel
         hbm_roof = roofline_of(per_kernel, P, args.steps, n_dev, seg_mode)
@@ -1263,7 +1281,7 @@ def main():
     # (contiguous block, batch.shard_bounds) + the all-gather of the 24-byte records.  On one GPU it is the proxy the
     # 8-GPU run reduces to: one rank's share at world 8 (128 pairs per step), gathered through a one-rank RCCL
     # communicator -- what a rank of the sharded job does per step, launch overheads and sweep tails included.
-    if not args.skip_secondary and not strong and args.duration == 7200.0:
+    if args.full and not args.skip_secondary and not strong and args.duration == 7200.0:
         try:
             result["strong_scaling" if world > 1 else "strong_scaling_proxy"] = strong_leg(
                 torch, _native, batch, synth, args, rank, world, dist if use_dist else None, comm, host_coll, n_dev,
@@ -1273,7 +1291,7 @@ def main():
                 raise
             result["strong_scaling_proxy"] = {"error": repr(exc)[:300]}
 
-    secondary = rank == 0 and world == 1 and not args.skip_secondary
+    secondary = args.full and rank == 0 and world == 1 and not args.skip_secondary
     if secondary and by_runs:
         # The SAME pairs through the batched-FFT path (FFS_ALGO_FFT: what rounds 1-3 timed as the headline, and what the
         # library still runs for float / byte inputs and for vectors whose boundary lists are long): the north star's
@@ -1529,7 +1547,7 @@ def main():
         except Exception as exc:
             result["ingest_inclusive"] = {"error": repr(exc)[:300]}
 
-    if rank == 0 and world == 1 and args.cpu_pairs > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_pairs > 0:
         from oracle import aligners_oracle as orc
 
         # SURVEY 8(d) CPU baseline on this box's host cores.  /root/reference does not exist here, so the timed
@@ -1591,15 +1609,15 @@ def main():
         except Exception as exc:  # a baseline figure must never take the bench line down
             result["cpu_baseline"]["parallel"] = {"error": repr(exc)[:200]}
 
-    if rank == 0 and world == 1 and not args.no_vad and not args.skip_secondary:
+    if args.full and rank == 0 and world == 1 and not args.no_vad and not args.skip_secondary:
         result["vad"] = vad_figures(torch, _native)
-    if rank == 0 and world == 1 and args.e2e_files > 0 and not args.skip_secondary:
+    if args.full and rank == 0 and world == 1 and args.e2e_files > 0 and not args.skip_secondary:
         try:
             result["end_to_end"] = e2e_figures(torch, _native, args.e2e_files)
         except Exception as exc:  # e.g. not enough pinnable host memory on the box
             result["end_to_end"] = {"error": repr(exc)[:300]}
 
-    if use_dist:
+    if use_dist and args.full:
         # every rank's records arrived, in rank order
         mine = gathered[rank * per * 24:(rank + 1) * per * 24]
         assert bool(torch.equal(mine, pair_out)), "all-gathered records differ from the local ones"

@@ -7,7 +7,7 @@
 
 Inputs (TAG = r06): <TAG>_kernel_stats.csv / <TAG>_kernel_stats_fft.csv (rocprofv3 --kernel-trace --stats of the bench
 command), <TAG>_bench_under_rocprof[_fft].json (the lines those profiled runs printed: HIP-event averages),
-<TAG>_bench.json (the default run), <TAG>_secondary_kernels.json, <TAG>_gputest.log, lds_issue_rates.json.
+<TAG>_bench.json (the `--full` run), <TAG>_secondary_kernels.json, <TAG>_gputest.log, lds_issue_rates.json.
 tests/test_docs_tables.py fails when the blocks in the two documents differ from what this script generates, and when a
 kernel time of the profiled run differs from the CSV's by more than 2 %.
 """
@@ -110,7 +110,7 @@ def design_block(a):
     lds = a["lds"]
     row = lds["ds_add_u32_32_waves_per_cu"]
     L = []
-    L.append("**Round-6 numbers** (MI355X, one GPU, `python bench.py`: %d pairs x 7 ratios per step, inputs resident in HBM; every "
+    L.append("**Round-6 numbers** (MI355X, one GPU, `python bench.py --full`: %d pairs x 7 ratios per step, inputs resident in HBM; every "
              "figure below is read from `profiles/%s_*` by `profiles/make_tables.py` -- `tests/test_docs_tables.py` fails when this "
              "block and the artefacts disagree)." % (ppl, TAG))
     L.append("")

@@ -9,7 +9,7 @@ for m in "$@"; do
   lib=ffsubsync_amd/libffsalign_$m.so; [ $m = default ] && lib=ffsubsync_amd/libffsalign.so
   [ -f $lib ] || continue
   echo "build=$m"
-  FFS_LIBRARY_PATH=$PWD/$lib timeout 300 python bench.py --steps 6 --warmup 2 --cpu-pairs 0 --no-vad --e2e-files 0 2>/dev/null | python -c "
+  FFS_LIBRARY_PATH=$PWD/$lib timeout 300 python bench.py --full --steps 6 --warmup 2 --cpu-pairs 0 --no-vad --e2e-files 0 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 us=lambda k:{n:round(v['us_per_pair'],2) for n,v in k.items()}

@@ -3,7 +3,7 @@
 #   GPU tests + smoke; PMC passes at the TIMED launch shape (512 pairs per launch) of the run-boundary kernels (default
 #   algorithm) and of the transform kernels (--algorithm fft; default plan + --reference-length); traffic_per_pair.json;
 #   rocprofv3 kernel trace of the bench command; rocprofv3 trace + PMC of the secondary kernels (VAD sweep, tokenizer,
-#   rasteriser, windowless / reference-length transforms); last the default bench line (reads the fresh traffic file).
+#   rasteriser, windowless / reference-length transforms); last the full bench line (`--full`: reads the fresh traffic file).
 #   rocprofv3 kernel trace of the transform path at the timed shape (bench.py --algorithm fft: <TAG>_kernel_stats_fft.csv);
 #   TAG=r05 bash profiles/refresh_all.sh
 set -u
@@ -47,5 +47,5 @@ python profiles/summarize_secondary.py "$S/trace" "$S/driver.json" "$S/pmc" > "$
 find "$S/trace" -name "*kernel_stats.csv" -exec cp {} "$O/${TAG}_secondary_kernel_stats.csv" \;
 rm -rf "$O"/pmc_*/*/*/*.db "$S"/trace/*/*.db "$S"/pmc/*/*/*.db gpurun_out/trace_$TAG/*/*.db 2>/dev/null
 rm -rf "$O"/pmc_runs "$O"/pmc_fft "$O"/pmc_ref "$S"/pmc "$S"/trace
-python bench.py > "$O/${TAG}_bench.json" 2> "$O/bench.err"; tail -c 400 "$O/${TAG}_bench.json"
+python bench.py --full > "$O/${TAG}_bench.json" 2> "$O/bench.err"; tail -c 400 "$O/${TAG}_bench.json"
 du -sh "$O"

@@ -89,7 +89,7 @@ def test_bench_dumps_what_its_timed_steps_computed(tmp_path):
     n = 64
     out = str(tmp_path / "dump")
     run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--pairs", str(n), "--steps", "3", "--warmup", "1",
-                          "--pairs-in-flight", "64", "--algorithm", "auto", "--skip-secondary", "--cpu-pairs", "0",
+                          "--pairs-in-flight", "64", "--algorithm", "auto", "--full", "--skip-secondary", "--cpu-pairs", "0",
                           "--dump-outputs", out], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-3000:])
     line = json.loads(run.stdout.strip().splitlines()[-1])
@@ -105,3 +105,33 @@ def test_bench_dumps_what_its_timed_steps_computed(tmp_path):
         assert np.array_equal(got["pair_" + f], pres[f].astype(np.float64)), f
     for f in cres.dtype.names:
         assert np.array_equal(got["cand_" + f], cres[f].astype(got["cand_" + f].dtype)), f
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_only_and_dumps_what_a_full_run_dumps(tmp_path):
+    """bench.py without --full: the same timed steps on the same pairs as a --full run -- identical dumped records, the
+    headline fields of the line -- and none of the legs, tables or checks that --full adds."""
+    import torch
+
+    assert torch.cuda.is_available()
+    n = 64
+    lines, dumps = {}, {}
+    for mode in ("plain", "full"):
+        out = str(tmp_path / mode)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--pairs", str(n), "--steps", "3", "--warmup", "1",
+               "--pairs-in-flight", "64", "--dump-outputs", out] + (["--full", "--skip-secondary", "--cpu-pairs", "0"]
+                                                                      if mode == "full" else [])
+        run = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert run.returncode == 0, (mode, run.stdout[-2000:], run.stderr[-3000:])
+        lines[mode] = json.loads(run.stdout.strip().splitlines()[-1])
+        dumps[mode] = _load(out)
+    plain, full = lines["plain"], lines["full"]
+    assert plain["full"] is False and full["full"] is True
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "n_gpus", "scaling"):
+        assert plain[k] == full[k], k
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["config"] == full["config"]
+    assert plain["offset_match"] == {} and plain["roofline"] is None and "kernels_us_per_pair" not in plain
+    assert "cpu_baseline" not in plain and plain["detail"] == {}
+    assert full["offset_match"]["pairs_matching_reference_golden"] == "%d/%d" % (n, n) and full["roofline"] is not None
+    a, b = dumps["plain"], dumps["full"]
+    assert set(a) == set(b) and all(np.array_equal(a[k], b[k]) for k in a)

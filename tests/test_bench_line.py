@@ -61,3 +61,19 @@ def test_emit_ends_with_the_compact_line(tmp_path, monkeypatch):
     assert len(last) < 4096 and len("\n".join(out)[-8192:].split("\n")[-1]) == len(last)
     assert json.loads(last)["detail_file"] == "bench_detail.json"
     assert json.loads(open(tmp_path / "bench_detail.json").read())["value"] == _full_record()["value"]
+
+
+def test_compact_line_of_a_plain_run():
+    """A run without --full has the headline fields and its config only: the line still carries the contract's headline
+    fields, says that it is a plain run, and leaves the legs --full adds empty."""
+    full = _full_record()
+    plain = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
+                                  "scaling", "vs_baseline", "dtype", "data", "config")}
+    plain["full"] = False
+    rec = json.loads(bench.compact_record(plain, "bench_detail.json"))
+    for k in ("metric", "value", "unit", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype"):
+        assert rec[k] == bench._num(full[k]), k
+    assert rec["config"]["pairs_per_gpu"] == full["config"]["pairs_per_gpu"]
+    assert rec["full"] is False and rec["roofline"] is None and rec["offset_match"] == {} and rec["detail"] == {}
+    assert "cpu_baseline" not in rec and "kernels_us_per_pair" not in rec
+    assert "full" not in json.loads(bench.compact_record(full))  # records written before the option say nothing

@@ -133,7 +133,7 @@ def test_bench_main_with_two_ranks_on_one_gpu_and_loud_failure_without_devices(t
     import json
 
     run = _launch(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--pairs", "32", "--steps", "2",
-                      "--warmup", "1", "--pairs-in-flight", "32", "--skip-secondary", "--cpu-pairs", "0"])
+                      "--warmup", "1", "--pairs-in-flight", "32", "--full", "--skip-secondary", "--cpu-pairs", "0"])
     assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-3000:])
     line = json.loads(run.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["value"] > 0 and line["scaling"] == "weak"
@@ -142,7 +142,7 @@ def test_bench_main_with_two_ranks_on_one_gpu_and_loud_failure_without_devices(t
     assert line["offset_match"]["pairs_matching_reference_golden"] == "32/32"  # rank 0's pairs, seeds 0..31
     for scaling in ("strong",):
         run = _launch(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--pairs", "33", "--steps", "1",
-                          "--warmup", "1", "--pairs-in-flight", "32", "--skip-secondary", "--cpu-pairs", "0",
+                          "--warmup", "1", "--pairs-in-flight", "32", "--full", "--skip-secondary", "--cpu-pairs", "0",
                           "--scaling", scaling])
         assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-3000:])
         line = json.loads(run.stdout.strip().splitlines()[-1])
@@ -169,7 +169,7 @@ def test_rccl_world_greater_than_one_when_several_devices_are_visible(torch):
     n = min(n_dev, 8)
     for scaling, pairs in (("weak", 64), ("strong", 64 * n + 1)):
         run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--pairs", str(pairs), "--steps", "2",
-                              "--warmup", "1", "--pairs-in-flight", "64", "--skip-secondary", "--cpu-pairs", "0", "--scaling", scaling],
+                              "--warmup", "1", "--pairs-in-flight", "64", "--full", "--skip-secondary", "--cpu-pairs", "0", "--scaling", scaling],
                              cwd=ROOT, capture_output=True, text=True, timeout=900)
         assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-3000:])
         line = json.loads(run.stdout.strip().splitlines()[-1])
