@@ -832,75 +832,93 @@ def scatter_segments(labels, src_off, dst_start, seg_len, out_len: int):
     return out
 
 
-class SplitPlan:
-    """Owns one ``ffs_split_plan``: the workspace of the split-aware aligner (``split_align.py``) for
-    ``pairs_in_flight`` problems of up to ``max_samples`` subtitle samples, ``max_blocks`` blocks and ``max_lags`` = 2W
-    lags."""
+def _pair_buffers(ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, *extra):
+    """The per-pair host arrays of a side-plan batch call as contiguous buffers: uint64 pointers, int64 lengths, float64
+    levels, then ``extra`` int64 arrays.  Returns (n_pairs, their addresses, the buffers); keep the buffers alive over
+    the call."""
+    kinds = (np.uint64, np.int64, np.float64, np.float64) * 2 + (np.int64,) * len(extra)
+    bufs = [np.ascontiguousarray(a, dtype=t)
+            for a, t in zip((ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi) + extra, kinds)]
+    n = bufs[0].size
+    if not all(b.size == n for b in bufs):
+        raise ValueError("one descriptor entry per pair")
+    return n, [b.ctypes.data for b in bufs], bufs
 
-    def __init__(self, pairs_in_flight: int, max_blocks: int, max_lags: int, max_samples: int,
-                 device: Optional[int] = None) -> None:
+
+class _SidePlan:
+    """Handle lifetime of the plans beside the headline aligner.  A subclass names its C entry points (``_create``,
+    ``_destroy``, ``_workspace``) and passes its size limits in the order ``_create`` takes them; ``fits`` takes the
+    same limits in the same order."""
+
+    _create = _destroy = _workspace = ""
+
+    def __init__(self, dims, device: Optional[int]) -> None:
         torch = require_gpu()
         self.lib = load()
         self.device = torch.cuda.current_device() if device is None else int(device)
-        self.pairs_in_flight, self.max_blocks = int(pairs_in_flight), int(max_blocks)
-        self.max_lags, self.max_samples = int(max_lags), int(max_samples)
+        self._dims = tuple(int(d) for d in dims)
         handle = ctypes.c_void_p()
-        check(self.lib.ffs_split_plan_create(self.device, self.pairs_in_flight, self.max_blocks, self.max_lags,
-                                             self.max_samples, ctypes.byref(handle)))
+        check(getattr(self.lib, self._create)(self.device, *self._dims, ctypes.byref(handle)))
         self.handle = handle
 
     @property
     def workspace_bytes(self) -> int:
-        return int(self.lib.ffs_split_plan_workspace_bytes(self.handle))
+        return int(getattr(self.lib, self._workspace)(self.handle))
 
-    def fits(self, pairs_in_flight: int, max_blocks: int, max_lags: int, max_samples: int) -> bool:
-        return (self.pairs_in_flight >= pairs_in_flight and self.max_blocks >= max_blocks and self.max_lags >= max_lags
-                and self.max_samples >= max_samples)
+    def fits(self, *dims) -> bool:
+        return all(have >= want for have, want in zip(self._dims, dims))
+
+    @staticmethod
+    def _stream(stream: Optional[int]):
+        return current_stream_ptr(require_gpu()) if stream is None else stream
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            getattr(self.lib, self._destroy)(self.handle)
+            self.handle = None
+
+    def __del__(self) -> None:  # pragma: no cover - interpreter shutdown ordering
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SplitPlan(_SidePlan):
+    """Owns one ``ffs_split_plan``: the workspace of the split-aware aligner (``split_align.py``) for
+    ``pairs_in_flight`` problems of up to ``max_samples`` subtitle samples, ``max_blocks`` blocks and ``max_lags`` = 2W
+    lags."""
+
+    _create, _destroy, _workspace = "ffs_split_plan_create", "ffs_split_plan_destroy", "ffs_split_plan_workspace_bytes"
+
+    def __init__(self, pairs_in_flight: int, max_blocks: int, max_lags: int, max_samples: int,
+                 device: Optional[int] = None) -> None:
+        self.pairs_in_flight, self.max_blocks = int(pairs_in_flight), int(max_blocks)
+        self.max_lags, self.max_samples = int(max_lags), int(max_samples)
+        super().__init__((pairs_in_flight, max_blocks, max_lags, max_samples), device)
 
     def align(self, ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, block_samples: int,
               max_offset_samples: int, split_penalty: float, offsets_out, scores_out, totals_out,
               stream: Optional[int] = None) -> None:
         """``ffs_align_split_batch`` on host descriptor arrays (one entry per pair) into int32 / float64 / float64 CUDA
         tensors of n_pairs * max_b, n_pairs * max_b and n_pairs entries (asynchronous)."""
-        torch = require_gpu()
-        u64 = lambda a: np.ascontiguousarray(a, dtype=np.uint64)
-        i64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)
-        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
-        rp, rl, rlo, rhi = u64(ref_ptr), i64(ref_len), f64(ref_lo), f64(ref_hi)
-        sp, sl, slo, shi = u64(sub_ptr), i64(sub_len), f64(sub_lo), f64(sub_hi)
-        n = rp.size
-        if not all(a.size == n for a in (rl, rlo, rhi, sp, sl, slo, shi)):
-            raise ValueError("one descriptor entry per pair")
-        st = current_stream_ptr(torch) if stream is None else stream
-        check(self.lib.ffs_align_split_batch(self.handle, n, rp.ctypes.data, rl.ctypes.data, rlo.ctypes.data,
-                                             rhi.ctypes.data, sp.ctypes.data, sl.ctypes.data, slo.ctypes.data,
-                                             shi.ctypes.data, int(block_samples), int(max_offset_samples),
+        n, ptrs, _bufs = _pair_buffers(ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi)
+        check(self.lib.ffs_align_split_batch(self.handle, n, *ptrs, int(block_samples), int(max_offset_samples),
                                              float(split_penalty), offsets_out.data_ptr(), scores_out.data_ptr(),
-                                             totals_out.data_ptr(), st))
+                                             totals_out.data_ptr(), self._stream(stream)))
 
     def align_report(self, ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, block_samples: int,
                      max_offset_samples: int, split_penalty: float, top_k: int, exclusion_samples: int, offsets_out,
                      scores_out, totals_out, report_out, n_pieces_out, stream: Optional[int] = None) -> None:
         """``ffs_align_split_report_batch``: ``align``'s outputs plus a uint8 CUDA tensor of n_pairs * max_b * 224 bytes
         of piece reports and an int32 one of n_pairs piece counts (asynchronous)."""
-        torch = require_gpu()
-        u64 = lambda a: np.ascontiguousarray(a, dtype=np.uint64)
-        i64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)
-        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
-        rp, rl, rlo, rhi = u64(ref_ptr), i64(ref_len), f64(ref_lo), f64(ref_hi)
-        sp, sl, slo, shi = u64(sub_ptr), i64(sub_len), f64(sub_lo), f64(sub_hi)
-        n = rp.size
-        if not all(a.size == n for a in (rl, rlo, rhi, sp, sl, slo, shi)):
-            raise ValueError("one descriptor entry per pair")
+        n, ptrs, _bufs = _pair_buffers(ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi)
         if n_pieces_out.numel() < n or report_out.numel() * report_out.element_size() < offsets_out.numel() * PIECE_REPORT_BYTES:
             raise ValueError("output buffer too small")
-        st = current_stream_ptr(torch) if stream is None else stream
-        check(self.lib.ffs_align_split_report_batch(self.handle, n, rp.ctypes.data, rl.ctypes.data, rlo.ctypes.data,
-                                                    rhi.ctypes.data, sp.ctypes.data, sl.ctypes.data, slo.ctypes.data,
-                                                    shi.ctypes.data, int(block_samples), int(max_offset_samples),
+        check(self.lib.ffs_align_split_report_batch(self.handle, n, *ptrs, int(block_samples), int(max_offset_samples),
                                                     float(split_penalty), int(top_k), int(exclusion_samples),
                                                     offsets_out.data_ptr(), scores_out.data_ptr(), totals_out.data_ptr(),
-                                                    report_out.data_ptr(), n_pieces_out.data_ptr(), st))
+                                                    report_out.data_ptr(), n_pieces_out.data_ptr(), self._stream(stream)))
 
     def refine(self, ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, block_samples: int,
                offsets, radius_samples: int, unmatched_margin: float, refine_out, n_breaks_out,
@@ -908,117 +926,50 @@ class SplitPlan:
         """``ffs_split_refine_batch``: the int32 CUDA tensor of n_pairs * max_b block offsets (as ``align`` wrote them)
         into a uint8 CUDA tensor of n_pairs * max_b * 88 bytes of break records and an int32 one of n_pairs break counts
         (asynchronous); ``unmatched_margin`` NaN = a single cut."""
-        torch = require_gpu()
-        u64 = lambda a: np.ascontiguousarray(a, dtype=np.uint64)
-        i64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)
-        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
-        rp, rl, rlo, rhi = u64(ref_ptr), i64(ref_len), f64(ref_lo), f64(ref_hi)
-        sp, sl, slo, shi = u64(sub_ptr), i64(sub_len), f64(sub_lo), f64(sub_hi)
-        n = rp.size
-        if not all(a.size == n for a in (rl, rlo, rhi, sp, sl, slo, shi)):
-            raise ValueError("one descriptor entry per pair")
+        n, ptrs, _bufs = _pair_buffers(ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi)
         if n_breaks_out.numel() < n or refine_out.numel() * refine_out.element_size() < offsets.numel() * BREAK_REFINE_BYTES:
             raise ValueError("output buffer too small")
-        st = current_stream_ptr(torch) if stream is None else stream
-        check(self.lib.ffs_split_refine_batch(self.handle, n, rp.ctypes.data, rl.ctypes.data, rlo.ctypes.data,
-                                              rhi.ctypes.data, sp.ctypes.data, sl.ctypes.data, slo.ctypes.data,
-                                              shi.ctypes.data, int(block_samples), offsets.data_ptr(),
+        check(self.lib.ffs_split_refine_batch(self.handle, n, *ptrs, int(block_samples), offsets.data_ptr(),
                                               int(radius_samples), float(unmatched_margin), refine_out.data_ptr(),
-                                              n_breaks_out.data_ptr(), st))
-
-    def close(self) -> None:
-        if getattr(self, "handle", None):
-            self.lib.ffs_split_plan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self) -> None:  # pragma: no cover - interpreter shutdown ordering
-        try:
-            self.close()
-        except Exception:
-            pass
+                                              n_breaks_out.data_ptr(), self._stream(stream)))
 
 
-class SplitRangePlan:
+class SplitRangePlan(_SidePlan):
     """Owns one ``ffs_split_range_plan``: the workspace of the lag-range split aligner (``cut_align.py``) for
     ``pairs_in_flight`` problems of up to ``max_samples`` samples per vector, ``max_blocks`` blocks and ``max_lags``
     lags."""
 
+    _create = "ffs_split_range_plan_create"
+    _destroy, _workspace = "ffs_split_range_plan_destroy", "ffs_split_range_plan_workspace_bytes"
+
     def __init__(self, pairs_in_flight: int, max_blocks: int, max_lags: int, max_samples: int,
                  device: Optional[int] = None) -> None:
-        torch = require_gpu()
-        self.lib = load()
-        self.device = torch.cuda.current_device() if device is None else int(device)
         self.pairs_in_flight, self.max_blocks = int(pairs_in_flight), int(max_blocks)
         self.max_lags, self.max_samples = int(max_lags), int(max_samples)
-        handle = ctypes.c_void_p()
-        check(self.lib.ffs_split_range_plan_create(self.device, self.pairs_in_flight, self.max_blocks, self.max_lags,
-                                                   self.max_samples, ctypes.byref(handle)))
-        self.handle = handle
-
-    @property
-    def workspace_bytes(self) -> int:
-        return int(self.lib.ffs_split_range_plan_workspace_bytes(self.handle))
-
-    def fits(self, pairs_in_flight: int, max_blocks: int, max_lags: int, max_samples: int) -> bool:
-        return (self.pairs_in_flight >= pairs_in_flight and self.max_blocks >= max_blocks and self.max_lags >= max_lags
-                and self.max_samples >= max_samples)
+        super().__init__((pairs_in_flight, max_blocks, max_lags, max_samples), device)
 
     def align(self, ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, block_samples: int, lag_lo,
               lag_hi, split_penalty: float, offsets_out, scores_out, totals_out, stream: Optional[int] = None) -> None:
         """``ffs_align_split_range_batch`` on host descriptor arrays (one entry per pair, ``lag_lo`` / ``lag_hi``
         included) into int32 / float64 / float64 CUDA tensors of n_pairs * max_b, n_pairs * max_b and n_pairs entries
         (asynchronous)."""
-        torch = require_gpu()
-        u64 = lambda a: np.ascontiguousarray(a, dtype=np.uint64)
-        i64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)
-        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
-        rp, rl, rlo, rhi = u64(ref_ptr), i64(ref_len), f64(ref_lo), f64(ref_hi)
-        sp, sl, slo, shi = u64(sub_ptr), i64(sub_len), f64(sub_lo), f64(sub_hi)
-        llo, lhi = i64(lag_lo), i64(lag_hi)
-        n = rp.size
-        if not all(a.size == n for a in (rl, rlo, rhi, sp, sl, slo, shi, llo, lhi)):
-            raise ValueError("one descriptor entry per pair")
-        st = current_stream_ptr(torch) if stream is None else stream
-        check(self.lib.ffs_align_split_range_batch(self.handle, n, rp.ctypes.data, rl.ctypes.data, rlo.ctypes.data,
-                                                   rhi.ctypes.data, sp.ctypes.data, sl.ctypes.data, slo.ctypes.data,
-                                                   shi.ctypes.data, int(block_samples), llo.ctypes.data, lhi.ctypes.data,
+        n, ptrs, _bufs = _pair_buffers(ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, lag_lo, lag_hi)
+        check(self.lib.ffs_align_split_range_batch(self.handle, n, *ptrs[:8], int(block_samples), *ptrs[8:],
                                                    float(split_penalty), offsets_out.data_ptr(), scores_out.data_ptr(),
-                                                   totals_out.data_ptr(), st))
-
-    def close(self) -> None:
-        if getattr(self, "handle", None):
-            self.lib.ffs_split_range_plan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self) -> None:  # pragma: no cover - interpreter shutdown ordering
-        try:
-            self.close()
-        except Exception:
-            pass
+                                                   totals_out.data_ptr(), self._stream(stream)))
 
 
-class QualityPlan:
+class QualityPlan(_SidePlan):
     """Owns one ``ffs_quality_plan``: the workspace of the alignment quality report (``quality.py``) for
     ``pairs_in_flight`` problems of up to ``max_samples`` samples per vector and ``max_lags`` lags, plus (made on first
     use) a bit buffer that boundary-list inputs are expanded into."""
 
+    _create, _destroy, _workspace = "ffs_quality_plan_create", "ffs_quality_plan_destroy", "ffs_quality_plan_workspace_bytes"
+
     def __init__(self, pairs_in_flight: int, max_lags: int, max_samples: int, device: Optional[int] = None) -> None:
-        torch = require_gpu()
-        self.lib = load()
-        self.device = torch.cuda.current_device() if device is None else int(device)
         self.pairs_in_flight, self.max_lags, self.max_samples = int(pairs_in_flight), int(max_lags), int(max_samples)
         self.scratch = None  # int32 CUDA tensor: FFS_DTYPE_U1 images of FFS_DTYPE_RUNS vectors
-        handle = ctypes.c_void_p()
-        check(self.lib.ffs_quality_plan_create(self.device, self.pairs_in_flight, self.max_lags, self.max_samples,
-                                               ctypes.byref(handle)))
-        self.handle = handle
-
-    @property
-    def workspace_bytes(self) -> int:
-        return int(self.lib.ffs_quality_plan_workspace_bytes(self.handle))
-
-    def fits(self, pairs_in_flight: int, max_lags: int, max_samples: int) -> bool:
-        return self.pairs_in_flight >= pairs_in_flight and self.max_lags >= max_lags and self.max_samples >= max_samples
+        super().__init__((pairs_in_flight, max_lags, max_samples), device)
 
     def scratch_words(self, n_words: int):
         """The plan's bit buffer, grown to at least ``n_words`` int32 words."""
@@ -1031,34 +982,40 @@ class QualityPlan:
                top_k: int, exclusion_samples: int, out, stream: Optional[int] = None) -> None:
         """``ffs_align_quality_batch`` on host descriptor arrays (one entry per pair) into a uint8 CUDA tensor of
         n_pairs * 160 bytes (asynchronous).  ``max_offset_samples`` None = no window."""
-        torch = require_gpu()
-        u64 = lambda a: np.ascontiguousarray(a, dtype=np.uint64)
-        i64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)
-        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
-        rp, rl, rlo, rhi = u64(ref_ptr), i64(ref_len), f64(ref_lo), f64(ref_hi)
-        sp, sl, slo, shi = u64(sub_ptr), i64(sub_len), f64(sub_lo), f64(sub_hi)
-        n = rp.size
-        if not all(a.size == n for a in (rl, rlo, rhi, sp, sl, slo, shi)):
-            raise ValueError("one descriptor entry per pair")
+        n, ptrs, _bufs = _pair_buffers(ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi)
         if out.numel() * out.element_size() < n * QUALITY_RESULT_BYTES:
             raise ValueError("output buffer too small")
         mo = -1 if max_offset_samples is None else int(max_offset_samples)
-        st = current_stream_ptr(torch) if stream is None else stream
-        check(self.lib.ffs_align_quality_batch(self.handle, n, rp.ctypes.data, rl.ctypes.data, rlo.ctypes.data,
-                                               rhi.ctypes.data, sp.ctypes.data, sl.ctypes.data, slo.ctypes.data,
-                                               shi.ctypes.data, mo, int(top_k), int(exclusion_samples), out.data_ptr(), st))
+        check(self.lib.ffs_align_quality_batch(self.handle, n, *ptrs, mo, int(top_k), int(exclusion_samples),
+                                               out.data_ptr(), self._stream(stream)))
 
     def close(self) -> None:
-        if getattr(self, "handle", None):
-            self.lib.ffs_quality_plan_destroy(self.handle)
-            self.handle = None
+        super().close()
         self.scratch = None
 
-    def __del__(self) -> None:  # pragma: no cover - interpreter shutdown ordering
-        try:
-            self.close()
-        except Exception:
-            pass
+
+class SidePlanCache:
+    """The cached side plan of each (device, role) for one plan class: ``get`` hands it back while it ``fits`` the call
+    and otherwise closes it and makes one of the call's size."""
+
+    def __init__(self, plan_class) -> None:
+        self.plan_class = plan_class
+        self.plans: dict = {}
+
+    def get(self, *dims, role: Optional[str] = None):
+        dev = require_gpu().cuda.current_device()
+        key = (dev, role)
+        plan = self.plans.get(key)
+        if plan is None or plan.handle is None or not plan.fits(*dims):
+            if plan is not None:
+                plan.close()
+            plan = self.plans[key] = self.plan_class(*dims, device=dev)
+        return plan
+
+    def clear(self) -> None:
+        for plan in self.plans.values():
+            plan.close()
+        self.plans.clear()
 
 
 class Comm:

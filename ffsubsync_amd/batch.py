@@ -43,6 +43,13 @@ class DeviceBatch:
     def n_cand(self) -> int:
         return self.offs.shape[1] - 1
 
+    def pair_arrays(self) -> tuple:
+        """Per-pair host arrays of a batch with one candidate per pair: the reference's pointers, lengths and two
+        levels, then the candidate's -- the first eight arguments of the split and quality plans' batch calls."""
+        ptr = np.uint64(self.data.data_ptr()) + self.offs.astype(np.uint64)
+        lens = self.lens.astype(np.int64)
+        return (ptr[:, 0], lens[:, 0], self.lo[:, 0], self.hi[:, 0], ptr[:, 1], lens[:, 1], self.lo[:, 1], self.hi[:, 1])
+
     def select_candidates(self, index: Sequence[int]) -> "DeviceBatch":
         """View with one candidate per pair (``index[p]`` of pair p's candidates), sharing ``data``:
         the single-ratio FFTAligner problem of every pair."""

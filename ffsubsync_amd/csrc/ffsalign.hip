@@ -2909,33 +2909,175 @@ int ffs_speech_bounds(const float* frames_dev, int64_t n_frames, int64_t* bounds
     return FFS_OK;
 }
 
-/* ---- split-aware alignment (csrc/ffs_split.h) ---------------------------------------------------------------- */
-
-struct ffs_split_plan {
-    int device;
-    int pairs_in_flight;
-    int64_t max_blocks, max_lags, max_samples;
-    int64_t lpad, pw_s, pw_r;  // padded lag row, prefix words per vector
-    void* work;
-    int64_t work_bytes;
-    ffsa::SplitWs ws;
-    int32_t* pre;              // [slot][pw_s + pw_r]
-    ffsa::SplitDesc* dev_desc; // [pairs_in_flight]
-    ffsa::SplitDesc* host_desc; // pinned staging of the same
-    uint32_t* curves;          // report calls only, made by the first: per-piece n11 rows, [slot][max_blocks][lpad]
-    int64_t curve_bytes;
-    ffsa::RefineDesc* refine_desc;       // refine calls only, made by the first: descriptors [pairs_in_flight] then
-    ffsa::RefineDesc* refine_host_desc;  // their pinned staging, and the null-score scratch [pairs_in_flight][4]
-    double* refine_scratch;
-    int64_t refine_bytes;
-    hipEvent_t refine_desc_free;
-    hipEvent_t desc_free;      // the last descriptor upload has left the staging buffer
-    hipEvent_t done;           // the plan's last call has finished with the workspace
-};
+/* ---- host code shared by the split, split range and quality plans --------------------------------------------- */
 
 namespace {
 int64_t split_align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
+
+// A device descriptor block, its pinned host staging and the event that marks the staging free again: fill the
+// staging after wait_free(), then upload() it.  The device block may end in `dev_extra` bytes of device-only scratch.
+struct DescStaging {
+    void* dev = nullptr;
+    void* host = nullptr;
+    hipEvent_t free_event = nullptr;  // the last upload has left the staging buffer
+
+    // FFS_OK, FFS_E_NOMEM when the device block is refused, FFS_E_HIP for the staging or the event (nothing kept)
+    int create(size_t bytes, size_t dev_extra = 0) {
+        if (hipMalloc(&dev, bytes + dev_extra) != hipSuccess) {
+            dev = nullptr;
+            return FFS_E_NOMEM;
+        }
+        if (hipHostMalloc(&host, bytes, hipHostMallocDefault) != hipSuccess ||
+            hipEventCreateWithFlags(&free_event, hipEventDisableTiming) != hipSuccess) {
+            release();
+            return FFS_E_HIP;
+        }
+        return FFS_OK;
+    }
+    void release() {
+        if (free_event) (void)hipEventDestroy(free_event);
+        if (host) (void)hipHostFree(host);
+        if (dev) (void)hipFree(dev);
+        dev = host = nullptr;
+        free_event = nullptr;
+    }
+    int wait_free() {
+        HIP_TRY(hipEventSynchronize(free_event));
+        return FFS_OK;
+    }
+    int upload(size_t bytes, hipStream_t st) {
+        HIP_TRY(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(free_event, st));
+        return FFS_OK;
+    }
+};
+
+// What every plan holds: its device, the pairs one sub-batch solves, the workspace and the `done` event.
+struct PlanCore {
+    int device = 0;
+    int pairs_in_flight = 0;
+    void* work = nullptr;
+    int64_t work_bytes = 0;
+    hipEvent_t done = nullptr;  // the plan's last call has finished with the workspace
+
+    // at create: the workspace, then `done`; on failure the caller destroys the plan
+    int open(int dev, int pif, int64_t bytes, const char* what) {
+        device = dev;
+        pairs_in_flight = pif;
+        if (hipMalloc(&work, bytes) != hipSuccess) {
+            work = nullptr;
+            return fail(FFS_E_NOMEM, "%s: %lld workspace bytes", what, (long long)bytes);
+        }
+        work_bytes = bytes;
+        if (hipEventCreateWithFlags(&done, hipEventDisableTiming) != hipSuccess) {
+            done = nullptr;
+            return fail(FFS_E_HIP, "%s: event", what);
+        }
+        return FFS_OK;
+    }
+    // at destroy, before anything else is freed: wait for the last call, then free the workspace
+    void close() {
+        (void)hipSetDevice(device);
+        if (done) {
+            (void)hipEventSynchronize(done);
+            (void)hipEventDestroy(done);
+        }
+        if (work) (void)hipFree(work);
+    }
+    // every batch call, after its checks: on the plan's device, `st` waits until the previous call (any stream) is done
+    int begin(hipStream_t st) {
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(hipStreamWaitEvent(st, done, 0));
+        return FFS_OK;
+    }
+    int end(hipStream_t st) {
+        HIP_TRY(hipEventRecord(done, st));
+        return FFS_OK;
+    }
+};
+
+struct Levels {
+    double s0, s1, r0, r1;      // 2 * level - 1 (aligners.py:55-57)
+    double c00, c01, c10, c11;  // s~_x * r~_y for (s bit, r bit) = (0,0), (0,1), (1,0), (1,1)
+};
+
+// The per-pair host arrays of a batch call.
+struct Pairs {
+    const void* const* ref_ptr;
+    const int64_t* ref_len;
+    const double *ref_lo, *ref_hi;
+    const void* const* sub_ptr;
+    const int64_t* sub_len;
+    const double *sub_lo, *sub_hi;
+
+    bool any_null() const { return !ref_ptr || !ref_len || !ref_lo || !ref_hi || !sub_ptr || !sub_len || !sub_lo || !sub_hi; }
+
+    // the checks of pair p that every batch call makes before its own limits
+    int check(int p) const {
+        if (ref_len[p] <= 0 || sub_len[p] <= 0)
+            return fail(FFS_E_EMPTY, "cannot align empty speech data (reference length=%lld, subtitle length=%lld)",
+                        (long long)(ref_len[p] > 0 ? ref_len[p] : 0), (long long)(sub_len[p] > 0 ? sub_len[p] : 0));
+        if (!ref_ptr[p] || !sub_ptr[p] || ((uintptr_t)ref_ptr[p] & 3) || ((uintptr_t)sub_ptr[p] & 3))
+            return fail(FFS_E_INVALID, "pair %d: null or misaligned vector", p);
+        if (!(std::isfinite(ref_lo[p]) && std::isfinite(ref_hi[p]) && std::isfinite(sub_lo[p]) && std::isfinite(sub_hi[p])))
+            return fail(FFS_E_INVALID, "pair %d: levels must be finite", p);
+        return FFS_OK;
+    }
+
+    Levels levels(int p) const {
+#pragma clang fp contract(off)
+        Levels v;
+        v.s0 = mapped(sub_lo[p]);
+        v.s1 = mapped(sub_hi[p]);
+        v.r0 = mapped(ref_lo[p]);
+        v.r1 = mapped(ref_hi[p]);
+        v.c00 = v.s0 * v.r0;
+        v.c01 = v.s0 * v.r1;
+        v.c10 = v.s1 * v.r0;
+        v.c11 = v.s1 * v.r1;
+        return v;
+    }
+
+    // pair p's SplitDesc, its prefixes at pre_s and pre_r in the workspace, its outputs at row p
+    ffsa::SplitDesc split_desc(int p, int32_t* pre_s, int32_t* pre_r) const {
+        const Levels v = levels(p);
+        ffsa::SplitDesc d;
+        d.r = (const uint32_t*)ref_ptr[p];
+        d.s = (const uint32_t*)sub_ptr[p];
+        d.R = ref_len[p];
+        d.S = sub_len[p];
+        d.c00 = v.c00;
+        d.c01 = v.c01;
+        d.c10 = v.c10;
+        d.c11 = v.c11;
+        d.pre_r = pre_r;
+        d.pre_s = pre_s;
+        d.out_row = p;
+        return d;
+    }
+};
+
+int check_block_samples(int64_t K) {
+    if (K < 256 || K > ffsa::SPLIT_MAX_K || K % 32 != 0)
+        return fail(FFS_E_INVALID, "block_samples=%lld: need a multiple of 32 in [256, 32768]", (long long)K);
+    return FFS_OK;
+}
 }  // namespace
+
+/* ---- split-aware alignment (csrc/ffs_split.h) ---------------------------------------------------------------- */
+
+struct ffs_split_plan : PlanCore {
+    int64_t max_blocks, max_lags, max_samples;
+    int64_t lpad, pw_s, pw_r;  // padded lag row, prefix words per vector
+    ffsa::SplitWs ws;
+    int32_t* pre;              // [slot][pw_s + pw_r]
+    DescStaging desc;          // SplitDesc[pairs_in_flight]
+    uint32_t* curves;          // report calls only, made by the first: per-piece n11 rows, [slot][max_blocks][lpad]
+    int64_t curve_bytes;
+    DescStaging refine;        // refine calls only, made by the first: RefineDesc[pairs_in_flight], then on the device
+    double* refine_scratch;    // the null-score scratch [pairs_in_flight][4]
+    int64_t refine_bytes;
+};
 
 int ffs_split_plan_create(int device, int pairs_in_flight, int64_t max_blocks, int64_t max_lags, int64_t max_samples,
                           ffs_split_plan** out) {
@@ -2947,8 +3089,6 @@ int ffs_split_plan_create(int device, int pairs_in_flight, int64_t max_blocks, i
     HIP_TRY(hipSetDevice(device));
     ffs_split_plan* p = new (std::nothrow) ffs_split_plan();
     if (!p) return fail(FFS_E_NOMEM, "split plan");
-    p->device = device;
-    p->pairs_in_flight = pairs_in_flight;
     p->max_blocks = max_blocks;
     p->max_lags = max_lags;
     p->max_samples = max_samples;
@@ -2963,10 +3103,9 @@ int ffs_split_plan_create(int device, int pairs_in_flight, int64_t max_blocks, i
     const int64_t n = pairs_in_flight;
     const int64_t b_counts = n * counts_slot * 2, b_stay = n * stay_slot * 8, b_v = n * v_slot * 8, b_arg = n * arg_slot * 4,
                   b_pre = n * pre_slot * 4;
-    p->work_bytes = b_counts + b_stay + b_v + b_arg + b_pre;
-    if (hipMalloc(&p->work, p->work_bytes) != hipSuccess) {
-        delete p;
-        return fail(FFS_E_NOMEM, "split plan: %lld workspace bytes", (long long)(b_counts + b_stay + b_v + b_arg + b_pre));
+    if (int rc = p->open(device, pairs_in_flight, b_counts + b_stay + b_v + b_arg + b_pre, "split plan")) {
+        ffs_split_plan_destroy(p);
+        return rc;
     }
     char* w = (char*)p->work;
     p->ws.counts = (uint16_t*)w;
@@ -2980,11 +3119,7 @@ int ffs_split_plan_create(int device, int pairs_in_flight, int64_t max_blocks, i
     p->ws.stay_slot = stay_slot;
     p->ws.v_slot = v_slot;
     p->ws.arg_slot = arg_slot;
-    const size_t desc_bytes = sizeof(ffsa::SplitDesc) * (size_t)pairs_in_flight;
-    if (hipMalloc((void**)&p->dev_desc, desc_bytes) != hipSuccess ||
-        hipHostMalloc((void**)&p->host_desc, desc_bytes, hipHostMallocDefault) != hipSuccess ||
-        hipEventCreateWithFlags(&p->desc_free, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&p->done, hipEventDisableTiming) != hipSuccess) {
+    if (p->desc.create(sizeof(ffsa::SplitDesc) * (size_t)pairs_in_flight) != FFS_OK) {
         ffs_split_plan_destroy(p);
         return fail(FFS_E_HIP, "split plan: descriptor buffers / events");
     }
@@ -2994,19 +3129,10 @@ int ffs_split_plan_create(int device, int pairs_in_flight, int64_t max_blocks, i
 
 int ffs_split_plan_destroy(ffs_split_plan* plan) {
     if (!plan) return FFS_OK;
-    (void)hipSetDevice(plan->device);
-    if (plan->done) {
-        (void)hipEventSynchronize(plan->done);
-        (void)hipEventDestroy(plan->done);
-    }
-    if (plan->desc_free) (void)hipEventDestroy(plan->desc_free);
-    if (plan->host_desc) (void)hipHostFree(plan->host_desc);
-    if (plan->dev_desc) (void)hipFree(plan->dev_desc);
-    if (plan->work) (void)hipFree(plan->work);
+    plan->close();
+    plan->desc.release();
     if (plan->curves) (void)hipFree(plan->curves);
-    if (plan->refine_desc) (void)hipFree(plan->refine_desc);
-    if (plan->refine_host_desc) (void)hipHostFree(plan->refine_host_desc);
-    if (plan->refine_desc_free) (void)hipEventDestroy(plan->refine_desc_free);
+    plan->refine.release();
     delete plan;
     return FFS_OK;
 }
@@ -3024,21 +3150,16 @@ struct SplitReportArgs {  // the per-piece report of ffs_align_split_report_batc
 };
 
 // ffs_align_split_batch, and with `rep` the piece reports after each sub-batch's DP
-int split_batch(ffs_split_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len, const double* ref_lo,
-                const double* ref_hi, const void* const* sub_ptr, const int64_t* sub_len, const double* sub_lo,
-                const double* sub_hi, int64_t block_samples, int64_t max_offset_samples, double split_penalty,
-                int32_t* block_offset_out_dev, double* block_score_out_dev, double* total_out_dev,
+int split_batch(ffs_split_plan* plan, int n_pairs, const Pairs& a, int64_t block_samples, int64_t max_offset_samples,
+                double split_penalty, int32_t* block_offset_out_dev, double* block_score_out_dev, double* total_out_dev,
                 const SplitReportArgs* rep, void* hip_stream) {
-#pragma clang fp contract(off)
     if (!plan) return fail(FFS_E_INVALID, "null split plan");
     if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
     if (n_pairs == 0) return FFS_OK;
-    if (!ref_ptr || !ref_len || !ref_lo || !ref_hi || !sub_ptr || !sub_len || !sub_lo || !sub_hi || !block_offset_out_dev ||
-        !block_score_out_dev || !total_out_dev)
+    if (a.any_null() || !block_offset_out_dev || !block_score_out_dev || !total_out_dev)
         return fail(FFS_E_INVALID, "null argument");
     const int64_t K = block_samples, W = max_offset_samples;
-    if (K < 256 || K > ffsa::SPLIT_MAX_K || K % 32 != 0)
-        return fail(FFS_E_INVALID, "block_samples=%lld: need a multiple of 32 in [256, 32768]", (long long)K);
+    if (int rc = check_block_samples(K)) return rc;
     if (W < 1 || 2 * W > 262144) return fail(FFS_E_INVALID, "max_offset_samples=%lld: need 1 <= W, 2W <= 262144", (long long)W);
     if (2 * W > plan->max_lags)
         return fail(FFS_E_INVALID, "2 * max_offset_samples = %lld exceeds the plan's max_lags %lld", (long long)(2 * W),
@@ -3052,23 +3173,18 @@ int split_batch(ffs_split_plan* plan, int n_pairs, const void* const* ref_ptr, c
     }
     int64_t max_b = 0;
     for (int p = 0; p < n_pairs; ++p) {
-        if (ref_len[p] <= 0 || sub_len[p] <= 0)
-            return fail(FFS_E_EMPTY, "cannot align empty speech data (reference length=%lld, subtitle length=%lld)",
-                        (long long)(ref_len[p] > 0 ? ref_len[p] : 0), (long long)(sub_len[p] > 0 ? sub_len[p] : 0));
-        if (!ref_ptr[p] || !sub_ptr[p] || ((uintptr_t)ref_ptr[p] & 3) || ((uintptr_t)sub_ptr[p] & 3))
-            return fail(FFS_E_INVALID, "pair %d: null or misaligned vector", p);
-        if (sub_len[p] > plan->max_samples)
+        if (int rc = a.check(p)) return rc;
+        if (a.sub_len[p] > plan->max_samples)
             return fail(FFS_E_INVALID, "pair %d: subtitle length %lld exceeds the plan's max_samples %lld", p,
-                        (long long)sub_len[p], (long long)plan->max_samples);
-        const int64_t B = (sub_len[p] + K - 1) / K;
+                        (long long)a.sub_len[p], (long long)plan->max_samples);
+        const int64_t B = (a.sub_len[p] + K - 1) / K;
         if (B > plan->max_blocks)
             return fail(FFS_E_INVALID, "pair %d: %lld blocks exceed the plan's max_blocks %lld", p, (long long)B,
                         (long long)plan->max_blocks);
-        if (!(std::isfinite(ref_lo[p]) && std::isfinite(ref_hi[p]) && std::isfinite(sub_lo[p]) && std::isfinite(sub_hi[p])))
-            return fail(FFS_E_INVALID, "pair %d: levels must be finite", p);
-        if (B > max_b) max_b = B;
+        max_b = std::max(max_b, B);
     }
-    HIP_TRY(hipSetDevice(plan->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (int rc = plan->begin(st)) return rc;
     if (rep && !plan->curves) {  // the first report call: one uint32 n11 row per (slot, block)
         const int64_t bytes = (int64_t)plan->pairs_in_flight * plan->ws.counts_slot * 4;
         if (hipMalloc((void**)&plan->curves, bytes) != hipSuccess) {
@@ -3077,59 +3193,42 @@ int split_batch(ffs_split_plan* plan, int n_pairs, const void* const* ref_ptr, c
         }
         plan->curve_bytes = bytes;
     }
-    hipStream_t st = (hipStream_t)hip_stream;
-    HIP_TRY(hipStreamWaitEvent(st, plan->done, 0));  // the previous call (any stream) is done with the workspace
     const int64_t L = 2 * W;
     const int n_tiles = (int)((L + ffsa::SPLIT_TILE - 1) / ffsa::SPLIT_TILE);
     const int64_t pre_slot = split_align_up(plan->pw_s + plan->pw_r, 64);
+    ffsa::SplitDesc* hd = (ffsa::SplitDesc*)plan->desc.host;
+    const ffsa::SplitDesc* dd = (const ffsa::SplitDesc*)plan->desc.dev;
     for (int p0 = 0; p0 < n_pairs; p0 += plan->pairs_in_flight) {
         const int np = std::min(plan->pairs_in_flight, n_pairs - p0);
-        HIP_TRY(hipEventSynchronize(plan->desc_free));  // the staging buffer's previous upload has been consumed
+        if (int rc = plan->desc.wait_free()) return rc;
         int64_t chunk_b = 0;
         for (int i = 0; i < np; ++i) {
-            const int p = p0 + i;
-            ffsa::SplitDesc& d = plan->host_desc[i];
-            d.r = (const uint32_t*)ref_ptr[p];
-            d.s = (const uint32_t*)sub_ptr[p];
-            d.R = ref_len[p];
-            d.S = sub_len[p];
-            const double s0 = 2.0 * sub_lo[p] - 1.0, s1 = 2.0 * sub_hi[p] - 1.0;  // aligners.py:55-57
-            const double r0 = 2.0 * ref_lo[p] - 1.0, r1 = 2.0 * ref_hi[p] - 1.0;
-            d.c00 = s0 * r0;
-            d.c01 = s0 * r1;
-            d.c10 = s1 * r0;
-            d.c11 = s1 * r1;
-            d.pre_s = plan->pre + (int64_t)i * pre_slot;
-            d.pre_r = d.pre_s + plan->pw_s;
-            d.out_row = p;
-            chunk_b = std::max(chunk_b, (d.S + K - 1) / K);
+            int32_t* pre_s = plan->pre + (int64_t)i * pre_slot;
+            hd[i] = a.split_desc(p0 + i, pre_s, pre_s + plan->pw_s);
+            chunk_b = std::max(chunk_b, (hd[i].S + K - 1) / K);
         }
-        HIP_TRY(hipMemcpyAsync(plan->dev_desc, plan->host_desc, sizeof(ffsa::SplitDesc) * np, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(plan->desc_free, st));
+        if (int rc = plan->desc.upload(sizeof(ffsa::SplitDesc) * np, st)) return rc;
         const int n_bgroups = (int)((chunk_b + ffsa::SPLIT_BPW - 1) / ffsa::SPLIT_BPW);
-        hipLaunchKernelGGL(ffsa::k_split_prefix, dim3(2 * np), dim3(ffsa::SPLIT_PREFIX_THREADS), 0, st, plan->dev_desc,
-                           (int64_t)W);
+        hipLaunchKernelGGL(ffsa::k_split_prefix, dim3(2 * np), dim3(ffsa::SPLIT_PREFIX_THREADS), 0, st, dd, (int64_t)W);
         hipLaunchKernelGGL(ffsa::k_split_counts, dim3((unsigned)((int64_t)n_tiles * n_bgroups * np)),
-                           dim3(ffsa::SPLIT_CNT_THREADS), 0, st, plan->dev_desc, plan->ws, (int)K, (int64_t)W, n_tiles,
-                           n_bgroups);
-        hipLaunchKernelGGL(ffsa::k_split_dp, dim3(np), dim3(ffsa::SPLIT_DP_THREADS), 0, st, plan->dev_desc, plan->ws, (int)K,
-                           (int64_t)W, split_penalty, max_b, block_offset_out_dev, block_score_out_dev, total_out_dev);
+                           dim3(ffsa::SPLIT_CNT_THREADS), 0, st, dd, plan->ws, (int)K, (int64_t)W, n_tiles, n_bgroups);
+        hipLaunchKernelGGL(ffsa::k_split_dp, dim3(np), dim3(ffsa::SPLIT_DP_THREADS), 0, st, dd, plan->ws, (int)K, (int64_t)W,
+                           split_penalty, max_b, block_offset_out_dev, block_score_out_dev, total_out_dev);
         if (rep) {
-            hipLaunchKernelGGL(ffsa::k_split_pieces, dim3(np), dim3(ffsa::PIECE_SCAN_THREADS), 0, st, plan->dev_desc, (int)K,
-                               max_b, block_offset_out_dev, (ffsa::PieceReport*)rep->out, rep->n_pieces);
+            hipLaunchKernelGGL(ffsa::k_split_pieces, dim3(np), dim3(ffsa::PIECE_SCAN_THREADS), 0, st, dd, (int)K, max_b,
+                               block_offset_out_dev, (ffsa::PieceReport*)rep->out, rep->n_pieces);
             const int n_sum_tiles = (int)((L + ffsa::PIECE_SUM_TILE - 1) / ffsa::PIECE_SUM_TILE);
             hipLaunchKernelGGL(ffsa::k_split_piece_sums, dim3((unsigned)((int64_t)n_sum_tiles * np)),
-                               dim3(ffsa::PIECE_SUM_THREADS), 0, st, plan->dev_desc, plan->ws, plan->curves, (int)K,
-                               (int64_t)W, n_sum_tiles, max_b, (const int32_t*)block_offset_out_dev);
+                               dim3(ffsa::PIECE_SUM_THREADS), 0, st, dd, plan->ws, plan->curves, (int)K, (int64_t)W,
+                               n_sum_tiles, max_b, (const int32_t*)block_offset_out_dev);
             // one workgroup per possible piece (at most one per block); those past the pair's count return at once
             hipLaunchKernelGGL(ffsa::k_split_piece_report, dim3((unsigned)(chunk_b * np)), dim3(ffsa::QUAL_PEAK_THREADS), 0,
-                               st, plan->dev_desc, plan->ws, (const uint32_t*)plan->curves, (int64_t)W, (int)chunk_b, max_b,
+                               st, dd, plan->ws, (const uint32_t*)plan->curves, (int64_t)W, (int)chunk_b, max_b,
                                rep->top_k, rep->exclusion, (const int32_t*)rep->n_pieces, (ffsa::PieceReport*)rep->out);
         }
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(plan->done, st));
-    return FFS_OK;
+    return plan->end(st);
 }
 }  // namespace
 
@@ -3138,9 +3237,9 @@ int ffs_align_split_batch(ffs_split_plan* plan, int n_pairs, const void* const* 
                           const double* sub_lo, const double* sub_hi, int64_t block_samples, int64_t max_offset_samples,
                           double split_penalty, int32_t* block_offset_out_dev, double* block_score_out_dev,
                           double* total_out_dev, void* hip_stream) {
-    return split_batch(plan, n_pairs, ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, block_samples,
-                       max_offset_samples, split_penalty, block_offset_out_dev, block_score_out_dev, total_out_dev, nullptr,
-                       hip_stream);
+    const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
+    return split_batch(plan, n_pairs, a, block_samples, max_offset_samples, split_penalty, block_offset_out_dev,
+                       block_score_out_dev, total_out_dev, nullptr, hip_stream);
 }
 
 int ffs_align_split_report_batch(ffs_split_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
@@ -3149,10 +3248,10 @@ int ffs_align_split_report_batch(ffs_split_plan* plan, int n_pairs, const void* 
                                  int64_t max_offset_samples, double split_penalty, int top_k, int64_t exclusion_samples,
                                  int32_t* block_offset_out_dev, double* block_score_out_dev, double* total_out_dev,
                                  ffs_piece_report* report_out_dev, int32_t* n_pieces_out_dev, void* hip_stream) {
+    const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
     const SplitReportArgs rep{top_k, exclusion_samples, report_out_dev, n_pieces_out_dev};
-    return split_batch(plan, n_pairs, ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, block_samples,
-                       max_offset_samples, split_penalty, block_offset_out_dev, block_score_out_dev, total_out_dev, &rep,
-                       hip_stream);
+    return split_batch(plan, n_pairs, a, block_samples, max_offset_samples, split_penalty, block_offset_out_dev,
+                       block_score_out_dev, total_out_dev, &rep, hip_stream);
 }
 
 /* ---- sample-exact break refinement (csrc/ffs_split_refine.h) -------------------------------------------------- */
@@ -3162,18 +3261,15 @@ int ffs_split_refine_batch(ffs_split_plan* plan, int n_pairs, const void* const*
                            const double* sub_lo, const double* sub_hi, int64_t block_samples,
                            const int32_t* block_offset_dev, int64_t radius_samples, double unmatched_margin,
                            ffs_break_refine* out_dev, int32_t* n_breaks_out_dev, void* hip_stream) {
-#pragma clang fp contract(off)
+    const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
     if (!plan) return fail(FFS_E_INVALID, "null split plan");
     if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
     if (n_pairs == 0) return FFS_OK;
-    if (!ref_ptr || !ref_len || !ref_lo || !ref_hi || !sub_ptr || !sub_len || !sub_lo || !sub_hi || !block_offset_dev ||
-        !out_dev || !n_breaks_out_dev)
-        return fail(FFS_E_INVALID, "null argument");
+    if (a.any_null() || !block_offset_dev || !out_dev || !n_breaks_out_dev) return fail(FFS_E_INVALID, "null argument");
     if (((uintptr_t)block_offset_dev & 3) || ((uintptr_t)out_dev & 7) || ((uintptr_t)n_breaks_out_dev & 3))
         return fail(FFS_E_INVALID, "misaligned block offsets or refine outputs");
     const int64_t K = block_samples, Rr = radius_samples;
-    if (K < 256 || K > ffsa::SPLIT_MAX_K || K % 32 != 0)
-        return fail(FFS_E_INVALID, "block_samples=%lld: need a multiple of 32 in [256, 32768]", (long long)K);
+    if (int rc = check_block_samples(K)) return rc;
     if (Rr < 1 || Rr > ffsa::REFINE_MAX_RADIUS)
         return fail(FFS_E_INVALID, "radius_samples=%lld: need 1 <= radius <= %lld", (long long)Rr,
                     (long long)ffsa::REFINE_MAX_RADIUS);
@@ -3182,93 +3278,67 @@ int ffs_split_refine_batch(ffs_split_plan* plan, int n_pairs, const void* const*
         return fail(FFS_E_INVALID, "unmatched_margin must be finite and >= 0, or NaN for a single cut");
     int64_t max_b = 0;
     for (int p = 0; p < n_pairs; ++p) {
-        if (ref_len[p] <= 0 || sub_len[p] <= 0)
-            return fail(FFS_E_EMPTY, "cannot align empty speech data (reference length=%lld, subtitle length=%lld)",
-                        (long long)(ref_len[p] > 0 ? ref_len[p] : 0), (long long)(sub_len[p] > 0 ? sub_len[p] : 0));
-        if (!ref_ptr[p] || !sub_ptr[p] || ((uintptr_t)ref_ptr[p] & 3) || ((uintptr_t)sub_ptr[p] & 3))
-            return fail(FFS_E_INVALID, "pair %d: null or misaligned vector", p);
+        if (int rc = a.check(p)) return rc;
         if (ref_len[p] > INT32_MAX / 2 || sub_len[p] > INT32_MAX / 2)
             return fail(FFS_E_INVALID, "pair %d: vectors longer than 2^30 samples", p);
-        if (!(std::isfinite(ref_lo[p]) && std::isfinite(ref_hi[p]) && std::isfinite(sub_lo[p]) && std::isfinite(sub_hi[p])))
-            return fail(FFS_E_INVALID, "pair %d: levels must be finite", p);
         max_b = std::max(max_b, (sub_len[p] + K - 1) / K);
     }
-    HIP_TRY(hipSetDevice(plan->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (int rc = plan->begin(st)) return rc;
     const int pif = plan->pairs_in_flight;
-    if (!plan->refine_desc) {  // the first refine call: descriptors, their staging and the null-score scratch
+    if (!plan->refine.dev) {  // the first refine call: descriptors, their staging and the null-score scratch
         const size_t desc_bytes = sizeof(ffsa::RefineDesc) * (size_t)pif, scratch_bytes = sizeof(double) * 4 * (size_t)pif;
-        void* dev = nullptr;
-        if (hipMalloc(&dev, desc_bytes + scratch_bytes) != hipSuccess) return fail(FFS_E_NOMEM, "split plan: refine workspace");
-        if (hipHostMalloc((void**)&plan->refine_host_desc, desc_bytes, hipHostMallocDefault) != hipSuccess ||
-            hipEventCreateWithFlags(&plan->refine_desc_free, hipEventDisableTiming) != hipSuccess) {
-            (void)hipFree(dev);
-            if (plan->refine_host_desc) (void)hipHostFree(plan->refine_host_desc);
-            plan->refine_host_desc = nullptr;
-            plan->refine_desc_free = nullptr;
-            return fail(FFS_E_HIP, "split plan: refine descriptor staging / event");
-        }
-        plan->refine_desc = (ffsa::RefineDesc*)dev;
-        plan->refine_scratch = (double*)((char*)dev + desc_bytes);
+        if (int rc = plan->refine.create(desc_bytes, scratch_bytes)) return fail(rc, "split plan: refine workspace");
+        plan->refine_scratch = (double*)((char*)plan->refine.dev + desc_bytes);
         plan->refine_bytes = (int64_t)(desc_bytes + scratch_bytes);
     }
-    hipStream_t st = (hipStream_t)hip_stream;
-    HIP_TRY(hipStreamWaitEvent(st, plan->done, 0));  // the previous call (any stream) is done with the plan
+    ffsa::RefineDesc* hd = (ffsa::RefineDesc*)plan->refine.host;
+    const ffsa::RefineDesc* dd = (const ffsa::RefineDesc*)plan->refine.dev;
     for (int p0 = 0; p0 < n_pairs; p0 += pif) {
         const int np = std::min(pif, n_pairs - p0);
-        HIP_TRY(hipEventSynchronize(plan->refine_desc_free));
+        if (int rc = plan->refine.wait_free()) return rc;
         int64_t chunk_b = 0;
         for (int i = 0; i < np; ++i) {
             const int p = p0 + i;
-            ffsa::RefineDesc& d = plan->refine_host_desc[i];
+            const Levels v = a.levels(p);
+            ffsa::RefineDesc& d = hd[i];
             d.r = (const uint32_t*)ref_ptr[p];
             d.s = (const uint32_t*)sub_ptr[p];
             d.R = ref_len[p];
             d.S = sub_len[p];
-            d.s0 = 2.0 * sub_lo[p] - 1.0;  // as split_batch
-            d.s1 = 2.0 * sub_hi[p] - 1.0;
-            d.r0 = 2.0 * ref_lo[p] - 1.0;
-            d.r1 = 2.0 * ref_hi[p] - 1.0;
-            d.c00 = d.s0 * d.r0;
-            d.c01 = d.s0 * d.r1;
-            d.c10 = d.s1 * d.r0;
-            d.c11 = d.s1 * d.r1;
+            d.r0 = v.r0;
+            d.r1 = v.r1;
+            d.s0 = v.s0;
+            d.s1 = v.s1;
+            d.c00 = v.c00;
+            d.c01 = v.c01;
+            d.c10 = v.c10;
+            d.c11 = v.c11;
             d.pair_ws = plan->refine_scratch + 4 * (int64_t)i;
             d.out_row = p;
             chunk_b = std::max(chunk_b, (d.S + K - 1) / K);
         }
-        HIP_TRY(hipMemcpyAsync(plan->refine_desc, plan->refine_host_desc, sizeof(ffsa::RefineDesc) * np,
-                               hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(plan->refine_desc_free, st));
-        hipLaunchKernelGGL(ffsa::k_refine_breaks, dim3(np), dim3(ffsa::REFINE_TABLE_THREADS), 0, st, plan->refine_desc,
-                           (int)K, max_b, Rr, unmatched_margin, block_offset_dev, (ffsa::BreakRefine*)out_dev,
-                           n_breaks_out_dev);
+        if (int rc = plan->refine.upload(sizeof(ffsa::RefineDesc) * np, st)) return rc;
+        hipLaunchKernelGGL(ffsa::k_refine_breaks, dim3(np), dim3(ffsa::REFINE_TABLE_THREADS), 0, st, dd, (int)K, max_b, Rr,
+                           unmatched_margin, block_offset_dev, (ffsa::BreakRefine*)out_dev, n_breaks_out_dev);
         if (chunk_b > 1) {  // one workgroup per possible break (at most one per block after the first)
             const int n_slots = (int)(chunk_b - 1);
             hipLaunchKernelGGL(ffsa::k_refine_cut, dim3((unsigned)((int64_t)n_slots * np)), dim3(ffsa::REFINE_THREADS), 0,
-                               st, plan->refine_desc, n_slots, max_b, single, (const int32_t*)n_breaks_out_dev,
-                               (ffsa::BreakRefine*)out_dev);
+                               st, dd, n_slots, max_b, single, (const int32_t*)n_breaks_out_dev, (ffsa::BreakRefine*)out_dev);
         }
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(plan->done, st));
-    return FFS_OK;
+    return plan->end(st);
 }
 
 /* ---- split-aware alignment over a lag range (csrc/ffs_split_range.h) ------------------------------------------- */
 
-struct ffs_split_range_plan {
-    int device;
-    int pairs_in_flight;
+struct ffs_split_range_plan : PlanCore {
     int64_t max_blocks, max_lags, max_samples;
     int64_t pw;                 // prefix words per vector
-    void* work;
-    int64_t work_bytes;
     ffsa::RangeWs ws;
     int32_t* pre;               // [slot][2 * pw]: s, then r
-    void* dev_desc;             // SplitDesc[pairs_in_flight], then RangeLag[pairs_in_flight]
-    void* host_desc;            // pinned staging of the same
-    hipEvent_t desc_free;       // the last descriptor upload has left the staging buffer
-    hipEvent_t done;            // the plan's last call has finished with the workspace
+    DescStaging desc;           // SplitDesc[pairs_in_flight], then RangeLag[pairs_in_flight]
 };
 
 int ffs_split_range_plan_create(int device, int pairs_in_flight, int64_t max_blocks, int64_t max_lags, int64_t max_samples,
@@ -3282,8 +3352,6 @@ int ffs_split_range_plan_create(int device, int pairs_in_flight, int64_t max_blo
     HIP_TRY(hipSetDevice(device));
     ffs_split_range_plan* p = new (std::nothrow) ffs_split_range_plan();
     if (!p) return fail(FFS_E_NOMEM, "split range plan");
-    p->device = device;
-    p->pairs_in_flight = pairs_in_flight;
     p->max_blocks = max_blocks;
     p->max_lags = max_lags;
     p->max_samples = max_samples;
@@ -3297,10 +3365,9 @@ int ffs_split_range_plan_create(int device, int pairs_in_flight, int64_t max_blo
     const int64_t n = pairs_in_flight;
     const int64_t b_stay = n * stay_slot * 8, b_v = n * v_slot * 8, b_pv = n * 2 * part_row * 8, b_pj = n * 2 * part_row * 4,
                   b_arg = n * arg_slot * 4, b_pre = n * pre_slot * 4;
-    p->work_bytes = b_stay + b_v + b_pv + b_pj + b_arg + b_pre;
-    if (hipMalloc(&p->work, p->work_bytes) != hipSuccess) {
-        delete p;
-        return fail(FFS_E_NOMEM, "split range plan: %lld workspace bytes", (long long)(b_stay + b_v + b_pv + b_pj + b_arg + b_pre));
+    if (int rc = p->open(device, pairs_in_flight, b_stay + b_v + b_pv + b_pj + b_arg + b_pre, "split range plan")) {
+        ffs_split_range_plan_destroy(p);
+        return rc;
     }
     char* w = (char*)p->work;
     p->ws.stay = (unsigned long long*)w;
@@ -3314,11 +3381,7 @@ int ffs_split_range_plan_create(int device, int pairs_in_flight, int64_t max_blo
     p->ws.v_slot = v_slot;
     p->ws.part_row = part_row;
     p->ws.arg_slot = arg_slot;
-    const size_t desc_bytes = (sizeof(ffsa::SplitDesc) + sizeof(ffsa::RangeLag)) * (size_t)pairs_in_flight;
-    if (hipMalloc(&p->dev_desc, desc_bytes) != hipSuccess ||
-        hipHostMalloc(&p->host_desc, desc_bytes, hipHostMallocDefault) != hipSuccess ||
-        hipEventCreateWithFlags(&p->desc_free, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&p->done, hipEventDisableTiming) != hipSuccess) {
+    if (p->desc.create((sizeof(ffsa::SplitDesc) + sizeof(ffsa::RangeLag)) * (size_t)pairs_in_flight) != FFS_OK) {
         ffs_split_range_plan_destroy(p);
         return fail(FFS_E_HIP, "split range plan: descriptor buffers / events");
     }
@@ -3328,15 +3391,8 @@ int ffs_split_range_plan_create(int device, int pairs_in_flight, int64_t max_blo
 
 int ffs_split_range_plan_destroy(ffs_split_range_plan* plan) {
     if (!plan) return FFS_OK;
-    (void)hipSetDevice(plan->device);
-    if (plan->done) {
-        (void)hipEventSynchronize(plan->done);
-        (void)hipEventDestroy(plan->done);
-    }
-    if (plan->desc_free) (void)hipEventDestroy(plan->desc_free);
-    if (plan->host_desc) (void)hipHostFree(plan->host_desc);
-    if (plan->dev_desc) (void)hipFree(plan->dev_desc);
-    if (plan->work) (void)hipFree(plan->work);
+    plan->close();
+    plan->desc.release();
     delete plan;
     return FFS_OK;
 }
@@ -3349,28 +3405,22 @@ int ffs_align_split_range_batch(ffs_split_range_plan* plan, int n_pairs, const v
                                 const int64_t* lag_lo, const int64_t* lag_hi, double split_penalty,
                                 int32_t* block_offset_out_dev, double* block_score_out_dev, double* total_out_dev,
                                 void* hip_stream) {
-#pragma clang fp contract(off)
+    const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
     if (!plan) return fail(FFS_E_INVALID, "null split range plan");
     if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
     if (n_pairs == 0) return FFS_OK;
-    if (!ref_ptr || !ref_len || !ref_lo || !ref_hi || !sub_ptr || !sub_len || !sub_lo || !sub_hi || !lag_lo || !lag_hi ||
-        !block_offset_out_dev || !block_score_out_dev || !total_out_dev)
+    if (a.any_null() || !lag_lo || !lag_hi || !block_offset_out_dev || !block_score_out_dev || !total_out_dev)
         return fail(FFS_E_INVALID, "null argument");
     if (((uintptr_t)block_offset_out_dev & 3) || ((uintptr_t)block_score_out_dev & 7) || ((uintptr_t)total_out_dev & 7))
         return fail(FFS_E_INVALID, "misaligned outputs");
     const int64_t K = block_samples;
-    if (K < 256 || K > ffsa::SPLIT_MAX_K || K % 32 != 0)
-        return fail(FFS_E_INVALID, "block_samples=%lld: need a multiple of 32 in [256, 32768]", (long long)K);
+    if (int rc = check_block_samples(K)) return rc;
     if (!(split_penalty >= 0.0)) return fail(FFS_E_INVALID, "split_penalty must be >= 0 (not NaN)");
     int64_t max_b = 0;
     for (int p = 0; p < n_pairs; ++p) {
-        if (ref_len[p] <= 0 || sub_len[p] <= 0)
-            return fail(FFS_E_EMPTY, "cannot align empty speech data (reference length=%lld, subtitle length=%lld)",
-                        (long long)(ref_len[p] > 0 ? ref_len[p] : 0), (long long)(sub_len[p] > 0 ? sub_len[p] : 0));
-        if (!ref_ptr[p] || !sub_ptr[p] || ((uintptr_t)ref_ptr[p] & 3) || ((uintptr_t)sub_ptr[p] & 3))
-            return fail(FFS_E_INVALID, "pair %d: null or misaligned vector", p);
+        if (int rc = a.check(p)) return rc;
         if (sub_len[p] > plan->max_samples || ref_len[p] > plan->max_samples)
-            return fail(FFS_E_INVALID, "pair %d: vector lengths %lld / %lld exceed the plan's max_samples %lld", p,
+            return fail(FFS_E_INVALID, "pair %d: lengths %lld / %lld exceed the plan's max_samples %lld", p,
                         (long long)ref_len[p], (long long)sub_len[p], (long long)plan->max_samples);
         const int64_t B = (sub_len[p] + K - 1) / K;
         if (B > plan->max_blocks)
@@ -3382,48 +3432,31 @@ int ffs_align_split_range_batch(ffs_split_range_plan* plan, int n_pairs, const v
         if (lag_hi[p] - lag_lo[p] + 1 > plan->max_lags)
             return fail(FFS_E_INVALID, "pair %d: %lld lags exceed the plan's max_lags %lld", p,
                         (long long)(lag_hi[p] - lag_lo[p] + 1), (long long)plan->max_lags);
-        if (!(std::isfinite(ref_lo[p]) && std::isfinite(ref_hi[p]) && std::isfinite(sub_lo[p]) && std::isfinite(sub_hi[p])))
-            return fail(FFS_E_INVALID, "pair %d: levels must be finite", p);
-        if (B > max_b) max_b = B;
+        max_b = std::max(max_b, B);
     }
-    HIP_TRY(hipSetDevice(plan->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    HIP_TRY(hipStreamWaitEvent(st, plan->done, 0));  // the previous call (any stream) is done with the workspace
+    if (int rc = plan->begin(st)) return rc;
     const int64_t pre_slot = split_align_up(2 * plan->pw, 64);
     const int pif = plan->pairs_in_flight;
-    ffsa::SplitDesc* hd = (ffsa::SplitDesc*)plan->host_desc;
+    ffsa::SplitDesc* hd = (ffsa::SplitDesc*)plan->desc.host;
     ffsa::RangeLag* hl = (ffsa::RangeLag*)(hd + pif);
-    const ffsa::SplitDesc* dd = (const ffsa::SplitDesc*)plan->dev_desc;
+    const ffsa::SplitDesc* dd = (const ffsa::SplitDesc*)plan->desc.dev;
     const ffsa::RangeLag* dl = (const ffsa::RangeLag*)(dd + pif);
     for (int p0 = 0; p0 < n_pairs; p0 += pif) {
         const int np = std::min(pif, n_pairs - p0);
-        HIP_TRY(hipEventSynchronize(plan->desc_free));  // the staging buffer's previous upload has been consumed
+        if (int rc = plan->desc.wait_free()) return rc;
         int64_t chunk_b = 0, max_tiles = 0;
         for (int i = 0; i < np; ++i) {
             const int p = p0 + i;
-            ffsa::SplitDesc& d = hd[i];
-            d.r = (const uint32_t*)ref_ptr[p];
-            d.s = (const uint32_t*)sub_ptr[p];
-            d.R = ref_len[p];
-            d.S = sub_len[p];
-            const double s0 = 2.0 * sub_lo[p] - 1.0, s1 = 2.0 * sub_hi[p] - 1.0;  // as split_batch
-            const double r0 = 2.0 * ref_lo[p] - 1.0, r1 = 2.0 * ref_hi[p] - 1.0;
-            d.c00 = s0 * r0;
-            d.c01 = s0 * r1;
-            d.c10 = s1 * r0;
-            d.c11 = s1 * r1;
-            d.pre_s = plan->pre + (int64_t)i * pre_slot;
-            d.pre_r = d.pre_s + plan->pw;
-            d.out_row = p;
+            int32_t* pre_s = plan->pre + (int64_t)i * pre_slot;
+            hd[i] = a.split_desc(p, pre_s, pre_s + plan->pw);
             hl[i].lag_lo = lag_lo[p];
             hl[i].L = lag_hi[p] - lag_lo[p] + 1;
-            chunk_b = std::max(chunk_b, (d.S + K - 1) / K);
+            chunk_b = std::max(chunk_b, (hd[i].S + K - 1) / K);
             max_tiles = std::max(max_tiles, (hl[i].L + ffsa::RANGE_TILE - 1) / ffsa::RANGE_TILE);
         }
         // one upload of both arrays (the RangeLag half is at a fixed offset: copy the whole used span)
-        HIP_TRY(hipMemcpyAsync(plan->dev_desc, plan->host_desc, sizeof(ffsa::SplitDesc) * pif + sizeof(ffsa::RangeLag) * np,
-                               hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(plan->desc_free, st));
+        if (int rc = plan->desc.upload(sizeof(ffsa::SplitDesc) * pif + sizeof(ffsa::RangeLag) * np, st)) return rc;
         // prefixes over every sample of both vectors (W = max_samples: min(R, S + W) = R)
         hipLaunchKernelGGL(ffsa::k_split_prefix, dim3(2 * np), dim3(ffsa::SPLIT_PREFIX_THREADS), 0, st, dd,
                            (int64_t)plan->max_samples);
@@ -3438,26 +3471,18 @@ int ffs_align_split_range_batch(ffs_split_range_plan* plan, int n_pairs, const v
                            block_score_out_dev);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(plan->done, st));
-    return FFS_OK;
+    return plan->end(st);
 }
 
 /* ---- alignment quality report (csrc/ffs_quality.h) ------------------------------------------------------------- */
 
-struct ffs_quality_plan {
-    int device;
-    int pairs_in_flight;
+struct ffs_quality_plan : PlanCore {
     int64_t max_lags, max_samples;
     int64_t lpad, pre_slot;     // padded curve row, prefix words per slot (both vectors)
-    void* work;
-    int64_t work_bytes;
     uint32_t* curve;            // [slot][lpad]
     double* sc;                 // [slot][lpad]
     int32_t* pre;               // [slot][pre_slot]
-    void* dev_desc;             // SplitDesc[pairs_in_flight] (k_split_prefix), then QualDesc[pairs_in_flight]
-    void* host_desc;            // pinned staging of the same
-    hipEvent_t desc_free;       // the last descriptor upload has left the staging buffer
-    hipEvent_t done;            // the plan's last call has finished with the workspace
+    DescStaging desc;           // SplitDesc[pairs_in_flight] (k_split_prefix), then QualDesc[pairs_in_flight]
 };
 
 int ffs_quality_plan_create(int device, int pairs_in_flight, int64_t max_lags, int64_t max_samples, ffs_quality_plan** out) {
@@ -3468,28 +3493,21 @@ int ffs_quality_plan_create(int device, int pairs_in_flight, int64_t max_lags, i
     HIP_TRY(hipSetDevice(device));
     ffs_quality_plan* p = new (std::nothrow) ffs_quality_plan();
     if (!p) return fail(FFS_E_NOMEM, "quality plan");
-    p->device = device;
-    p->pairs_in_flight = pairs_in_flight;
     p->max_lags = max_lags;
     p->max_samples = max_samples;
     p->lpad = split_align_up(max_lags, 64);
     p->pre_slot = split_align_up(2 * (max_samples / 32 + 2), 64);
     const int64_t n = pairs_in_flight;
     const int64_t b_curve = n * p->lpad * 4, b_sc = n * p->lpad * 8, b_pre = n * p->pre_slot * 4;
-    p->work_bytes = b_curve + b_sc + b_pre;
-    if (hipMalloc(&p->work, p->work_bytes) != hipSuccess) {
-        delete p;
-        return fail(FFS_E_NOMEM, "quality plan: %lld workspace bytes", (long long)(b_curve + b_sc + b_pre));
+    if (int rc = p->open(device, pairs_in_flight, b_curve + b_sc + b_pre, "quality plan")) {
+        ffs_quality_plan_destroy(p);
+        return rc;
     }
     char* w = (char*)p->work;
     p->sc = (double*)w;
     p->curve = (uint32_t*)(w + b_sc);
     p->pre = (int32_t*)(w + b_sc + b_curve);
-    const size_t desc_bytes = (sizeof(ffsa::SplitDesc) + sizeof(ffsa::QualDesc)) * (size_t)pairs_in_flight;
-    if (hipMalloc(&p->dev_desc, desc_bytes) != hipSuccess ||
-        hipHostMalloc(&p->host_desc, desc_bytes, hipHostMallocDefault) != hipSuccess ||
-        hipEventCreateWithFlags(&p->desc_free, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&p->done, hipEventDisableTiming) != hipSuccess) {
+    if (p->desc.create((sizeof(ffsa::SplitDesc) + sizeof(ffsa::QualDesc)) * (size_t)pairs_in_flight) != FFS_OK) {
         ffs_quality_plan_destroy(p);
         return fail(FFS_E_HIP, "quality plan: descriptor buffers / events");
     }
@@ -3499,15 +3517,8 @@ int ffs_quality_plan_create(int device, int pairs_in_flight, int64_t max_lags, i
 
 int ffs_quality_plan_destroy(ffs_quality_plan* plan) {
     if (!plan) return FFS_OK;
-    (void)hipSetDevice(plan->device);
-    if (plan->done) {
-        (void)hipEventSynchronize(plan->done);
-        (void)hipEventDestroy(plan->done);
-    }
-    if (plan->desc_free) (void)hipEventDestroy(plan->desc_free);
-    if (plan->host_desc) (void)hipHostFree(plan->host_desc);
-    if (plan->dev_desc) (void)hipFree(plan->dev_desc);
-    if (plan->work) (void)hipFree(plan->work);
+    plan->close();
+    plan->desc.release();
     delete plan;
     return FFS_OK;
 }
@@ -3518,27 +3529,21 @@ int ffs_align_quality_batch(ffs_quality_plan* plan, int n_pairs, const void* con
                             const double* ref_lo, const double* ref_hi, const void* const* sub_ptr, const int64_t* sub_len,
                             const double* sub_lo, const double* sub_hi, int64_t max_offset_samples, int top_k,
                             int64_t exclusion_samples, ffs_quality_result* out_dev, void* hip_stream) {
+    const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
     if (!plan) return fail(FFS_E_INVALID, "null quality plan");
     if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
     if (n_pairs == 0) return FFS_OK;
-    if (!ref_ptr || !ref_len || !ref_lo || !ref_hi || !sub_ptr || !sub_len || !sub_lo || !sub_hi || !out_dev)
-        return fail(FFS_E_INVALID, "null argument");
+    if (a.any_null() || !out_dev) return fail(FFS_E_INVALID, "null argument");
     if (max_offset_samples < -1) return fail(FFS_E_INVALID, "max_offset_samples=%lld: need >= 0, or -1 for none", (long long)max_offset_samples);
     if (top_k < 1 || top_k > ffsa::QUAL_MAX_PEAKS) return fail(FFS_E_INVALID, "top_k=%d outside [1, 8]", top_k);
     if (exclusion_samples < 1) return fail(FFS_E_INVALID, "exclusion_samples=%lld: need >= 1", (long long)exclusion_samples);
     if ((uintptr_t)out_dev & 7) return fail(FFS_E_INVALID, "misaligned output records");
     int64_t max_sw = 0;
     for (int p = 0; p < n_pairs; ++p) {
-        if (ref_len[p] <= 0 || sub_len[p] <= 0)
-            return fail(FFS_E_EMPTY, "cannot align empty speech data (reference length=%lld, subtitle length=%lld)",
-                        (long long)(ref_len[p] > 0 ? ref_len[p] : 0), (long long)(sub_len[p] > 0 ? sub_len[p] : 0));
-        if (!ref_ptr[p] || !sub_ptr[p] || ((uintptr_t)ref_ptr[p] & 3) || ((uintptr_t)sub_ptr[p] & 3))
-            return fail(FFS_E_INVALID, "pair %d: null or misaligned vector", p);
+        if (int rc = a.check(p)) return rc;
         if (ref_len[p] > plan->max_samples || sub_len[p] > plan->max_samples)
             return fail(FFS_E_INVALID, "pair %d: lengths %lld / %lld exceed the plan's max_samples %lld", p,
                         (long long)ref_len[p], (long long)sub_len[p], (long long)plan->max_samples);
-        if (!(std::isfinite(ref_lo[p]) && std::isfinite(ref_hi[p]) && std::isfinite(sub_lo[p]) && std::isfinite(sub_hi[p])))
-            return fail(FFS_E_INVALID, "pair %d: levels must be finite", p);
         const int64_t n_ref = ffs_fft_length(ref_len[p], sub_len[p]);
         int64_t wl = 0, wh = -1;
         if (lag_window(ref_len[p], sub_len[p], n_ref, max_offset_samples, &wl, &wh) && wh - wl + 1 > plan->max_lags)
@@ -3546,31 +3551,26 @@ int ffs_align_quality_batch(ffs_quality_plan* plan, int n_pairs, const void* con
                         (long long)plan->max_lags);
         max_sw = std::max(max_sw, (sub_len[p] + 31) / 32);
     }
-    HIP_TRY(hipSetDevice(plan->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    HIP_TRY(hipStreamWaitEvent(st, plan->done, 0));  // the previous call (any stream) is done with the workspace
-    ffsa::SplitDesc* hs = (ffsa::SplitDesc*)plan->host_desc;
-    ffsa::QualDesc* hq = (ffsa::QualDesc*)(hs + plan->pairs_in_flight);
-    const ffsa::SplitDesc* ds = (const ffsa::SplitDesc*)plan->dev_desc;
-    const ffsa::QualDesc* dq = (const ffsa::QualDesc*)(ds + plan->pairs_in_flight);
+    if (int rc = plan->begin(st)) return rc;
+    const int pif = plan->pairs_in_flight;
+    ffsa::SplitDesc* hs = (ffsa::SplitDesc*)plan->desc.host;
+    ffsa::QualDesc* hq = (ffsa::QualDesc*)(hs + pif);
+    const ffsa::SplitDesc* ds = (const ffsa::SplitDesc*)plan->desc.dev;
+    const ffsa::QualDesc* dq = (const ffsa::QualDesc*)(ds + pif);
     int n_sm = 0;
     HIP_TRY(hipDeviceGetAttribute(&n_sm, hipDeviceAttributeMultiprocessorCount, plan->device));
-    for (int p0 = 0; p0 < n_pairs; p0 += plan->pairs_in_flight) {
-        const int np = std::min(plan->pairs_in_flight, n_pairs - p0);
-        HIP_TRY(hipEventSynchronize(plan->desc_free));  // the staging buffer's previous upload has been consumed
+    for (int p0 = 0; p0 < n_pairs; p0 += pif) {
+        const int np = std::min(pif, n_pairs - p0);
+        if (int rc = plan->desc.wait_free()) return rc;
         int64_t max_count = 0;
         for (int i = 0; i < np; ++i) {
             const int p = p0 + i;
             const int64_t R = ref_len[p], S = sub_len[p];
+            int32_t* pre_s = plan->pre + (int64_t)i * plan->pre_slot;
             ffsa::SplitDesc& sd = hs[i];
-            memset(&sd, 0, sizeof sd);
-            sd.r = (const uint32_t*)ref_ptr[p];
-            sd.s = (const uint32_t*)sub_ptr[p];
-            sd.R = R;
-            sd.S = S;
-            sd.pre_s = plan->pre + (int64_t)i * plan->pre_slot;
-            sd.pre_r = sd.pre_s + (S / 32 + 2);
-            sd.out_row = p;
+            sd = a.split_desc(p, pre_s, pre_s + (S / 32 + 2));
+            const Levels v = a.levels(p);
             ffsa::QualDesc& q = hq[i];
             memset(&q, 0, sizeof q);
             q.r = sd.r;
@@ -3587,10 +3587,10 @@ int ffs_align_quality_batch(ffs_quality_plan* plan, int n_pairs, const void* con
             }
             q.cd.R = (int32_t)R;
             q.cd.S = (int32_t)S;
-            q.cd.s0 = mapped(sub_lo[p]);
-            q.cd.s1 = mapped(sub_hi[p]);
-            q.cd.r0 = mapped(ref_lo[p]);
-            q.cd.r1 = mapped(ref_hi[p]);
+            q.cd.s0 = v.s0;
+            q.cd.s1 = v.s1;
+            q.cd.r0 = v.r0;
+            q.cd.r1 = v.r1;
             q.pre_r = sd.pre_r;
             q.pre_s = sd.pre_s;
             q.curve = plan->curve + (int64_t)i * plan->lpad;
@@ -3598,9 +3598,8 @@ int ffs_align_quality_batch(ffs_quality_plan* plan, int n_pairs, const void* con
             q.out_row = p;
             max_count = std::max(max_count, q.n_count);
         }
-        HIP_TRY(hipMemcpyAsync((void*)ds, hs, sizeof(ffsa::SplitDesc) * np, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync((void*)dq, hq, sizeof(ffsa::QualDesc) * np, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(plan->desc_free, st));
+        // one upload of both arrays (the QualDesc half is at a fixed offset: copy the whole used span)
+        if (int rc = plan->desc.upload(sizeof(ffsa::SplitDesc) * pif + sizeof(ffsa::QualDesc) * np, st)) return rc;
         HIP_TRY(hipMemsetAsync(plan->curve, 0, (size_t)np * plan->lpad * 4, st));
         // prefixes over every sample of both vectors (W beyond any length: k_split_prefix then covers all of r)
         hipLaunchKernelGGL(ffsa::k_split_prefix, dim3(2 * np), dim3(ffsa::SPLIT_PREFIX_THREADS), 0, st, ds,
@@ -3620,8 +3619,7 @@ int ffs_align_quality_batch(ffs_quality_plan* plan, int n_pairs, const void* con
                            exclusion_samples, (ffsa::QualResult*)out_dev);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(plan->done, st));
-    return FFS_OK;
+    return plan->end(st);
 }
 
 }  // extern "C"

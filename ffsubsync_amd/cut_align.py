@@ -20,7 +20,8 @@ import numpy as np
 
 from . import _native, split_refine
 from .constants import SAMPLE_RATE, candidate_ratios
-from .split_align import (DEFAULT_BLOCK_SAMPLES, Piece, SplitResult, _check_batch, empty_error, pieces_from_blocks)
+from .split_align import (DEFAULT_BLOCK_SAMPLES, Piece, SplitResult, _check_batch, empty_error, split_outputs,
+                          split_results, validate_block_samples)
 
 # Chosen on the CPU model over the full range (profiles/cut_calibration.py; synthetic data only)
 DEFAULT_CUT_PENALTY = 8192.0
@@ -45,9 +46,7 @@ class CutSyncResult:
 
 def validate_args(block_samples, split_penalty) -> None:
     """Host-side checks of the call parameters (ValueError before any native call)."""
-    k = int(block_samples)
-    if k != block_samples or k % 32 or not 256 <= k <= 32768:
-        raise ValueError("block_samples=%r: need a multiple of 32 in [256, 32768]" % (block_samples,))
+    validate_block_samples(block_samples)
     p = float(split_penalty)
     if math.isnan(p) or p < 0:
         raise ValueError("split_penalty=%r: need a number >= 0 (inf = never split)" % (split_penalty,))
@@ -73,28 +72,18 @@ def full_range(ref_len: int, sub_len: int) -> Tuple[int, int]:
     return -(int(sub_len) - 1), int(ref_len) - 1
 
 
-_plan_cache: dict = {}
+_plans = _native.SidePlanCache(_native.SplitRangePlan)
 
 
 def _get_plan(n_pairs: int, max_blocks: int, max_lags: int, max_samples: int, pairs_in_flight: Optional[int]):
-    torch = _native.require_gpu()
-    dev = torch.cuda.current_device()
     if pairs_in_flight is None:  # bound the workspace (stay bits + one fp64 row: ~140 MB per 2 h full-range pair) to ~12 GiB
         per_pair = max_blocks * (max_lags / 8.0 + 8) + max_lags * 8.0 + max_samples / 4.0 + 4096
         pairs_in_flight = int(max(1, min(n_pairs, 256, (12 << 30) // per_pair)))
-    plan = _plan_cache.get(dev)
-    if plan is None or plan.handle is None or not plan.fits(pairs_in_flight, max_blocks, max_lags, max_samples):
-        if plan is not None:
-            plan.close()
-        plan = _native.SplitRangePlan(pairs_in_flight, max_blocks, max_lags, max_samples, dev)
-        _plan_cache[dev] = plan
-    return plan
+    return _plans.get(pairs_in_flight, max_blocks, max_lags, max_samples)
 
 
 def clear_plan_cache() -> None:
-    for plan in _plan_cache.values():
-        plan.close()
-    _plan_cache.clear()
+    _plans.clear()
 
 
 def split_align_range_batch(batch, lag_ranges=None, block_samples: int = DEFAULT_BLOCK_SAMPLES,
@@ -116,7 +105,7 @@ def split_align_range_batch(batch, lag_ranges=None, block_samples: int = DEFAULT
             raise ValueError("%d lag ranges for %d pairs" % (len(lag_ranges), n))
         ranges = [validate_range(r) for r in lag_ranges]
     ranges = [validate_range(r) for r in ranges]
-    torch = _native.require_gpu()
+    _native.require_gpu()
     if batch.dtype == _native.FFS_DTYPE_U8:
         batch = batch.to_bits()
     k = int(block_samples)
@@ -125,23 +114,9 @@ def split_align_range_batch(batch, lag_ranges=None, block_samples: int = DEFAULT
     n_blocks = (sub_len + k - 1) // k
     max_b = int(n_blocks.max())
     plan = _get_plan(n, max_b, int((hi - lo + 1).max()), int(max(sub_len.max(), ref_len.max())), pairs_in_flight)
-    base = np.uint64(batch.data.data_ptr())
-    dev = batch.data.device
-    offs_out = torch.empty(n * max_b, dtype=torch.int32, device=dev)
-    scores_out = torch.empty(n * max_b, dtype=torch.float64, device=dev)
-    totals_out = torch.empty(n, dtype=torch.float64, device=dev)
-    plan.align(base + batch.offs[:, 0].astype(np.uint64), ref_len, batch.lo[:, 0], batch.hi[:, 0],
-               base + batch.offs[:, 1].astype(np.uint64), sub_len, batch.lo[:, 1], batch.hi[:, 1], k, lo, hi,
-               float(split_penalty), offs_out, scores_out, totals_out)
-    offs_h = offs_out.cpu().numpy().reshape(n, max_b)
-    scores_h = scores_out.cpu().numpy().reshape(n, max_b)
-    totals_h = totals_out.cpu().numpy()
-    out = []
-    for p in range(n):
-        nb = int(n_blocks[p])
-        bo, bs = offs_h[p, :nb].copy(), scores_h[p, :nb].copy()
-        out.append(SplitResult(pieces_from_blocks(bo, bs, k, int(sub_len[p])), float(totals_h[p]), bo, bs))
-    return out
+    outs = split_outputs(n, max_b, batch.data.device)
+    plan.align(*batch.pair_arrays(), k, lo, hi, float(split_penalty), *outs)
+    return split_results(outs, n_blocks, k, sub_len)
 
 
 def _device_refs(problems):

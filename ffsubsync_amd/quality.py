@@ -23,6 +23,7 @@ import numpy as np
 
 from . import _native
 from .constants import SAMPLE_RATE, candidate_ratios
+from .split_align import empty_error
 
 DEFAULT_TOP_K = 3
 DEFAULT_EXCLUSION_SAMPLES = 300  # 3 s at 100 Hz: a runner-up closer than that is the same peak's shoulder
@@ -116,8 +117,7 @@ def _check_batch(batch) -> None:
     lens = np.asarray(batch.lens)
     for p in range(lens.shape[0]):
         if lens[p, 0] <= 0 or lens[p, 1] <= 0:
-            raise ValueError("cannot align empty speech data (reference length=%d, subtitle length=%d); the reference or "
-                             "subtitles may contain no detectable speech" % (max(int(lens[p, 0]), 0), max(int(lens[p, 1]), 0)))
+            raise empty_error(max(int(lens[p, 0]), 0), max(int(lens[p, 1]), 0))
     levels = np.concatenate([np.ravel(batch.lo), np.ravel(batch.hi)])
     if not np.all(np.isfinite(levels)):
         raise ValueError("two-level vectors need finite levels")
@@ -138,27 +138,17 @@ def n_lags(ref_len: int, sub_len: int, max_offset_samples: Optional[int]) -> int
     return max(hi - lo, 0)
 
 
-_plan_cache: dict = {}
+_plans = _native.SidePlanCache(_native.QualityPlan)
 
 
 def _get_plan(n_pairs: int, max_lags: int, max_samples: int, pairs_in_flight: Optional[int]):
-    torch = _native.require_gpu()
-    dev = torch.cuda.current_device()
     if pairs_in_flight is None:  # bound the workspace (12 B per lag: 144 KB per pair at +-60 s) to ~2 GiB
         pairs_in_flight = int(max(1, min(n_pairs, 1024, (2 << 30) // (12 * max_lags + 1))))
-    plan = _plan_cache.get(dev)
-    if plan is None or plan.handle is None or not plan.fits(pairs_in_flight, max_lags, max_samples):
-        if plan is not None:
-            plan.close()
-        plan = _native.QualityPlan(pairs_in_flight, max_lags, max_samples, dev)
-        _plan_cache[dev] = plan
-    return plan
+    return _plans.get(pairs_in_flight, max_lags, max_samples)
 
 
 def clear_plan_cache() -> None:
-    for plan in _plan_cache.values():
-        plan.close()
-    _plan_cache.clear()
+    _plans.clear()
 
 
 def quality_batch(batch, max_offset_samples: Optional[int], top_k: int = DEFAULT_TOP_K,
@@ -178,8 +168,7 @@ def quality_batch(batch, max_offset_samples: Optional[int], top_k: int = DEFAULT
     plan = _get_plan(n, max(max_lags, 1), int(max(ref_len.max(), sub_len.max())), pairs_in_flight)
     if batch.dtype == _native.FFS_DTYPE_U8:
         batch = batch.to_bits()
-    base = batch.data.data_ptr()
-    ptrs = (np.uint64(base) + batch.offs.astype(np.uint64)).reshape(n, 2)
+    args = list(batch.pair_arrays())
     if batch.dtype == _native.FFS_DTYPE_RUNS:
         words = (batch.lens.astype(np.int64) + 31) // 32
         slots = (words + 15) // 16 * 16  # 64-byte aligned images
@@ -191,12 +180,11 @@ def quality_batch(batch, max_offset_samples: Optional[int], top_k: int = DEFAULT
         for p in range(n):
             for v in range(2):
                 dst = scratch.data_ptr() + 4 * int(starts[p, v])
-                _native.check(lib.ffs_runs_to_bits(int(ptrs[p, v]), int(batch.lens[p, v]), dst, st))
+                _native.check(lib.ffs_runs_to_bits(int(args[4 * v][p]), int(batch.lens[p, v]), dst, st))
                 bits_ptr[p, v] = dst
-        ptrs = bits_ptr
+        args[0], args[4] = bits_ptr[:, 0], bits_ptr[:, 1]
     out = torch.empty(max(n, 1) * _native.QUALITY_RESULT_BYTES, dtype=torch.uint8, device=batch.data.device)
-    plan.report(ptrs[:, 0], ref_len, batch.lo[:, 0], batch.hi[:, 0], ptrs[:, 1], sub_len, batch.lo[:, 1], batch.hi[:, 1],
-                max_offset_samples, top_k, exclusion_samples, out)
+    plan.report(*args, max_offset_samples, top_k, exclusion_samples, out)
     recs = out.cpu().numpy().view(_native.QUALITY_RESULT_DTYPE)[:n]
     if raw:
         return recs

@@ -57,11 +57,16 @@ class SplitSyncResult:
     cue_piece: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int64))
 
 
-def validate_args(block_samples, max_offset_samples, split_penalty) -> None:
-    """Host-side checks of the call parameters (ValueError before any native call)."""
+def validate_block_samples(block_samples) -> None:
+    """The block size check that every split entry point makes (ValueError)."""
     k = int(block_samples)
     if k != block_samples or k % 32 or not 256 <= k <= 32768:
         raise ValueError("block_samples=%r: need a multiple of 32 in [256, 32768]" % (block_samples,))
+
+
+def validate_args(block_samples, max_offset_samples, split_penalty) -> None:
+    """Host-side checks of the call parameters (ValueError before any native call)."""
+    validate_block_samples(block_samples)
     w = int(max_offset_samples)
     if w != max_offset_samples or w < 1 or 2 * w > MAX_LAGS:
         raise ValueError("max_offset_samples=%r: need an integer W >= 1 with 2W <= %d" % (max_offset_samples, MAX_LAGS))
@@ -105,32 +110,21 @@ def _check_batch(batch) -> None:
         raise ValueError("two-level vectors need finite levels")
 
 
-_plan_cache: dict = {}
+_plans = _native.SidePlanCache(_native.SplitPlan)
 
 
 def _get_plan(n_pairs: int, max_blocks: int, max_lags: int, max_samples: int, pairs_in_flight: Optional[int],
               report: bool = False):
     """The cached plan of this device; report calls (``split_report``) get their own, sized for the per-piece n11 rows
     the first report call adds (4 more bytes per block and lag)."""
-    torch = _native.require_gpu()
-    dev = torch.cuda.current_device()
     if pairs_in_flight is None:  # bound the workspace (~170 MB of counts per pair at 2 h, +-10 min, K = 1024) to ~12 GiB
         per_pair = max_blocks * (max_lags + 64) * (6.2 if report else 2.2) + 1
         pairs_in_flight = int(max(1, min(n_pairs, 256, (12 << 30) // per_pair)))
-    key = (dev, "report") if report else dev
-    plan = _plan_cache.get(key)
-    if plan is None or plan.handle is None or not plan.fits(pairs_in_flight, max_blocks, max_lags, max_samples):
-        if plan is not None:
-            plan.close()
-        plan = _native.SplitPlan(pairs_in_flight, max_blocks, max_lags, max_samples, dev)
-        _plan_cache[key] = plan
-    return plan
+    return _plans.get(pairs_in_flight, max_blocks, max_lags, max_samples, role="report" if report else None)
 
 
 def clear_plan_cache() -> None:
-    for plan in _plan_cache.values():
-        plan.close()
-    _plan_cache.clear()
+    _plans.clear()
 
 
 def split_align_batch(batch, max_offset_samples: int, block_samples: int = DEFAULT_BLOCK_SAMPLES,
@@ -153,35 +147,45 @@ def _solve(batch, max_offset_samples, block_samples, split_penalty, pairs_in_fli
         batch = batch.to_bits()
     k, w = int(block_samples), int(max_offset_samples)
     n = batch.n_pairs
-    ref_len, sub_len = batch.lens[:, 0].astype(np.int64), batch.lens[:, 1].astype(np.int64)
+    sub_len = batch.lens[:, 1].astype(np.int64)
     n_blocks = (sub_len + k - 1) // k
     max_b = int(n_blocks.max())
     plan = _get_plan(n, max_b, 2 * w, int(sub_len.max()), pairs_in_flight, report is not None)
-    base = np.uint64(batch.data.data_ptr())
     dev = batch.data.device
-    offs_out = torch.empty(n * max_b, dtype=torch.int32, device=dev)
-    scores_out = torch.empty(n * max_b, dtype=torch.float64, device=dev)
-    totals_out = torch.empty(n, dtype=torch.float64, device=dev)
-    args = (base + batch.offs[:, 0].astype(np.uint64), ref_len, batch.lo[:, 0], batch.hi[:, 0],
-            base + batch.offs[:, 1].astype(np.uint64), sub_len, batch.lo[:, 1], batch.hi[:, 1], k, w, float(split_penalty))
+    outs = split_outputs(n, max_b, dev)
+    args = batch.pair_arrays() + (k, w, float(split_penalty))
     recs = counts = None
     if report is None:
-        plan.align(*args, offs_out, scores_out, totals_out)
+        plan.align(*args, *outs)
     else:
         rep_out = torch.empty(n * max_b * _native.PIECE_REPORT_BYTES, dtype=torch.uint8, device=dev)
         n_out = torch.empty(n, dtype=torch.int32, device=dev)
-        plan.align_report(*args, int(report[0]), int(report[1]), offs_out, scores_out, totals_out, rep_out, n_out)
+        plan.align_report(*args, int(report[0]), int(report[1]), *outs, rep_out, n_out)
         recs = rep_out.cpu().numpy().view(_native.PIECE_REPORT_DTYPE).reshape(n, max_b)
         counts = n_out.cpu().numpy()
-    offs_h = offs_out.cpu().numpy().reshape(n, max_b)
-    scores_h = scores_out.cpu().numpy().reshape(n, max_b)
-    totals_h = totals_out.cpu().numpy()
+    return split_results(outs, n_blocks, k, sub_len), recs, counts
+
+
+def split_outputs(n_pairs: int, max_b: int, device):
+    """The device outputs of a split call: block offsets, block scores (n_pairs * max_b each) and totals (n_pairs)."""
+    torch = _native.require_gpu()
+    return (torch.empty(n_pairs * max_b, dtype=torch.int32, device=device),
+            torch.empty(n_pairs * max_b, dtype=torch.float64, device=device),
+            torch.empty(n_pairs, dtype=torch.float64, device=device))
+
+
+def split_results(outs, n_blocks, block_samples: int, sub_len) -> List[SplitResult]:
+    """One ``SplitResult`` per pair from the outputs of ``split_outputs`` after the call."""
+    n, max_b = len(n_blocks), int(max(n_blocks))
+    offs_h = outs[0].cpu().numpy().reshape(n, max_b)
+    scores_h = outs[1].cpu().numpy().reshape(n, max_b)
+    totals_h = outs[2].cpu().numpy()
     out = []
     for p in range(n):
         nb = int(n_blocks[p])
         bo, bs = offs_h[p, :nb].copy(), scores_h[p, :nb].copy()
-        out.append(SplitResult(pieces_from_blocks(bo, bs, k, int(sub_len[p])), float(totals_h[p]), bo, bs))
-    return out, recs, counts
+        out.append(SplitResult(pieces_from_blocks(bo, bs, block_samples, int(sub_len[p])), float(totals_h[p]), bo, bs))
+    return out
 
 
 def _scaled_us(us: int, ratio: float) -> int:

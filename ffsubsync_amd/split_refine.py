@@ -23,7 +23,7 @@ import numpy as np
 from . import _native, quality, split_report
 from .constants import SAMPLE_RATE
 from .split_align import (DEFAULT_BLOCK_SAMPLES, DEFAULT_SPLIT_PENALTY, Piece, SplitResult, _check_batch, _scaled_us,
-                          _td_us)
+                          _td_us, validate_block_samples)
 
 # Chosen on the CPU model (profiles/split_refine_calibration.py; synthetic data only, 64 seeds, 2 h,
 # +-10 min, K = 1024, the DP's own coarse breaks): the largest workload event is 240 s, so 270 s of radius covers a cut
@@ -64,9 +64,7 @@ def from_record(rec) -> RefinedBreak:
 
 def validate_args(block_samples, radius_samples, unmatched_margin) -> None:
     """Host-side checks of the call parameters (ValueError before any native call)."""
-    k = int(block_samples)
-    if k != block_samples or k % 32 or not 256 <= k <= 32768:
-        raise ValueError("block_samples=%r: need a multiple of 32 in [256, 32768]" % (block_samples,))
+    validate_block_samples(block_samples)
     r = int(radius_samples)
     if r != radius_samples or not 1 <= r <= _native.REFINE_MAX_RADIUS:
         raise ValueError("radius_samples=%r: need an integer in [1, %d]" % (radius_samples, _native.REFINE_MAX_RADIUS))
@@ -76,27 +74,16 @@ def validate_args(block_samples, radius_samples, unmatched_margin) -> None:
             raise ValueError("unmatched_margin=%r: need a finite number >= 0, or None for a single cut" % (unmatched_margin,))
 
 
-_plan_cache: dict = {}
+_plans = _native.SidePlanCache(_native.SplitPlan)
 
 
 def _get_plan(n_pairs: int):
     """A split plan of this device that holds no split workspace: refine calls use its sub-batching and descriptors."""
-    torch = _native.require_gpu()
-    dev = torch.cuda.current_device()
-    pif = int(max(1, min(n_pairs, 256)))
-    plan = _plan_cache.get(dev)
-    if plan is None or plan.handle is None or plan.pairs_in_flight < pif:
-        if plan is not None:
-            plan.close()
-        plan = _native.SplitPlan(pif, 1, 2, 1, dev)
-        _plan_cache[dev] = plan
-    return plan
+    return _plans.get(int(max(1, min(n_pairs, 256))), 1, 2, 1)
 
 
 def clear_plan_cache() -> None:
-    for plan in _plan_cache.values():
-        plan.close()
-    _plan_cache.clear()
+    _plans.clear()
 
 
 def refine_breaks_batch(batch, split_results: Sequence[SplitResult], block_samples: int = DEFAULT_BLOCK_SAMPLES,
@@ -128,12 +115,9 @@ def refine_breaks_batch(batch, split_results: Sequence[SplitResult], block_sampl
     offs_dev = torch.from_numpy(offs.reshape(-1)).to(dev)
     rec_out = torch.empty(n * max_b * _native.BREAK_REFINE_BYTES, dtype=torch.uint8, device=dev)
     n_out = torch.empty(n, dtype=torch.int32, device=dev)
-    base = np.uint64(batch.data.data_ptr())
     plan = _get_plan(n)
-    plan.refine(base + batch.offs[:, 0].astype(np.uint64), batch.lens[:, 0].astype(np.int64), batch.lo[:, 0],
-                batch.hi[:, 0], base + batch.offs[:, 1].astype(np.uint64), sub_len, batch.lo[:, 1], batch.hi[:, 1], k,
-                offs_dev, int(radius_samples), math.nan if unmatched_margin is None else float(unmatched_margin), rec_out,
-                n_out)
+    plan.refine(*batch.pair_arrays(), k, offs_dev, int(radius_samples),
+                math.nan if unmatched_margin is None else float(unmatched_margin), rec_out, n_out)
     recs = rec_out.cpu().numpy().view(_native.BREAK_REFINE_DTYPE).reshape(n, max_b)
     counts = n_out.cpu().numpy()
     if raw:

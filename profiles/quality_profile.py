@@ -39,15 +39,13 @@ def main() -> None:
         rows = np.arange(n_pairs) % db.n_pairs
         tb = DeviceBatch(db.data, db.offs[rows], db.lens[rows], db.lo[rows], db.hi[rows], db.dtype)
         quality.quality_batch(tb, w, top_k, e)  # warm: plan, code objects
-        plan = next(iter(quality._plan_cache.values()))
-        base = np.uint64(tb.data.data_ptr())
+        plan = next(iter(quality._plans.plans.values()))
         out = torch.empty(n_pairs * _native.QUALITY_RESULT_BYTES, dtype=torch.uint8, device=tb.data.device)
         times = []
         for _ in range(args.repeats):
             start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             start.record()
-            plan.report(base + tb.offs[:, 0].astype(np.uint64), tb.lens[:, 0], tb.lo[:, 0], tb.hi[:, 0],
-                        base + tb.offs[:, 1].astype(np.uint64), tb.lens[:, 1], tb.lo[:, 1], tb.hi[:, 1], w, top_k, e, out)
+            plan.report(*tb.pair_arrays(), w, top_k, e, out)
             stop.record()
             torch.cuda.synchronize()
             times.append(start.elapsed_time(stop))

@@ -40,7 +40,7 @@ def main() -> None:
         sub_len = db.lens[:, 1]
         blocks = int(((sub_len + k - 1) // k).sum())
         sa.split_align_batch(db, w)  # warm: plan, code objects
-        plan = next(iter(sa._plan_cache.values()))
+        plan = next(iter(sa._plans.plans.values()))
         times = []
         for _ in range(args.repeats):
             start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -69,10 +69,7 @@ def main() -> None:
         rec = torch.empty(n_pairs * max_b * _native.BREAK_REFINE_BYTES, dtype=torch.uint8, device=dev)
         cnt = torch.empty(n_pairs, dtype=torch.int32, device=dev)
         plan = sr._get_plan(n_pairs)
-        base = np.uint64(db.data.data_ptr())
-        call = lambda: plan.refine(base + db.offs[:, 0].astype(np.uint64), db.lens[:, 0].astype(np.int64), db.lo[:, 0],
-                                   db.hi[:, 0], base + db.offs[:, 1].astype(np.uint64), sl, db.lo[:, 1], db.hi[:, 1], k,
-                                   offs_d, radius, beta, rec, cnt)
+        call = lambda: plan.refine(*db.pair_arrays(), k, offs_d, radius, beta, rec, cnt)
         ms_dev, t_dev, _ = _best(call, args.repeats)
         n_brk = sum(len(b) for b in brks)
         result["calls"][str(n_pairs)] = {

@@ -57,11 +57,11 @@ def main() -> None:
     for n_pairs in (1, 256):
         db = batch.pack_pairs([rasters[i % len(rasters)] for i in range(n_pairs)])
         ms_r, t_r, reps = _best(lambda: sr.split_report_batch(db, w), args.repeats)
-        rplan = sa._plan_cache[(torch.cuda.current_device(), "report")]
+        rplan = sa._plans.plans[(torch.cuda.current_device(), "report")]
         pif, ws_r = rplan.pairs_in_flight, rplan.workspace_bytes
         sa.clear_plan_cache()
         ms_p, t_p, _ = _best(lambda: sa.split_align_batch(db, w), args.repeats)
-        pplan = sa._plan_cache[torch.cuda.current_device()]
+        pplan = sa._plans.plans[(torch.cuda.current_device(), None)]
         pif_p, ws_p = pplan.pairs_in_flight, pplan.workspace_bytes
         sa.clear_plan_cache()
         ms_q, t_q, _ = _best(lambda: sa.split_align_batch(db, w, pairs_in_flight=pif), args.repeats)
