@@ -114,6 +114,7 @@ EXPORTED_SYMBOLS = (
     "ffs_split_range_plan_destroy",
     "ffs_split_range_plan_workspace_bytes",
     "ffs_align_split_range_batch",
+    "ffs_split_range_report_batch",
     "ffs_quality_plan_create",
     "ffs_quality_plan_destroy",
     "ffs_quality_plan_workspace_bytes",
@@ -309,6 +310,11 @@ def load():
         lib.ffs_align_split_range_batch.argtypes = [c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
                                                     c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p,
                                                     c.c_void_p, c.c_double, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
+        lib.ffs_split_range_report_batch.restype = c.c_int
+        lib.ffs_split_range_report_batch.argtypes = [c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                                                     c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p,
+                                                     c.c_void_p, c.c_void_p, c.c_int, c.c_int64, c.c_void_p, c.c_void_p,
+                                                     c.c_void_p]
         lib.ffs_quality_plan_create.restype = c.c_int
         lib.ffs_quality_plan_create.argtypes = [c.c_int, c.c_int, c.c_int64, c.c_int64, c.POINTER(c.c_void_p)]
         lib.ffs_quality_plan_destroy.restype = c.c_int
@@ -957,6 +963,19 @@ class SplitRangePlan(_SidePlan):
         check(self.lib.ffs_align_split_range_batch(self.handle, n, *ptrs[:8], int(block_samples), *ptrs[8:],
                                                    float(split_penalty), offsets_out.data_ptr(), scores_out.data_ptr(),
                                                    totals_out.data_ptr(), self._stream(stream)))
+
+    def report(self, ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, block_samples: int, lag_lo,
+               lag_hi, offsets, top_k: int, exclusion_samples: int, report_out, n_pieces_out,
+               stream: Optional[int] = None) -> None:
+        """``ffs_split_range_report_batch``: the piece reports of the int32 CUDA tensor of n_pairs * max_b block offsets
+        (as ``align`` wrote them) over each pair's range into a uint8 CUDA tensor of n_pairs * max_b * 224 bytes and an
+        int32 one of n_pairs piece counts.  The call waits for the stream's earlier work (it reads the offsets back)."""
+        n, ptrs, _bufs = _pair_buffers(ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, lag_lo, lag_hi)
+        if n_pieces_out.numel() < n or report_out.numel() * report_out.element_size() < offsets.numel() * PIECE_REPORT_BYTES:
+            raise ValueError("output buffer too small")
+        check(self.lib.ffs_split_range_report_batch(self.handle, n, *ptrs[:8], int(block_samples), *ptrs[8:],
+                                                    offsets.data_ptr(), int(top_k), int(exclusion_samples),
+                                                    report_out.data_ptr(), n_pieces_out.data_ptr(), self._stream(stream)))
 
 
 class QualityPlan(_SidePlan):

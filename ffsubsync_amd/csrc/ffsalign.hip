@@ -30,6 +30,7 @@
 #include "ffs_split_report.h"
 #include "ffs_split_refine.h"
 #include "ffs_split_range.h"
+#include "ffs_cut_report.h"
 
 using namespace ffsa;
 
@@ -1002,7 +1003,7 @@ void fill_xform(XformDesc* x, const VecView* a, const VecView* b, const void* sa
 extern "C" {
 
 const char* ffs_last_error(void) { return g_err.c_str(); }
-int ffs_version(void) { return 350; }
+int ffs_version(void) { return 360; }
 
 int64_t ffs_fft_length(int64_t ref_len, int64_t sub_len) {
     if (ref_len <= 0 || sub_len <= 0) return 0;
@@ -3339,6 +3340,11 @@ struct ffs_split_range_plan : PlanCore {
     ffsa::RangeWs ws;
     int32_t* pre;               // [slot][2 * pw]: s, then r
     DescStaging desc;           // SplitDesc[pairs_in_flight], then RangeLag[pairs_in_flight]
+    uint32_t* rows = nullptr;   // report calls only, made by the first: piece n11 rows, [slot][CUT_ROUND_PIECES][lpad]
+    int64_t lpad = 0;
+    DescStaging items;          // report calls only: CutItem[item_cap]
+    int64_t item_cap = 0;
+    int64_t report_bytes = 0;
 };
 
 int ffs_split_range_plan_create(int device, int pairs_in_flight, int64_t max_blocks, int64_t max_lags, int64_t max_samples,
@@ -3393,11 +3399,41 @@ int ffs_split_range_plan_destroy(ffs_split_range_plan* plan) {
     if (!plan) return FFS_OK;
     plan->close();
     plan->desc.release();
+    if (plan->rows) (void)hipFree(plan->rows);
+    plan->items.release();
     delete plan;
     return FFS_OK;
 }
 
-int64_t ffs_split_range_plan_workspace_bytes(const ffs_split_range_plan* plan) { return plan ? plan->work_bytes : 0; }
+int64_t ffs_split_range_plan_workspace_bytes(const ffs_split_range_plan* plan) {
+    return plan ? plan->work_bytes + plan->report_bytes : 0;
+}
+
+namespace {
+// the per-pair checks of the range calls (lengths and blocks against the plan, the lag ranges); the largest block count
+int range_pairs_check(const ffs_split_range_plan* plan, int n_pairs, const Pairs& a, int64_t K, const int64_t* lag_lo,
+                      const int64_t* lag_hi, int64_t* max_b) {
+    *max_b = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+        if (int rc = a.check(p)) return rc;
+        if (a.sub_len[p] > plan->max_samples || a.ref_len[p] > plan->max_samples)
+            return fail(FFS_E_INVALID, "pair %d: lengths %lld / %lld exceed the plan's max_samples %lld", p,
+                        (long long)a.ref_len[p], (long long)a.sub_len[p], (long long)plan->max_samples);
+        const int64_t B = (a.sub_len[p] + K - 1) / K;
+        if (B > plan->max_blocks)
+            return fail(FFS_E_INVALID, "pair %d: %lld blocks exceed the plan's max_blocks %lld", p, (long long)B,
+                        (long long)plan->max_blocks);
+        if (lag_lo[p] > lag_hi[p] || lag_lo[p] < -(int64_t)INT32_MAX || lag_hi[p] > INT32_MAX)
+            return fail(FFS_E_INVALID, "pair %d: lag range [%lld, %lld]: need -(2^31 - 1) <= lag_lo <= lag_hi <= 2^31 - 1", p,
+                        (long long)lag_lo[p], (long long)lag_hi[p]);
+        if (lag_hi[p] - lag_lo[p] + 1 > plan->max_lags)
+            return fail(FFS_E_INVALID, "pair %d: %lld lags exceed the plan's max_lags %lld", p,
+                        (long long)(lag_hi[p] - lag_lo[p] + 1), (long long)plan->max_lags);
+        *max_b = std::max(*max_b, B);
+    }
+    return FFS_OK;
+}
+}  // namespace
 
 int ffs_align_split_range_batch(ffs_split_range_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
                                 const double* ref_lo, const double* ref_hi, const void* const* sub_ptr,
@@ -3417,23 +3453,7 @@ int ffs_align_split_range_batch(ffs_split_range_plan* plan, int n_pairs, const v
     if (int rc = check_block_samples(K)) return rc;
     if (!(split_penalty >= 0.0)) return fail(FFS_E_INVALID, "split_penalty must be >= 0 (not NaN)");
     int64_t max_b = 0;
-    for (int p = 0; p < n_pairs; ++p) {
-        if (int rc = a.check(p)) return rc;
-        if (sub_len[p] > plan->max_samples || ref_len[p] > plan->max_samples)
-            return fail(FFS_E_INVALID, "pair %d: lengths %lld / %lld exceed the plan's max_samples %lld", p,
-                        (long long)ref_len[p], (long long)sub_len[p], (long long)plan->max_samples);
-        const int64_t B = (sub_len[p] + K - 1) / K;
-        if (B > plan->max_blocks)
-            return fail(FFS_E_INVALID, "pair %d: %lld blocks exceed the plan's max_blocks %lld", p, (long long)B,
-                        (long long)plan->max_blocks);
-        if (lag_lo[p] > lag_hi[p] || lag_lo[p] < -(int64_t)INT32_MAX || lag_hi[p] > INT32_MAX)
-            return fail(FFS_E_INVALID, "pair %d: lag range [%lld, %lld]: need -(2^31 - 1) <= lag_lo <= lag_hi <= 2^31 - 1", p,
-                        (long long)lag_lo[p], (long long)lag_hi[p]);
-        if (lag_hi[p] - lag_lo[p] + 1 > plan->max_lags)
-            return fail(FFS_E_INVALID, "pair %d: %lld lags exceed the plan's max_lags %lld", p,
-                        (long long)(lag_hi[p] - lag_lo[p] + 1), (long long)plan->max_lags);
-        max_b = std::max(max_b, B);
-    }
+    if (int rc = range_pairs_check(plan, n_pairs, a, K, lag_lo, lag_hi, &max_b)) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
     if (int rc = plan->begin(st)) return rc;
     const int64_t pre_slot = split_align_up(2 * plan->pw, 64);
@@ -3469,6 +3489,142 @@ int ffs_align_split_range_batch(ffs_split_range_plan* plan, int n_pairs, const v
         hipLaunchKernelGGL(ffsa::k_range_scores, dim3((unsigned)((max_b + waves - 1) / waves), (unsigned)np),
                            dim3(ffsa::RANGE_SCORE_THREADS), 0, st, dd, dl, (int)K, max_b, block_offset_out_dev,
                            block_score_out_dev);
+        HIP_TRY(hipGetLastError());
+    }
+    return plan->end(st);
+}
+
+/* ---- per-piece report over a lag range (csrc/ffs_cut_report.h) ------------------------------------------------- */
+
+int ffs_split_range_report_batch(ffs_split_range_plan* plan, int n_pairs, const void* const* ref_ptr,
+                                 const int64_t* ref_len, const double* ref_lo, const double* ref_hi,
+                                 const void* const* sub_ptr, const int64_t* sub_len, const double* sub_lo,
+                                 const double* sub_hi, int64_t block_samples, const int64_t* lag_lo,
+                                 const int64_t* lag_hi, const int32_t* block_offset_dev, int top_k,
+                                 int64_t exclusion_samples, ffs_piece_report* out_dev, int32_t* n_pieces_out_dev,
+                                 void* hip_stream) {
+    const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
+    if (!plan) return fail(FFS_E_INVALID, "null split range plan");
+    if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
+    if (n_pairs == 0) return FFS_OK;
+    if (a.any_null() || !lag_lo || !lag_hi || !block_offset_dev || !out_dev || !n_pieces_out_dev)
+        return fail(FFS_E_INVALID, "null argument");
+    if (((uintptr_t)block_offset_dev & 3) || ((uintptr_t)out_dev & 7) || ((uintptr_t)n_pieces_out_dev & 3))
+        return fail(FFS_E_INVALID, "misaligned block offsets or report outputs");
+    const int64_t K = block_samples;
+    if (int rc = check_block_samples(K)) return rc;
+    if (top_k < 1 || top_k > ffsa::QUAL_MAX_PEAKS) return fail(FFS_E_INVALID, "top_k=%d outside [1, 8]", top_k);
+    if (exclusion_samples < 1) return fail(FFS_E_INVALID, "exclusion_samples=%lld: need >= 1", (long long)exclusion_samples);
+    int64_t max_b = 0;
+    if (int rc = range_pairs_check(plan, n_pairs, a, K, lag_lo, lag_hi, &max_b)) return rc;
+    // the block offsets on the host (after the stream's earlier work): checked against the ranges, then the rounds'
+    // work items are made from their pieces
+    hipStream_t st = (hipStream_t)hip_stream;
+    std::vector<int32_t> offs((size_t)n_pairs * max_b);
+    HIP_TRY(hipSetDevice(plan->device));
+    HIP_TRY(hipMemcpyAsync(offs.data(), block_offset_dev, offs.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int p = 0; p < n_pairs; ++p) {
+        const int64_t B = (sub_len[p] + K - 1) / K;
+        for (int64_t b = 0; b < B; ++b) {
+            const int64_t o = offs[(size_t)p * max_b + b];
+            if (o < lag_lo[p] || o > lag_hi[p])
+                return fail(FFS_E_INVALID, "pair %d: block %lld offset %lld outside the lag range [%lld, %lld]", p,
+                            (long long)b, (long long)o, (long long)lag_lo[p], (long long)lag_hi[p]);
+        }
+    }
+    if (int rc = plan->begin(st)) return rc;
+    const int pif = plan->pairs_in_flight;
+    constexpr int G = ffsa::CUT_ROUND_PIECES, CW = ffsa::CUT_CHUNK_WORDS;
+    if (!plan->rows) {  // the first report call: G n11 rows per pair in flight, and the work items of one sub-batch
+        plan->lpad = split_align_up(plan->max_lags, 64);
+        const int64_t row_bytes = (int64_t)pif * G * plan->lpad * 4;
+        // a pair's items over all its rounds: sum of ceil(piece words / CW) <= ceil(words / CW) + pieces
+        plan->item_cap = (int64_t)pif * ((plan->max_samples / 32 + 1 + CW - 1) / CW + plan->max_blocks);
+        const int64_t item_bytes = plan->item_cap * (int64_t)sizeof(ffsa::CutItem);
+        if (hipMalloc((void**)&plan->rows, row_bytes) != hipSuccess) {
+            plan->rows = nullptr;
+            return fail(FFS_E_NOMEM, "split range plan: %lld report workspace bytes", (long long)row_bytes);
+        }
+        if (int rc = plan->items.create((size_t)item_bytes)) {
+            (void)hipFree(plan->rows);
+            plan->rows = nullptr;
+            return fail(rc, "split range plan: report work items");
+        }
+        plan->report_bytes = row_bytes + item_bytes;
+    }
+    const int64_t pre_slot = split_align_up(2 * plan->pw, 64);
+    ffsa::SplitDesc* hd = (ffsa::SplitDesc*)plan->desc.host;
+    ffsa::RangeLag* hl = (ffsa::RangeLag*)(hd + pif);
+    const ffsa::SplitDesc* dd = (const ffsa::SplitDesc*)plan->desc.dev;
+    const ffsa::RangeLag* dl = (const ffsa::RangeLag*)(dd + pif);
+    ffsa::CutItem* hi_items = (ffsa::CutItem*)plan->items.host;
+    const ffsa::CutItem* di_items = (const ffsa::CutItem*)plan->items.dev;
+    std::vector<int64_t> round_start;  // per round: its first work item (+ the end)
+    for (int p0 = 0; p0 < n_pairs; p0 += pif) {
+        const int np = std::min(pif, n_pairs - p0);
+        if (int rc = plan->desc.wait_free()) return rc;
+        int64_t max_l = 0;
+        for (int i = 0; i < np; ++i) {
+            const int p = p0 + i;
+            int32_t* pre_s = plan->pre + (int64_t)i * pre_slot;
+            hd[i] = a.split_desc(p, pre_s, pre_s + plan->pw);
+            hl[i].lag_lo = lag_lo[p];
+            hl[i].L = lag_hi[p] - lag_lo[p] + 1;
+            max_l = std::max(max_l, hl[i].L);
+        }
+        if (int rc = plan->desc.upload(sizeof(ffsa::SplitDesc) * pif + sizeof(ffsa::RangeLag) * np, st)) return rc;
+        // the pieces of each pair (maximal runs of equal block offsets, as k_split_pieces forms them) -> work items,
+        // round by round: round r holds the pieces r*G .. r*G + G - 1 of every pair
+        std::vector<std::vector<int64_t>> starts(np);
+        int64_t max_pieces = 0;
+        for (int i = 0; i < np; ++i) {
+            const int p = p0 + i;
+            const int64_t B = (sub_len[p] + K - 1) / K;
+            const int32_t* o = offs.data() + (size_t)p * max_b;
+            for (int64_t b = 0; b < B; ++b)
+                if (b == 0 || o[b] != o[b - 1]) starts[i].push_back(b);
+            starts[i].push_back(B);
+            max_pieces = std::max(max_pieces, (int64_t)starts[i].size() - 1);
+        }
+        const int64_t n_rounds = (max_pieces + G - 1) / G;
+        if (int rc = plan->items.wait_free()) return rc;
+        round_start.assign(1, 0);
+        int64_t n_items = 0;
+        for (int64_t r = 0; r < n_rounds; ++r) {
+            for (int i = 0; i < np; ++i) {
+                const int64_t S = sub_len[p0 + i];
+                for (int g = 0; g < G; ++g) {
+                    const int64_t k = r * G + g;
+                    if (k + 1 >= (int64_t)starts[i].size()) break;
+                    const int64_t w0 = starts[i][k] * K / 32, w1 = (std::min(starts[i][k + 1] * K, S) + 31) / 32;
+                    for (int64_t c = w0; c < w1; c += CW) {
+                        ffsa::CutItem& it = hi_items[n_items++];
+                        it.g0 = c;
+                        it.row = i * G + g;
+                        it.nw = (int32_t)std::min<int64_t>(CW, w1 - c);
+                    }
+                }
+            }
+            round_start.push_back(n_items);
+        }
+        if (int rc = plan->items.upload(sizeof(ffsa::CutItem) * n_items, st)) return rc;
+        hipLaunchKernelGGL(ffsa::k_split_prefix, dim3(2 * np), dim3(ffsa::SPLIT_PREFIX_THREADS), 0, st, dd,
+                           (int64_t)plan->max_samples);
+        hipLaunchKernelGGL(ffsa::k_split_pieces, dim3(np), dim3(ffsa::PIECE_SCAN_THREADS), 0, st, dd, (int)K, max_b,
+                           block_offset_dev, (ffsa::PieceReport*)out_dev, n_pieces_out_dev);
+        const int64_t n_tiles = (max_l + ffsa::QUAL_TILE - 1) / ffsa::QUAL_TILE;
+        for (int64_t r = 0; r < n_rounds; ++r) {
+            HIP_TRY(hipMemsetAsync(plan->rows, 0, (size_t)np * G * plan->lpad * 4, st));
+            for (int64_t q = round_start[r]; q < round_start[r + 1]; q += ffsa::CUT_MAX_ITEMS) {
+                const int64_t nq = std::min<int64_t>(ffsa::CUT_MAX_ITEMS, round_start[r + 1] - q);
+                hipLaunchKernelGGL(ffsa::k_cut_piece_counts, dim3((unsigned)n_tiles, (unsigned)nq),
+                                   dim3(ffsa::QUAL_CNT_THREADS), 0, st, dd, dl, di_items + q, plan->rows, plan->lpad);
+            }
+            hipLaunchKernelGGL(ffsa::k_cut_piece_report, dim3((unsigned)(np * G)), dim3(ffsa::QUAL_PEAK_THREADS), 0, st,
+                               dd, dl, (const uint32_t*)plan->rows, plan->lpad, (int)(r * G), max_b, top_k,
+                               exclusion_samples, (const int32_t*)n_pieces_out_dev, (ffsa::PieceReport*)out_dev);
+        }
         HIP_TRY(hipGetLastError());
     }
     return plan->end(st);

@@ -86,14 +86,9 @@ def clear_plan_cache() -> None:
     _plans.clear()
 
 
-def split_align_range_batch(batch, lag_ranges=None, block_samples: int = DEFAULT_BLOCK_SAMPLES,
-                            split_penalty: float = DEFAULT_CUT_PENALTY,
-                            pairs_in_flight: Optional[int] = None) -> List[SplitResult]:
-    """Piecewise offsets of every pair of a ``batch.DeviceBatch`` with ONE candidate per pair, as
-    ``split_align.split_align_batch``, over lags d in [lag_lo, lag_hi]: ``lag_ranges`` is one (lag_lo, lag_hi) for
-    every pair, a list of one per pair, or None for each pair's full overlap range [-(S-1), R-1]."""
-    validate_args(block_samples, split_penalty)
-    _check_batch(batch)
+def lag_arrays(batch, lag_ranges) -> Tuple[np.ndarray, np.ndarray]:
+    """(lag_lo, lag_hi) int64 arrays of one pair each: ``lag_ranges`` one (lag_lo, lag_hi) for every pair, a list of one
+    per pair, or None for each pair's full overlap range [-(S-1), R-1] (ValueError for a bad range)."""
     n = batch.n_pairs
     ref_len, sub_len = batch.lens[:, 0].astype(np.int64), batch.lens[:, 1].astype(np.int64)
     if lag_ranges is None:
@@ -105,12 +100,24 @@ def split_align_range_batch(batch, lag_ranges=None, block_samples: int = DEFAULT
             raise ValueError("%d lag ranges for %d pairs" % (len(lag_ranges), n))
         ranges = [validate_range(r) for r in lag_ranges]
     ranges = [validate_range(r) for r in ranges]
+    return np.array([r[0] for r in ranges], np.int64), np.array([r[1] for r in ranges], np.int64)
+
+
+def split_align_range_batch(batch, lag_ranges=None, block_samples: int = DEFAULT_BLOCK_SAMPLES,
+                            split_penalty: float = DEFAULT_CUT_PENALTY,
+                            pairs_in_flight: Optional[int] = None) -> List[SplitResult]:
+    """Piecewise offsets of every pair of a ``batch.DeviceBatch`` with ONE candidate per pair, as
+    ``split_align.split_align_batch``, over lags d in [lag_lo, lag_hi]: ``lag_ranges`` is one (lag_lo, lag_hi) for
+    every pair, a list of one per pair, or None for each pair's full overlap range [-(S-1), R-1]."""
+    validate_args(block_samples, split_penalty)
+    _check_batch(batch)
+    n = batch.n_pairs
+    ref_len, sub_len = batch.lens[:, 0].astype(np.int64), batch.lens[:, 1].astype(np.int64)
+    lo, hi = lag_arrays(batch, lag_ranges)
     _native.require_gpu()
     if batch.dtype == _native.FFS_DTYPE_U8:
         batch = batch.to_bits()
     k = int(block_samples)
-    lo = np.array([r[0] for r in ranges], np.int64)
-    hi = np.array([r[1] for r in ranges], np.int64)
     n_blocks = (sub_len + k - 1) // k
     max_b = int(n_blocks.max())
     plan = _get_plan(n, max_b, int((hi - lo + 1).max()), int(max(sub_len.max(), ref_len.max())), pairs_in_flight)
@@ -176,10 +183,16 @@ def cut_sync(problems, lag_range=None, block_samples: int = DEFAULT_BLOCK_SAMPLE
     split_refine.validate_args(block_samples, radius_samples, unmatched_margin)
     if lag_range is not None:
         lag_range = validate_range(lag_range)
+    split = lambda chosen: split_align_range_batch(chosen, lag_range, block_samples, split_penalty)
+    return _cut_sync(problems, lag_range, block_samples, radius_samples, unmatched_margin, sample_rate, ratios, split)
+
+
+def _cut_sync(problems, lag_range, block_samples, radius_samples, unmatched_margin, sample_rate, ratios, split):
+    """``cut_sync``'s work (arguments checked) with ``split(chosen batch)`` -> one SplitResult per problem."""
     ratios = list(candidate_ratios() if ratios is None else ratios)
     db, best, pres = solve_ratios_windowless(problems, ratios, sample_rate)
     chosen = db.select_candidates(best)
-    results = split_align_range_batch(chosen, lag_range, block_samples, split_penalty)
+    results = split(chosen)
     breaks = split_refine.refine_breaks_batch(chosen, results, block_samples, radius_samples, unmatched_margin)
     out = []
     for p, ((_, (start_us, end_us, _meta)), res, brk) in enumerate(zip(problems, results, breaks)):

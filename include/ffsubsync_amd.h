@@ -602,6 +602,30 @@ int ffs_align_split_range_batch(ffs_split_range_plan* plan, int n_pairs, const v
                                 int32_t* block_offset_out_dev, double* block_score_out_dev, double* total_out_dev,
                                 void* hip_stream);
 
+/* ---- per-piece report of a split over any lag range (csrc/ffs_cut_report.h) ---------------------------------------
+ * Replaces: nothing in the reference.  The contract below is pinned against the numpy model tests/cut_report_model.py.
+ *
+ * ffs_align_split_report_batch's piece records for the block offsets of a split solve (block_offset_dev[p * max_b + b],
+ * as ffs_align_split_range_batch writes them, every o_b inside [lag_lo_p, lag_hi_p]) over the lag set
+ * d in [lag_lo_p, lag_hi_p] instead of [-W+1, W]: each piece's curve has n11 counted exactly from the bits, lags without
+ * overlap score exactly 0.0 and count, and n_lags = lag_hi - lag_lo + 1.  At [-W+1, W], given the windowed split's block
+ * offsets, the records are bit-identical to ffs_align_split_report_batch's.  report_out_dev: n_pairs * max_b records
+ * (8-byte aligned; records past the count zero); n_pieces_out_dev: n_pairs int32.
+ *
+ * The call reads the block offsets back once (it waits for hip_stream's earlier work) to check them and to schedule its
+ * rounds; the kernels run on hip_stream.  Pieces are reported 8 per pair and round, so the first report call on a plan
+ * adds pairs_in_flight * 8 uint32 rows of max_lags plus a small work-item table, whatever the piece count; it is counted
+ * by ffs_split_range_plan_workspace_bytes from then on.  FFS_E_INVALID / FFS_E_EMPTY as ffs_align_split_range_batch,
+ * and FFS_E_INVALID for top_k outside [1, 8], exclusion_samples < 1, a null / misaligned offset or report pointer, or a
+ * block offset outside its pair's range; all before any launch, the outputs untouched. */
+int ffs_split_range_report_batch(ffs_split_range_plan* plan, int n_pairs, const void* const* ref_ptr,
+                                 const int64_t* ref_len, const double* ref_lo, const double* ref_hi,
+                                 const void* const* sub_ptr, const int64_t* sub_len, const double* sub_lo,
+                                 const double* sub_hi, int64_t block_samples, const int64_t* lag_lo,
+                                 const int64_t* lag_hi, const int32_t* block_offset_dev, int top_k,
+                                 int64_t exclusion_samples, ffs_piece_report* report_out_dev,
+                                 int32_t* n_pieces_out_dev, void* hip_stream);
+
 /* Thread-local description of the last error returned on this thread ("" if none). */
 const char* ffs_last_error(void);
 
