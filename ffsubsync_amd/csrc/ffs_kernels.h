@@ -2498,7 +2498,8 @@ __global__ void k_vad_tokenize(const float* __restrict__ valid, long long n_fram
     const long long n = (f0 + chunk) < n_frames ? chunk : (n_frames - f0);
     const float* v = valid + f0;
     float* o = out + f0;
-    // markers live in the output buffer itself (slot n, the one past the end, is tracked separately)
+    // marker CODES live in the output buffer itself: +1 = start of a token, -1 = the frame behind its end (slot n, the
+    // one past the end, needs none); the last pass turns their counts into labels
     for (long long i = 0; i < n; ++i) o[i] = 0.0f;
     enum { SILENCE = 0, POSSIBLE_SILENCE = 1, NOISE = 3 };
     int state = SILENCE, silence_len = 0;
@@ -2509,7 +2510,7 @@ __global__ void k_vad_tokenize(const float* __restrict__ valid, long long n_fram
         if (len >= min_len || (len > 0 && contiguous)) {
             const long long end = start + len - 1;
             o[start] = 1.0f;
-            if (end + 1 < n) o[end + 1] = non_speech - 1.0f;
+            if (end + 1 < n) o[end + 1] = -1.0f;
             if (truncated) {
                 start = cur + 1;
                 contiguous = true;
@@ -2566,11 +2567,14 @@ __global__ void k_vad_tokenize(const float* __restrict__ valid, long long n_fram
     }
     // _post_process: flush a token still open at the end of the chunk
     if ((state == NOISE || state == POSSIBLE_SILENCE) && len > 0 && len > silence_len) deliver(false, n - 1);
-    // clip(cumsum(markers)[:-1], 0, 1)
-    float acc = 0.0f;
+    // clip(cumsum(markers)[:-1], 0, 1) from the marker counts, in the arithmetic of k_vad_tokenize_scan's P5 (the two
+    // kernels return the same bits): the end marker is (double)non_speech - 1, the sum is rounded to float once
+    const double m_end = (double)non_speech - 1.0;
+    long long cp = 0, cm = 0;
     for (long long i = 0; i < n; ++i) {
-        acc += o[i];
-        o[i] = fminf(fmaxf(acc, 0.0f), 1.0f);
+        cp += o[i] > 0.0f;
+        cm += o[i] < 0.0f;
+        o[i] = (float)fmin(fmax((double)cp + (double)cm * m_end, 0.0), 1.0);
     }
 }
 
@@ -2600,8 +2604,9 @@ __global__ void k_vad_tokenize(const float* __restrict__ valid, long long n_fram
 //       island's pieces in two more bit arrays (P: +1, M: non_speech - 1; a frame in both carries the +1); the island's
 //       end is min(n, last valid frame in front of the next start + max_sil + 1);
 //   P5  clip(cumsum) per frame without a sum over frames: label(i) = clamp(#P(<= i) + #M(<= i) (non_speech - 1), 0, 1),
-//       the counts from a packed prefix count per word + a popcount (fp64; equal to the sequential sum whenever that one
-//       is exact -- every term is a float -- which is what rounds 4-6's blocked prefix sum relied on as well).
+//       the counts from a packed prefix count per word + a popcount; fp64 with the end marker (double)non_speech - 1,
+//       rounded to float once (k_vad_tokenize ends with the same expression: identical bits from both kernels, and
+//       the first silence behind a token is non_speech itself, as k_vad_energy writes it).
 // Frames map to lanes the same way in P0 and P5: wave v owns the words v, v + 16, ...; lane k of the wave holds the
 // wave's k-th word of every bit array in a register (v_readlane hands it to the whole wave: no LDS round trip per word),
 // lane l of the wave is frame 64 w + l of the word being processed -- loads and stores are coalesced.
@@ -2856,7 +2861,7 @@ __global__ __launch_bounds__(TOK_THREADS) void k_vad_tokenize_scan(const float* 
         unsigned long long p_reg = 0ull, m_reg = 0ull;
         int pp_reg = 0;
         if (own) p_reg = s_P[my_w], m_reg = s_M[my_w] & ~p_reg, pp_reg = s_PP[my_w];
-        const double m_end = (double)(non_speech - 1.0f);
+        const double m_end = (double)non_speech - 1.0;  // not non_speech - 1.0f, which rounds
         const unsigned long long le = ~0ull >> (63 - lane);  // this frame and the frames of its word in front of it
         for (int k = 0; wave + NWV * k < W; ++k) {
             const int i = ((wave + NWV * k) << 6) + lane;

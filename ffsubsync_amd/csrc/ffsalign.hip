@@ -2654,12 +2654,15 @@ int ffs_pack_bits(const void* src_dev, int src_dtype, int64_t n, double threshol
     const long long n_words = (n + 31) / 32;
     long long blocks = (n_words + 255) / 256;
     if (blocks > 65536) blocks = 65536;
+    // the kernel compares floats: for a float x, x > threshold <=> x > (the largest float not above the threshold)
+    float thr = (float)threshold;
+    if ((double)thr > threshold) thr = nextafterf(thr, -INFINITY);
     if (src_dtype == FFS_DTYPE_U8)
         hipLaunchKernelGGL((k_pack_bits<0>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)hip_stream, src_dev, (long long)n,
-                           (float)threshold, dst_dev, n_words);
+                           thr, dst_dev, n_words);
     else
         hipLaunchKernelGGL((k_pack_bits<1>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)hip_stream, src_dev, (long long)n,
-                           (float)threshold, dst_dev, n_words);
+                           thr, dst_dev, n_words);
     HIP_TRY(hipGetLastError());
     return FFS_OK;
 }
@@ -2669,7 +2672,10 @@ int ffs_scatter_segments(const float* seg_labels_dev, const int64_t* seg_src_off
     if (n_segments < 0 || out_len < 0 || (n_segments > 0 && (!seg_src_off || !seg_dst_start || !seg_len)))
         return fail(FFS_E_INVALID, "bad argument");
     if (out_len == 0) return FFS_OK;
-    if (!out_dev || (n_segments > 0 && !seg_labels_dev)) return fail(FFS_E_INVALID, "null device pointer");
+    if (!out_dev) return fail(FFS_E_INVALID, "null device pointer");
+    if (!seg_labels_dev)  // fine as long as no window holds a label (a detector that returned nothing)
+        for (int i = 0; i < n_segments; ++i)
+            if (seg_len[i] > 0) return fail(FFS_E_INVALID, "null device pointer");
     hipStream_t st = (hipStream_t)hip_stream;
     DeviceGuard guard;
     int rc;

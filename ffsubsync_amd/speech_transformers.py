@@ -41,6 +41,12 @@ def _as_int16_bytes(asegment) -> np.ndarray:
     return buf[: buf.size // BYTES_PER_SAMPLE * BYTES_PER_SAMPLE].view("<i2")
 
 
+def _labels_float64(speech, non_speech_label: float) -> np.ndarray:
+    """The detectors' float64 result from the sweep run with label 0: exactly ``non_speech_label`` where the frame is
+    not speech (speech_transformers.py:133-150), not its float32 rounding -- the kernel's labels are float32."""
+    return np.where(speech.cpu().numpy() != 0, 1.0, float(non_speech_label))
+
+
 def _make_energy_detector(sample_rate: int, frame_rate: int, non_speech_label: float,
                           energy_threshold_db: float = DEFAULT_ENERGY_THRESHOLD_DB
                           ) -> Callable[[Union[bytes, np.ndarray]], np.ndarray]:
@@ -53,8 +59,7 @@ def _make_energy_detector(sample_rate: int, frame_rate: int, non_speech_label: f
         if pcm.size == 0:
             return np.zeros(0, dtype=float)
         dev = torch.from_numpy(pcm.copy()).cuda()
-        labels = _native.vad_energy(dev, frame_len, energy_threshold_db, non_speech_label)
-        return labels.cpu().numpy().astype(float)
+        return _labels_float64(_native.vad_energy(dev, frame_len, energy_threshold_db, 0.0), non_speech_label)
 
     return _detect
 
@@ -212,12 +217,17 @@ class ComputeSpeechFrameBoundariesMixin:
 
     def fit_boundaries(self, speech_frames) -> "ComputeSpeechFrameBoundariesMixin":
         torch = _native.require_gpu()
-        if hasattr(speech_frames, "frames_float"):  # a DeviceRaster
-            frames = speech_frames.frames_float()
+        # the reference compares the caller's values with 0.5 (:310-317); the kernel compares float32, so anything wider
+        # or narrower is compared here, in its own precision, and the kernel scans the 0/1 outcome
+        if hasattr(speech_frames, "bytes01"):  # a DeviceRaster: two float64 levels
+            hi, lo = float(speech_frames.hi > 0.5), float(speech_frames.lo > 0.5)
+            frames = (speech_frames.bytes01() != 0).to(torch.float32) * (hi - lo) + lo
         elif isinstance(speech_frames, np.ndarray) or not hasattr(speech_frames, "is_cuda"):
-            frames = torch.from_numpy(np.asarray(speech_frames, dtype=np.float32)).cuda()
+            frames = torch.from_numpy((np.asarray(speech_frames) > 0.5).astype(np.float32)).cuda()
+        elif speech_frames.dtype == torch.float32:
+            frames = speech_frames.cuda()
         else:
-            frames = speech_frames.to(torch.float32)
+            frames = (speech_frames > 0.5).to(torch.float32).cuda()
         lo, hi = _native.speech_bounds(frames)
         if hi is not None:
             self.start_frame_, self.end_frame_ = lo, hi
@@ -300,10 +310,10 @@ class PCMSpeechTransformer(TransformerMixin):
             copied[k] = torch.cuda.Event()
             copied[k].record()
             pcm = device[k][:n].view(torch.int16)
-            labels.append(_native.vad_energy(pcm, frame_len, DEFAULT_ENERGY_THRESHOLD_DB, self._non_speech_label))
+            labels.append(_native.vad_energy(pcm, frame_len, DEFAULT_ENERGY_THRESHOLD_DB, 0.0))
         if not labels:
             return []
-        return [torch.cat(labels).cpu().numpy().astype(float)]
+        return [_labels_float64(torch.cat(labels), self._non_speech_label)]
 
     def fit(self, source, *_) -> "PCMSpeechTransformer":
         bytes_per_window = BYTES_PER_SAMPLE * self.frame_rate // self.sample_rate  # :683-684

@@ -90,13 +90,6 @@ class DeviceRaster:
         out = np.where(host != 0, self.hi, self.lo).astype(float)
         return out if dtype is None else out.astype(dtype)
 
-    def frames_float(self):
-        """float32 CUDA tensor of the sample values (for the boundary scan)."""
-        import torch
-
-        b = self.bytes01()
-        return torch.where(b != 0, torch.tensor(self.hi, device=b.device),
-                           torch.tensor(self.lo, device=b.device)).to(torch.float32)
 
 
 def _microseconds(td: timedelta) -> int:
@@ -183,7 +176,7 @@ class DeviceSubtitleSpeechTransformer(TransformerMixin, ComputeSpeechFrameBounda
         self.subtitle_speech_results_ = DeviceRaster(words, 0.0, min(1.0 / self.framerate_ratio, 1.0), n)
         _attach_interval_lists([self.subtitle_speech_results_], start_us, end_us, meta, [1.0], self.sample_rate,
                                self.start_seconds)
-        self.fit_boundaries(self.subtitle_speech_results_.frames_float())
+        self.fit_boundaries(self.subtitle_speech_results_)
         return self
 
     def transform(self, *_) -> DeviceRaster:

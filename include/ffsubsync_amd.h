@@ -227,7 +227,10 @@ int ffs_correlate_full(ffs_plan* plan, int dtype,
  *                                                                           : non_speech_label
  * for f in [0, ceil(n_samples/frame_len)); the last frame may be short.  Replaces the
  * per-frame Python loop of the detector closures (speech_transformers.py:133-150, 169-181)
- * with the AudioEnergyValidator rule (threshold 50 dB in the reference, :124). */
+ * with the AudioEnergyValidator rule (threshold 50 dB in the reference, :124).  The rule is evaluated as
+ * sum(x^2) >= 10^(energy_threshold_db/10) * n on the exact 64-bit sum, so a frame exactly at the threshold is
+ * speech.  The labels are float32: a non_speech_label that float32 cannot hold (0.1) comes back rounded, and a
+ * caller that owes float64 labels (the detector closures) maps the speech flags on the host instead. */
 int ffs_vad_energy(const int16_t* pcm_dev, int64_t n_samples, int frame_len,
                    double energy_threshold_db, float non_speech_label,
                    float* labels_dev, void* hip_stream);
@@ -254,14 +257,21 @@ int ffs_vad_energy_bits(const int16_t* pcm_dev, int64_t n_samples, int frame_len
  * Chunks of up to 28672 frames with max_length >= min_length >= 0 run as one workgroup per chunk (k_vad_tokenize_scan:
  * validity and island starts as bit words, markers written island by island; model:
  * oracle/vad_oracle.py::tokenize_chunk_words); anything else as one thread per chunk walking the state machine.
- * Identical outputs. */
+ * Identical outputs, bit for bit.
+ * Precision: the labels are float32 and non_speech_label arrives as a float.  With cp / cm the number of start / end
+ * markers at or in front of a frame, labels_dev[f] = (float)clip(cp + cm * ((double)non_speech_label - 1), 0, 1),
+ * evaluated in fp64 and rounded once: equal to the reference's float64 result for labels float32 holds exactly
+ * (0, 0.25, -1), within (cm + 1) * 2^-25 of it otherwise, and the first silence behind a token is
+ * (float)non_speech_label itself, as ffs_vad_energy writes it. */
 int ffs_vad_tokenize(const float* valid_dev, int64_t n_frames, int64_t chunk_frames, int min_length,
                      int max_length, int max_continuous_silence, float non_speech_label,
                      float* labels_dev, void* hip_stream);
 
 /* ComputeSpeechFrameBoundariesMixin.fit_boundaries (speech_transformers.py:310-317):
  * bounds_dev[0] = first index with frames[i] > 0.5, bounds_dev[1] = last such index;
- * both -1 when there is none. */
+ * both -1 when there is none.  The comparison is float32's (NaN is not speech): a caller whose values are wider
+ * than float32 compares them itself and passes the 0/1 outcome (fit_boundaries does), because a float64 just above
+ * 0.5 narrows to 0.5. */
 int ffs_speech_bounds(const float* frames_dev, int64_t n_frames, int64_t* bounds_dev,
                       void* hip_stream);
 
@@ -336,15 +346,20 @@ int ffs_rasterize_batch_runs(const int64_t* start_us, const int64_t* end_us, con
 int ffs_two_level_pack(const double* x, int64_t n, double* lo_out, double* hi_out, uint32_t* words);
 
 /* Two-level vector -> FFS_DTYPE_U1 on the device.  src_dtype FFS_DTYPE_U8: bit = (byte != 0);
- * FFS_DTYPE_F32: bit = (x > threshold), e.g. VAD labels against 0.5 or (lo+hi)/2.  Writes
- * ceil(n/32) words; unused high bits of the last word are 0. */
+ * FFS_DTYPE_F32: bit = (x > threshold), e.g. VAD labels against 0.5 or (lo+hi)/2, decided against the double
+ * threshold exactly (the kernel compares with the largest float not above it, which is the same predicate for a
+ * float x: float32(0.1) > 0.1 is 1); NaN samples give 0.  Writes ceil(n/32) words; unused high bits of the last
+ * word are 0. */
 int ffs_pack_bits(const void* src_dev, int src_dtype, int64_t n, double threshold, uint32_t* dst_dev,
                   void* hip_stream);
 
 /* Sparse reference assembly of MultiSegmentVideoSpeechTransformer.fit (speech_transformers.py:871-890):
  * out = zeros(out_len); out[dst_start[i] : dst_start[i]+len[i]] = labels[src_off[i] : src_off[i]+len[i]]
  * for every sampled window i (clipped at out_len, Python slice semantics), in one device pass.
- * seg_* are HOST arrays of n_segments entries; seg_labels_dev holds the windows' VAD labels. */
+ * seg_* are HOST arrays of n_segments entries; seg_labels_dev holds the windows' VAD labels (it may be null when
+ * every window is empty).  Windows of ONE call must not overlap inside [0, out_len): they are copied concurrently
+ * and overlapping ones race.  A caller with overlapping windows splits them into calls of non-overlapping runs and
+ * applies those in order, later window wins, as the reference's loop does (assemble_sparse_reference). */
 int ffs_scatter_segments(const float* seg_labels_dev, const int64_t* seg_src_off, const int64_t* seg_dst_start,
                          const int64_t* seg_len, int n_segments, float* out_dev, int64_t out_len,
                          void* hip_stream);
