@@ -115,6 +115,10 @@ EXPORTED_SYMBOLS = (
     "ffs_split_range_plan_workspace_bytes",
     "ffs_align_split_range_batch",
     "ffs_split_range_report_batch",
+    "ffs_drift_plan_create",
+    "ffs_drift_plan_destroy",
+    "ffs_drift_plan_workspace_bytes",
+    "ffs_align_drift_batch",
     "ffs_quality_plan_create",
     "ffs_quality_plan_destroy",
     "ffs_quality_plan_workspace_bytes",
@@ -315,6 +319,17 @@ def load():
                                                      c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p,
                                                      c.c_void_p, c.c_void_p, c.c_int, c.c_int64, c.c_void_p, c.c_void_p,
                                                      c.c_void_p]
+        lib.ffs_drift_plan_create.restype = c.c_int
+        lib.ffs_drift_plan_create.argtypes = [c.c_int, c.c_int, c.c_int64, c.c_int64, c.c_int64, c.POINTER(c.c_void_p)]
+        lib.ffs_drift_plan_destroy.restype = c.c_int
+        lib.ffs_drift_plan_destroy.argtypes = [c.c_void_p]
+        lib.ffs_drift_plan_workspace_bytes.restype = c.c_int64
+        lib.ffs_drift_plan_workspace_bytes.argtypes = [c.c_void_p]
+        lib.ffs_align_drift_batch.restype = c.c_int
+        lib.ffs_align_drift_batch.argtypes = [c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                                              c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64,
+                                              c.c_double, c.c_int, c.c_double, c.c_void_p, c.c_void_p, c.c_void_p,
+                                              c.c_void_p, c.c_void_p]
         lib.ffs_quality_plan_create.restype = c.c_int
         lib.ffs_quality_plan_create.argtypes = [c.c_int, c.c_int, c.c_int64, c.c_int64, c.POINTER(c.c_void_p)]
         lib.ffs_quality_plan_destroy.restype = c.c_int
@@ -938,6 +953,34 @@ class SplitPlan(_SidePlan):
         check(self.lib.ffs_split_refine_batch(self.handle, n, *ptrs, int(block_samples), offsets.data_ptr(),
                                               int(radius_samples), float(unmatched_margin), refine_out.data_ptr(),
                                               n_breaks_out.data_ptr(), self._stream(stream)))
+
+
+MAX_DRIFT_STEP = 7  # DRIFT_MAX_STEP (csrc/ffs_drift.h): the 4-bit code holds STAY, 14 moves and JUMP
+
+
+class DriftPlan(_SidePlan):
+    """Owns one ``ffs_drift_plan``: the workspace of the drift-tolerant aligner (``drift_align.py``) for
+    ``pairs_in_flight`` problems of up to ``max_samples`` subtitle samples, ``max_blocks`` blocks and ``max_lags`` = 2W
+    lags."""
+
+    _create, _destroy, _workspace = "ffs_drift_plan_create", "ffs_drift_plan_destroy", "ffs_drift_plan_workspace_bytes"
+
+    def __init__(self, pairs_in_flight: int, max_blocks: int, max_lags: int, max_samples: int,
+                 device: Optional[int] = None) -> None:
+        self.pairs_in_flight, self.max_blocks = int(pairs_in_flight), int(max_blocks)
+        self.max_lags, self.max_samples = int(max_lags), int(max_samples)
+        super().__init__((pairs_in_flight, max_blocks, max_lags, max_samples), device)
+
+    def align(self, ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, block_samples: int,
+              max_offset_samples: int, split_penalty: float, max_step: int, step_cost: float, offsets_out, scores_out,
+              jumps_out, totals_out, stream: Optional[int] = None) -> None:
+        """``ffs_align_drift_batch`` on host descriptor arrays (one entry per pair) into int32 / float64 / uint8 /
+        float64 CUDA tensors of n_pairs * max_b (three times) and n_pairs entries (asynchronous)."""
+        n, ptrs, _bufs = _pair_buffers(ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi)
+        check(self.lib.ffs_align_drift_batch(self.handle, n, *ptrs, int(block_samples), int(max_offset_samples),
+                                             float(split_penalty), int(max_step), float(step_cost),
+                                             offsets_out.data_ptr(), scores_out.data_ptr(), jumps_out.data_ptr(),
+                                             totals_out.data_ptr(), self._stream(stream)))
 
 
 class SplitRangePlan(_SidePlan):

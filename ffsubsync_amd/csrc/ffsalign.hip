@@ -31,6 +31,7 @@
 #include "ffs_split_refine.h"
 #include "ffs_split_range.h"
 #include "ffs_cut_report.h"
+#include "ffs_drift.h"
 
 using namespace ffsa;
 
@@ -1003,7 +1004,7 @@ void fill_xform(XformDesc* x, const VecView* a, const VecView* b, const void* sa
 extern "C" {
 
 const char* ffs_last_error(void) { return g_err.c_str(); }
-int ffs_version(void) { return 360; }
+int ffs_version(void) { return 370; }
 
 int64_t ffs_fft_length(int64_t ref_len, int64_t sub_len) {
     if (ref_len <= 0 || sub_len <= 0) return 0;
@@ -3631,6 +3632,141 @@ int ffs_split_range_report_batch(ffs_split_range_plan* plan, int n_pairs, const 
                                dd, dl, (const uint32_t*)plan->rows, plan->lpad, (int)(r * G), max_b, top_k,
                                exclusion_samples, (const int32_t*)n_pieces_out_dev, (ffsa::PieceReport*)out_dev);
         }
+        HIP_TRY(hipGetLastError());
+    }
+    return plan->end(st);
+}
+
+/* ---- drift-tolerant alignment (csrc/ffs_drift.h) --------------------------------------------------------------- */
+
+struct ffs_drift_plan : PlanCore {
+    int64_t max_blocks, max_lags, max_samples;
+    int64_t lpad, pw_s, pw_r;    // padded lag row, prefix words per vector
+    ffsa::SplitWs ws;            // counts, two V rows per slot (v_slot = 2 rows), arg; no stay bits
+    unsigned long long* codes;   // [slot][max_blocks][lpad / 64][DRIFT_PLANES]
+    int64_t codes_slot;
+    int32_t* pre;                // [slot][pw_s + pw_r]
+    DescStaging desc;            // SplitDesc[pairs_in_flight]
+};
+
+int ffs_drift_plan_create(int device, int pairs_in_flight, int64_t max_blocks, int64_t max_lags, int64_t max_samples,
+                          ffs_drift_plan** out) {
+    if (!out) return fail(FFS_E_INVALID, "null output handle");
+    *out = nullptr;
+    if (pairs_in_flight < 1 || max_blocks < 1 || max_lags < 2 || max_lags > 262144 || max_samples < 1)
+        return fail(FFS_E_INVALID, "drift plan: need pairs_in_flight >= 1, max_blocks >= 1, 2 <= max_lags <= 262144, "
+                                   "max_samples >= 1");
+    HIP_TRY(hipSetDevice(device));
+    ffs_drift_plan* p = new (std::nothrow) ffs_drift_plan();
+    if (!p) return fail(FFS_E_NOMEM, "drift plan");
+    p->max_blocks = max_blocks;
+    p->max_lags = max_lags;
+    p->max_samples = max_samples;
+    p->lpad = split_align_up(max_lags, 64);
+    p->pw_s = max_samples / 32 + 2;
+    p->pw_r = (max_samples + max_lags / 2) / 32 + 2;
+    const int64_t counts_slot = split_align_up(max_blocks * p->lpad, 128);                              // uint16
+    const int64_t codes_slot = split_align_up(max_blocks * (p->lpad / 64) * ffsa::DRIFT_PLANES, 32);    // uint64
+    const int64_t v_slot = 2 * split_align_up(p->lpad, 32);                                             // double, two rows
+    const int64_t arg_slot = split_align_up(max_blocks, 64);                                            // int32
+    const int64_t pre_slot = split_align_up(p->pw_s + p->pw_r, 64);                                     // int32
+    const int64_t n = pairs_in_flight;
+    const int64_t b_counts = n * counts_slot * 2, b_codes = n * codes_slot * 8, b_v = n * v_slot * 8, b_arg = n * arg_slot * 4,
+                  b_pre = n * pre_slot * 4;
+    if (int rc = p->open(device, pairs_in_flight, b_counts + b_codes + b_v + b_arg + b_pre, "drift plan")) {
+        ffs_drift_plan_destroy(p);
+        return rc;
+    }
+    char* w = (char*)p->work;
+    p->ws.counts = (uint16_t*)w;
+    p->ws.stay = nullptr;
+    p->codes = (unsigned long long*)(w + b_counts);
+    p->ws.V = (double*)(w + b_counts + b_codes);
+    p->ws.arg = (int32_t*)(w + b_counts + b_codes + b_v);
+    p->pre = (int32_t*)(w + b_counts + b_codes + b_v + b_arg);
+    p->ws.counts_row = p->lpad;
+    p->ws.stay_row = p->lpad / 64;
+    p->ws.counts_slot = counts_slot;
+    p->ws.stay_slot = 0;
+    p->codes_slot = codes_slot;
+    p->ws.v_slot = v_slot;
+    p->ws.arg_slot = arg_slot;
+    if (p->desc.create(sizeof(ffsa::SplitDesc) * (size_t)pairs_in_flight) != FFS_OK) {
+        ffs_drift_plan_destroy(p);
+        return fail(FFS_E_HIP, "drift plan: descriptor buffers / events");
+    }
+    *out = p;
+    return FFS_OK;
+}
+
+int ffs_drift_plan_destroy(ffs_drift_plan* plan) {
+    if (!plan) return FFS_OK;
+    plan->close();
+    plan->desc.release();
+    delete plan;
+    return FFS_OK;
+}
+
+int64_t ffs_drift_plan_workspace_bytes(const ffs_drift_plan* plan) { return plan ? plan->work_bytes : 0; }
+
+int ffs_align_drift_batch(ffs_drift_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
+                          const double* ref_lo, const double* ref_hi, const void* const* sub_ptr, const int64_t* sub_len,
+                          const double* sub_lo, const double* sub_hi, int64_t block_samples, int64_t max_offset_samples,
+                          double split_penalty, int max_step, double step_cost, int32_t* block_offset_out_dev,
+                          double* block_score_out_dev, uint8_t* block_jump_out_dev, double* total_out_dev,
+                          void* hip_stream) {
+    const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
+    if (!plan) return fail(FFS_E_INVALID, "null drift plan");
+    if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
+    if (n_pairs == 0) return FFS_OK;
+    if (a.any_null() || !block_offset_out_dev || !block_score_out_dev || !block_jump_out_dev || !total_out_dev)
+        return fail(FFS_E_INVALID, "null argument");
+    const int64_t K = block_samples, W = max_offset_samples;
+    if (int rc = check_block_samples(K)) return rc;
+    if (W < 1 || 2 * W > 262144) return fail(FFS_E_INVALID, "max_offset_samples=%lld: need 1 <= W, 2W <= 262144", (long long)W);
+    if (2 * W > plan->max_lags)
+        return fail(FFS_E_INVALID, "2 * max_offset_samples = %lld exceeds the plan's max_lags %lld", (long long)(2 * W),
+                    (long long)plan->max_lags);
+    if (!(split_penalty >= 0.0)) return fail(FFS_E_INVALID, "split_penalty must be >= 0 (not NaN)");
+    if (max_step < 0 || max_step > ffsa::DRIFT_MAX_STEP)
+        return fail(FFS_E_INVALID, "max_step=%d outside [0, %d]", max_step, ffsa::DRIFT_MAX_STEP);
+    if (!(step_cost >= 0.0) || !std::isfinite(step_cost)) return fail(FFS_E_INVALID, "step_cost must be finite and >= 0");
+    int64_t max_b = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+        if (int rc = a.check(p)) return rc;
+        if (a.sub_len[p] > plan->max_samples)
+            return fail(FFS_E_INVALID, "pair %d: subtitle length %lld exceeds the plan's max_samples %lld", p,
+                        (long long)a.sub_len[p], (long long)plan->max_samples);
+        const int64_t B = (a.sub_len[p] + K - 1) / K;
+        if (B > plan->max_blocks)
+            return fail(FFS_E_INVALID, "pair %d: %lld blocks exceed the plan's max_blocks %lld", p, (long long)B,
+                        (long long)plan->max_blocks);
+        max_b = std::max(max_b, B);
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (int rc = plan->begin(st)) return rc;
+    const int64_t L = 2 * W;
+    const int n_tiles = (int)((L + ffsa::SPLIT_TILE - 1) / ffsa::SPLIT_TILE);
+    const int64_t pre_slot = split_align_up(plan->pw_s + plan->pw_r, 64);
+    ffsa::SplitDesc* hd = (ffsa::SplitDesc*)plan->desc.host;
+    const ffsa::SplitDesc* dd = (const ffsa::SplitDesc*)plan->desc.dev;
+    for (int p0 = 0; p0 < n_pairs; p0 += plan->pairs_in_flight) {
+        const int np = std::min(plan->pairs_in_flight, n_pairs - p0);
+        if (int rc = plan->desc.wait_free()) return rc;
+        int64_t chunk_b = 0;
+        for (int i = 0; i < np; ++i) {
+            int32_t* pre_s = plan->pre + (int64_t)i * pre_slot;
+            hd[i] = a.split_desc(p0 + i, pre_s, pre_s + plan->pw_s);
+            chunk_b = std::max(chunk_b, (hd[i].S + K - 1) / K);
+        }
+        if (int rc = plan->desc.upload(sizeof(ffsa::SplitDesc) * np, st)) return rc;
+        const int n_bgroups = (int)((chunk_b + ffsa::SPLIT_BPW - 1) / ffsa::SPLIT_BPW);
+        hipLaunchKernelGGL(ffsa::k_split_prefix, dim3(2 * np), dim3(ffsa::SPLIT_PREFIX_THREADS), 0, st, dd, (int64_t)W);
+        hipLaunchKernelGGL(ffsa::k_split_counts, dim3((unsigned)((int64_t)n_tiles * n_bgroups * np)),
+                           dim3(ffsa::SPLIT_CNT_THREADS), 0, st, dd, plan->ws, (int)K, (int64_t)W, n_tiles, n_bgroups);
+        hipLaunchKernelGGL(ffsa::k_drift_dp, dim3(np), dim3(ffsa::SPLIT_DP_THREADS), 0, st, dd, plan->ws, plan->codes,
+                           plan->codes_slot, (int)K, (int64_t)W, split_penalty, max_step, step_cost, max_b,
+                           block_offset_out_dev, block_score_out_dev, block_jump_out_dev, total_out_dev);
         HIP_TRY(hipGetLastError());
     }
     return plan->end(st);

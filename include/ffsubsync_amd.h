@@ -641,6 +641,46 @@ int ffs_split_range_report_batch(ffs_split_range_plan* plan, int n_pairs, const 
                                  int64_t exclusion_samples, ffs_piece_report* report_out_dev,
                                  int32_t* n_pieces_out_dev, void* hip_stream);
 
+/* ---- drift-tolerant alignment: the split DP with small offset steps between blocks (csrc/ffs_drift.h) -------------
+ * Replaces: nothing in the reference.  The contract below is pinned against the numpy model tests/drift_model.py, bit
+ * for bit.
+ *
+ * ffs_align_split_batch's problem, blocks, lag window and block scores m_b(d), unchanged.  The DP may also take a
+ * block's offset from a NEIGHBOURING lag of the block before it: a residual framerate ratio or a slowly wandering clock
+ * moves the offset by a sample or two per block, which a jump (P for any change) cannot follow.  With s = max_step in
+ * [0, 7], Q = step_cost (finite, >= 0), c_a = Q * a (one fp64 product), lag index j in [0, L), L = 2W:
+ * V_0 = m_0; for b >= 1: J = max_j V_{b-1}(j), a_{b-1} = the largest j attaining it, T = J - P, and per j
+ *     best, code = V_{b-1}(j), STAY
+ *     for a = 1..s, for e in (+a, -a): if 0 <= j-e < L and V_{b-1}(j-e) - c_a > best: best, code = that, e
+ *     if T > best: best, code = T, JUMP
+ *     V_b(j) = best + m_b(j)
+ * (every comparison strict: ties keep the earlier option; every fp64 operation rounded on its own, no fused
+ * multiply-add).  End = the largest j attaining max V_{B-1} (= total); backtrack o_{b-1} = a_{b-1} after JUMP, else
+ * o_b - e.  At max_step = 0 every output equals ffs_align_split_batch's bit for bit.
+ *
+ * A plan owns the workspace for pairs_in_flight problems of up to max_samples subtitle samples, max_blocks blocks and
+ * max_lags = 2W lags: per pair max_blocks * max_lags * 2 bytes of uint16 counts plus a 4-bit code per (block, lag)
+ * (max_blocks * max_lags / 2 bytes) and two fp64 rows of max_lags (211 MB at 2 h, +-10 min, K = 1024).  A plan of its
+ * own: split plans do not grow.  A plan serves one host thread at a time; successive calls (any streams) are ordered
+ * by the library. */
+typedef struct ffs_drift_plan ffs_drift_plan;
+int ffs_drift_plan_create(int device, int pairs_in_flight, int64_t max_blocks, int64_t max_lags, int64_t max_samples,
+                          ffs_drift_plan** out);
+int ffs_drift_plan_destroy(ffs_drift_plan* plan);
+int64_t ffs_drift_plan_workspace_bytes(const ffs_drift_plan* plan);
+/* Solve n_pairs problems; arguments, limits, errors and sub-batching as ffs_align_split_batch, and FFS_E_INVALID for
+ * max_step outside [0, 7] or a step_cost that is negative, NaN or infinite (all before any launch).  Outputs as
+ * ffs_align_split_batch's (block_offset_out_dev, block_score_out_dev: n_pairs * max_b; total_out_dev: n_pairs) plus
+ * block_jump_out_dev[p * max_b + b] (uint8): 1 where block b >= 1 was entered by JUMP, else 0 (block 0 and entries
+ * b >= B_p are 0) -- a jump and a step can give the same offset difference, so the flag is an output.  Segments (maximal
+ * runs of blocks with no jump inside) are formed by the caller. */
+int ffs_align_drift_batch(ffs_drift_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
+                          const double* ref_lo, const double* ref_hi, const void* const* sub_ptr, const int64_t* sub_len,
+                          const double* sub_lo, const double* sub_hi, int64_t block_samples, int64_t max_offset_samples,
+                          double split_penalty, int max_step, double step_cost, int32_t* block_offset_out_dev,
+                          double* block_score_out_dev, uint8_t* block_jump_out_dev, double* total_out_dev,
+                          void* hip_stream);
+
 /* Thread-local description of the last error returned on this thread ("" if none). */
 const char* ffs_last_error(void);
 
