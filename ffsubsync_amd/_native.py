@@ -54,6 +54,17 @@ PIECE_REPORT_DTYPE = np.dtype(
 )
 PIECE_REPORT_BYTES = 224
 assert PIECE_REPORT_DTYPE.itemsize == PIECE_REPORT_BYTES
+# ffs_segment_report (include/ffsubsync_amd.h; static size 264 bytes)
+SEGMENT_OWN_NOT_PEAK = 4  # FFS_SEGMENT_OWN_NOT_PEAK: the segment's peak 1 is not at shift 0 (its own path)
+SEGMENT_REPORT_DTYPE = np.dtype(
+    [("first_block", "<i8"), ("end_block", "<i8"), ("start_sample", "<i8"), ("end_sample", "<i8"),
+     ("first_offset", "<i8"), ("last_offset", "<i8"), ("min_offset", "<i8"), ("max_offset", "<i8"),
+     ("own_score", "<f8"), ("prev_score", "<f8"), ("next_score", "<f8"), ("flat_score", "<f8"), ("flat_offset", "<i8"),
+     ("mean", "<f8"), ("std", "<f8"), ("n_lags", "<i8"), ("peak_score", "<f8", (QUALITY_MAX_PEAKS,)),
+     ("peak_shift", "<i8", (QUALITY_MAX_PEAKS,)), ("n_peaks", "<i4"), ("flags", "<i4")], align=True
+)
+SEGMENT_REPORT_BYTES = 264
+assert SEGMENT_REPORT_DTYPE.itemsize == SEGMENT_REPORT_BYTES
 # ffs_break_refine (include/ffsubsync_amd.h; static size 88 bytes)
 REFINE_MAX_RADIUS = 131072  # FFS_REFINE_MAX_RADIUS
 REFINE_CLIPPED = 1  # FFS_REFINE_CLIPPED: the window was narrowed by a neighbouring break's midpoint
@@ -119,6 +130,7 @@ EXPORTED_SYMBOLS = (
     "ffs_drift_plan_destroy",
     "ffs_drift_plan_workspace_bytes",
     "ffs_align_drift_batch",
+    "ffs_align_drift_report_batch",
     "ffs_quality_plan_create",
     "ffs_quality_plan_destroy",
     "ffs_quality_plan_workspace_bytes",
@@ -330,6 +342,12 @@ def load():
                                               c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64,
                                               c.c_double, c.c_int, c.c_double, c.c_void_p, c.c_void_p, c.c_void_p,
                                               c.c_void_p, c.c_void_p]
+        lib.ffs_align_drift_report_batch.restype = c.c_int
+        lib.ffs_align_drift_report_batch.argtypes = [c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                                                     c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64,
+                                                     c.c_double, c.c_int, c.c_double, c.c_int, c.c_int64, c.c_void_p,
+                                                     c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                                                     c.c_void_p]
         lib.ffs_quality_plan_create.restype = c.c_int
         lib.ffs_quality_plan_create.argtypes = [c.c_int, c.c_int, c.c_int64, c.c_int64, c.POINTER(c.c_void_p)]
         lib.ffs_quality_plan_destroy.restype = c.c_int
@@ -981,6 +999,24 @@ class DriftPlan(_SidePlan):
                                              float(split_penalty), int(max_step), float(step_cost),
                                              offsets_out.data_ptr(), scores_out.data_ptr(), jumps_out.data_ptr(),
                                              totals_out.data_ptr(), self._stream(stream)))
+
+    def report(self, ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, block_samples: int,
+               max_offset_samples: int, split_penalty: float, max_step: int, step_cost: float, top_k: int,
+               exclusion_samples: int, offsets_out, scores_out, jumps_out, totals_out, report_out, n_segments_out,
+               stream: Optional[int] = None) -> None:
+        """``ffs_align_drift_report_batch``: ``align``'s outputs plus a uint8 CUDA tensor of n_pairs * max_b * 264
+        bytes of segment reports and an int32 one of n_pairs segment counts.  The call reads each sub-batch's segment
+        counts back, so it waits for the stream."""
+        n, ptrs, _bufs = _pair_buffers(ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi)
+        if (n_segments_out.numel() < n
+                or report_out.numel() * report_out.element_size() < offsets_out.numel() * SEGMENT_REPORT_BYTES):
+            raise ValueError("output buffer too small")
+        check(self.lib.ffs_align_drift_report_batch(self.handle, n, *ptrs, int(block_samples), int(max_offset_samples),
+                                                    float(split_penalty), int(max_step), float(step_cost), int(top_k),
+                                                    int(exclusion_samples), offsets_out.data_ptr(),
+                                                    scores_out.data_ptr(), jumps_out.data_ptr(), totals_out.data_ptr(),
+                                                    report_out.data_ptr(), n_segments_out.data_ptr(),
+                                                    self._stream(stream)))
 
 
 class SplitRangePlan(_SidePlan):

@@ -32,6 +32,7 @@
 #include "ffs_split_range.h"
 #include "ffs_cut_report.h"
 #include "ffs_drift.h"
+#include "ffs_drift_report.h"
 
 using namespace ffsa;
 
@@ -3647,6 +3648,8 @@ struct ffs_drift_plan : PlanCore {
     int64_t codes_slot;
     int32_t* pre;                // [slot][pw_s + pw_r]
     DescStaging desc;            // SplitDesc[pairs_in_flight]
+    double* rows;                // report calls only, made by the first: [slot][DRIFT_ROUND_SEGMENTS][lpad] path curves
+    int64_t row_bytes;
 };
 
 int ffs_drift_plan_create(int device, int pairs_in_flight, int64_t max_blocks, int64_t max_lags, int64_t max_samples,
@@ -3703,19 +3706,26 @@ int ffs_drift_plan_destroy(ffs_drift_plan* plan) {
     if (!plan) return FFS_OK;
     plan->close();
     plan->desc.release();
+    if (plan->rows) (void)hipFree(plan->rows);
     delete plan;
     return FFS_OK;
 }
 
-int64_t ffs_drift_plan_workspace_bytes(const ffs_drift_plan* plan) { return plan ? plan->work_bytes : 0; }
+int64_t ffs_drift_plan_workspace_bytes(const ffs_drift_plan* plan) { return plan ? plan->work_bytes + plan->row_bytes : 0; }
 
-int ffs_align_drift_batch(ffs_drift_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
-                          const double* ref_lo, const double* ref_hi, const void* const* sub_ptr, const int64_t* sub_len,
-                          const double* sub_lo, const double* sub_hi, int64_t block_samples, int64_t max_offset_samples,
-                          double split_penalty, int max_step, double step_cost, int32_t* block_offset_out_dev,
-                          double* block_score_out_dev, uint8_t* block_jump_out_dev, double* total_out_dev,
-                          void* hip_stream) {
-    const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
+namespace {
+struct DriftReportArgs {  // the per-segment report of ffs_align_drift_report_batch
+    int top_k;
+    int64_t exclusion;
+    ffs_segment_report* out;
+    int32_t* n_segments;
+};
+
+// ffs_align_drift_batch, and with `rep` the segment reports after each sub-batch's DP
+int drift_batch(ffs_drift_plan* plan, int n_pairs, const Pairs& a, int64_t block_samples, int64_t max_offset_samples,
+                double split_penalty, int max_step, double step_cost, int32_t* block_offset_out_dev,
+                double* block_score_out_dev, uint8_t* block_jump_out_dev, double* total_out_dev, const DriftReportArgs* rep,
+                void* hip_stream) {
     if (!plan) return fail(FFS_E_INVALID, "null drift plan");
     if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
     if (n_pairs == 0) return FFS_OK;
@@ -3731,6 +3741,12 @@ int ffs_align_drift_batch(ffs_drift_plan* plan, int n_pairs, const void* const* 
     if (max_step < 0 || max_step > ffsa::DRIFT_MAX_STEP)
         return fail(FFS_E_INVALID, "max_step=%d outside [0, %d]", max_step, ffsa::DRIFT_MAX_STEP);
     if (!(step_cost >= 0.0) || !std::isfinite(step_cost)) return fail(FFS_E_INVALID, "step_cost must be finite and >= 0");
+    if (rep) {
+        if (rep->top_k < 1 || rep->top_k > ffsa::QUAL_MAX_PEAKS) return fail(FFS_E_INVALID, "top_k=%d outside [1, 8]", rep->top_k);
+        if (rep->exclusion < 1) return fail(FFS_E_INVALID, "exclusion_samples=%lld: need >= 1", (long long)rep->exclusion);
+        if (!rep->out || !rep->n_segments) return fail(FFS_E_INVALID, "null argument");
+        if (((uintptr_t)rep->out & 7) || ((uintptr_t)rep->n_segments & 3)) return fail(FFS_E_INVALID, "misaligned report outputs");
+    }
     int64_t max_b = 0;
     for (int p = 0; p < n_pairs; ++p) {
         if (int rc = a.check(p)) return rc;
@@ -3745,11 +3761,21 @@ int ffs_align_drift_batch(ffs_drift_plan* plan, int n_pairs, const void* const* 
     }
     hipStream_t st = (hipStream_t)hip_stream;
     if (int rc = plan->begin(st)) return rc;
+    constexpr int G = ffsa::DRIFT_ROUND_SEGMENTS;
+    if (rep && !plan->rows) {  // the first report call: G fp64 path-curve rows per slot
+        const int64_t bytes = (int64_t)plan->pairs_in_flight * G * plan->lpad * 8;
+        if (hipMalloc((void**)&plan->rows, bytes) != hipSuccess) {
+            plan->rows = nullptr;
+            return fail(FFS_E_NOMEM, "drift plan: %lld report workspace bytes", (long long)bytes);
+        }
+        plan->row_bytes = bytes;
+    }
     const int64_t L = 2 * W;
     const int n_tiles = (int)((L + ffsa::SPLIT_TILE - 1) / ffsa::SPLIT_TILE);
     const int64_t pre_slot = split_align_up(plan->pw_s + plan->pw_r, 64);
     ffsa::SplitDesc* hd = (ffsa::SplitDesc*)plan->desc.host;
     const ffsa::SplitDesc* dd = (const ffsa::SplitDesc*)plan->desc.dev;
+    std::vector<int32_t> n_seg;  // report calls: the sub-batch's segment counts, read back to size its rounds
     for (int p0 = 0; p0 < n_pairs; p0 += plan->pairs_in_flight) {
         const int np = std::min(plan->pairs_in_flight, n_pairs - p0);
         if (int rc = plan->desc.wait_free()) return rc;
@@ -3767,9 +3793,56 @@ int ffs_align_drift_batch(ffs_drift_plan* plan, int n_pairs, const void* const* 
         hipLaunchKernelGGL(ffsa::k_drift_dp, dim3(np), dim3(ffsa::SPLIT_DP_THREADS), 0, st, dd, plan->ws, plan->codes,
                            plan->codes_slot, (int)K, (int64_t)W, split_penalty, max_step, step_cost, max_b,
                            block_offset_out_dev, block_score_out_dev, block_jump_out_dev, total_out_dev);
+        if (rep) {
+            ffsa::SegmentReport* out = (ffsa::SegmentReport*)rep->out;
+            hipLaunchKernelGGL(ffsa::k_drift_segments, dim3(np), dim3(ffsa::DRIFT_SEG_THREADS), 0, st, dd, (int)K, max_b,
+                               (const int32_t*)block_offset_out_dev, (const uint8_t*)block_jump_out_dev, out,
+                               rep->n_segments);
+            HIP_TRY(hipGetLastError());
+            // rounds of G segments per pair: as many as the sub-batch's largest segment count asks for
+            n_seg.resize((size_t)np);
+            HIP_TRY(hipMemcpyAsync(n_seg.data(), rep->n_segments + p0, sizeof(int32_t) * np, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            const int most = *std::max_element(n_seg.begin(), n_seg.end());
+            const int n_sum_tiles = (int)((L + ffsa::DRIFT_SUM_TILE - 1) / ffsa::DRIFT_SUM_TILE);
+            for (int first = 0; first < most; first += G) {
+                hipLaunchKernelGGL(ffsa::k_drift_path_sums, dim3((unsigned)((int64_t)n_sum_tiles * G * np)),
+                                   dim3(ffsa::DRIFT_SUM_THREADS), 0, st, dd, plan->ws, plan->rows, plan->lpad, (int)K,
+                                   (int64_t)W, n_sum_tiles, first, max_b, (const int32_t*)block_offset_out_dev,
+                                   (const int32_t*)rep->n_segments, (const ffsa::SegmentReport*)out);
+                hipLaunchKernelGGL(ffsa::k_drift_segment_report, dim3((unsigned)(G * np)), dim3(ffsa::QUAL_PEAK_THREADS),
+                                   0, st, dd, plan->ws, (const double*)plan->rows, plan->lpad, (int64_t)W, first, max_b,
+                                   rep->top_k, rep->exclusion, (const int32_t*)rep->n_segments, out);
+            }
+        }
         HIP_TRY(hipGetLastError());
     }
     return plan->end(st);
+}
+}  // namespace
+
+int ffs_align_drift_batch(ffs_drift_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
+                          const double* ref_lo, const double* ref_hi, const void* const* sub_ptr, const int64_t* sub_len,
+                          const double* sub_lo, const double* sub_hi, int64_t block_samples, int64_t max_offset_samples,
+                          double split_penalty, int max_step, double step_cost, int32_t* block_offset_out_dev,
+                          double* block_score_out_dev, uint8_t* block_jump_out_dev, double* total_out_dev,
+                          void* hip_stream) {
+    const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
+    return drift_batch(plan, n_pairs, a, block_samples, max_offset_samples, split_penalty, max_step, step_cost,
+                       block_offset_out_dev, block_score_out_dev, block_jump_out_dev, total_out_dev, nullptr, hip_stream);
+}
+
+int ffs_align_drift_report_batch(ffs_drift_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
+                                 const double* ref_lo, const double* ref_hi, const void* const* sub_ptr,
+                                 const int64_t* sub_len, const double* sub_lo, const double* sub_hi, int64_t block_samples,
+                                 int64_t max_offset_samples, double split_penalty, int max_step, double step_cost, int top_k,
+                                 int64_t exclusion_samples, int32_t* block_offset_out_dev, double* block_score_out_dev,
+                                 uint8_t* block_jump_out_dev, double* total_out_dev, ffs_segment_report* report_out_dev,
+                                 int32_t* n_segments_out_dev, void* hip_stream) {
+    const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
+    const DriftReportArgs rep{top_k, exclusion_samples, report_out_dev, n_segments_out_dev};
+    return drift_batch(plan, n_pairs, a, block_samples, max_offset_samples, split_penalty, max_step, step_cost,
+                       block_offset_out_dev, block_score_out_dev, block_jump_out_dev, total_out_dev, &rep, hip_stream);
 }
 
 /* ---- alignment quality report (csrc/ffs_quality.h) ------------------------------------------------------------- */

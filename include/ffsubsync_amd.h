@@ -681,6 +681,69 @@ int ffs_align_drift_batch(ffs_drift_plan* plan, int n_pairs, const void* const* 
                           double* block_score_out_dev, uint8_t* block_jump_out_dev, double* total_out_dev,
                           void* hip_stream);
 
+/* ---- per-segment path report of a drift solve: segment, jump and drift evidence (csrc/ffs_drift_report.h) ----------
+ * Replaces: nothing in the reference.  The contract below is pinned against the numpy model
+ * tests/drift_report_model.py, bit for bit.
+ *
+ * The drift solve of ffs_align_drift_batch (same arguments, same block_offset / block_score / block_jump / total outputs
+ * bit for bit), then per pair its segments -- maximal runs [f_i, e_i) of blocks with no jump inside, subtitle samples
+ * [f_i K, min(e_i K, S)), block offsets o_b, o_min / o_max over the run -- in report_out_dev[p * max_b + i] (records past
+ * the segment count are zero) and the segment count in n_segments_out_dev[p].
+ * Shift set delta in [-W+1-o_min, W-o_max]: exactly the shifts for which every block's lag o_b + delta stays inside the
+ * window; it always holds 0, n_lags = 2W - (o_max - o_min) >= 1.  Path curve p_i(delta): for block b at lag
+ * d = o_b + delta, a = max(bK, -d), e = min((b+1)K, S, R-d); where e > a, ov = e - a, n1x = ones of s in [a, e), nx1 = ones
+ * of r in [a+d, e+d), n11 = the drift solve's uint16 block count (else all 0); the four are summed over the segment's
+ * blocks as exact integers and scored ONCE, ((n00*c00 + n01*c01) + n10*c10) + n11*c11 in fp64 with every operation
+ * rounded on its own; exactly 0.0 where the summed overlap is 0.  (own_score is therefore not in general the sum of the
+ * block scores -- different rounding; with 0/1 levels every term is an integer and they are equal.)  Moments over the
+ * n_lags shifts (two passes, population std) and up to top_k greedy peaks with exclusion distance E, largest shift on
+ * ties, as ffs_quality_result; peaks are reported as shifts, 0 being the path itself.
+ * own_score = p_i(0); prev_score = p_i(last_offset_{i-1} - first_offset_i) -- the path moved so that it continues the
+ * previous segment without a jump -- and next_score = p_i(first_offset_{i+1} - last_offset_i); NaN without that
+ * neighbour or when that shift lies outside the shift set.  flat_score = max over d in [o_min, o_max] of the constant-lag
+ * piece curve of the segment's samples (ffs_piece_report's c at d, n11 = the uint32 sum of the segment's block counts),
+ * flat_offset the largest d attaining it: the best the segment can do without drifting.
+ * At max_step = 0 every segment is a piece and its record equals ffs_align_split_report_batch's in every shared field
+ * (peak_shift + offset = peak_offset), flat_score has the bits of own_score and flat_offset = offset.
+ *
+ * Segments are reported 8 per pair and round; the call reads each sub-batch's segment counts back to size its rounds, so
+ * it waits for hip_stream.  The first report call on a plan adds pairs_in_flight * 8 fp64 rows of max_lags, counted by
+ * ffs_drift_plan_workspace_bytes from then on; plans that never report keep the drift workspace alone. */
+#define FFS_SEGMENT_OWN_NOT_PEAK 4 /* the segment's peak 1 is not at shift 0 */
+
+typedef struct ffs_segment_report {
+    int64_t first_block, end_block;     /* blocks [first_block, end_block) */
+    int64_t start_sample, end_sample;   /* subtitle samples [start_sample, end_sample) */
+    int64_t first_offset, last_offset;  /* o_b of the first and of the last block (samples) */
+    int64_t min_offset, max_offset;     /* o_min, o_max over the blocks */
+    double own_score;                   /* p_i(0) */
+    double prev_score, next_score;      /* p_i at the shift continuing that neighbour; NaN without it / outside the set */
+    double flat_score;                  /* the best constant lag of [o_min, o_max] */
+    int64_t flat_offset;                /* the largest lag attaining it */
+    double mean, std;                   /* of p_i over the n_lags shifts */
+    int64_t n_lags;                     /* 2W - (o_max - o_min) */
+    double peak_score[8];               /* peaks 0 .. n_peaks-1 (entries beyond: 0) */
+    int64_t peak_shift[8];              /* samples; 0 = the path itself */
+    int32_t n_peaks, flags;             /* flags: FFS_QUALITY_FLAT, FFS_SEGMENT_OWN_NOT_PEAK */
+} ffs_segment_report;
+#ifdef __cplusplus
+static_assert(sizeof(ffs_segment_report) == 264, "ffs_segment_report is 264 bytes");
+#else
+_Static_assert(sizeof(ffs_segment_report) == 264, "ffs_segment_report is 264 bytes");
+#endif
+
+/* ffs_align_drift_batch plus the segment reports, in one call on hip_stream.  report_out_dev: n_pairs * max_b records
+ * (8-byte aligned); n_segments_out_dev: n_pairs int32.  FFS_E_INVALID / FFS_E_EMPTY as ffs_align_drift_batch, and
+ * FFS_E_INVALID for top_k outside [1, 8], exclusion_samples < 1 or a null / misaligned report output; all before any
+ * launch, the outputs untouched. */
+int ffs_align_drift_report_batch(ffs_drift_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
+                                 const double* ref_lo, const double* ref_hi, const void* const* sub_ptr,
+                                 const int64_t* sub_len, const double* sub_lo, const double* sub_hi, int64_t block_samples,
+                                 int64_t max_offset_samples, double split_penalty, int max_step, double step_cost, int top_k,
+                                 int64_t exclusion_samples, int32_t* block_offset_out_dev, double* block_score_out_dev,
+                                 uint8_t* block_jump_out_dev, double* total_out_dev, ffs_segment_report* report_out_dev,
+                                 int32_t* n_segments_out_dev, void* hip_stream);
+
 /* Thread-local description of the last error returned on this thread ("" if none). */
 const char* ffs_last_error(void);
 
