@@ -65,6 +65,15 @@ SEGMENT_REPORT_DTYPE = np.dtype(
 )
 SEGMENT_REPORT_BYTES = 264
 assert SEGMENT_REPORT_DTYPE.itemsize == SEGMENT_REPORT_BYTES
+# ffs_smooth_segment (include/ffsubsync_amd.h; static size 32 bytes) and the limits of the smooth fit
+SMOOTH_MAX_KNOT_BLOCKS = 256  # FFS_SMOOTH_MAX_KNOT_BLOCKS
+SMOOTH_MAX_RADIUS = 16  # FFS_SMOOTH_MAX_RADIUS
+SMOOTH_SEGMENT_DTYPE = np.dtype(
+    [("fit_total", "<f8"), ("line_score", "<f8"), ("bend_total", "<f8"), ("n_knots", "<i4"), ("reserved", "<i4")], align=True
+)
+SMOOTH_SEGMENT_BYTES = 32
+assert SMOOTH_SEGMENT_DTYPE.itemsize == SMOOTH_SEGMENT_BYTES
+SMOOTH_BLOCK_BYTES = 33 * 33 * 9 + 36  # smooth workspace per block of a pair in flight: line scores, back-pointers, tables
 # ffs_break_refine (include/ffsubsync_amd.h; static size 88 bytes)
 REFINE_MAX_RADIUS = 131072  # FFS_REFINE_MAX_RADIUS
 REFINE_CLIPPED = 1  # FFS_REFINE_CLIPPED: the window was narrowed by a neighbouring break's midpoint
@@ -131,6 +140,7 @@ EXPORTED_SYMBOLS = (
     "ffs_drift_plan_workspace_bytes",
     "ffs_align_drift_batch",
     "ffs_align_drift_report_batch",
+    "ffs_align_drift_smooth_batch",
     "ffs_quality_plan_create",
     "ffs_quality_plan_destroy",
     "ffs_quality_plan_workspace_bytes",
@@ -348,6 +358,12 @@ def load():
                                                      c.c_double, c.c_int, c.c_double, c.c_int, c.c_int64, c.c_void_p,
                                                      c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
                                                      c.c_void_p]
+        lib.ffs_align_drift_smooth_batch.restype = c.c_int
+        lib.ffs_align_drift_smooth_batch.argtypes = [c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                                                     c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64,
+                                                     c.c_double, c.c_int, c.c_double, c.c_int, c.c_int, c.c_double,
+                                                     c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                                                     c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
         lib.ffs_quality_plan_create.restype = c.c_int
         lib.ffs_quality_plan_create.argtypes = [c.c_int, c.c_int, c.c_int64, c.c_int64, c.POINTER(c.c_void_p)]
         lib.ffs_quality_plan_destroy.restype = c.c_int
@@ -1016,6 +1032,25 @@ class DriftPlan(_SidePlan):
                                                     int(exclusion_samples), offsets_out.data_ptr(),
                                                     scores_out.data_ptr(), jumps_out.data_ptr(), totals_out.data_ptr(),
                                                     report_out.data_ptr(), n_segments_out.data_ptr(),
+                                                    self._stream(stream)))
+
+    def smooth(self, ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, block_samples: int,
+               max_offset_samples: int, split_penalty: float, max_step: int, step_cost: float, knot_blocks: int,
+               radius: int, bend_cost: float, offsets_out, scores_out, jumps_out, totals_out, smooth_out, knot_out,
+               segments_out, n_segments_out, stream: Optional[int] = None) -> None:
+        """``ffs_align_drift_smooth_batch``: ``align``'s outputs plus int32 smooth offsets and uint8 knot flags of
+        n_pairs * max_b entries, a CUDA tensor of n_pairs * max_b * 32 bytes of segment records and an int32 one of
+        n_pairs segment counts (asynchronous)."""
+        n, ptrs, _bufs = _pair_buffers(ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi)
+        if (n_segments_out.numel() < n or smooth_out.numel() < offsets_out.numel() or knot_out.numel() < offsets_out.numel()
+                or segments_out.numel() * segments_out.element_size() < offsets_out.numel() * SMOOTH_SEGMENT_BYTES):
+            raise ValueError("output buffer too small")
+        check(self.lib.ffs_align_drift_smooth_batch(self.handle, n, *ptrs, int(block_samples), int(max_offset_samples),
+                                                    float(split_penalty), int(max_step), float(step_cost),
+                                                    int(knot_blocks), int(radius), float(bend_cost),
+                                                    offsets_out.data_ptr(), scores_out.data_ptr(), jumps_out.data_ptr(),
+                                                    totals_out.data_ptr(), smooth_out.data_ptr(), knot_out.data_ptr(),
+                                                    segments_out.data_ptr(), n_segments_out.data_ptr(),
                                                     self._stream(stream)))
 
 

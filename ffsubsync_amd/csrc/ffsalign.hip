@@ -33,6 +33,7 @@
 #include "ffs_cut_report.h"
 #include "ffs_drift.h"
 #include "ffs_drift_report.h"
+#include "ffs_drift_smooth.h"
 
 using namespace ffsa;
 
@@ -1005,7 +1006,7 @@ void fill_xform(XformDesc* x, const VecView* a, const VecView* b, const void* sa
 extern "C" {
 
 const char* ffs_last_error(void) { return g_err.c_str(); }
-int ffs_version(void) { return 370; }
+int ffs_version(void) { return 380; }
 
 int64_t ffs_fft_length(int64_t ref_len, int64_t sub_len) {
     if (ref_len <= 0 || sub_len <= 0) return 0;
@@ -3650,6 +3651,9 @@ struct ffs_drift_plan : PlanCore {
     DescStaging desc;            // SplitDesc[pairs_in_flight]
     double* rows;                // report calls only, made by the first: [slot][DRIFT_ROUND_SEGMENTS][lpad] path curves
     int64_t row_bytes;
+    void* smooth_mem;            // smooth calls only, made by the first: the tables of ffsa::SmoothWs
+    ffsa::SmoothWs sw;
+    int64_t smooth_bytes;
 };
 
 int ffs_drift_plan_create(int device, int pairs_in_flight, int64_t max_blocks, int64_t max_lags, int64_t max_samples,
@@ -3707,11 +3711,14 @@ int ffs_drift_plan_destroy(ffs_drift_plan* plan) {
     plan->close();
     plan->desc.release();
     if (plan->rows) (void)hipFree(plan->rows);
+    if (plan->smooth_mem) (void)hipFree(plan->smooth_mem);
     delete plan;
     return FFS_OK;
 }
 
-int64_t ffs_drift_plan_workspace_bytes(const ffs_drift_plan* plan) { return plan ? plan->work_bytes + plan->row_bytes : 0; }
+int64_t ffs_drift_plan_workspace_bytes(const ffs_drift_plan* plan) {
+    return plan ? plan->work_bytes + plan->row_bytes + plan->smooth_bytes : 0;
+}
 
 namespace {
 struct DriftReportArgs {  // the per-segment report of ffs_align_drift_report_batch
@@ -3721,11 +3728,44 @@ struct DriftReportArgs {  // the per-segment report of ffs_align_drift_report_ba
     int32_t* n_segments;
 };
 
-// ffs_align_drift_batch, and with `rep` the segment reports after each sub-batch's DP
+struct DriftSmoothArgs {  // the smooth fit of ffs_align_drift_smooth_batch
+    int knot_blocks, radius;
+    double bend_cost;
+    int32_t* smooth_offset;
+    uint8_t* knot;
+    ffs_smooth_segment* out;
+    int32_t* n_segments;
+};
+
+// the smooth workspace of a plan, made by its first smooth call: segment / interval tables, line scores, back-pointers
+int drift_smooth_workspace(ffs_drift_plan* plan) {
+    if (plan->smooth_mem) return FFS_OK;
+    const int64_t n = plan->pairs_in_flight, mb = split_align_up(plan->max_blocks, 16);
+    const int64_t b_t = n * mb * ffsa::SMOOTH_MAX_STATES * 8, b_back = split_align_up(n * mb * ffsa::SMOOTH_MAX_STATES, 64),
+                  b_seg = n * mb * (int64_t)sizeof(ffsa::SmoothSeg), b_iv = n * mb * (int64_t)sizeof(ffsa::SmoothInt),
+                  b_of = n * mb * 4, b_n = split_align_up(n * 4, 64);
+    const int64_t bytes = b_t + b_back + b_seg + b_iv + b_of + b_n;
+    if (hipMalloc(&plan->smooth_mem, bytes) != hipSuccess) {
+        plan->smooth_mem = nullptr;
+        return fail(FFS_E_NOMEM, "drift plan: %lld smooth workspace bytes", (long long)bytes);
+    }
+    char* w = (char*)plan->smooth_mem;
+    plan->sw.T = (double*)w;
+    plan->sw.back = (uint8_t*)(w + b_t);
+    plan->sw.seg = (ffsa::SmoothSeg*)(w + b_t + b_back);
+    plan->sw.iv = (ffsa::SmoothInt*)(w + b_t + b_back + b_seg);
+    plan->sw.seg_of = (int32_t*)(w + b_t + b_back + b_seg + b_iv);
+    plan->sw.n_int = (int32_t*)(w + b_t + b_back + b_seg + b_iv + b_of);
+    plan->sw.stride = mb;
+    plan->smooth_bytes = bytes;
+    return FFS_OK;
+}
+
+// ffs_align_drift_batch; with `rep` the segment reports, with `fit` the smooth fit after each sub-batch's DP
 int drift_batch(ffs_drift_plan* plan, int n_pairs, const Pairs& a, int64_t block_samples, int64_t max_offset_samples,
                 double split_penalty, int max_step, double step_cost, int32_t* block_offset_out_dev,
                 double* block_score_out_dev, uint8_t* block_jump_out_dev, double* total_out_dev, const DriftReportArgs* rep,
-                void* hip_stream) {
+                const DriftSmoothArgs* fit, void* hip_stream) {
     if (!plan) return fail(FFS_E_INVALID, "null drift plan");
     if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
     if (n_pairs == 0) return FFS_OK;
@@ -3747,6 +3787,17 @@ int drift_batch(ffs_drift_plan* plan, int n_pairs, const Pairs& a, int64_t block
         if (!rep->out || !rep->n_segments) return fail(FFS_E_INVALID, "null argument");
         if (((uintptr_t)rep->out & 7) || ((uintptr_t)rep->n_segments & 3)) return fail(FFS_E_INVALID, "misaligned report outputs");
     }
+    if (fit) {
+        if (fit->knot_blocks < 1 || fit->knot_blocks > ffsa::SMOOTH_MAX_KNOT_BLOCKS)
+            return fail(FFS_E_INVALID, "knot_blocks=%d outside [1, %d]", fit->knot_blocks, ffsa::SMOOTH_MAX_KNOT_BLOCKS);
+        if (fit->radius < 0 || fit->radius > ffsa::SMOOTH_MAX_RADIUS)
+            return fail(FFS_E_INVALID, "radius=%d outside [0, %d]", fit->radius, ffsa::SMOOTH_MAX_RADIUS);
+        if (!(fit->bend_cost >= 0.0) || !std::isfinite(fit->bend_cost))
+            return fail(FFS_E_INVALID, "bend_cost must be finite and >= 0");
+        if (!fit->smooth_offset || !fit->knot || !fit->out || !fit->n_segments) return fail(FFS_E_INVALID, "null argument");
+        if (((uintptr_t)fit->smooth_offset & 3) || ((uintptr_t)fit->out & 7) || ((uintptr_t)fit->n_segments & 3))
+            return fail(FFS_E_INVALID, "misaligned smooth outputs");
+    }
     int64_t max_b = 0;
     for (int p = 0; p < n_pairs; ++p) {
         if (int rc = a.check(p)) return rc;
@@ -3761,6 +3812,8 @@ int drift_batch(ffs_drift_plan* plan, int n_pairs, const Pairs& a, int64_t block
     }
     hipStream_t st = (hipStream_t)hip_stream;
     if (int rc = plan->begin(st)) return rc;
+    if (fit)
+        if (int rc = drift_smooth_workspace(plan)) return rc;
     constexpr int G = ffsa::DRIFT_ROUND_SEGMENTS;
     if (rep && !plan->rows) {  // the first report call: G fp64 path-curve rows per slot
         const int64_t bytes = (int64_t)plan->pairs_in_flight * G * plan->lpad * 8;
@@ -3815,6 +3868,19 @@ int drift_batch(ffs_drift_plan* plan, int n_pairs, const Pairs& a, int64_t block
                                    rep->top_k, rep->exclusion, (const int32_t*)rep->n_segments, out);
             }
         }
+        if (fit) {
+            ffsa::SmoothSegment* out = (ffsa::SmoothSegment*)fit->out;
+            hipLaunchKernelGGL(ffsa::k_smooth_intervals, dim3(np), dim3(ffsa::SMOOTH_INT_THREADS), 0, st, dd, plan->sw, (int)K,
+                               fit->knot_blocks, max_b, (const int32_t*)block_offset_out_dev,
+                               (const uint8_t*)block_jump_out_dev, fit->smooth_offset, fit->knot, out, fit->n_segments);
+            hipLaunchKernelGGL(ffsa::k_drift_line_sums, dim3((unsigned)(np * ffsa::SMOOTH_LINE_GROUPS)),
+                               dim3(ffsa::SMOOTH_LINE_THREADS), 0, st, dd, plan->ws, plan->sw, (int)K, (int64_t)W, fit->radius,
+                               max_b, (const int32_t*)block_offset_out_dev);
+            hipLaunchKernelGGL(ffsa::k_drift_knot_dp, dim3((unsigned)(np * ffsa::SMOOTH_DP_GROUPS)),
+                               dim3(ffsa::SMOOTH_DP_THREADS), 0, st, dd, plan->sw, fit->knot_blocks, fit->radius,
+                               fit->bend_cost, max_b, (const int32_t*)block_offset_out_dev,
+                               (const int32_t*)fit->n_segments, fit->smooth_offset, out);
+        }
         HIP_TRY(hipGetLastError());
     }
     return plan->end(st);
@@ -3829,7 +3895,8 @@ int ffs_align_drift_batch(ffs_drift_plan* plan, int n_pairs, const void* const* 
                           void* hip_stream) {
     const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
     return drift_batch(plan, n_pairs, a, block_samples, max_offset_samples, split_penalty, max_step, step_cost,
-                       block_offset_out_dev, block_score_out_dev, block_jump_out_dev, total_out_dev, nullptr, hip_stream);
+                       block_offset_out_dev, block_score_out_dev, block_jump_out_dev, total_out_dev, nullptr, nullptr,
+                       hip_stream);
 }
 
 int ffs_align_drift_report_batch(ffs_drift_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
@@ -3842,7 +3909,24 @@ int ffs_align_drift_report_batch(ffs_drift_plan* plan, int n_pairs, const void* 
     const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
     const DriftReportArgs rep{top_k, exclusion_samples, report_out_dev, n_segments_out_dev};
     return drift_batch(plan, n_pairs, a, block_samples, max_offset_samples, split_penalty, max_step, step_cost,
-                       block_offset_out_dev, block_score_out_dev, block_jump_out_dev, total_out_dev, &rep, hip_stream);
+                       block_offset_out_dev, block_score_out_dev, block_jump_out_dev, total_out_dev, &rep, nullptr,
+                       hip_stream);
+}
+
+int ffs_align_drift_smooth_batch(ffs_drift_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
+                                 const double* ref_lo, const double* ref_hi, const void* const* sub_ptr,
+                                 const int64_t* sub_len, const double* sub_lo, const double* sub_hi, int64_t block_samples,
+                                 int64_t max_offset_samples, double split_penalty, int max_step, double step_cost,
+                                 int knot_blocks, int radius, double bend_cost, int32_t* block_offset_out_dev,
+                                 double* block_score_out_dev, uint8_t* block_jump_out_dev, double* total_out_dev,
+                                 int32_t* smooth_offset_out_dev, uint8_t* knot_out_dev, ffs_smooth_segment* segment_out_dev,
+                                 int32_t* n_segments_out_dev, void* hip_stream) {
+    const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
+    const DriftSmoothArgs fit{knot_blocks, radius, bend_cost, smooth_offset_out_dev, knot_out_dev, segment_out_dev,
+                              n_segments_out_dev};
+    return drift_batch(plan, n_pairs, a, block_samples, max_offset_samples, split_penalty, max_step, step_cost,
+                       block_offset_out_dev, block_score_out_dev, block_jump_out_dev, total_out_dev, nullptr, &fit,
+                       hip_stream);
 }
 
 /* ---- alignment quality report (csrc/ffs_quality.h) ------------------------------------------------------------- */

@@ -744,6 +744,61 @@ int ffs_align_drift_report_batch(ffs_drift_plan* plan, int n_pairs, const void* 
                                  uint8_t* block_jump_out_dev, double* total_out_dev, ffs_segment_report* report_out_dev,
                                  int32_t* n_segments_out_dev, void* hip_stream);
 
+/* ---- smooth drift fit: each segment's path as a polyline of knots (csrc/ffs_drift_smooth.h) ------------------------
+ * Replaces: nothing in the reference.  The contract below is pinned against the numpy model
+ * tests/drift_smooth_model.py, bit for bit.
+ *
+ * The drift solve of ffs_align_drift_batch (same arguments, same four outputs bit for bit), then inside every segment
+ * [f, e) of it (as ffs_align_drift_report_batch forms them), with M = knot_blocks in [1, 256], R = radius in [0, 16],
+ * lambda = bend_cost (finite, >= 0) and n = e - 1 - f:
+ *   a one-block segment is returned as it is (its block is its one knot; fit_total = line_score = bend_total = 0.0);
+ *   knots: I = max(1, (n + M/2) / M) intervals (integer division), knot blocks k_i = f + i M for i < I and k_I = e - 1;
+ *     interval i has n_i = k_{i+1} - k_i blocks and holds the blocks k_i <= b < k_{i+1}, the last interval b = k_I too;
+ *   candidates: knot i at lag c_i = o_{k_i} + u, u in [-R, R], only where -W + 1 <= c_i <= W;
+ *   digital line: block b of interval i has lag d_b = c_i + floor((2 (c_{i+1} - c_i)(b - k_i) + n_i) / (2 n_i));
+ *   line score T_i(c_i, c_{i+1}): ov, n1x, nx1, n11 of ffs_segment_report's path curve summed as exact integers over the
+ *     interval's blocks at their lags d_b, then scored ONCE by that expression; exactly 0.0 where the overlap is 0;
+ *   bend cost at an interior knot i between intervals of n_a and n_b blocks, D1 = c_i - c_{i-1}, D2 = c_{i+1} - c_i:
+ *     g = |D2 n_a - D1 n_b| (int64), then ((lambda * (double)g) * (double)M) / (double)(n_a n_b), every fp64 operation
+ *     rounded on its own -- lambda |D2 - D1| between equal intervals, nothing for a straight line of any slope;
+ *   optimum: V_1 = T_0, V_{i+1}(c_i, c_{i+1}) = max over c_{i-1} of (V_i(c_{i-1}, c_i) - bend_i) + T_i(c_i, c_{i+1}),
+ *     fit_total = max V_I.  Ties: candidates are tried in the order u = 0, +1, -1, +2, -2, ... and one replaces the best
+ *     so far only when strictly greater -- over the predecessor at every step, over the final state with u_I as the
+ *     outer and u_{I-1} as the inner loop.  Ties stay on the path.
+ * Outputs: smooth_offset_out_dev[p * max_b + b] = d_b (int32; entries b >= B_p are 0); knot_out_dev[p * max_b + b]
+ * (uint8) = 1 where b is a knot; segment_out_dev[p * max_b + i] for segment i (records past the segment count are zero):
+ * fit_total, line_score (the chosen T_i summed in interval order from 0.0), bend_total (the chosen bend costs in knot
+ * order from 0.0) and n_knots; n_segments_out_dev[p].  Nothing is read back: the call is asynchronous.
+ * The first smooth call on a plan adds some pairs_in_flight * max_blocks * 9837 bytes (33 * 33 fp64 line scores and
+ * back-pointer bytes per interval, the segment and interval tables; 6.9 MB per pair at 2 h, K = 1024), counted by ffs_drift_plan_workspace_bytes from then on; plans that never call it keep
+ * their size, and drift results after it stay bit-identical.
+ * FFS_E_INVALID / FFS_E_EMPTY as ffs_align_drift_batch, and FFS_E_INVALID for knot_blocks, radius or bend_cost outside
+ * the ranges above or a null / misaligned output (smooth offsets and counts 4-byte, records 8-byte aligned); all before
+ * any launch, the outputs untouched. */
+#define FFS_SMOOTH_MAX_KNOT_BLOCKS 256
+#define FFS_SMOOTH_MAX_RADIUS 16
+
+typedef struct ffs_smooth_segment {
+    double fit_total;          /* the Viterbi maximum: line scores minus bend costs */
+    double line_score;         /* sum of the chosen lines' scores */
+    double bend_total;         /* sum of the chosen knots' bend costs */
+    int32_t n_knots, reserved; /* I + 1 (1 for a one-block segment); 0 */
+} ffs_smooth_segment;
+#ifdef __cplusplus
+static_assert(sizeof(ffs_smooth_segment) == 32, "ffs_smooth_segment is 32 bytes");
+#else
+_Static_assert(sizeof(ffs_smooth_segment) == 32, "ffs_smooth_segment is 32 bytes");
+#endif
+
+int ffs_align_drift_smooth_batch(ffs_drift_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
+                                 const double* ref_lo, const double* ref_hi, const void* const* sub_ptr,
+                                 const int64_t* sub_len, const double* sub_lo, const double* sub_hi, int64_t block_samples,
+                                 int64_t max_offset_samples, double split_penalty, int max_step, double step_cost,
+                                 int knot_blocks, int radius, double bend_cost, int32_t* block_offset_out_dev,
+                                 double* block_score_out_dev, uint8_t* block_jump_out_dev, double* total_out_dev,
+                                 int32_t* smooth_offset_out_dev, uint8_t* knot_out_dev, ffs_smooth_segment* segment_out_dev,
+                                 int32_t* n_segments_out_dev, void* hip_stream);
+
 /* Thread-local description of the last error returned on this thread ("" if none). */
 const char* ffs_last_error(void);
 
