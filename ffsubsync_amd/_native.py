@@ -145,12 +145,18 @@ EXPORTED_SYMBOLS = (
     "ffs_quality_plan_destroy",
     "ffs_quality_plan_workspace_bytes",
     "ffs_align_quality_batch",
+    "ffs_match_plan_create",
+    "ffs_match_plan_destroy",
+    "ffs_match_plan_workspace_bytes",
+    "ffs_match_quality_batch",
     "ffs_last_error",
     "ffs_version",
 )
 KERNEL_NAMES = ("pass_a", "mid", "pass_c", "nominees", "rescore", "runs_extract", "runs_corr", "levels")
 FFS_ALGO_AUTO, FFS_ALGO_FFT, FFS_ALGO_RUNS = 0, 1, 2
 ALGORITHMS = {"auto": FFS_ALGO_AUTO, "fft": FFS_ALGO_FFT, "runs": FFS_ALGO_RUNS}
+FFS_MATCH_AUTO, FFS_MATCH_RUNS, FFS_MATCH_BITS = 0, 1, 2  # ffs_match_quality_batch's `algorithm`
+MATCH_ALGORITHMS = {"auto": FFS_MATCH_AUTO, "runs": FFS_MATCH_RUNS, "bits": FFS_MATCH_BITS}
 
 
 def algorithm_code(algorithm) -> int:
@@ -374,6 +380,17 @@ def load():
         lib.ffs_align_quality_batch.argtypes = [c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
                                                 c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int,
                                                 c.c_int64, c.c_void_p, c.c_void_p]
+        lib.ffs_match_plan_create.restype = c.c_int
+        lib.ffs_match_plan_create.argtypes = [c.c_int, c.c_int, c.c_int64, c.c_int64, c.c_int64, c.POINTER(c.c_void_p)]
+        lib.ffs_match_plan_destroy.restype = c.c_int
+        lib.ffs_match_plan_destroy.argtypes = [c.c_void_p]
+        lib.ffs_match_plan_workspace_bytes.restype = c.c_int64
+        lib.ffs_match_plan_workspace_bytes.argtypes = [c.c_void_p]
+        lib.ffs_match_quality_batch.restype = c.c_int
+        lib.ffs_match_quality_batch.argtypes = [c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                                                c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int,
+                                                c.c_void_p, c.c_void_p, c.c_int64, c.c_int, c.c_int64, c.c_int,
+                                                c.c_void_p, c.c_void_p]
         lib.ffs_last_error.restype = c.c_char_p
         lib.ffs_last_error.argtypes = []
         lib.ffs_version.restype = c.c_int
@@ -1125,6 +1142,53 @@ class QualityPlan(_SidePlan):
     def close(self) -> None:
         super().close()
         self.scratch = None
+
+
+def match_algorithm_code(algorithm) -> int:
+    """FFS_MATCH_* code of "auto" / "runs" / "bits" (any case, surrounding blanks ignored) or of a code itself."""
+    if isinstance(algorithm, (int, np.integer)) and not isinstance(algorithm, bool) and int(algorithm) in MATCH_ALGORITHMS.values():
+        return int(algorithm)
+    name = algorithm.strip().lower() if isinstance(algorithm, str) else None
+    if name not in MATCH_ALGORITHMS:
+        raise ValueError("unknown algorithm %r: expected one of %s" % (algorithm, ", ".join(sorted(MATCH_ALGORITHMS))))
+    return MATCH_ALGORITHMS[name]
+
+
+class MatchPlan(_SidePlan):
+    """Owns one ``ffs_match_plan``: the workspace of the all-pairs quality report from boundary lists (``match.py``) for
+    ``pairs_in_flight`` pairs of up to ``max_lags`` lags and ``max_vectors`` vectors (references and subtitle vectors
+    together) of up to ``max_samples`` samples."""
+
+    _create, _destroy, _workspace = "ffs_match_plan_create", "ffs_match_plan_destroy", "ffs_match_plan_workspace_bytes"
+
+    def __init__(self, pairs_in_flight: int, max_lags: int, max_samples: int, max_vectors: int,
+                 device: Optional[int] = None) -> None:
+        self.pairs_in_flight, self.max_lags = int(pairs_in_flight), int(max_lags)
+        self.max_samples, self.max_vectors = int(max_samples), int(max_vectors)
+        super().__init__((pairs_in_flight, max_lags, max_samples, max_vectors), device)
+
+    def report(self, ref_list, ref_len, ref_lo, ref_hi, sub_list, sub_len, sub_lo, sub_hi, pair_ref, pair_sub,
+               max_offset_samples, top_k: int, exclusion_samples: int, out, algorithm="auto",
+               stream: Optional[int] = None) -> None:
+        """``ffs_match_quality_batch``: host tables of the references and of the subtitle vectors (device pointers of
+        their ``ffs_runs_list`` blocks, lengths, two levels) and the index pairs, into a uint8 CUDA tensor of
+        n_pairs * 160 bytes.  ``max_offset_samples`` None = no window."""
+        kinds = (np.uint64, np.int64, np.float64, np.float64)
+        rt = [np.ascontiguousarray(a, dtype=t) for a, t in zip((ref_list, ref_len, ref_lo, ref_hi), kinds)]
+        stb = [np.ascontiguousarray(a, dtype=t) for a, t in zip((sub_list, sub_len, sub_lo, sub_hi), kinds)]
+        if not all(b.size == rt[0].size for b in rt) or not all(b.size == stb[0].size for b in stb):
+            raise ValueError("one table entry per vector")
+        pr = np.ascontiguousarray(pair_ref, dtype=np.int32)
+        ps = np.ascontiguousarray(pair_sub, dtype=np.int32)
+        if pr.size != ps.size:
+            raise ValueError("one reference index and one subtitle index per pair")
+        if out.numel() * out.element_size() < pr.size * QUALITY_RESULT_BYTES:
+            raise ValueError("output buffer too small")
+        mo = -1 if max_offset_samples is None else int(max_offset_samples)
+        check(self.lib.ffs_match_quality_batch(self.handle, rt[0].size, *[b.ctypes.data for b in rt], stb[0].size,
+                                               *[b.ctypes.data for b in stb], pr.size, pr.ctypes.data, ps.ctypes.data, mo,
+                                               int(top_k), int(exclusion_samples), match_algorithm_code(algorithm),
+                                               out.data_ptr(), self._stream(stream)))
 
 
 class SidePlanCache:

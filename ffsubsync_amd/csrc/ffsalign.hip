@@ -27,6 +27,7 @@
 #include "ffs_runs.h"
 #include "ffs_split.h"
 #include "ffs_quality.h"
+#include "ffs_match.h"
 #include "ffs_split_report.h"
 #include "ffs_split_refine.h"
 #include "ffs_split_range.h"
@@ -4069,6 +4070,270 @@ int ffs_align_quality_batch(ffs_quality_plan* plan, int n_pairs, const void* con
             const int64_t n_chunks = (max_sw + cw - 1) / cw;
             hipLaunchKernelGGL(ffsa::k_quality_counts, dim3((unsigned)(np * n_tiles * n_chunks)), dim3(ffsa::QUAL_CNT_THREADS),
                                0, st, dq, (int)n_tiles, (int)n_chunks, (int)cw);
+        }
+        hipLaunchKernelGGL(ffsa::k_quality_peaks, dim3(np), dim3(ffsa::QUAL_PEAK_THREADS), 0, st, dq, top_k,
+                           exclusion_samples, (ffsa::QualResult*)out_dev);
+        HIP_TRY(hipGetLastError());
+    }
+    return plan->end(st);
+}
+
+/* ---- all-pairs quality report from boundary lists (csrc/ffs_match.h) ------------------------------------------- */
+
+struct ffs_match_plan : PlanCore {
+    int64_t max_lags, max_samples, max_vectors;
+    int64_t lpad, vec_words, pre_words;  // padded curve row; bit words / prefix words per vector slot
+    uint32_t* curve;                     // [slot][lpad]
+    double* sc;                          // [slot][lpad]
+    uint32_t* bits;                      // [vector][vec_words]
+    int32_t* pre;                        // [vector][pre_words]
+    ffsa::MatchHdr* hdr_dev;             // [vector]
+    ffsa::MatchHdr* hdr_host;            // pinned
+    DescStaging vec;                     // per call: list pointers, ExpandVec and SplitDesc tables of the vectors
+    DescStaging desc;                    // per sub-batch: QualDesc[pairs_in_flight], then MatchLists[pairs_in_flight]
+    size_t off_expand, off_split, vec_bytes;
+};
+
+int ffs_match_plan_create(int device, int pairs_in_flight, int64_t max_lags, int64_t max_samples, int64_t max_vectors,
+                          ffs_match_plan** out) {
+    if (!out) return fail(FFS_E_INVALID, "null output handle");
+    *out = nullptr;
+    if (pairs_in_flight < 1 || max_lags < 1 || max_lags > (int64_t(1) << 31) || max_samples < 1 ||
+        max_samples >= (int64_t(1) << 29) || max_vectors < 2 || max_vectors > (int64_t(1) << 24))
+        return fail(FFS_E_INVALID, "match plan: need pairs_in_flight >= 1, 1 <= max_lags <= 2^31, 1 <= max_samples < 2^29, "
+                                   "2 <= max_vectors <= 2^24");
+    HIP_TRY(hipSetDevice(device));
+    ffs_match_plan* p = new (std::nothrow) ffs_match_plan();
+    if (!p) return fail(FFS_E_NOMEM, "match plan");
+    p->max_lags = max_lags;
+    p->max_samples = max_samples;
+    p->max_vectors = max_vectors;
+    p->lpad = split_align_up(max_lags, 64);
+    p->vec_words = split_align_up(max_samples / 32 + 1, 16);
+    p->pre_words = split_align_up(max_samples / 32 + 2, 16);
+    const int64_t n = pairs_in_flight, nv = max_vectors;
+    const int64_t b_sc = n * p->lpad * 8, b_curve = n * p->lpad * 4, b_bits = nv * p->vec_words * 4,
+                  b_pre = nv * p->pre_words * 4, b_hdr = split_align_up(nv * (int64_t)sizeof(ffsa::MatchHdr), 64);
+    if (int rc = p->open(device, pairs_in_flight, b_sc + b_curve + b_bits + b_pre + b_hdr, "match plan")) {
+        ffs_match_plan_destroy(p);
+        return rc;
+    }
+    char* w = (char*)p->work;
+    p->sc = (double*)w;
+    p->curve = (uint32_t*)(w + b_sc);
+    p->bits = (uint32_t*)(w + b_sc + b_curve);
+    p->pre = (int32_t*)(w + b_sc + b_curve + b_bits);
+    p->hdr_dev = (ffsa::MatchHdr*)(w + b_sc + b_curve + b_bits + b_pre);
+    p->off_expand = (size_t)split_align_up(nv * 8, 64);
+    p->off_split = p->off_expand + (size_t)split_align_up(nv * (int64_t)sizeof(ExpandVec), 64);
+    p->vec_bytes = p->off_split + sizeof(ffsa::SplitDesc) * (size_t)((nv + 1) / 2);
+    if (hipHostMalloc((void**)&p->hdr_host, (size_t)nv * sizeof(ffsa::MatchHdr), hipHostMallocDefault) != hipSuccess) {
+        p->hdr_host = nullptr;
+        ffs_match_plan_destroy(p);
+        return fail(FFS_E_HIP, "match plan: header staging");
+    }
+    if (p->vec.create(p->vec_bytes) != FFS_OK ||
+        p->desc.create((sizeof(ffsa::QualDesc) + sizeof(ffsa::MatchLists)) * (size_t)pairs_in_flight) != FFS_OK) {
+        ffs_match_plan_destroy(p);
+        return fail(FFS_E_HIP, "match plan: descriptor buffers / events");
+    }
+    *out = p;
+    return FFS_OK;
+}
+
+int ffs_match_plan_destroy(ffs_match_plan* plan) {
+    if (!plan) return FFS_OK;
+    plan->close();
+    plan->vec.release();
+    plan->desc.release();
+    if (plan->hdr_host) (void)hipHostFree(plan->hdr_host);
+    delete plan;
+    return FFS_OK;
+}
+
+int64_t ffs_match_plan_workspace_bytes(const ffs_match_plan* plan) { return plan ? plan->work_bytes : 0; }
+
+int ffs_match_quality_batch(ffs_match_plan* plan, int n_ref, const void* const* ref_list, const int64_t* ref_len,
+                            const double* ref_lo, const double* ref_hi, int n_sub, const void* const* sub_list,
+                            const int64_t* sub_len, const double* sub_lo, const double* sub_hi, int n_pairs,
+                            const int32_t* pair_ref, const int32_t* pair_sub, int64_t max_offset_samples, int top_k,
+                            int64_t exclusion_samples, int algorithm, ffs_quality_result* out_dev, void* hip_stream) {
+    if (!plan) return fail(FFS_E_INVALID, "null match plan");
+    if (n_pairs < 0 || n_ref < 0 || n_sub < 0) return fail(FFS_E_INVALID, "n_pairs / n_ref / n_sub < 0");
+    if (n_pairs == 0) return FFS_OK;
+    if (!ref_list || !ref_len || !ref_lo || !ref_hi || !sub_list || !sub_len || !sub_lo || !sub_hi || !pair_ref || !pair_sub ||
+        !out_dev)
+        return fail(FFS_E_INVALID, "null argument");
+    if (max_offset_samples < -1) return fail(FFS_E_INVALID, "max_offset_samples=%lld: need >= 0, or -1 for none", (long long)max_offset_samples);
+    if (top_k < 1 || top_k > ffsa::QUAL_MAX_PEAKS) return fail(FFS_E_INVALID, "top_k=%d outside [1, 8]", top_k);
+    if (exclusion_samples < 1) return fail(FFS_E_INVALID, "exclusion_samples=%lld: need >= 1", (long long)exclusion_samples);
+    if ((uintptr_t)out_dev & 7) return fail(FFS_E_INVALID, "misaligned output records");
+    if (algorithm != FFS_MATCH_AUTO && algorithm != FFS_MATCH_RUNS && algorithm != FFS_MATCH_BITS)
+        return fail(FFS_E_INVALID, "algorithm=%d: need FFS_MATCH_AUTO, FFS_MATCH_RUNS or FFS_MATCH_BITS", algorithm);
+    const int64_t nv = (int64_t)n_ref + n_sub;
+    if (nv > plan->max_vectors)
+        return fail(FFS_E_INVALID, "%d references + %d subtitle vectors exceed the plan's max_vectors %lld", n_ref, n_sub,
+                    (long long)plan->max_vectors);
+    // vector v < n_ref: reference v; else subtitle vector v - n_ref
+    auto v_list = [&](int64_t v) { return v < n_ref ? ref_list[v] : sub_list[v - n_ref]; };
+    auto v_len = [&](int64_t v) { return v < n_ref ? ref_len[v] : sub_len[v - n_ref]; };
+    for (int64_t v = 0; v < nv; ++v) {
+        const bool is_ref = v < n_ref;
+        const int64_t i = is_ref ? v : v - n_ref;
+        const char* role = is_ref ? "reference" : "subtitle vector";
+        if (v_len(v) <= 0)
+            return fail(FFS_E_EMPTY, "cannot align empty speech data (%s %lld has length %lld)", role, (long long)i,
+                        (long long)(v_len(v) > 0 ? v_len(v) : 0));
+        if (!v_list(v) || ((uintptr_t)v_list(v) & 7)) return fail(FFS_E_INVALID, "%s %lld: null or misaligned list block", role, (long long)i);
+        if (v_len(v) > plan->max_samples)
+            return fail(FFS_E_INVALID, "%s %lld: %lld samples exceed the plan's max_samples %lld", role, (long long)i,
+                        (long long)v_len(v), (long long)plan->max_samples);
+        const double lo = is_ref ? ref_lo[i] : sub_lo[i], hi = is_ref ? ref_hi[i] : sub_hi[i];
+        if (!(std::isfinite(lo) && std::isfinite(hi))) return fail(FFS_E_INVALID, "%s %lld: levels must be finite", role, (long long)i);
+    }
+    for (int p = 0; p < n_pairs; ++p) {
+        if (pair_ref[p] < 0 || pair_ref[p] >= n_ref || pair_sub[p] < 0 || pair_sub[p] >= n_sub)
+            return fail(FFS_E_INVALID, "pair %d: index (%d, %d) outside the %d references x %d subtitle vectors", p,
+                        (int)pair_ref[p], (int)pair_sub[p], n_ref, n_sub);
+        const int64_t R = ref_len[pair_ref[p]], S = sub_len[pair_sub[p]];
+        int64_t wl = 0, wh = -1;
+        if (lag_window(R, S, ffs_fft_length(R, S), max_offset_samples, &wl, &wh) && wh - wl + 1 > plan->max_lags)
+            return fail(FFS_E_INVALID, "pair %d: %lld lags exceed the plan's max_lags %lld", p, (long long)(wh - wl + 1),
+                        (long long)plan->max_lags);
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (int rc = plan->begin(st)) return rc;
+    // the lists' headers (the one device step in front of the checks: it writes the plan's workspace only)
+    if (int rc = plan->vec.wait_free()) return rc;
+    char* hv = (char*)plan->vec.host;
+    const char* dv = (const char*)plan->vec.dev;
+    const void** h_ptr = (const void**)hv;
+    ExpandVec* h_ev = (ExpandVec*)(hv + plan->off_expand);
+    ffsa::SplitDesc* h_sd = (ffsa::SplitDesc*)(hv + plan->off_split);
+    memset(h_sd, 0, sizeof(ffsa::SplitDesc) * (size_t)((nv + 1) / 2));
+    for (int64_t v = 0; v < nv; ++v) {
+        const char* blk = (const char*)v_list(v);
+        uint32_t* bits = plan->bits + v * plan->vec_words;
+        int32_t* pre = plan->pre + v * plan->pre_words;
+        h_ptr[v] = blk;
+        h_ev[v] = ExpandVec{(const int2*)(blk + 16), (const int2*)blk, (unsigned*)bits, (int32_t)v_len(v), 0};
+        ffsa::SplitDesc& sd = h_sd[v >> 1];  // two vectors per descriptor: the even one as its `s`, the odd one as its `r`
+        if (v & 1) {
+            sd.r = bits;
+            sd.R = v_len(v);
+            sd.pre_r = pre;
+        } else {
+            sd.s = bits;
+            sd.S = v_len(v);
+            sd.pre_s = pre;
+        }
+    }
+    if (int rc = plan->vec.upload(plan->vec_bytes, st)) return rc;
+    hipLaunchKernelGGL(ffsa::k_match_headers, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, (const int2* const*)dv,
+                       (int)nv, plan->hdr_dev);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(plan->hdr_host, plan->hdr_dev, (size_t)nv * sizeof(ffsa::MatchHdr), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const ffsa::MatchHdr* hd = plan->hdr_host;
+    for (int64_t v = 0; v < nv; ++v) {
+        const bool is_ref = v < n_ref;
+        const long long i = is_ref ? v : v - n_ref;
+        const char* role = is_ref ? "reference" : "subtitle vector";
+        if (hd[v].n >= hd[v].cap)
+            return fail(FFS_E_INVALID, "%s %lld: truncated boundary list (%d boundaries, capacity %d)", role, i, hd[v].n, hd[v].cap);
+        if (hd[v].n < 0 || (hd[v].n & 1) || hd[v].len != v_len(v))
+            return fail(FFS_E_INVALID, "%s %lld: not the boundary list of a vector of %lld samples (n=%d, len=%d)", role, i,
+                        (long long)v_len(v), hd[v].n, hd[v].len);
+    }
+    // per vector, once: bits and word prefixes in the workspace
+    int64_t max_len = 0;
+    for (int64_t v = 0; v < nv; ++v) max_len = std::max(max_len, v_len(v));
+    const int chunks_per_vec = (int)(((max_len + 31) / 32 + 255) / 256);
+    hipLaunchKernelGGL(k_runs_expand, dim3((unsigned)(nv * chunks_per_vec)), dim3(256), 0, st,
+                       (const ExpandVec*)(dv + plan->off_expand), chunks_per_vec, (int*)nullptr);
+    hipLaunchKernelGGL(ffsa::k_split_prefix, dim3((unsigned)nv), dim3(ffsa::SPLIT_PREFIX_THREADS), 0, st,
+                       (const ffsa::SplitDesc*)(dv + plan->off_split), (int64_t)(int64_t(1) << 40));
+    HIP_TRY(hipGetLastError());
+    const int pif = plan->pairs_in_flight;
+    ffsa::QualDesc* hq = (ffsa::QualDesc*)plan->desc.host;
+    ffsa::MatchLists* hl = (ffsa::MatchLists*)(hq + pif);
+    const ffsa::QualDesc* dq = (const ffsa::QualDesc*)plan->desc.dev;
+    const ffsa::MatchLists* dl = (const ffsa::MatchLists*)(dq + pif);
+    int n_sm = 0;
+    HIP_TRY(hipDeviceGetAttribute(&n_sm, hipDeviceAttributeMultiprocessorCount, plan->device));
+    std::vector<int> order((size_t)pif);
+    for (int p0 = 0; p0 < n_pairs; p0 += pif) {
+        const int np = std::min(pif, n_pairs - p0);
+        if (int rc = plan->desc.wait_free()) return rc;
+        // list pairs first, bit pairs behind them (k_quality_peaks finds a pair's record by its out_row)
+        int n_runs = 0, n_bits = 0;
+        for (int i = 0; i < np; ++i) {
+            const int p = p0 + i;
+            const int64_t vr = pair_ref[p], vs = (int64_t)n_ref + pair_sub[p];
+            bool runs = algorithm == FFS_MATCH_RUNS;
+            if (algorithm == FFS_MATCH_AUTO)  // coincidences per lag |P||Q| / R against S / 32 word steps per lag
+                runs = (double)hd[vr].n * (double)hd[vs].n * FFS_MATCH_AUTO_COST <= (double)v_len(vr) * ((double)v_len(vs) / 32.0);
+            if (runs)
+                order[(size_t)n_runs++] = p;
+            else
+                order[(size_t)(np - 1 - n_bits++)] = p;
+        }
+        int64_t max_lags_runs = 0, max_count_bits = 0, max_sw = 0;
+        for (int i = 0; i < np; ++i) {
+            const int p = order[(size_t)i];
+            const int ir = pair_ref[p], is = pair_sub[p];
+            const int64_t vr = ir, vs = (int64_t)n_ref + is;
+            const int64_t R = ref_len[ir], S = sub_len[is];
+            ffsa::QualDesc& q = hq[i];
+            memset(&q, 0, sizeof q);
+            q.r = plan->bits + vr * plan->vec_words;
+            q.s = plan->bits + vs * plan->vec_words;
+            q.R = R;
+            q.S = S;
+            int64_t wl = 0, wh = -1;
+            if (lag_window(R, S, ffs_fft_length(R, S), max_offset_samples, &wl, &wh)) {
+                q.d_lo = wl;
+                q.n_lags = wh - wl + 1;
+                const int64_t clo = std::max(wl, 1 - S), chi = std::min(wh, R - 1);
+                q.c_lo = clo;
+                q.n_count = chi >= clo ? chi - clo + 1 : 0;
+            }
+            q.cd.R = (int32_t)R;
+            q.cd.S = (int32_t)S;
+            q.cd.s0 = mapped(sub_lo[is]);
+            q.cd.s1 = mapped(sub_hi[is]);
+            q.cd.r0 = mapped(ref_lo[ir]);
+            q.cd.r1 = mapped(ref_hi[ir]);
+            q.pre_r = plan->pre + vr * plan->pre_words;
+            q.pre_s = plan->pre + vs * plan->pre_words;
+            q.curve = plan->curve + (int64_t)i * plan->lpad;
+            q.sc = plan->sc + (int64_t)i * plan->lpad;
+            q.out_row = p;
+            hl[i] = ffsa::MatchLists{(const int2*)((const char*)ref_list[ir] + 16), (const int2*)((const char*)sub_list[is] + 16),
+                                     hd[vr].n, hd[vs].n, hd[vr].ones, 0};
+            if (i < n_runs) {
+                max_lags_runs = std::max(max_lags_runs, q.n_lags);
+            } else {
+                max_count_bits = std::max(max_count_bits, q.n_count);
+                max_sw = std::max(max_sw, (S + 31) / 32);
+            }
+        }
+        // one upload of both arrays (the MatchLists half is at a fixed offset: copy the whole used span)
+        if (int rc = plan->desc.upload(sizeof(ffsa::QualDesc) * pif + sizeof(ffsa::MatchLists) * np, st)) return rc;
+        if (n_runs > 0 && max_lags_runs > 0) {
+            const int64_t n_tiles = (max_lags_runs + ffsa::MATCH_TILE - 1) / ffsa::MATCH_TILE;
+            hipLaunchKernelGGL(ffsa::k_runs_curve, dim3((unsigned)(n_runs * n_tiles)), dim3(ffsa::MATCH_THREADS), 0, st, dq, dl,
+                               (int)n_tiles);
+        }
+        if (n_bits > 0 && max_count_bits > 0) {  // k_quality_counts as ffs_align_quality_batch launches it
+            HIP_TRY(hipMemsetAsync(plan->curve + (int64_t)n_runs * plan->lpad, 0, (size_t)n_bits * plan->lpad * 4, st));
+            const int64_t n_tiles = (max_count_bits + ffsa::QUAL_TILE - 1) / ffsa::QUAL_TILE;
+            const int64_t want = std::max<int64_t>(1, (int64_t)n_sm * 4);
+            int64_t cw = (n_bits * n_tiles * max_sw + want - 1) / want;
+            cw = std::min<int64_t>(ffsa::QUAL_MAX_CHUNK, std::max<int64_t>(64, cw));
+            const int64_t n_chunks = (max_sw + cw - 1) / cw;
+            hipLaunchKernelGGL(ffsa::k_quality_counts, dim3((unsigned)(n_bits * n_tiles * n_chunks)), dim3(ffsa::QUAL_CNT_THREADS),
+                               0, st, dq + n_runs, (int)n_tiles, (int)n_chunks, (int)cw);
         }
         hipLaunchKernelGGL(ffsa::k_quality_peaks, dim3(np), dim3(ffsa::QUAL_PEAK_THREADS), 0, st, dq, top_k,
                            exclusion_samples, (ffsa::QualResult*)out_dev);

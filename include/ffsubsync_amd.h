@@ -488,6 +488,49 @@ int ffs_align_quality_batch(ffs_quality_plan* plan, int n_pairs, const void* con
                             const double* sub_lo, const double* sub_hi, int64_t max_offset_samples, int top_k,
                             int64_t exclusion_samples, ffs_quality_result* out_dev, void* hip_stream);
 
+/* ---- all-pairs quality report from boundary lists: which subtitle belongs to which video (csrc/ffs_match.h) ------
+ * Replaces: nothing in the reference.  The records are those of ffs_align_quality_batch, byte for byte; the contract of
+ * the lag set, the scores, the moments and the peaks is the section above and is pinned by the same model
+ * (tests/quality_model.py; tests/match_model.py states the matrix and the assignment built on it).
+ *
+ * Inputs: two TABLES of device-resident two-level vectors, n_ref references and n_sub subtitle vectors, each an
+ * `ffs_runs_list` block (FFS_DTYPE_RUNS, 8-byte aligned) with its length in samples and its two levels, and n_pairs
+ * index pairs (pair_ref[p], pair_sub[p]) in host arrays -- any order, repeats allowed; an N x M call lists all N * M.
+ * Output: out_dev[p] = the ffs_quality_result of reference pair_ref[p] against subtitle vector pair_sub[p], equal to
+ * what ffs_align_quality_batch writes for the same two vectors as bits, on every `algorithm`.
+ *
+ * Work per VECTOR, once per call whatever the number of its partners: its bits (one expansion launch over the table) and
+ * their word prefix popcounts, into the plan's workspace.  Work per PAIR: the n11 curve over the lag window straight from
+ * the two lists (k_runs_curve: ~|P| * |Q| * lags / R boundary coincidences; FFS_MATCH_RUNS), or the bit-parallel count of
+ * ffs_align_quality_batch on the per-vector bits (FFS_MATCH_BITS); FFS_MATCH_AUTO picks per pair: lists while
+ * |P| * |Q| * FFS_MATCH_AUTO_COST <= R * S / 32 (DESIGN 3.13 has the measurement behind the constant).
+ *
+ * A plan owns the workspace: per pair in flight max_lags * 12 bytes (uint32 n11 curve + fp64 scores), per vector
+ * ~max_samples / 4 bytes (bits + prefixes; 180 KB for a 2 h vector) for up to max_vectors vectors (references and
+ * subtitle vectors together).  max_samples < 2^29.  Calls with more pairs run in sub-batches of pairs_in_flight on the
+ * caller's stream.  A plan serves one host thread at a time; successive calls (any streams) are ordered by the library.
+ *
+ * Refused with nothing written to out_dev, each with a message naming the cause: FFS_E_EMPTY for a vector of length 0;
+ * FFS_E_INVALID for top_k outside [1, 8], exclusion_samples < 1, max_offset_samples < -1, an unknown algorithm, a null or
+ * misaligned block, non-finite levels, n_ref + n_sub > max_vectors, a vector longer than max_samples, a lag set larger
+ * than max_lags, a pair index out of range -- all before any device work -- and a truncated list (n >= cap) or one whose
+ * header names another length.  The list headers live on the device: the call gathers them into the workspace and waits
+ * for that copy (one synchronisation of hip_stream per call) before it launches anything that depends on them. */
+#define FFS_MATCH_AUTO 0 /* per pair, from the list lengths */
+#define FFS_MATCH_RUNS 1 /* every pair from its boundary lists */
+#define FFS_MATCH_BITS 2 /* every pair by the bit-parallel count on the per-vector bits */
+
+typedef struct ffs_match_plan ffs_match_plan;
+int ffs_match_plan_create(int device, int pairs_in_flight, int64_t max_lags, int64_t max_samples, int64_t max_vectors,
+                          ffs_match_plan** out);
+int ffs_match_plan_destroy(ffs_match_plan* plan);
+int64_t ffs_match_plan_workspace_bytes(const ffs_match_plan* plan);
+int ffs_match_quality_batch(ffs_match_plan* plan, int n_ref, const void* const* ref_list, const int64_t* ref_len,
+                            const double* ref_lo, const double* ref_hi, int n_sub, const void* const* sub_list,
+                            const int64_t* sub_len, const double* sub_lo, const double* sub_hi, int n_pairs,
+                            const int32_t* pair_ref, const int32_t* pair_sub, int64_t max_offset_samples, int top_k,
+                            int64_t exclusion_samples, int algorithm, ffs_quality_result* out_dev, void* hip_stream);
+
 /* ---- per-piece quality report of a split solve: break evidence (csrc/ffs_split_report.h) -------------------------
  * Replaces: nothing in the reference.  The contract below is pinned against the numpy model tests/split_report_model.py.
  *
