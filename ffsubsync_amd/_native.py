@@ -141,6 +141,10 @@ EXPORTED_SYMBOLS = (
     "ffs_align_drift_batch",
     "ffs_align_drift_report_batch",
     "ffs_align_drift_smooth_batch",
+    "ffs_drift_range_plan_create",
+    "ffs_drift_range_plan_destroy",
+    "ffs_drift_range_plan_workspace_bytes",
+    "ffs_align_drift_range_batch",
     "ffs_quality_plan_create",
     "ffs_quality_plan_destroy",
     "ffs_quality_plan_workspace_bytes",
@@ -370,6 +374,18 @@ def load():
                                                      c.c_double, c.c_int, c.c_double, c.c_int, c.c_int, c.c_double,
                                                      c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
                                                      c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
+        lib.ffs_drift_range_plan_create.restype = c.c_int
+        lib.ffs_drift_range_plan_create.argtypes = [c.c_int, c.c_int, c.c_int64, c.c_int64, c.c_int64, c.c_int,
+                                                    c.POINTER(c.c_void_p)]
+        lib.ffs_drift_range_plan_destroy.restype = c.c_int
+        lib.ffs_drift_range_plan_destroy.argtypes = [c.c_void_p]
+        lib.ffs_drift_range_plan_workspace_bytes.restype = c.c_int64
+        lib.ffs_drift_range_plan_workspace_bytes.argtypes = [c.c_void_p]
+        lib.ffs_align_drift_range_batch.restype = c.c_int
+        lib.ffs_align_drift_range_batch.argtypes = [c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                                                    c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p,
+                                                    c.c_void_p, c.c_double, c.c_int, c.c_double, c.c_void_p, c.c_void_p,
+                                                    c.c_void_p, c.c_void_p, c.c_void_p]
         lib.ffs_quality_plan_create.restype = c.c_int
         lib.ffs_quality_plan_create.argtypes = [c.c_int, c.c_int, c.c_int64, c.c_int64, c.POINTER(c.c_void_p)]
         lib.ffs_quality_plan_destroy.restype = c.c_int
@@ -1107,6 +1123,33 @@ class SplitRangePlan(_SidePlan):
         check(self.lib.ffs_split_range_report_batch(self.handle, n, *ptrs[:8], int(block_samples), *ptrs[8:],
                                                     offsets.data_ptr(), int(top_k), int(exclusion_samples),
                                                     report_out.data_ptr(), n_pieces_out.data_ptr(), self._stream(stream)))
+
+
+class DriftRangePlan(_SidePlan):
+    """Owns one ``ffs_drift_range_plan``: the workspace of the lag-range drift aligner (``drift_range.py``) for
+    ``pairs_in_flight`` problems of up to ``max_samples`` samples per vector, ``max_blocks`` blocks, ``max_lags`` lags
+    and calls at ``max_step`` up to ``max_step_cap``."""
+
+    _create = "ffs_drift_range_plan_create"
+    _destroy, _workspace = "ffs_drift_range_plan_destroy", "ffs_drift_range_plan_workspace_bytes"
+
+    def __init__(self, pairs_in_flight: int, max_blocks: int, max_lags: int, max_samples: int, max_step_cap: int,
+                 device: Optional[int] = None) -> None:
+        self.pairs_in_flight, self.max_blocks = int(pairs_in_flight), int(max_blocks)
+        self.max_lags, self.max_samples, self.max_step_cap = int(max_lags), int(max_samples), int(max_step_cap)
+        super().__init__((pairs_in_flight, max_blocks, max_lags, max_samples, max_step_cap), device)
+
+    def align(self, ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, block_samples: int, lag_lo,
+              lag_hi, split_penalty: float, max_step: int, step_cost: float, offsets_out, scores_out, jumps_out,
+              totals_out, stream: Optional[int] = None) -> None:
+        """``ffs_align_drift_range_batch`` on host descriptor arrays (one entry per pair, ``lag_lo`` / ``lag_hi``
+        included) into int32 / float64 / uint8 / float64 CUDA tensors of n_pairs * max_b (three times) and n_pairs
+        entries (asynchronous)."""
+        n, ptrs, _bufs = _pair_buffers(ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, lag_lo, lag_hi)
+        check(self.lib.ffs_align_drift_range_batch(self.handle, n, *ptrs[:8], int(block_samples), *ptrs[8:],
+                                                   float(split_penalty), int(max_step), float(step_cost),
+                                                   offsets_out.data_ptr(), scores_out.data_ptr(), jumps_out.data_ptr(),
+                                                   totals_out.data_ptr(), self._stream(stream)))
 
 
 class QualityPlan(_SidePlan):

@@ -35,6 +35,7 @@
 #include "ffs_drift.h"
 #include "ffs_drift_report.h"
 #include "ffs_drift_smooth.h"
+#include "ffs_drift_range.h"
 
 using namespace ffsa;
 
@@ -3421,27 +3422,33 @@ int64_t ffs_split_range_plan_workspace_bytes(const ffs_split_range_plan* plan) {
 
 namespace {
 // the per-pair checks of the range calls (lengths and blocks against the plan, the lag ranges); the largest block count
-int range_pairs_check(const ffs_split_range_plan* plan, int n_pairs, const Pairs& a, int64_t K, const int64_t* lag_lo,
-                      const int64_t* lag_hi, int64_t* max_b) {
+// against explicit limits (the split range and drift range plans share them)
+int range_limits_check(int64_t plan_max_samples, int64_t plan_max_blocks, int64_t plan_max_lags, int n_pairs,
+                       const Pairs& a, int64_t K, const int64_t* lag_lo, const int64_t* lag_hi, int64_t* max_b) {
     *max_b = 0;
     for (int p = 0; p < n_pairs; ++p) {
         if (int rc = a.check(p)) return rc;
-        if (a.sub_len[p] > plan->max_samples || a.ref_len[p] > plan->max_samples)
+        if (a.sub_len[p] > plan_max_samples || a.ref_len[p] > plan_max_samples)
             return fail(FFS_E_INVALID, "pair %d: lengths %lld / %lld exceed the plan's max_samples %lld", p,
-                        (long long)a.ref_len[p], (long long)a.sub_len[p], (long long)plan->max_samples);
+                        (long long)a.ref_len[p], (long long)a.sub_len[p], (long long)plan_max_samples);
         const int64_t B = (a.sub_len[p] + K - 1) / K;
-        if (B > plan->max_blocks)
+        if (B > plan_max_blocks)
             return fail(FFS_E_INVALID, "pair %d: %lld blocks exceed the plan's max_blocks %lld", p, (long long)B,
-                        (long long)plan->max_blocks);
+                        (long long)plan_max_blocks);
         if (lag_lo[p] > lag_hi[p] || lag_lo[p] < -(int64_t)INT32_MAX || lag_hi[p] > INT32_MAX)
             return fail(FFS_E_INVALID, "pair %d: lag range [%lld, %lld]: need -(2^31 - 1) <= lag_lo <= lag_hi <= 2^31 - 1", p,
                         (long long)lag_lo[p], (long long)lag_hi[p]);
-        if (lag_hi[p] - lag_lo[p] + 1 > plan->max_lags)
+        if (lag_hi[p] - lag_lo[p] + 1 > plan_max_lags)
             return fail(FFS_E_INVALID, "pair %d: %lld lags exceed the plan's max_lags %lld", p,
-                        (long long)(lag_hi[p] - lag_lo[p] + 1), (long long)plan->max_lags);
+                        (long long)(lag_hi[p] - lag_lo[p] + 1), (long long)plan_max_lags);
         *max_b = std::max(*max_b, B);
     }
     return FFS_OK;
+}
+
+int range_pairs_check(const ffs_split_range_plan* plan, int n_pairs, const Pairs& a, int64_t K, const int64_t* lag_lo,
+                      const int64_t* lag_hi, int64_t* max_b) {
+    return range_limits_check(plan->max_samples, plan->max_blocks, plan->max_lags, n_pairs, a, K, lag_lo, lag_hi, max_b);
 }
 }  // namespace
 
@@ -3928,6 +3935,140 @@ int ffs_align_drift_smooth_batch(ffs_drift_plan* plan, int n_pairs, const void* 
     return drift_batch(plan, n_pairs, a, block_samples, max_offset_samples, split_penalty, max_step, step_cost,
                        block_offset_out_dev, block_score_out_dev, block_jump_out_dev, total_out_dev, nullptr, &fit,
                        hip_stream);
+}
+
+/* ---- drift-tolerant alignment over a lag range (csrc/ffs_drift_range.h) ---------------------------------------- */
+
+struct ffs_drift_range_plan : PlanCore {
+    int64_t max_blocks, max_lags, max_samples;
+    int max_step_cap;
+    int64_t pw;                 // prefix words per vector
+    ffsa::RangeWs ws;           // stay = the code planes (max_step_cap's count), V = two rows per slot
+    int32_t* pre;               // [slot][2 * pw]: s, then r
+    DescStaging desc;           // SplitDesc[pairs_in_flight], then RangeLag[pairs_in_flight]
+};
+
+int ffs_drift_range_plan_create(int device, int pairs_in_flight, int64_t max_blocks, int64_t max_lags, int64_t max_samples,
+                                int max_step_cap, ffs_drift_range_plan** out) {
+    if (!out) return fail(FFS_E_INVALID, "null output handle");
+    *out = nullptr;
+    if (pairs_in_flight < 1 || pairs_in_flight > 65535 || max_blocks < 1 || max_lags < 1 || max_lags > INT32_MAX ||
+        max_samples < 1 || max_samples > INT32_MAX / 2 || max_step_cap < 0 || max_step_cap > ffsa::DRIFT_RANGE_MAX_STEP)
+        return fail(FFS_E_INVALID, "drift range plan: need 1 <= pairs_in_flight <= 65535, max_blocks >= 1, "
+                                   "1 <= max_lags <= 2^31 - 1, 1 <= max_samples <= 2^30 - 1, 0 <= max_step_cap <= 7");
+    HIP_TRY(hipSetDevice(device));
+    ffs_drift_range_plan* p = new (std::nothrow) ffs_drift_range_plan();
+    if (!p) return fail(FFS_E_NOMEM, "drift range plan");
+    p->max_blocks = max_blocks;
+    p->max_lags = max_lags;
+    p->max_samples = max_samples;
+    p->max_step_cap = max_step_cap;
+    p->pw = max_samples / 32 + 2;
+    const int64_t row = (max_lags + 63) / 64;  // 64-lag words per block row and plane
+    const int64_t part_row = split_align_up((max_lags + ffsa::RANGE_TILE - 1) / ffsa::RANGE_TILE, 32);
+    const int64_t codes_slot = split_align_up(max_blocks * row * ffsa::drift_range_planes(max_step_cap), 32);  // uint64
+    const int64_t v_slot = 2 * split_align_up(row * 64, 32);                // double, two rows
+    const int64_t arg_slot = split_align_up(max_blocks, 64);                // int32
+    const int64_t pre_slot = split_align_up(2 * p->pw, 64);                 // int32
+    const int64_t n = pairs_in_flight;
+    const int64_t b_codes = n * codes_slot * 8, b_v = n * v_slot * 8, b_pv = n * 2 * part_row * 8,
+                  b_pj = n * 2 * part_row * 4, b_arg = n * arg_slot * 4, b_pre = n * pre_slot * 4;
+    if (int rc = p->open(device, pairs_in_flight, b_codes + b_v + b_pv + b_pj + b_arg + b_pre, "drift range plan")) {
+        ffs_drift_range_plan_destroy(p);
+        return rc;
+    }
+    char* w = (char*)p->work;
+    p->ws.stay = (unsigned long long*)w;
+    p->ws.V = (double*)(w + b_codes);
+    p->ws.pv = (double*)(w + b_codes + b_v);
+    p->ws.pj = (int32_t*)(w + b_codes + b_v + b_pv);
+    p->ws.arg = (int32_t*)(w + b_codes + b_v + b_pv + b_pj);
+    p->pre = (int32_t*)(w + b_codes + b_v + b_pv + b_pj + b_arg);
+    p->ws.stay_row = row;
+    p->ws.stay_slot = codes_slot;
+    p->ws.v_slot = v_slot;
+    p->ws.part_row = part_row;
+    p->ws.arg_slot = arg_slot;
+    if (p->desc.create((sizeof(ffsa::SplitDesc) + sizeof(ffsa::RangeLag)) * (size_t)pairs_in_flight) != FFS_OK) {
+        ffs_drift_range_plan_destroy(p);
+        return fail(FFS_E_HIP, "drift range plan: descriptor buffers / events");
+    }
+    *out = p;
+    return FFS_OK;
+}
+
+int ffs_drift_range_plan_destroy(ffs_drift_range_plan* plan) {
+    if (!plan) return FFS_OK;
+    plan->close();
+    plan->desc.release();
+    delete plan;
+    return FFS_OK;
+}
+
+int64_t ffs_drift_range_plan_workspace_bytes(const ffs_drift_range_plan* plan) { return plan ? plan->work_bytes : 0; }
+
+int ffs_align_drift_range_batch(ffs_drift_range_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
+                                const double* ref_lo, const double* ref_hi, const void* const* sub_ptr,
+                                const int64_t* sub_len, const double* sub_lo, const double* sub_hi, int64_t block_samples,
+                                const int64_t* lag_lo, const int64_t* lag_hi, double split_penalty, int max_step,
+                                double step_cost, int32_t* block_offset_out_dev, double* block_score_out_dev,
+                                uint8_t* block_jump_out_dev, double* total_out_dev, void* hip_stream) {
+    const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
+    if (!plan) return fail(FFS_E_INVALID, "null drift range plan");
+    if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
+    if (n_pairs == 0) return FFS_OK;
+    if (a.any_null() || !lag_lo || !lag_hi || !block_offset_out_dev || !block_score_out_dev || !block_jump_out_dev ||
+        !total_out_dev)
+        return fail(FFS_E_INVALID, "null argument");
+    if (((uintptr_t)block_offset_out_dev & 3) || ((uintptr_t)block_score_out_dev & 7) || ((uintptr_t)total_out_dev & 7))
+        return fail(FFS_E_INVALID, "misaligned outputs");
+    const int64_t K = block_samples;
+    if (int rc = check_block_samples(K)) return rc;
+    if (!(split_penalty >= 0.0)) return fail(FFS_E_INVALID, "split_penalty must be >= 0 (not NaN)");
+    if (max_step < 0 || max_step > plan->max_step_cap)
+        return fail(FFS_E_INVALID, "max_step=%d outside [0, %d] (the plan's max_step_cap)", max_step, plan->max_step_cap);
+    if (!(step_cost >= 0.0) || !std::isfinite(step_cost)) return fail(FFS_E_INVALID, "step_cost must be finite and >= 0");
+    int64_t max_b = 0;
+    if (int rc = range_limits_check(plan->max_samples, plan->max_blocks, plan->max_lags, n_pairs, a, K, lag_lo, lag_hi,
+                                    &max_b))
+        return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (int rc = plan->begin(st)) return rc;
+    const int planes = ffsa::drift_range_planes(max_step);
+    const int64_t pre_slot = split_align_up(2 * plan->pw, 64);
+    const int pif = plan->pairs_in_flight;
+    ffsa::SplitDesc* hd = (ffsa::SplitDesc*)plan->desc.host;
+    ffsa::RangeLag* hl = (ffsa::RangeLag*)(hd + pif);
+    const ffsa::SplitDesc* dd = (const ffsa::SplitDesc*)plan->desc.dev;
+    const ffsa::RangeLag* dl = (const ffsa::RangeLag*)(dd + pif);
+    for (int p0 = 0; p0 < n_pairs; p0 += pif) {
+        const int np = std::min(pif, n_pairs - p0);
+        if (int rc = plan->desc.wait_free()) return rc;
+        int64_t chunk_b = 0, max_tiles = 0;
+        for (int i = 0; i < np; ++i) {
+            const int p = p0 + i;
+            int32_t* pre_s = plan->pre + (int64_t)i * pre_slot;
+            hd[i] = a.split_desc(p, pre_s, pre_s + plan->pw);
+            hl[i].lag_lo = lag_lo[p];
+            hl[i].L = lag_hi[p] - lag_lo[p] + 1;
+            chunk_b = std::max(chunk_b, (hd[i].S + K - 1) / K);
+            max_tiles = std::max(max_tiles, (hl[i].L + ffsa::RANGE_TILE - 1) / ffsa::RANGE_TILE);
+        }
+        if (int rc = plan->desc.upload(sizeof(ffsa::SplitDesc) * pif + sizeof(ffsa::RangeLag) * np, st)) return rc;
+        hipLaunchKernelGGL(ffsa::k_split_prefix, dim3(2 * np), dim3(ffsa::SPLIT_PREFIX_THREADS), 0, st, dd,
+                           (int64_t)plan->max_samples);
+        for (int64_t b = 0; b < chunk_b; ++b)
+            hipLaunchKernelGGL(ffsa::k_range_drift_step, dim3((unsigned)max_tiles, (unsigned)np), dim3(ffsa::RANGE_THREADS),
+                               0, st, dd, dl, plan->ws, (int)K, b, split_penalty, max_step, step_cost, planes);
+        hipLaunchKernelGGL(ffsa::k_range_drift_backtrack, dim3(np), dim3(ffsa::RANGE_THREADS), 0, st, dd, dl, plan->ws,
+                           (int)K, max_b, max_step, planes, block_offset_out_dev, block_jump_out_dev, total_out_dev);
+        constexpr int waves = ffsa::RANGE_SCORE_THREADS / 64;
+        hipLaunchKernelGGL(ffsa::k_range_scores, dim3((unsigned)((max_b + waves - 1) / waves), (unsigned)np),
+                           dim3(ffsa::RANGE_SCORE_THREADS), 0, st, dd, dl, (int)K, max_b, block_offset_out_dev,
+                           block_score_out_dev);
+        HIP_TRY(hipGetLastError());
+    }
+    return plan->end(st);
 }
 
 /* ---- alignment quality report (csrc/ffs_quality.h) ------------------------------------------------------------- */

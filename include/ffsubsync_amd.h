@@ -724,6 +724,43 @@ int ffs_align_drift_batch(ffs_drift_plan* plan, int n_pairs, const void* const* 
                           double* block_score_out_dev, uint8_t* block_jump_out_dev, double* total_out_dev,
                           void* hip_stream);
 
+/* ---- drift-tolerant alignment over any lag range: another cut AND a residual ratio (csrc/ffs_drift_range.h) --------
+ * Replaces: nothing in the reference.  The contract below is pinned against the numpy model
+ * tests/drift_range_model.py, bit for bit.
+ *
+ * ffs_align_drift_batch's DP over ffs_align_split_range_batch's lag set: d in [lag_lo_p, lag_hi_p] per pair, lag index
+ * j = d - lag_lo, L = lag_hi - lag_lo + 1, any contiguous int32 range, not clipped to the overlap range; the block scores
+ * m_b(j) are the range split's (absent samples, the no-FMA fp64 score; lags without overlap score 0).  Per block b >= 1
+ * and lag index j the options are tried in the order STAY; +1, -1, ..., +s, -s (each needing 0 <= j - e < L and costing
+ * c_a = Q * a, one fp64 product); JUMP to T = J_{b-1} - P, each replacing the best so far only when strictly greater; the
+ * largest lag index wins every maximum; backtrack and block_jump as ffs_align_drift_batch.  s = max_step in [0, 7],
+ * Q = step_cost finite and >= 0.  Two identities: at max_step = 0 offsets, scores and total equal
+ * ffs_align_split_range_batch's bit for bit (block_jump[b] = 1 exactly where the offset changes); at [-W+1, W] all four
+ * outputs equal ffs_align_drift_batch's bit for bit.
+ *
+ * One launch per block step covers every pair in flight, as the range split; a cell reads its neighbours of the previous
+ * row, so a pair keeps TWO fp64 rows of max_lags, and a code per (block, lag) in bit planes: ceil(log2(2s + 2)) planes
+ * for a plan made with max_step_cap = s (1 at 0, 2 at 1, 3 at 2..3, 4 at 4..7), max_blocks * max_lags / 8 bytes each
+ * (127 MB per plane at 2 h against 2 h over the full range, K = 1024: 380 MB at max_step_cap 2).  A call at a smaller
+ * max_step writes only the planes it needs.  A plan of its own: split range and drift plans do not grow.  Limits as
+ * ffs_split_range_plan_create, and max_step_cap in [0, 7].  A plan serves one host thread at a time; successive calls
+ * (any streams) are ordered by the library. */
+typedef struct ffs_drift_range_plan ffs_drift_range_plan;
+int ffs_drift_range_plan_create(int device, int pairs_in_flight, int64_t max_blocks, int64_t max_lags, int64_t max_samples,
+                                int max_step_cap, ffs_drift_range_plan** out);
+int ffs_drift_range_plan_destroy(ffs_drift_range_plan* plan);
+int64_t ffs_drift_range_plan_workspace_bytes(const ffs_drift_range_plan* plan);
+/* ffs_align_split_range_batch's arguments plus max_step, step_cost and block_jump_out_dev (uint8, n_pairs * max_b, as
+ * ffs_align_drift_batch writes it); sub-batches of pairs_in_flight on hip_stream.  FFS_E_INVALID / FFS_E_EMPTY for
+ * everything ffs_align_split_range_batch refuses, max_step outside [0, max_step_cap], or a step_cost that is negative,
+ * NaN or infinite; all before any launch, the outputs untouched. */
+int ffs_align_drift_range_batch(ffs_drift_range_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
+                                const double* ref_lo, const double* ref_hi, const void* const* sub_ptr,
+                                const int64_t* sub_len, const double* sub_lo, const double* sub_hi, int64_t block_samples,
+                                const int64_t* lag_lo, const int64_t* lag_hi, double split_penalty, int max_step,
+                                double step_cost, int32_t* block_offset_out_dev, double* block_score_out_dev,
+                                uint8_t* block_jump_out_dev, double* total_out_dev, void* hip_stream);
+
 /* ---- per-segment path report of a drift solve: segment, jump and drift evidence (csrc/ffs_drift_report.h) ----------
  * Replaces: nothing in the reference.  The contract below is pinned against the numpy model
  * tests/drift_report_model.py, bit for bit.
