@@ -107,9 +107,9 @@ constexpr unsigned kPoolCapacity = 1u << 20;
 // (118 lag tiles per candidate cost as much as 6 M coincidences).  Twelve keeps the choice on the winning side in both.
 constexpr long long kRunsBudgetPerPoint = 12;
 // Plan-owned boundary lists (vectors that arrive as bits) start with room for this many entries each -- subtitle-like vectors
-// have ~2 000 -- and the stride grows (x 4, up to RUNS_CAP) when a call meets a longer list: that call's sub-batch goes through
-// the transforms (a list that fills its slot counts as over budget), the next call has the room.  A 256 KB stride for 16 KB
-// lists cost 4 % of k_runs_extract (65 536 lists spread over 16 GB of address space).
+// have ~2 000 -- and the stride grows (x 4, up to RUNS_CAP) when a call meets a longer list: that same call is solved again
+// with the longer stride (align_impl), and the plan keeps it.  A 256 KB stride for 16 KB lists cost 4 % of k_runs_extract
+// (65 536 lists spread over 16 GB of address space).
 constexpr int kRunsStride0 = 4096;
 // calls of at most this many candidates upload their descriptors once and launch the extraction behind them (see late_extract)
 constexpr size_t kSmallCallCands = 4096;
@@ -244,7 +244,8 @@ struct ffs_plan {
     int algo = FFS_ALGO_AUTO;
     int runs_split = 0;                 // FFS_RUNS_SPLIT: workgroups per pair in k_runs_corr (0: the rule at the launch site)
     long long runs_budget = -1;         // FFS_RUNS_BUDGET: boundary coincidences per candidate above which the transforms take over (-1: the rule in ffs_plan_create)
-    int2* runs_e = nullptr;             // [vectors][runs_stride] (boundary position, ones in front of it) of the vectors that arrive as bits
+    int2* runs_e = nullptr;             // [vectors][runs_stride] lists of the vectors that arrive as bits: references and threshold planes as
+                                        // (boundary position, ones in front of it), candidates as 4-byte positions only (RunsRef, COMPACT)
     int runs_stride = 4096;             // entries per plan-owned list (kRunsStride0; FFS_RUNS_STRIDE; grows up to RUNS_CAP)
     size_t runs_e_entries = 0;          // entries allocated behind runs_e
     int2* runs_n = nullptr;             // [vectors] (boundaries, ones)
@@ -388,16 +389,19 @@ int ensure_runs(ffs_plan* p, size_t n_vec, size_t n_best, size_t n_chunks) {
         return FFS_OK;
     };
     int rc;
-    if (n_vec > p->runs_vecs || n_vec * (size_t)p->runs_stride > p->runs_e_entries) {  // more vectors, or a longer stride
+    // more vectors, or a longer stride than the lists were allocated for: then every vector the plan had room for gets the
+    // longer list at once (a stream of calls meets its longest list in a small call as readily as in a large one)
+    if (n_vec > p->runs_vecs || (n_vec && p->runs_vecs * (size_t)p->runs_stride > p->runs_e_entries)) {
         if ((rc = quiesce())) return rc;
         (void)hipFree(p->runs_e);
         (void)hipFree(p->runs_n);
         p->workspace_bytes -= (int64_t)(p->runs_e_entries * sizeof(int2) + p->runs_vecs * sizeof(int2));
         p->runs_e = nullptr;
         p->runs_n = nullptr;
+        const size_t old_vecs = p->runs_vecs;  // (a longer stride alone keeps the room for as many vectors as before)
         p->runs_vecs = 0;
         p->runs_e_entries = 0;
-        const size_t cap = (n_vec > p->runs_vecs ? n_vec : p->runs_vecs) + n_vec / 4 + 64;
+        const size_t cap = (n_vec > old_vecs ? n_vec : old_vecs) + n_vec / 4 + 64;
         const size_t entries = cap * (size_t)p->runs_stride;
         if (hipMalloc((void**)&p->runs_e, entries * sizeof(int2)) != hipSuccess ||
             hipMalloc((void**)&p->runs_n, cap * sizeof(int2)) != hipSuccess) {
@@ -1252,377 +1256,489 @@ int ffs_plan_destroy(ffs_plan* p) {
 
 int64_t ffs_plan_workspace_bytes(const ffs_plan* p) { return p ? p->workspace_bytes : 0; }
 
-// Leaves the plan's stream bookkeeping consistent on every exit once work has been queued (an error return after a
-// kernel launch must still record the call's last event: the next call on another stream waits for it).
+}  // extern "C"
+
+// ---- the main solve (ffs_align_batch*) -----------------------------------------------------------------------------
+namespace {
+
+// One call as the entry points hand it over.  `dtype` = the candidates' element type, `ref_dt` = the references';
+// vec_bound (may be null): FFS_DTYPE_RUNS vectors only -- a host-known upper bound of the list's length (0: unknown).
+struct AlignArgs {
+    int n_pairs, n_cand, ref_dt, dtype;
+    const void* const* vec_ptr;
+    const int64_t* vec_len;
+    const double *vec_lo, *vec_hi;
+    const int32_t* vec_bound;
+    int64_t max_offset_samples, filter_max_offset;
+    ffs_cand_result* cand_out_dev;
+    ffs_pair_result* pair_out_dev;
+    void* hip_stream;
+};
+
+bool runs_able(int dt) { return dt == FFS_DTYPE_U1 || dt == FFS_DTYPE_RUNS; }
+int as_bits(int dt) { return dt == FFS_DTYPE_RUNS ? FFS_DTYPE_U1 : dt; }  // list-only vectors reach the transforms as bits
+size_t esz_of(int dt) { return dt == FFS_DTYPE_U8 ? 1 : (dt == FFS_DTYPE_F32 ? 4 : (dt == FFS_DTYPE_F64 ? 8 : 0)); }
+double now_ns() {
+    return (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// One contract for every path, checked before anything is queued: no empty vector (aligners.py:58-66), no null or
+// misaligned pointer, no vector of 2^30 samples or more (positions are 32-bit; 0x3fffffff is the run-boundary kernels'
+// "beyond everything").  The plan-length check (FFS_E_TOO_LONG whichever path would have served the pair) is part of
+// fill_cand, which every path runs for every candidate.
+int check_align_args(const ffs_plan* p, const AlignArgs& a) {
+    auto known = [](int dt) {
+        return dt == FFS_DTYPE_U8 || dt == FFS_DTYPE_F32 || dt == FFS_DTYPE_U1 || dt == FFS_DTYPE_F64 || dt == FFS_DTYPE_RUNS;
+    };
+    auto amask_of = [](int dt) -> uintptr_t { return dt == FFS_DTYPE_U8 ? 0 : (dt == FFS_DTYPE_F64 || dt == FFS_DTYPE_RUNS ? 7 : 3); };
+    if (!p) return fail(FFS_E_INVALID, "plan is null");
+    if (a.n_pairs < 0 || a.n_cand < 1 || a.n_cand > p->max_cand)
+        return fail(FFS_E_INVALID, "n_cand=%d outside [1, plan max_cand=%d]", a.n_cand, p->max_cand);
+    if (!known(a.dtype) || !known(a.ref_dt)) return fail(FFS_E_INVALID, "unknown dtype %d / %d", a.ref_dt, a.dtype);
+    if (!a.vec_ptr || !a.vec_len || !a.vec_lo || !a.vec_hi || !a.cand_out_dev || !a.pair_out_dev)
+        return fail(FFS_E_INVALID, "null argument");
+    const int stride = 1 + a.n_cand;
+    for (int pi = 0; pi < a.n_pairs; ++pi) {
+        const size_t b = (size_t)pi * stride;
+        for (int v = 0; v < stride; ++v) {
+            const int dt = v ? a.dtype : a.ref_dt;
+            if (a.vec_len[b] <= 0 || a.vec_len[b + v] <= 0)
+                return fail(FFS_E_EMPTY, "cannot align empty speech data (reference length=%lld, subtitle length=%lld)",
+                            (long long)a.vec_len[b], (long long)a.vec_len[b + (v ? v : 1)]);
+            if (!a.vec_ptr[b + v]) return fail(FFS_E_INVALID, "null device pointer for pair %d", pi);
+            if ((uintptr_t)a.vec_ptr[b + v] & amask_of(dt))
+                return fail(FFS_E_INVALID, "float / bit-packed vectors and boundary lists must be aligned to their element (pair %d)", pi);
+            if (a.vec_len[b + v] >= (int64_t(1) << 30))
+                return fail(FFS_E_TOO_LONG, "vector of %lld samples (pair %d): at most 2^30 - 1", (long long)a.vec_len[b + v], pi);
+        }
+    }
+    return FFS_OK;
+}
+
+// Byte offsets of n bit images packed one behind the other, each starting on a 64-byte line: image i holds `planes`
+// planes of len[i * step] bits when want(i), nothing otherwise.  (*off)[n] = the bytes of them all; returns the longest
+// wanted length (at least 1).
+template <class Pred>
+int64_t bit_image_offsets(const int64_t* len, size_t n, size_t step, int planes, Pred want, std::vector<size_t>* off) {
+    off->assign(n + 1, 0);
+    int64_t len_max = 1;
+    for (size_t i = 0; i < n; ++i) {
+        const int64_t l = len[i * step];
+        (*off)[i + 1] = (*off)[i] + (want(i) ? ((planes * ((size_t)(l + 31) / 32) * 4 + 63) & ~(size_t)63) : 0);
+        if (want(i) && l > len_max) len_max = l;
+    }
+    return len_max;
+}
+
+// A plan-owned device buffer that only ever grows (pack_buf, lvl_buf): the previous call may still be reading the old one.
+template <class T>
+int grow_device_buf(ffs_plan* p, T** buf, size_t* bytes, size_t need) {
+    if (need <= *bytes) return FFS_OK;
+    if (p->has_last) HIP_TRY(hipEventSynchronize(p->last_done));
+    (void)hipFree(*buf);
+    *buf = nullptr;
+    *bytes = 0;
+    HIP_TRY(hipMalloc((void**)buf, need + need / 4));
+    *bytes = need + need / 4;
+    return FFS_OK;
+}
+
+// 0/1 BYTES (the north star's literal input format): one pass packs every vector of the call to bits (bit = byte != 0,
+// exactly the two-level reading the byte kernels apply), then the call continues as FFS_DTYPE_U1 -- run-boundary path
+// where the lists are short, transforms on an eighth of the input bytes otherwise.  Identical records
+// (tests/test_gpu_headline.py::test_byte_inputs_give_the_same_records; FFS_ALGO_FFT keeps the byte kernels).
+// Rewrites `a` to read the packed images (`packed` owns its pointer table).  A stream entry of its own: the solve enters again.
+int pack_byte_vectors(ffs_plan* p, AlignArgs* a, std::vector<const void*>* packed) {
+    hipStream_t st = (hipStream_t)a->hip_stream;
+    const size_t n_vec = (size_t)a->n_pairs * (size_t)(1 + a->n_cand);
+    std::vector<size_t> off;
+    const int64_t len_max = bit_image_offsets(a->vec_len, n_vec, 1, 1, [](size_t) { return true; }, &off);
+    HIP_TRY(hipSetDevice(p->device));
+    int rc;
+    if ((rc = enter_stream(p, st))) return rc;
+    if ((rc = grow_device_buf(p, &p->pack_buf, &p->pack_bytes, off[n_vec]))) return rc;
+    if ((rc = ensure_desc(p, n_vec * sizeof(PackVec) + 4096))) return rc;
+    HIP_TRY(hipEventSynchronize(p->upload_done));
+    p->cur_half = 0;
+    PackVec* hp = (PackVec*)p->host_desc;
+    packed->resize(n_vec);
+    for (size_t i = 0; i < n_vec; ++i) {
+        unsigned* dst = (unsigned*)((char*)p->pack_buf + off[i]);
+        hp[i] = PackVec{(const unsigned char*)a->vec_ptr[i], dst, (int32_t)a->vec_len[i], 0};
+        (*packed)[i] = dst;
+    }
+    HIP_TRY(hipMemcpyAsync(p->dev_desc, hp, n_vec * sizeof(PackVec), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(p->upload_done, st));
+    const int chunks_per_vec = (int)(((len_max + 31) / 32 + 255) / 256);
+    hipLaunchKernelGGL(k_pack_bytes_batch, dim3((unsigned)(n_vec * chunks_per_vec)), dim3(256), 0, st, (const PackVec*)p->dev_desc,
+                       chunks_per_vec);
+    HIP_TRY(hipGetLastError());
+    if ((rc = leave_stream(p, st))) return rc;
+    a->ref_dt = a->dtype = FFS_DTYPE_U1;
+    a->vec_ptr = packed->data();
+    a->vec_bound = nullptr;
+    return FFS_OK;
+}
+
+// Expands the call's list-only vectors (role `ref`/`cand` of type FFS_DTYPE_RUNS) to bits in the plan's pack buffer;
+// `out` = the call's pointer table with those vectors replaced.  Queued on `st`, inside the caller's stream entry.
+int expand_list_vectors(ffs_plan* p, const AlignArgs& a, hipStream_t st, std::vector<const void*>* out) {
+    const size_t stride = 1 + (size_t)a.n_cand, n_vec = (size_t)a.n_pairs * stride;
+    auto is_list = [&](size_t i) { return ((i % stride) ? a.dtype : a.ref_dt) == FFS_DTYPE_RUNS; };
+    std::vector<size_t> off;
+    const int64_t len_max = bit_image_offsets(a.vec_len, n_vec, 1, 1, is_list, &off);
+    int rc;
+    if ((rc = grow_device_buf(p, &p->pack_buf, &p->pack_bytes, off[n_vec]))) return rc;
+    ExpandVec* d_ev = nullptr;
+    std::vector<ExpandVec> hev(n_vec);
+    out->assign(a.vec_ptr, a.vec_ptr + n_vec);
+    for (size_t i = 0; i < n_vec; ++i) {
+        unsigned* dst = is_list(i) ? (unsigned*)((char*)p->pack_buf + off[i]) : nullptr;
+        hev[i] = ExpandVec{(const int2*)((const char*)a.vec_ptr[i] + 16), (const int2*)a.vec_ptr[i], dst, (int32_t)a.vec_len[i], 0};
+        if (dst) (*out)[i] = dst;
+    }
+    // (rare path; the table is followed by one int the kernel raises when a block's header does not fit the block)
+    const size_t tab = n_vec * sizeof(ExpandVec);
+    int bad_list = 0;
+    HIP_TRY(hipMallocAsync((void**)&d_ev, tab + sizeof(int), st));
+    hipError_t he = hipMemcpyAsync(d_ev, hev.data(), tab, hipMemcpyHostToDevice, st);
+    if (he == hipSuccess) he = hipMemsetAsync((char*)d_ev + tab, 0, sizeof(int), st);
+    if (he == hipSuccess) he = hipStreamSynchronize(st);
+    if (he == hipSuccess) {
+        const int chunks_per_vec = (int)(((len_max + 31) / 32 + 255) / 256);
+        hipLaunchKernelGGL(k_runs_expand, dim3((unsigned)(n_vec * chunks_per_vec)), dim3(256), 0, st, (const ExpandVec*)d_ev, chunks_per_vec,
+                           (int*)((char*)d_ev + tab));
+        he = hipGetLastError();
+    }
+    if (he == hipSuccess) he = hipMemcpyAsync(&bad_list, (char*)d_ev + tab, sizeof(int), hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess) he = hipStreamSynchronize(st);
+    const hipError_t hf = hipFreeAsync(d_ev, st);  // (on every path: an error above must not leak the table)
+    HIP_TRY(he);
+    HIP_TRY(hf);
+    if (bad_list)
+        return fail(FFS_E_INVALID, "a boundary list of the call is truncated (more entries than its block holds) or was made for "
+                    "another vector length: nothing can solve it -- pass the vector as bits");
+    return FFS_OK;
+}
+
+// Boundary lists where only the transforms (or the direct kernel of short plans) may run: the call continues on bits.
+// A stream entry of its own, like pack_byte_vectors.
+int lists_to_bits(ffs_plan* p, AlignArgs* a, std::vector<const void*>* bits_ptr) {
+    hipStream_t st = (hipStream_t)a->hip_stream;
+    HIP_TRY(hipSetDevice(p->device));
+    int rc;
+    if ((rc = enter_stream(p, st))) return rc;
+    if ((rc = expand_list_vectors(p, *a, st, bits_ptr))) return rc;
+    if ((rc = leave_stream(p, st))) return rc;
+    a->ref_dt = as_bits(a->ref_dt);
+    a->dtype = as_bits(a->dtype);
+    a->vec_ptr = bits_ptr->data();
+    a->vec_bound = nullptr;
+    return FFS_OK;
+}
+
+// The descriptor block of one solve, the same in the pinned host block and in either device block:
+// [PoolHeader][CandDesc n_cands][RunsRef n_rr][multi-level tables][XformDesc n_xf][NomList n_cands][RescoreAcc n_cands*KNOM]
+// [PoolBest n_cands].  Everything up to the transform descriptors is written by the host and uploaded; the rest lives on
+// the device only.
+struct DescLayout {
+    size_t n_pairs = 0, n_cands = 0, n_rr = 0;
+    size_t o_pool = 0;   // PoolHeader (uploaded: count = 0, capacity)
+    size_t o_cand = 64;
+    size_t o_rv = 0;     // RunsRef[n_rr] when runs_ok
+    // multi-level tables behind it: LevelInfo | sample pointers | plane pointers | lengths | plane words, one per pair
+    size_t o_li = 0, o_mp = 0, o_mq = 0, o_ml = 0, o_mw = 0;
+    size_t o_xf = 0, o_nom = 0, o_acc = 0, o_pbest = 0, total = 0;
+
+    DescLayout() = default;
+    DescLayout(size_t n_pairs_, size_t n_cand, size_t n_rr_, bool ml_on, bool runs_ok, size_t n_xf_alloc)
+        : n_pairs(n_pairs_), n_cands(n_pairs_ * n_cand), n_rr(n_rr_) {
+        const size_t ml_pairs = ml_on ? n_pairs : 0;
+        o_rv = o_cand + n_cands * sizeof(CandDesc);
+        o_li = (o_rv + (runs_ok ? n_rr * sizeof(RunsRef) : 0) + 63) & ~(size_t)63;
+        o_mp = o_li + ml_pairs * sizeof(LevelInfo);
+        o_mq = o_mp + ml_pairs * 8;
+        o_ml = o_mq + ml_pairs * 8;
+        o_mw = o_ml + ml_pairs * 4;
+        o_xf = (o_mw + ml_pairs * 4 + 63) & ~(size_t)63;
+        o_nom = (o_xf + n_xf_alloc * sizeof(XformDesc) + 255) & ~(size_t)255;
+        o_acc = o_nom + n_cands * sizeof(NomList);
+        o_pbest = o_acc + n_cands * KNOM * sizeof(RescoreAcc);  // zeroed together with acc
+        total = o_pbest + n_cands * sizeof(PoolBest);
+    }
+    PoolHeader* pool(char* b) const { return (PoolHeader*)(b + o_pool); }
+    CandDesc* cands(char* b) const { return (CandDesc*)(b + o_cand); }
+    RunsRef* runs_refs(char* b) const { return (RunsRef*)(b + o_rv); }
+    LevelInfo* level_info(char* b) const { return (LevelInfo*)(b + o_li); }
+    const void** level_samples(char* b) const { return (const void**)(b + o_mp); }
+    unsigned** level_planes(char* b) const { return (unsigned**)(b + o_mq); }
+    int32_t* level_lens(char* b) const { return (int32_t*)(b + o_ml); }
+    int32_t* level_words(char* b) const { return (int32_t*)(b + o_mw); }
+    XformDesc* xforms(char* b) const { return (XformDesc*)(b + o_xf); }
+    NomList* nominees(char* b) const { return (NomList*)(b + o_nom); }
+    RescoreAcc* acc(char* b) const { return (RescoreAcc*)(b + o_acc); }
+    PoolBest* pool_best(char* b) const { return (PoolBest*)(b + o_pbest); }
+    // the byte ranges that go up (offset, bytes)
+    size_t table_at() const { return o_rv; }
+    size_t table_bytes(size_t n_refs) const { return n_refs * sizeof(RunsRef); }  // the first n_refs of the vector table
+    size_t level_tables_bytes() const { return o_xf - o_rv; }                      // the vector table and the multi-level tables
+    size_t head_bytes(size_t n_refs) const { return o_rv + n_refs * sizeof(RunsRef); }  // from 0: header, candidates (+ table)
+    size_t transform_bytes(size_t n_xf) const { return o_xf + n_xf * sizeof(XformDesc); }  // from 0: all the host writes
+    size_t refresh_at() const { return o_cand; }
+    size_t refresh_bytes(size_t n_xf) const { return transform_bytes(n_xf) - o_cand; }  // candidates .. transform descriptors
+    size_t acc_bytes(size_t n) const { return n * KNOM * sizeof(RescoreAcc); }
+    size_t acc_and_best_bytes() const { return acc_bytes(n_cands) + n_cands * sizeof(PoolBest); }
+};
+
+// Leaves the plan's bookkeeping consistent on every exit of a solve once work has been queued: an error return after a
+// kernel launch must still record the call's last event (the next call on another stream waits for it), and one after a
+// copy from the pinned block must leave upload_done behind that copy (the next call waits for it before it writes the block).
 struct StreamLeave {
     ffs_plan* p;
     hipStream_t st;
     bool armed = false;
+    bool upload_open = false;  // a copy from the pinned block is queued on upload_st with no upload_done behind it yet
+    hipStream_t upload_st = nullptr;
     ~StreamLeave() {
+        if (upload_open) (void)hipEventRecord(p->upload_done, upload_st);
         if (armed) (void)leave_stream(p, st);
     }
 };
 
-int grow_pack_buf(ffs_plan* p, size_t bytes) {
-    if (bytes <= p->pack_bytes) return FFS_OK;
-    if (p->has_last) HIP_TRY(hipEventSynchronize(p->last_done));
-    (void)hipFree(p->pack_buf);
-    p->pack_buf = nullptr;
-    p->pack_bytes = 0;
-    HIP_TRY(hipMalloc((void**)&p->pack_buf, bytes + bytes / 4));
-    p->pack_bytes = bytes + bytes / 4;
-    return FFS_OK;
-}
+// One solve of at most 65 536 run-boundary vectors: the call's state, with its phases as member functions in the order
+// solve_call() runs them.
+struct AlignCall {
+    ffs_plan* const p;
+    const AlignArgs& a;
+    const hipStream_t st;
+    StreamLeave leave;
+    // shape
+    const int n_pairs, n_cand, stride, n_packed, n_slots, n_chunks;
+    const size_t n_vec, n_cands;
+    size_t n_rr = 0;       // RunsRef entries: every vector, then three threshold planes per pair of a multi-level call
+    size_t flag_bytes = 0;  // sub-batch flags + two 8-byte statistics behind them (boundaries of the call, its longest plan-owned list)
+    // decided once
+    bool lists_in, ml, runs_ok, need_extract, ml_on = false, mixed, use_copy = false, dense_stream = false;
+    int t_dtype, t_ref_dt;  // the types the transform kernels see (list-only vectors are expanded to bits before they run)
+    int hflags = 0;
+    long long budget = 0;
+    DescLayout L;
+    char *hb = nullptr, *db = nullptr;  // the pinned block, the device block of this call
+    CandDesc* hc = nullptr;
+    const CandDesc* dc = nullptr;
+    const RunsRef* d_rv = nullptr;
+    const XformDesc* dx = nullptr;
+    NomList* dn = nullptr;
+    RescoreAcc* da = nullptr;
+    PoolBest* dpb = nullptr;
+    PoolArgs pa{};
+    CandResult* cres;
+    PairResult* pres;
+    // changes during the call
+    bool late_extract = false;   // small calls: table and extraction go behind the candidate descriptors (upload_descriptors)
+    bool probe_first = false;    // a density probe stands in for the extraction so far
+    bool flags_cleared = false;  // the extraction kernel's first workgroup has cleared the flags (a memset otherwise)
+    bool copy_entered = false;   // the copy stream already waits for the last call that used this device block
+    bool proven = false, xf_built = false, retry = false;
+    int tiles_max = 1;
+    int64_t lvl_len_max = 1;
+    const void* const* xptr;  // the vectors as the transform path reads them (list-only vectors: their expansion)
+    std::vector<const void*> expanded;
+    BinList bins;
+    bool pruned = false, seg = false;
+    int seg_blocks = 0;
+    int64_t seg_lo = 0;
+    size_t n_xf;
+    std::vector<char> chunk_fft;
+    bool any_fft = false;
+    double ht0 = 0, ht1 = 0, ht2 = 0, ht3 = 0;  // FFS_HOST_TIMING marks
 
-// vec_bound (may be null): FFS_DTYPE_RUNS vectors only -- a host-known upper bound of the list's length (0: unknown).
-static int align_impl(ffs_plan* p, int n_pairs, int n_cand, int ref_dt, int dtype, const void* const* vec_ptr,
-                      const int64_t* vec_len, const double* vec_lo, const double* vec_hi, const int32_t* vec_bound,
-                      int64_t max_offset_samples, int64_t filter_max_offset, ffs_cand_result* cand_out_dev,
-                      ffs_pair_result* pair_out_dev, void* hip_stream) {
-    // `dtype` = the candidates' element type, `ref_dt` = the references'; `mixed` when they differ: the first pass
-    // runs once per role (row_sel) and the exact re-evaluation goes through the type-generic instantiations (DT 4)
-    auto known = [](int dt) {
-        return dt == FFS_DTYPE_U8 || dt == FFS_DTYPE_F32 || dt == FFS_DTYPE_U1 || dt == FFS_DTYPE_F64 || dt == FFS_DTYPE_RUNS;
-    };
-    auto esz_of = [](int dt) -> size_t { return dt == FFS_DTYPE_U8 ? 1 : (dt == FFS_DTYPE_F32 ? 4 : (dt == FFS_DTYPE_F64 ? 8 : 0)); };
-    auto amask_of = [](int dt) -> uintptr_t { return dt == FFS_DTYPE_U8 ? 0 : (dt == FFS_DTYPE_F64 || dt == FFS_DTYPE_RUNS ? 7 : 3); };
-    if (!p) return fail(FFS_E_INVALID, "plan is null");
-    if (n_pairs < 0 || n_cand < 1 || n_cand > p->max_cand)
-        return fail(FFS_E_INVALID, "n_cand=%d outside [1, plan max_cand=%d]", n_cand, p->max_cand);
-    if (!known(dtype) || !known(ref_dt)) return fail(FFS_E_INVALID, "unknown dtype %d / %d", ref_dt, dtype);
-    if (!vec_ptr || !vec_len || !vec_lo || !vec_hi || !cand_out_dev || !pair_out_dev)
-        return fail(FFS_E_INVALID, "null argument");
-    if (n_pairs == 0) return FFS_OK;
-    const int stride = 1 + n_cand;
-    const size_t n_vec = (size_t)n_pairs * (size_t)stride;
-    // ---- one contract for every path, checked before anything is queued: no empty vector (aligners.py:58-66), no null
-    // or misaligned pointer, no vector of 2^30 samples or more (positions are 32-bit; 0x3fffffff is the run-boundary
-    // kernels' "beyond everything").  The plan-length check (FFS_E_TOO_LONG whichever path would have served the pair) is
-    // part of fill_cand, which every path runs for every candidate.
-    for (int pi = 0; pi < n_pairs; ++pi) {
-        const size_t b = (size_t)pi * stride;
-        for (int v = 0; v < stride; ++v) {
-            const int dt = v ? dtype : ref_dt;
-            if (vec_len[b] <= 0 || vec_len[b + v] <= 0)
-                return fail(FFS_E_EMPTY, "cannot align empty speech data (reference length=%lld, subtitle length=%lld)",
-                            (long long)vec_len[b], (long long)vec_len[b + (v ? v : 1)]);
-            if (!vec_ptr[b + v]) return fail(FFS_E_INVALID, "null device pointer for pair %d", pi);
-            if ((uintptr_t)vec_ptr[b + v] & amask_of(dt))
-                return fail(FFS_E_INVALID, "float / bit-packed vectors and boundary lists must be aligned to their element (pair %d)", pi);
-            if (vec_len[b + v] >= (int64_t(1) << 30))
-                return fail(FFS_E_TOO_LONG, "vector of %lld samples (pair %d): at most 2^30 - 1", (long long)vec_len[b + v], pi);
-        }
+    AlignCall(ffs_plan* p_, const AlignArgs& a_)
+        : p(p_), a(a_), st((hipStream_t)a_.hip_stream), leave{p_, (hipStream_t)a_.hip_stream},
+          n_pairs(a_.n_pairs), n_cand(a_.n_cand), stride(1 + a_.n_cand), n_packed((a_.n_cand + 1) / 2), n_slots(1 + (a_.n_cand + 1) / 2),
+          n_chunks((a_.n_pairs + p_->pairs_in_flight - 1) / p_->pairs_in_flight), n_vec((size_t)a_.n_pairs * (1 + a_.n_cand)),
+          n_cands((size_t)a_.n_pairs * a_.n_cand), cres((CandResult*)a_.cand_out_dev), pres((PairResult*)a_.pair_out_dev),
+          xptr(a_.vec_ptr), n_xf((size_t)a_.n_pairs * (1 + (a_.n_cand + 1) / 2)) {
+        memset(&bins, 0, sizeof bins);
+        const bool may_run = p->algo != FFS_ALGO_FFT && !p->direct_only;
+        lists_in = a.dtype == FFS_DTYPE_RUNS || a.ref_dt == FFS_DTYPE_RUNS;
+        // Run-boundary path: two-level vectors on both sides, as bits (FFS_DTYPE_U1: their lists are extracted here) or as
+        // boundary lists (FFS_DTYPE_RUNS); everything else, and every sub-batch whose lists turn out too long, goes through
+        // the transforms.  Multi-level float references (the `weighted` fused VAD's four levels,
+        // speech_transformers.py:290-293) against two-level candidates: the reference's threshold planes are made on the
+        // device (k_levels_*), their lists extracted, and the run-boundary kernel adds the levels up (ffs_runs.h, LevelInfo).
+        ml = may_run && (a.ref_dt == FFS_DTYPE_F64 || a.ref_dt == FFS_DTYPE_F32) && runs_able(a.dtype);
+        runs_ok = may_run && runs_able(a.dtype) && (runs_able(a.ref_dt) || ml);
+        need_extract = runs_ok && (ml || a.dtype == FFS_DTYPE_U1 || a.ref_dt == FFS_DTYPE_U1);
+        n_rr = n_vec + (ml ? 3 * (size_t)n_pairs : 0);
+        flag_bytes = (((size_t)n_chunks * sizeof(int) + 7) & ~(size_t)7) + 16;
+        // `mixed` when the two roles differ in type: the first pass runs once per role (row_sel) and the exact
+        // re-evaluation goes through the type-generic instantiations (DT 4)
+        t_dtype = as_bits(a.dtype), t_ref_dt = as_bits(a.ref_dt);
+        mixed = t_ref_dt != t_dtype;
+        hflags = p->direct_only ? 0 : half_flags_of(p, ref_half_ok(p));
+        budget = p->algo == FFS_ALGO_RUNS ? INT64_MAX / 4
+                 : p->runs_budget >= 0    ? p->runs_budget
+                                          : kRunsBudgetPerPoint * (long long)p->N * (n_cand + 1) / (2 * n_cand);
     }
-    hipStream_t st = (hipStream_t)hip_stream;
-    const bool lists_in = dtype == FFS_DTYPE_RUNS || ref_dt == FFS_DTYPE_RUNS;
-    auto runs_able = [](int dt) { return dt == FFS_DTYPE_U1 || dt == FFS_DTYPE_RUNS; };
-    if (p->algo != FFS_ALGO_FFT && !p->direct_only && dtype == FFS_DTYPE_U8 && ref_dt == FFS_DTYPE_U8) {
-        // 0/1 BYTES (the north star's literal input format): one pass packs every vector of the call to bits (bit =
-        // byte != 0, exactly the two-level reading the byte kernels apply), then the call continues as FFS_DTYPE_U1 --
-        // run-boundary path where the lists are short, transforms on an eighth of the input bytes otherwise.  Identical
-        // records (tests/test_gpu_headline.py::test_byte_inputs_give_the_same_records; FFS_ALGO_FFT keeps the byte kernels).
-        std::vector<size_t> off(n_vec + 1, 0);
-        int64_t len_max = 1;
-        for (size_t i = 0; i < n_vec; ++i) {
-            off[i + 1] = off[i] + (((size_t)(vec_len[i] + 31) / 32 * 4 + 63) & ~(size_t)63);
-            if (vec_len[i] > len_max) len_max = vec_len[i];
-        }
-        HIP_TRY(hipSetDevice(p->device));
-        int rc0;
-        if ((rc0 = enter_stream(p, st))) return rc0;
-        if ((rc0 = grow_pack_buf(p, off[n_vec]))) return rc0;
-        if ((rc0 = ensure_desc(p, n_vec * sizeof(PackVec) + 4096))) return rc0;
-        HIP_TRY(hipEventSynchronize(p->upload_done));
-        p->cur_half = 0;
-        PackVec* hp = (PackVec*)p->host_desc;
-        std::vector<const void*> packed(n_vec);
-        for (size_t i = 0; i < n_vec; ++i) {
-            unsigned* dst = (unsigned*)((char*)p->pack_buf + off[i]);
-            hp[i] = PackVec{(const unsigned char*)vec_ptr[i], dst, (int32_t)vec_len[i], 0};
-            packed[i] = dst;
-        }
-        HIP_TRY(hipMemcpyAsync(p->dev_desc, hp, n_vec * sizeof(PackVec), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(p->upload_done, st));
-        const int chunks_per_vec = (int)(((len_max + 31) / 32 + 255) / 256);
-        hipLaunchKernelGGL(k_pack_bytes_batch, dim3((unsigned)(n_vec * chunks_per_vec)), dim3(256), 0, st, (const PackVec*)p->dev_desc,
-                           chunks_per_vec);
-        HIP_TRY(hipGetLastError());
-        if ((rc0 = leave_stream(p, st))) return rc0;
-        return align_impl(p, n_pairs, n_cand, FFS_DTYPE_U1, FFS_DTYPE_U1, packed.data(), vec_len, vec_lo, vec_hi, nullptr,
-                          max_offset_samples, filter_max_offset, cand_out_dev, pair_out_dev, hip_stream);
-    }
-    // Expands the call's list-only vectors (role `ref`/`cand` of type FFS_DTYPE_RUNS) to bits in the plan's pack buffer;
-    // `out` = the call's pointer table with those vectors replaced.  Queued on `st`.
-    auto expand_lists = [&](std::vector<const void*>* out) -> int {
-        std::vector<size_t> off(n_vec + 1, 0);
-        int64_t len_max = 1;
-        for (size_t i = 0; i < n_vec; ++i) {
-            const bool is_list = ((i % stride) ? dtype : ref_dt) == FFS_DTYPE_RUNS;
-            off[i + 1] = off[i] + (is_list ? (((size_t)(vec_len[i] + 31) / 32 * 4 + 63) & ~(size_t)63) : 0);
-            if (is_list && vec_len[i] > len_max) len_max = vec_len[i];
-        }
-        int rc0;
-        if ((rc0 = grow_pack_buf(p, off[n_vec]))) return rc0;
-        ExpandVec* d_ev = nullptr;
-        std::vector<ExpandVec> hev(n_vec);
-        out->assign(vec_ptr, vec_ptr + n_vec);
-        for (size_t i = 0; i < n_vec; ++i) {
-            const bool is_list = ((i % stride) ? dtype : ref_dt) == FFS_DTYPE_RUNS;
-            unsigned* dst = is_list ? (unsigned*)((char*)p->pack_buf + off[i]) : nullptr;
-            hev[i] = ExpandVec{(const int2*)((const char*)vec_ptr[i] + 16), (const int2*)vec_ptr[i], dst, (int32_t)vec_len[i], 0};
-            if (is_list) (*out)[i] = dst;
-        }
-        // (rare path; the table is followed by one int the kernel raises when a block's header does not fit the block)
-        const size_t tab = n_vec * sizeof(ExpandVec);
-        int bad_list = 0;
-        HIP_TRY(hipMallocAsync((void**)&d_ev, tab + sizeof(int), st));
-        hipError_t he = hipMemcpyAsync(d_ev, hev.data(), tab, hipMemcpyHostToDevice, st);
-        if (he == hipSuccess) he = hipMemsetAsync((char*)d_ev + tab, 0, sizeof(int), st);
-        if (he == hipSuccess) he = hipStreamSynchronize(st);
-        if (he == hipSuccess) {
-            const int chunks_per_vec = (int)(((len_max + 31) / 32 + 255) / 256);
-            hipLaunchKernelGGL(k_runs_expand, dim3((unsigned)(n_vec * chunks_per_vec)), dim3(256), 0, st, (const ExpandVec*)d_ev, chunks_per_vec,
-                               (int*)((char*)d_ev + tab));
-            he = hipGetLastError();
-        }
-        if (he == hipSuccess) he = hipMemcpyAsync(&bad_list, (char*)d_ev + tab, sizeof(int), hipMemcpyDeviceToHost, st);
-        if (he == hipSuccess) he = hipStreamSynchronize(st);
-        const hipError_t hf = hipFreeAsync(d_ev, st);  // (on every path: an error above must not leak the table)
-        HIP_TRY(he);
-        HIP_TRY(hf);
-        if (bad_list)
-            return fail(FFS_E_INVALID, "a boundary list of the call is truncated (more entries than its block holds) or was made for "
-                        "another vector length: nothing can solve it -- pass the vector as bits");
-        return FFS_OK;
-    };
-    if (lists_in && (p->algo == FFS_ALGO_FFT || p->direct_only || !runs_able(dtype) || !runs_able(ref_dt))) {
-        // boundary lists where only the transforms (or the direct kernel of short plans) may run: as bits
-        HIP_TRY(hipSetDevice(p->device));
-        int rc0;
-        if ((rc0 = enter_stream(p, st))) return rc0;
-        std::vector<const void*> bits_ptr;
-        if ((rc0 = expand_lists(&bits_ptr))) return rc0;
-        if ((rc0 = leave_stream(p, st))) return rc0;
-        return align_impl(p, n_pairs, n_cand, ref_dt == FFS_DTYPE_RUNS ? FFS_DTYPE_U1 : ref_dt,
-                          dtype == FFS_DTYPE_RUNS ? FFS_DTYPE_U1 : dtype, bits_ptr.data(), vec_len, vec_lo, vec_hi, nullptr,
-                          max_offset_samples, filter_max_offset, cand_out_dev, pair_out_dev, hip_stream);
-    }
-    {
-        // The plan-owned boundary lists take 256 KiB per vector: a call with more than 65 536 vectors of bit-packed
-        // two-level samples is solved as consecutive sub-calls (results land where one call would put them).
-        // (a multi-level float reference brings three threshold planes of its own)
-        const bool ml_split = (ref_dt == FFS_DTYPE_F64 || ref_dt == FFS_DTYPE_F32) && runs_able(dtype);
-        const int64_t per_pair = stride + (ml_split ? 3 : 0);
-        const int64_t max_pairs = (int64_t(1) << 16) / per_pair > 0 ? (int64_t(1) << 16) / per_pair : 1;
-        if (p->algo != FFS_ALGO_FFT && !p->direct_only && runs_able(dtype) && (runs_able(ref_dt) || ml_split) && n_pairs > max_pairs) {
-            for (int64_t p0 = 0; p0 < n_pairs; p0 += max_pairs) {
-                const int np = (int)((n_pairs - p0) < max_pairs ? (n_pairs - p0) : max_pairs);
-                const int rc_sub = align_impl(p, np, n_cand, ref_dt, dtype, vec_ptr + p0 * stride, vec_len + p0 * stride,
-                                              vec_lo + p0 * stride, vec_hi + p0 * stride, vec_bound ? vec_bound + p0 * stride : nullptr,
-                                              max_offset_samples, filter_max_offset, cand_out_dev + p0 * n_cand, pair_out_dev + p0,
-                                              hip_stream);
-                if (rc_sub) return rc_sub;
-            }
-            return FFS_OK;
-        }
-    }
-    static_assert(sizeof(CandResult) == sizeof(ffs_cand_result), "ABI struct mismatch");
-    static_assert(sizeof(PairResult) == sizeof(ffs_pair_result), "ABI struct mismatch");
-    HIP_TRY(hipSetDevice(p->device));
-    int rc;
-    if ((rc = enter_stream(p, st))) return rc;
-    StreamLeave leave{p, st};
-    auto now_ns = [] { return (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double ht0 = p->host_timing ? now_ns() : 0.0;
-    double ht1 = ht0, ht2 = ht0, ht3 = ht0;
-
-    const int n_packed = (n_cand + 1) / 2;
-    const int n_slots = 1 + n_packed;  // length-N buffers per pair, in either layout
-    const int xf_per_pair = n_slots;
-    const int sel_ref = 0 | (1 << 16), sel_cand = 1 | ((n_slots - 1) << 16);  // row_sel of the two first-pass launches when mixed
-    const bool ref_half = !p->direct_only && ref_half_ok(p);
     // odd candidate count: the last packed transform carries one real candidate -> half of its rows suffice
     // (needs the one-row-per-block mid kernels, like ref_half; the plan that runs the kernels decides)
-    auto half_flags_of = [&](const ffs_plan* q, bool rh) {
+    int half_flags_of(const ffs_plan* q, bool rh) const {
         const bool hl = (n_cand % 2 == 1) && q->allow_half_last && ref_half_ok(q) && q->N1 >= 4;
         return (rh ? HALF_REF : 0) | (hl ? HALF_LAST : 0);
-    };
-    const int hflags = p->direct_only ? 0 : half_flags_of(p, ref_half);
-    const int slot_map = n_slots;  // see slot_stride()/cand_slot() in ffs_kernels.h
-    const size_t n_cands = (size_t)n_pairs * n_cand;
-    size_t n_xf = (size_t)n_pairs * xf_per_pair;
-    const size_t n_xf_alloc = p->seg ? (size_t)n_pairs * kSegBlocks * n_slots : n_xf;  // block-segmented mode needs more
-    const int n_chunks = (n_pairs + p->pairs_in_flight - 1) / p->pairs_in_flight;
-    // Run-boundary path: two-level vectors on both sides, as bits (FFS_DTYPE_U1: their lists are extracted here) or as
-    // boundary lists (FFS_DTYPE_RUNS); everything else, and every sub-batch whose lists turn out too long, goes through
-    // the transforms.  Its buffers come first: without them (out of memory) an AUTO call on bits still has the transforms.
-    // Multi-level float references (the `weighted` fused VAD's four levels, speech_transformers.py:290-293) against
-    // two-level candidates: the reference's threshold planes are made on the device (k_levels_*), their lists extracted,
-    // and the run-boundary kernel adds the levels up (ffs_runs.h, LevelInfo); whatever does not qualify takes the transforms.
-    const bool ml = p->algo != FFS_ALGO_FFT && !p->direct_only && (ref_dt == FFS_DTYPE_F64 || ref_dt == FFS_DTYPE_F32) && runs_able(dtype);
-    bool runs_ok = p->algo != FFS_ALGO_FFT && !p->direct_only && runs_able(dtype) && (runs_able(ref_dt) || ml);
-    const bool need_extract = runs_ok && (ml || dtype == FFS_DTYPE_U1 || ref_dt == FFS_DTYPE_U1);
-    const size_t n_rr = n_vec + (ml ? 3 * (size_t)n_pairs : 0);  // RunsRef entries: every vector, then three threshold planes per pair
-    if (runs_ok && (rc = ensure_runs(p, need_extract ? n_rr : 0, 0, (size_t)n_chunks))) {
-        if (lists_in || p->algo != FFS_ALGO_AUTO) return rc;
-        runs_ok = false;  // FFS_ALGO_AUTO: "only the time differs" -- the transforms need no list buffers
     }
-    // the types the transform kernels see (list-only vectors are expanded to bits before they run)
-    const int t_dtype = dtype == FFS_DTYPE_RUNS ? FFS_DTYPE_U1 : dtype, t_ref_dt = ref_dt == FFS_DTYPE_RUNS ? FFS_DTYPE_U1 : ref_dt;
-    const bool mixed = t_ref_dt != t_dtype;
-    // descriptor block layout: [PoolHeader][CandDesc n_cands][RunsRef n_vec][XformDesc n_xf][NomList n_cands][RescoreAcc n_cands*KNOM]
-    const size_t o_pool = 0;  // PoolHeader (uploaded: count = 0, capacity)
-    const size_t o_cand = 64;
-    const size_t o_rv = o_cand + n_cands * sizeof(CandDesc);  // RunsRef[n_rr] when runs_ok
-    // multi-level tables behind it: LevelInfo | sample pointers | plane pointers | lengths | plane words, one per pair
-    const size_t o_li = (o_rv + (runs_ok ? n_rr * sizeof(RunsRef) : 0) + 63) & ~(size_t)63;
-    const bool ml_on = runs_ok && ml;
-    const size_t o_mp = o_li + (ml_on ? (size_t)n_pairs * sizeof(LevelInfo) : 0);
-    const size_t o_mq = o_mp + (ml_on ? (size_t)n_pairs * 8 : 0);
-    const size_t o_ml = o_mq + (ml_on ? (size_t)n_pairs * 8 : 0);
-    const size_t o_mw = o_ml + (ml_on ? (size_t)n_pairs * 4 : 0);
-    const size_t o_xf = (o_mw + (ml_on ? (size_t)n_pairs * 4 : 0) + 63) & ~(size_t)63;
-    const size_t host_bytes_max = o_xf + (n_xf_alloc > n_xf ? n_xf_alloc : n_xf) * sizeof(XformDesc);
-    const size_t o_nom = (host_bytes_max + 255) & ~(size_t)255;
-    const size_t o_acc = o_nom + n_cands * sizeof(NomList);
-    const size_t o_pbest = o_acc + n_cands * KNOM * sizeof(RescoreAcc);  // zeroed together with acc
-    const size_t total = o_pbest + n_cands * sizeof(PoolBest);
-    if ((rc = ensure_desc(p, total))) return rc;
-    HIP_TRY(hipEventSynchronize(p->upload_done));  // previous call's upload has left the pinned buffer
-    char* hb = (char*)p->host_desc;
-    {
-        PoolHeader* ph = (PoolHeader*)(hb + o_pool);
-        memset(hb + o_pool, 0, 64);
-        ph->capacity = kPoolCapacity;
+    void mark(double* t) const {
+        if (p->host_timing) *t = now_ns();
     }
-    CandDesc* hc = (CandDesc*)(hb + o_cand);
-    XformDesc* hx = (XformDesc*)(hb + o_xf);
-    RunsRef* hrv = (RunsRef*)(hb + o_rv);
-    const bool ml_early = runs_ok && ml;
-    const bool use_copy = runs_ok && need_extract && !ml_early && !(p->algo == FFS_ALGO_AUTO && p->runs_prev_fft && !lists_in) && ensure_copy(p);
-    p->cur_half = use_copy ? 1 - p->cur_half : 0;
-    char* db = (char*)(p->cur_half ? p->dev_desc2 : p->dev_desc);
-    bool probe_first = false;           // (run-boundary path) a density probe stands in for the extraction so far
-    // sub-batch flags + two 8-byte statistics behind them (boundaries of the call, its longest plan-owned list): cleared by the
-    // extraction kernel's first workgroup when one is launched, by a memset otherwise
-    const size_t flag_bytes = (((size_t)n_chunks * sizeof(int) + 7) & ~(size_t)7) + 16;
-    bool flags_cleared = false;
-    // Small calls: ONE upload (vector table + candidate descriptors) and the extraction behind it, instead of the table, the
-    // extraction and then the candidates -- the host takes longer to build ~1000 descriptors than the device to extract
-    // 1000 lists, so the early launch only moved a 20 us hole behind the extraction and cost one more stream operation
-    // (profiles/small_step_timeline.py).  Large calls keep the early launch: the device reads the vectors while the host
-    // builds tens of thousands of descriptors.
-    bool late_extract = false;
-    const void* const* xptr = vec_ptr;  // the vectors as the transform path reads them (list-only vectors: their expansion)
-    std::vector<const void*> expanded;
-    if (runs_ok) {
-        // Run-boundary path, step 1: what the kernels need of every vector.  The lists of vectors that arrive as bits are
-        // extracted first -- the launch needs only this table, so the candidate descriptors are built while the device
-        // reads the vectors.
+    VecView view(const void* const* ptrs, size_t i) const { return VecView{ptrs[i], a.vec_len[i], a.vec_lo[i], a.vec_hi[i]}; }
+
+    // The ONE place that copies from the pinned block: [off, off + bytes) goes up on the call's stream, or on the copy
+    // stream behind the last call that used this device block (the call's stream then waits for the copy).  upload_done
+    // is recorded behind the copy -- except behind the vector table that goes ahead of the descriptors (`table_ahead`: they
+    // follow on the same stream and record it; should the call fail before that, `leave` does).
+    int upload(size_t off, size_t bytes, bool on_copy, bool table_ahead = false) {
+        const hipStream_t us = on_copy ? p->copy_stream : st;
+        if (on_copy && !copy_entered) {
+            if (p->half_used[p->cur_half]) HIP_TRY(hipStreamWaitEvent(us, p->half_done[p->cur_half], 0));
+            copy_entered = true;
+        }
+        HIP_TRY(hipMemcpyAsync(db + off, hb + off, bytes, hipMemcpyHostToDevice, us));
+        leave.armed = true;
+        leave.upload_open = true;
+        leave.upload_st = us;
+        const hipEvent_t ev = table_ahead ? p->copy_ev : p->upload_done;
+        if (!table_ahead || on_copy) HIP_TRY(hipEventRecord(ev, us));
+        if (on_copy) HIP_TRY(hipStreamWaitEvent(st, ev, 0));
+        if (!table_ahead) leave.upload_open = false;
+        return FFS_OK;
+    }
+    void launch_extraction(size_t n_refs, bool clear_flags, bool plain_lists) {
+        ProfSpan span(p, st, FFS_K_RUNS_EXTRACT);
+        if (plain_lists)  // the call's own vectors: candidates' lists compact (see RunsRef)
+            runs_extract_launch(d_rv, n_refs, false, st, clear_flags ? p->runs_flags : nullptr, clear_flags ? (int)(flag_bytes / sizeof(int)) : 0,
+                                stride, (int)n_vec);
+        else  // (full lists: see runs_corr_body, p_sh)
+            runs_extract_launch(d_rv, n_refs, false, st, p->runs_flags, (int)(flag_bytes / sizeof(int)));
+        flags_cleared = flags_cleared || clear_flags;
+    }
+
+    // ---- phases, in the order of solve_call ------------------------------------------------------------------------
+    // The run-boundary buffers come first: without them (out of memory) an AUTO call on bits still has the transforms.
+    int prepare() {
+        int rc;
+        if (runs_ok && (rc = ensure_runs(p, need_extract ? n_rr : 0, 0, (size_t)n_chunks))) {
+            if (lists_in || p->algo != FFS_ALGO_AUTO) return rc;
+            runs_ok = false;  // FFS_ALGO_AUTO: "only the time differs" -- the transforms need no list buffers
+        }
+        ml_on = runs_ok && ml;
+        L = DescLayout((size_t)n_pairs, (size_t)n_cand, n_rr, ml_on, runs_ok,
+                       p->seg ? (size_t)n_pairs * kSegBlocks * n_slots : n_xf);  // block-segmented mode needs more
+        if ((rc = ensure_desc(p, L.total))) return rc;
+        HIP_TRY(hipEventSynchronize(p->upload_done));  // previous call's upload has left the pinned buffer
+        hb = (char*)p->host_desc;
+        memset(L.pool(hb), 0, 64);
+        L.pool(hb)->capacity = kPoolCapacity;
+        // a stream of dense calls (the previous one needed the transforms): probe before extracting, upload on the call's stream
+        dense_stream = p->algo == FFS_ALGO_AUTO && p->runs_prev_fft && !lists_in;
+        use_copy = runs_ok && need_extract && !ml_on && !dense_stream && ensure_copy(p);
+        p->cur_half = use_copy ? 1 - p->cur_half : 0;
+        db = (char*)(p->cur_half ? p->dev_desc2 : p->dev_desc);
+        hc = L.cands(hb);
+        dc = L.cands(db);
+        d_rv = L.runs_refs(db);
+        dx = L.xforms(db);
+        dn = L.nominees(db);
+        da = L.acc(db);
+        dpb = L.pool_best(db);
+        pa = PoolArgs{dn, L.pool(db), nullptr, dpb, n_chunks};  // .entries: once the transform workspace exists
+        pa.half_last = (hflags & HALF_LAST) ? 1 : 0;
+        chunk_fft.assign((size_t)n_chunks, runs_ok ? 0 : 1);
+        any_fft = !runs_ok;
+        return FFS_OK;
+    }
+    // Run-boundary path, step 1: what the kernels need of every vector.
+    int fill_runs_table() {
+        RunsRef* hrv = L.runs_refs(hb);
         for (size_t i = 0; i < n_vec; ++i) {
-            const int dt = (i % stride) ? dtype : ref_dt;
+            const int dt = (i % stride) ? a.dtype : a.ref_dt;
             if (dt == FFS_DTYPE_RUNS)  // caller-owned block: 16-byte header (n, ones, len, capacity), then the entries
-                hrv[i] = RunsRef{(const int2*)((const char*)vec_ptr[i] + 16), (const int2*)vec_ptr[i], nullptr, (int32_t)vec_len[i], 0};
+                hrv[i] = RunsRef{(const int2*)((const char*)a.vec_ptr[i] + 16), (const int2*)a.vec_ptr[i], nullptr, (int32_t)a.vec_len[i], 0};
             else if (dt == FFS_DTYPE_U1)
-                hrv[i] = RunsRef{p->runs_e + i * (size_t)p->runs_stride, p->runs_n + i, (const unsigned*)vec_ptr[i], (int32_t)vec_len[i], p->runs_stride};
+                hrv[i] = RunsRef{p->runs_e + i * (size_t)p->runs_stride, p->runs_n + i, (const unsigned*)a.vec_ptr[i], (int32_t)a.vec_len[i], p->runs_stride};
             else  // a multi-level reference: its threshold planes follow the vectors
-                hrv[i] = RunsRef{nullptr, p->runs_n + i, nullptr, (int32_t)vec_len[i], p->runs_stride};
+                hrv[i] = RunsRef{nullptr, p->runs_n + i, nullptr, (int32_t)a.vec_len[i], p->runs_stride};
         }
-        if (ml_on) {
-            std::vector<size_t> poff((size_t)n_pairs + 1, 0);
-            int64_t len_max = 1;
-            for (int pi = 0; pi < n_pairs; ++pi) {
-                const size_t pw = (size_t)(vec_len[(size_t)pi * stride] + 31) / 32;
-                poff[pi + 1] = poff[pi] + ((3 * pw * 4 + 63) & ~(size_t)63);
-                if (vec_len[(size_t)pi * stride] > len_max) len_max = vec_len[(size_t)pi * stride];
-            }
-            if (poff[n_pairs] > p->lvl_bytes) {
-                if (p->has_last) HIP_TRY(hipEventSynchronize(p->last_done));
-                (void)hipFree(p->lvl_buf);
-                p->lvl_buf = nullptr;
-                p->lvl_bytes = 0;
-                HIP_TRY(hipMalloc((void**)&p->lvl_buf, poff[n_pairs] + poff[n_pairs] / 4));
-                p->lvl_bytes = poff[n_pairs] + poff[n_pairs] / 4;
-            }
-            const void** h_vp = (const void**)(hb + o_mp);
-            unsigned** h_pp = (unsigned**)(hb + o_mq);
-            int32_t* h_len = (int32_t*)(hb + o_ml);
-            int32_t* h_pw = (int32_t*)(hb + o_mw);
-            for (int pi = 0; pi < n_pairs; ++pi) {
-                const size_t b = (size_t)pi * stride;
-                const int32_t pw = (int32_t)((vec_len[b] + 31) / 32);
-                unsigned* planes = (unsigned*)((char*)p->lvl_buf + poff[pi]);
-                h_vp[pi] = vec_ptr[b];
-                h_pp[pi] = planes;
-                h_len[pi] = (int32_t)vec_len[b];
-                h_pw[pi] = pw;
-                for (int k = 0; k < 3; ++k) {
-                    const size_t r = n_vec + 3 * (size_t)pi + k;
-                    hrv[r] = RunsRef{p->runs_e + r * (size_t)p->runs_stride, p->runs_n + r, planes + (size_t)k * pw, (int32_t)vec_len[b], p->runs_stride};
-                }
-            }
-            HIP_TRY(hipMemcpyAsync(db + o_rv, hb + o_rv, o_xf - o_rv, hipMemcpyHostToDevice, st));
-            leave.armed = true;
-            LevelInfo* d_li = (LevelInfo*)(db + o_li);
-            const unsigned chunks = (unsigned)((len_max + 16383) / 16384);
-            {
-            ProfSpan lspan(p, st, FFS_K_LEVELS);
-            if (ref_dt == FFS_DTYPE_F64) {
-                hipLaunchKernelGGL((k_levels_sample<double>), dim3((unsigned)n_pairs), dim3(256), 0, st, (const double* const*)(db + o_mp),
-                                   (const int*)(db + o_ml), d_li);
-                hipLaunchKernelGGL((k_levels_bits<double>), dim3(chunks, (unsigned)n_pairs), dim3(256), 0, st, (const double* const*)(db + o_mp),
-                                   (const int*)(db + o_ml), d_li, (unsigned* const*)(db + o_mq), (const int*)(db + o_mw));
-            } else {
-                hipLaunchKernelGGL((k_levels_sample<float>), dim3((unsigned)n_pairs), dim3(256), 0, st, (const float* const*)(db + o_mp),
-                                   (const int*)(db + o_ml), d_li);
-                hipLaunchKernelGGL((k_levels_bits<float>), dim3(chunks, (unsigned)n_pairs), dim3(256), 0, st, (const float* const*)(db + o_mp),
-                                   (const int*)(db + o_ml), d_li, (unsigned* const*)(db + o_mq), (const int*)(db + o_mw));
-            }
-            }
-            HIP_TRY(hipGetLastError());
-            {
-                ProfSpan span(p, st, FFS_K_RUNS_EXTRACT);
-                runs_extract_launch((const RunsRef*)(db + o_rv), n_rr, false, st, p->runs_flags, (int)(flag_bytes / sizeof(int)));  // (full lists: see runs_corr_body, p_sh)
-                flags_cleared = true;
-            }
-            HIP_TRY(hipGetLastError());
-        } else if (need_extract && n_cands <= kSmallCallCands && !(p->algo == FFS_ALGO_AUTO && p->runs_prev_fft && !lists_in)) {
-            late_extract = true;  // (uploaded and launched behind the candidate descriptors, below)
-        } else if (need_extract) {
-            if (use_copy) {
-                if (p->half_used[p->cur_half]) HIP_TRY(hipStreamWaitEvent(p->copy_stream, p->half_done[p->cur_half], 0));
-                HIP_TRY(hipMemcpyAsync(db + o_rv, hb + o_rv, n_vec * sizeof(RunsRef), hipMemcpyHostToDevice, p->copy_stream));
-                HIP_TRY(hipEventRecord(p->copy_ev, p->copy_stream));
-                HIP_TRY(hipStreamWaitEvent(st, p->copy_ev, 0));
-            } else {
-                HIP_TRY(hipMemcpyAsync(db + o_rv, hb + o_rv, n_vec * sizeof(RunsRef), hipMemcpyHostToDevice, st));
-            }
-            leave.armed = true;
-            // A stream of dense calls (the previous one needed the transforms): sample the vectors first -- when the
-            // estimate puts every sub-batch far over budget the lists are never extracted (decided below, once the
-            // candidate descriptors exist); otherwise the extraction is launched then.
-            probe_first = p->algo == FFS_ALGO_AUTO && p->runs_prev_fft && !lists_in;
-            if (probe_first) {
-                hipLaunchKernelGGL(k_runs_probe, dim3((unsigned)((n_vec + 3) / 4)), dim3(256), 0, st, (const RunsRef*)(db + o_rv), (int)n_vec);
-            } else {
-                ProfSpan span(p, st, FFS_K_RUNS_EXTRACT);
-                runs_extract_launch((const RunsRef*)(db + o_rv), n_vec, false, st, p->runs_flags, (int)(flag_bytes / sizeof(int)), (int)stride, (int)n_vec);
-                flags_cleared = true;
-            }
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    if (p->host_timing) ht1 = now_ns();
-    int tiles_max = 1;
-    auto fill_all_cands = [&](const void* const* ptrs, int rdt, int cdt) -> int {
+        if (!ml_on) return FFS_OK;
+        // three threshold planes per reference, in the plan's plane buffer: their lists are extracted like the vectors'
+        std::vector<size_t> poff;
+        lvl_len_max = bit_image_offsets(a.vec_len, (size_t)n_pairs, (size_t)stride, 3, [](size_t) { return true; }, &poff);
+        int rc;
+        if ((rc = grow_device_buf(p, &p->lvl_buf, &p->lvl_bytes, poff[n_pairs]))) return rc;
         for (int pi = 0; pi < n_pairs; ++pi) {
             const size_t b = (size_t)pi * stride;
-            const VecView ref{ptrs[b], vec_len[b], vec_lo[b], vec_hi[b]};
+            const int32_t pw = (int32_t)((a.vec_len[b] + 31) / 32);
+            unsigned* planes = (unsigned*)((char*)p->lvl_buf + poff[pi]);
+            L.level_samples(hb)[pi] = a.vec_ptr[b];
+            L.level_planes(hb)[pi] = planes;
+            L.level_lens(hb)[pi] = (int32_t)a.vec_len[b];
+            L.level_words(hb)[pi] = pw;
+            for (int k = 0; k < 3; ++k) {
+                const size_t r = n_vec + 3 * (size_t)pi + k;
+                hrv[r] = RunsRef{p->runs_e + r * (size_t)p->runs_stride, p->runs_n + r, planes + (size_t)k * pw, (int32_t)a.vec_len[b], p->runs_stride};
+            }
+        }
+        return FFS_OK;
+    }
+    template <class T>
+    void launch_levels() {
+        const unsigned chunks = (unsigned)((lvl_len_max + 16383) / 16384);
+        LevelInfo* d_li = L.level_info(db);
+        hipLaunchKernelGGL((k_levels_sample<T>), dim3((unsigned)n_pairs), dim3(256), 0, st, (const T* const*)L.level_samples(db),
+                           (const int*)L.level_lens(db), d_li);
+        hipLaunchKernelGGL((k_levels_bits<T>), dim3(chunks, (unsigned)n_pairs), dim3(256), 0, st, (const T* const*)L.level_samples(db),
+                           (const int*)L.level_lens(db), d_li, (unsigned* const*)L.level_planes(db), (const int*)L.level_words(db));
+    }
+    // The lists of vectors that arrive as bits are extracted first -- the launch needs only the vector table, so the
+    // candidate descriptors are built while the device reads the vectors.  Small calls: ONE upload (vector table + candidate
+    // descriptors) and the extraction behind it, instead of the table, the extraction and then the candidates -- the host
+    // takes longer to build ~1000 descriptors than the device to extract 1000 lists, so the early launch only moved a 20 us
+    // hole behind the extraction and cost one more stream operation (profiles/small_step_timeline.py).
+    int start_extraction_early() {
+        int rc;
+        if (ml_on) {
+            if ((rc = upload(L.table_at(), L.level_tables_bytes(), false, true))) return rc;
+            {
+                ProfSpan lspan(p, st, FFS_K_LEVELS);
+                if (a.ref_dt == FFS_DTYPE_F64) launch_levels<double>();
+                else launch_levels<float>();
+            }
+            HIP_TRY(hipGetLastError());
+            launch_extraction(n_rr, true, false);
+            HIP_TRY(hipGetLastError());
+        } else if (need_extract && n_cands <= kSmallCallCands && !dense_stream) {
+            late_extract = true;
+        } else if (need_extract) {
+            if ((rc = upload(L.table_at(), L.table_bytes(n_vec), use_copy, true))) return rc;
+            // A stream of dense calls: sample the vectors first -- when the estimate puts every sub-batch far over budget
+            // the lists are never extracted (probe_dense_stream, once the candidate descriptors exist); otherwise the
+            // extraction is launched then.
+            probe_first = dense_stream;
+            if (probe_first)
+                hipLaunchKernelGGL(k_runs_probe, dim3((unsigned)((n_vec + 3) / 4)), dim3(256), 0, st, d_rv, (int)n_vec);
+            else
+                launch_extraction(n_vec, true, true);
+            HIP_TRY(hipGetLastError());
+        }
+        return FFS_OK;
+    }
+    int fill_all_cands(const void* const* ptrs) {
+        for (int pi = 0; pi < n_pairs; ++pi) {
+            const size_t b = (size_t)pi * stride;
+            const VecView ref = view(ptrs, b);
             for (int j = 0; j < n_cand; ++j) {
-                const VecView sub{ptrs[b + 1 + j], vec_len[b + 1 + j], vec_lo[b + 1 + j], vec_hi[b + 1 + j]};
                 CandDesc& cd = hc[(size_t)pi * n_cand + j];
-                int rcf;
-                if ((rcf = fill_cand(p, ref, sub, max_offset_samples, &cd, rdt, cdt))) return rcf;
+                int rc;
+                if ((rc = fill_cand(p, ref, view(ptrs, b + 1 + j), a.max_offset_samples, &cd, t_ref_dt, t_dtype))) return rc;
                 if (runs_ok && !(cd.flags & CAND_NO_LAGS)) {
                     const int t = (cd.d_hi - cd.d_lo + RUNS_T) / RUNS_T;
                     if (t > tiles_max) tiles_max = t;
@@ -1630,55 +1746,54 @@ static int align_impl(ffs_plan* p, int n_pairs, int n_cand, int ref_dt, int dtyp
             }
         }
         return FFS_OK;
-    };
-    if ((rc = fill_all_cands(vec_ptr, t_ref_dt, t_dtype))) return rc;
-    // ---- descriptors of the transform path (built only when some sub-batch needs it) -------------------------
-    BinList bins;
-    memset(&bins, 0, sizeof bins);
-    bool pruned = false, seg = false;
-    int seg_blocks = 0;
-    int64_t seg_lo = 0;
-    auto build_xforms = [&]() -> int {
-    for (size_t i = 0; i < n_cands; ++i)
-        if ((rc = finish_cand_for_transforms(p, max_offset_samples, &hc[i]))) return rc;
-    std::vector<VecView> views((size_t)n_pairs * stride);  // per pair: reference, candidates (reachable prefixes)
-    for (int pi = 0; pi < n_pairs; ++pi) {
-        const size_t b = (size_t)pi * stride;
-        VecView ref{xptr[b], vec_len[b], vec_lo[b], vec_hi[b]};
-        std::vector<VecView> subs(n_cand);
-        int64_t ref_used = 1;
-        for (int j = 0; j < n_cand; ++j) {
-            subs[j] = VecView{xptr[b + 1 + j], vec_len[b + 1 + j], vec_lo[b + 1 + j], vec_hi[b + 1 + j]};
-            const CandDesc& cd = hc[(size_t)pi * n_cand + j];
-            // the transforms only read the prefixes that can reach the lag window (the exact re-evaluation
-            // keeps working on the whole vectors through the candidate descriptor)
-            int64_t s_eff, r_eff;
-            effective_lengths(ref.len, subs[j].len, cd.d_lo, cd.d_hi, &s_eff, &r_eff);
-            if (!(cd.flags & CAND_NO_LAGS)) {
-                subs[j].len = s_eff;
-                if (r_eff > ref_used) ref_used = r_eff;
-            }
-        }
-        ref.len = ref_used;
-        views[b] = ref;
-        for (int j = 0; j < n_cand; ++j) views[b + 1 + j] = subs[j];
-        fill_xform(&hx[(size_t)pi * n_slots], &ref, nullptr);
-        for (int k = 0; k < n_packed; ++k)
-            fill_xform(&hx[(size_t)pi * n_slots + 1 + k], &subs[2 * k], (2 * k + 1 < n_cand) ? &subs[2 * k + 1] : nullptr);
     }
-    // last-pass bins reachable by any lag window of this call (pruned pass C when there are few)
-    std::vector<int> bin_set;
-    bool bins_overflow = p->direct_only;
-    for (size_t i = 0; i < n_cands && !bins_overflow; ++i) add_bins(p, hc[i], &bin_set, &bins_overflow);
-    bins.n = (int)bin_set.size();
-    for (int i = 0; i < bins.n; ++i) bins.b[i] = bin_set[i];
-    pruned = p->allow_pruned && !bins_overflow && bins.n > 0 && bins.n * 2 <= p->N1;
+    // ---- descriptors of the transform path (built only when some sub-batch needs it) -------------------------
+    int build_xforms() {
+        int rc;
+        xf_built = true;
+        XformDesc* hx = L.xforms(hb);
+        for (size_t i = 0; i < n_cands; ++i)
+            if ((rc = finish_cand_for_transforms(p, a.max_offset_samples, &hc[i]))) return rc;
+        std::vector<VecView> views((size_t)n_pairs * stride);  // per pair: reference, candidates (reachable prefixes)
+        for (int pi = 0; pi < n_pairs; ++pi) {
+            const size_t b = (size_t)pi * stride;
+            VecView* v = &views[b];
+            v[0] = view(xptr, b);
+            int64_t ref_used = 1;
+            for (int j = 0; j < n_cand; ++j) {
+                v[1 + j] = view(xptr, b + 1 + j);
+                const CandDesc& cd = hc[(size_t)pi * n_cand + j];
+                // the transforms only read the prefixes that can reach the lag window (the exact re-evaluation
+                // keeps working on the whole vectors through the candidate descriptor)
+                int64_t s_eff, r_eff;
+                effective_lengths(v[0].len, v[1 + j].len, cd.d_lo, cd.d_hi, &s_eff, &r_eff);
+                if (!(cd.flags & CAND_NO_LAGS)) {
+                    v[1 + j].len = s_eff;
+                    if (r_eff > ref_used) ref_used = r_eff;
+                }
+            }
+            v[0].len = ref_used;
+            fill_xform(&hx[(size_t)pi * n_slots], &v[0], nullptr);
+            for (int k = 0; k < n_packed; ++k)
+                fill_xform(&hx[(size_t)pi * n_slots + 1 + k], &v[1 + 2 * k], (2 * k + 1 < n_cand) ? &v[2 + 2 * k] : nullptr);
+        }
+        // last-pass bins reachable by any lag window of this call (pruned pass C when there are few)
+        std::vector<int> bin_set;
+        bool bins_overflow = p->direct_only;
+        for (size_t i = 0; i < n_cands && !bins_overflow; ++i) add_bins(p, hc[i], &bin_set, &bins_overflow);
+        bins.n = (int)bin_set.size();
+        for (int i = 0; i < bins.n; ++i) bins.b[i] = bin_set[i];
+        pruned = p->allow_pruned && !bins_overflow && bins.n > 0 && bins.n * 2 <= p->N1;
+        if (p->seg && p->allow_seg && p->allow_pruned && !p->direct_only && a.max_offset_samples >= 0 && p->seg->N2 == 4096 &&
+            ref_half_ok(p->seg))
+            build_seg_xforms(views);
+        return FFS_OK;
+    }
     // Block-segmented mode (see k_mid_seg): every candidate is cut into n_blocks <= 3 blocks of B samples,
     // block k is correlated with the reference stretch [kB + D_lo, kB + D_lo + M) by a length-M transform
     // (lag d at output index d - D_lo, nothing wraps), the blocks' spectrum products are added in the
-    // mid pass.  [D_lo, D_hi] = union of the call's lag windows.
-    if (p->seg && p->allow_seg && p->allow_pruned && !p->direct_only && max_offset_samples >= 0 && p->seg->N2 == 4096 &&
-        ref_half_ok(p->seg)) {
+    // mid pass.  [D_lo, D_hi] = union of the call's lag windows.  Taken when the window is narrow enough.
+    void build_seg_xforms(const std::vector<VecView>& views) {
         const ffs_plan* sp = p->seg;
         int64_t d_lo = INT64_MAX, d_hi = INT64_MIN, s_max = 1;
         for (size_t i = 0; i < n_cands; ++i) {
@@ -1688,406 +1803,424 @@ static int align_impl(ffs_plan* p, int n_pairs, int n_cand, int ref_dt, int dtyp
             const int64_t sl = views[(i / n_cand) * stride + 1 + i % n_cand].len;
             if (sl > s_max) s_max = sl;
         }
-        if (d_lo <= d_hi) {
-            const int64_t W = d_hi - d_lo + 1, B = sp->N - (W - 1);
-            const int64_t nb = (W - 1) / sp->N2 + 1;
-            if (B >= 1 && nb <= MAXBINS && nb * 2 <= sp->N1 && (s_max + B - 1) / B <= kSegBlocks) {
-                seg = true;
-                seg_blocks = (int)((s_max + B - 1) / B);
-                seg_lo = d_lo;
-                // byte / float vectors move the pointer to the block's first sample, bit-packed ones the bit offset
-                const size_t esz = esz_of(t_dtype), esz_r = esz_of(t_ref_dt);
-                n_xf = (size_t)n_pairs * seg_blocks * n_slots;
-                for (int pi = 0; pi < n_pairs; ++pi) {
-                    const VecView& ref = views[(size_t)pi * stride];
-                    for (int k = 0; k < seg_blocks; ++k) {
-                        XformDesc* x = &hx[((size_t)pi * seg_blocks + k) * n_slots];
-                        VecView rb = ref;  // positions [lead, len) of the block input = ref[start + n]
-                        const int64_t start = (int64_t)k * B + d_lo;
-                        rb.lead = start < 0 ? -start : 0;
-                        rb.len = ref.len - start < sp->N ? ref.len - start : sp->N;
-                        if (rb.len <= rb.lead) {
-                            rb.len = rb.lead = 0;  // nothing of the reference in this stretch
-                        } else {
-                            rb.ptr = (const char*)ref.ptr + start * (int64_t)esz_r;  // may point in front of the vector (lead)
-                            if (!esz_r) rb.off = ref.off + start;
-                        }
-                        fill_xform(x, &rb, nullptr, ref.ptr);
-                        std::vector<VecView> sb(n_cand);
-                        for (int j = 0; j < n_cand; ++j) {
-                            sb[j] = views[(size_t)pi * stride + 1 + j];
-                            const int64_t left = sb[j].len - (int64_t)k * B;
-                            sb[j].len = left <= 0 ? 0 : (left < B ? left : B);
-                            if (sb[j].len > 0) {
-                                sb[j].ptr = (const char*)sb[j].ptr + (int64_t)k * B * (int64_t)esz;
-                                if (!esz) sb[j].off += (int64_t)k * B;
-                            }
-                        }
-                        for (int kk = 0; kk < n_packed; ++kk)
-                            fill_xform(x + 1 + kk, &sb[2 * kk], (2 * kk + 1 < n_cand) ? &sb[2 * kk + 1] : nullptr, ref.ptr);
+        if (d_lo > d_hi) return;
+        const int64_t W = d_hi - d_lo + 1, B = sp->N - (W - 1);
+        const int64_t nb = (W - 1) / sp->N2 + 1;
+        if (!(B >= 1 && nb <= MAXBINS && nb * 2 <= sp->N1 && (s_max + B - 1) / B <= kSegBlocks)) return;
+        seg = true;
+        seg_blocks = (int)((s_max + B - 1) / B);
+        seg_lo = d_lo;
+        // byte / float vectors move the pointer to the block's first sample, bit-packed ones the bit offset
+        const size_t esz = esz_of(t_dtype), esz_r = esz_of(t_ref_dt);
+        XformDesc* hx = L.xforms(hb);
+        n_xf = (size_t)n_pairs * seg_blocks * n_slots;
+        std::vector<VecView> sb(n_cand);
+        for (int pi = 0; pi < n_pairs; ++pi) {
+            const VecView& ref = views[(size_t)pi * stride];
+            for (int k = 0; k < seg_blocks; ++k) {
+                XformDesc* x = &hx[((size_t)pi * seg_blocks + k) * n_slots];
+                VecView rb = ref;  // positions [lead, len) of the block input = ref[start + n]
+                const int64_t start = (int64_t)k * B + d_lo;
+                rb.lead = start < 0 ? -start : 0;
+                rb.len = ref.len - start < sp->N ? ref.len - start : sp->N;
+                if (rb.len <= rb.lead) {
+                    rb.len = rb.lead = 0;  // nothing of the reference in this stretch
+                } else {
+                    rb.ptr = (const char*)ref.ptr + start * (int64_t)esz_r;  // may point in front of the vector (lead)
+                    if (!esz_r) rb.off = ref.off + start;
+                }
+                fill_xform(x, &rb, nullptr, ref.ptr);
+                for (int j = 0; j < n_cand; ++j) {
+                    sb[j] = views[(size_t)pi * stride + 1 + j];
+                    const int64_t left = sb[j].len - (int64_t)k * B;
+                    sb[j].len = left <= 0 ? 0 : (left < B ? left : B);
+                    if (sb[j].len > 0) {
+                        sb[j].ptr = (const char*)sb[j].ptr + (int64_t)k * B * (int64_t)esz;
+                        if (!esz) sb[j].off += (int64_t)k * B;
                     }
                 }
-                memset(&bins, 0, sizeof bins);
-                bins.n = (int)nb;
-                for (int i = 0; i < bins.n; ++i) bins.b[i] = i;
-                pruned = true;
+                for (int kk = 0; kk < n_packed; ++kk)
+                    fill_xform(x + 1 + kk, &sb[2 * kk], (2 * kk + 1 < n_cand) ? &sb[2 * kk + 1] : nullptr, ref.ptr);
             }
         }
+        memset(&bins, 0, sizeof bins);
+        bins.n = (int)nb;
+        for (int i = 0; i < bins.n; ++i) bins.b[i] = i;
+        pruned = true;
+    }
+    // One upload when the transforms run anyway (the whole block); with the run-boundary path [header, candidates], plus
+    // the vector table when no extraction was launched ahead of it -- small calls launch theirs here, behind the upload.
+    // On the copy stream (use_copy) the block passes the previous call's kernels / goes up beside this call's extraction.
+    int upload_descriptors() {
+        int rc;
+        const bool with_table = !need_extract || late_extract;
+        if ((rc = upload(0, runs_ok ? L.head_bytes(with_table ? n_rr : 0) : L.transform_bytes(n_xf), use_copy))) return rc;
+        if (late_extract) {
+            launch_extraction(n_vec, true, true);
+            HIP_TRY(hipGetLastError());
+        }
+        return FFS_OK;
+    }
+    int run_direct() {
+        FFS_BY_RESCORE_DTYPE(mixed, t_dtype, hipLaunchKernelGGL((k_direct<DT>), dim3((unsigned)n_cands), dim3(256), 0, st, dc, cres));
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_finalize_pairs, dim3((n_pairs + 255) / 256), dim3(256), 0, st, cres, pres, n_pairs, n_cand,
+                           (long long)a.filter_max_offset);
+        HIP_TRY(hipGetLastError());
+        return FFS_OK;
+    }
+
+    // ---- run-boundary path: exact correlation of every candidate whose lists are short enough, candidate and pair
+    // records written by the kernel itself; which sub-batches need the transforms instead is decided on the device
+    // (k_runs_chunk_flags) and read back as one int per sub-batch -- after everything else of the call is queued
+    unsigned long long* d_stats() const { return (unsigned long long*)((char*)p->runs_flags + flag_bytes - 16); }  // [boundaries, longest list]
+    void launch_chunk_flags(int from_estimates) {
+        hipLaunchKernelGGL(k_runs_chunk_flags, dim3((unsigned)n_chunks, runs_flag_split((long long)p->pairs_in_flight * n_cand)), dim3(256), 0, st,
+                           dc, n_pairs, n_cand, p->pairs_in_flight, d_rv, budget, p->runs_flags, d_stats(), from_estimates);
+    }
+    int read_flags_async() {
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(p->runs_flags_host, p->runs_flags, flag_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipEventRecord(p->runs_ev, st));
+        return FFS_OK;
+    }
+    int run_boundary_path() {
+        int rc;
+        if ((rc = ensure_runs(p, need_extract ? n_rr : 0, tiles_max > 1 ? n_cands * (size_t)tiles_max : 0, (size_t)n_chunks))) return rc;
+        proven = bounds_prove_budget();
+        bool skip_runs = false;  // the probe says every sub-batch is dense: transforms only, nothing extracted
+        if (probe_first && (rc = probe_dense_stream(&skip_runs))) return rc;
+        if (skip_runs) return transforms_only();
+        if ((rc = launch_flags_and_corr())) return rc;
+        mark(&ht2);
+        p->runs_calls += 1;
+        p->runs_chunks += n_chunks;
+        p->runs_last_boundaries = -1;  // (not known on the host when nothing was copied back)
+        return proven ? FFS_OK : read_back_and_decide();
+    }
+    // Lists that arrive with host-known length bounds (the rasteriser's: two entries per subtitle) settle the question on
+    // the host: within budget even at the bounds -> no flags kernel, no copy back, no wait.  A bound of RUNS_CAP or more
+    // (16-bit histogram cells, as in k_runs_chunk_flags) proves nothing: the device decides.
+    bool bounds_prove_budget() const {
+        if (need_extract || !a.vec_bound) return false;
+        for (int pi = 0; pi < n_pairs; ++pi) {
+            const size_t bq = (size_t)pi * stride;
+            if (a.vec_bound[bq] <= 0) return false;
+            for (int j = 0; j < n_cand; ++j) {
+                const CandDesc& cd = hc[(size_t)pi * n_cand + j];
+                if (a.vec_bound[bq + 1 + j] <= 0 ||
+                    (!(cd.flags & CAND_NO_LAGS) &&
+                     runs_over_budget(a.vec_bound[bq + 1 + j], a.vec_bound[bq], RUNS_CAP, RUNS_CAP, (long long)cd.d_hi - cd.d_lo + 1, cd.R, budget)))
+                    return false;
+            }
+        }
+        return true;
+    }
+    // Flags from the ESTIMATED counts against the budget (the estimate's sampling error is a few per cent of a count whose
+    // square enters: a sub-batch within that of the break-even costs the same either way).  *skip_runs: every sub-batch is dense.
+    int probe_dense_stream(bool* skip_runs) {
+        int rc;
+        HIP_TRY(hipMemsetAsync(p->runs_flags, 0, flag_bytes, st));
+        launch_chunk_flags(1);
+        if ((rc = read_flags_async())) return rc;
+        if ((rc = build_xforms())) return rc;  // (while the probe runs: needed in either case of a dense stream)
+        HIP_TRY(hipEventSynchronize(p->runs_ev));
+        *skip_runs = true;
+        for (int ch = 0; ch < n_chunks; ++ch) *skip_runs = *skip_runs && p->runs_flags_host[ch] == 1;
+        if (!*skip_runs) launch_extraction(n_vec, false, true);  // not (any more) a dense stream: the usual order from here on
+        HIP_TRY(hipGetLastError());
+        return FFS_OK;
+    }
+    int transforms_only() {
+        int rc;
+        for (int ch = 0; ch < n_chunks; ++ch) chunk_fft[ch] = 1;
+        any_fft = true;
+        p->runs_calls += 1;
+        p->runs_chunks += n_chunks;
+        p->runs_fft_chunks += n_chunks;
+        p->runs_last_boundaries = -1;
+        if ((rc = upload(L.refresh_at(), L.refresh_bytes(n_xf), false))) return rc;
+        return clear_accumulators();
+    }
+    int launch_flags_and_corr() {
+        const int* d_flags = proven ? p->runs_zero_flags : p->runs_flags;
+        int rc;
+        if (!proven) {
+            // (flags + the statistics behind them: cleared by the extraction kernel of this call unless a probe has
+            // written estimates into them since, or no extraction ran)
+            if (!flags_cleared || probe_first) HIP_TRY(hipMemsetAsync(p->runs_flags, 0, flag_bytes, st));
+            if (ml_on)
+                hipLaunchKernelGGL(k_runs_chunk_flags_ml, dim3((unsigned)n_chunks), dim3(256), 0, st, dc, n_pairs, n_cand, p->pairs_in_flight,
+                                   d_rv, (const LevelInfo*)L.level_info(db), (int)n_vec, budget, p->runs_flags, d_stats());
+            else
+                launch_chunk_flags(0);
+            if ((rc = read_flags_async())) return rc;
+        }
+        {
+            ProfSpan span(p, st, FFS_K_RUNS_CORR);
+            if (ml_on) {
+                hipLaunchKernelGGL(k_runs_corr_ml, dim3((unsigned)n_cands, (unsigned)tiles_max), dim3(RUNS_THREADS), 0, st, dc, n_cand, d_rv,
+                                   cres, p->runs_best, tiles_max, d_flags, p->pairs_in_flight, (const LevelInfo*)L.level_info(db), (int)n_vec);
+            } else {
+                // One workgroup per candidate.  The kernel can also walk several candidates of a pair in one workgroup
+                // (FFS_RUNS_SPLIT = workgroups per pair; the reference's list is then staged once for them), measured in
+                // round 6: 7 x fewer stagings, but the 7 x longer workgroups leave the chip idle longer at the end of a
+                // launch -- 0.248 against 0.238 us per pair at 4096 pairs (profiles/r06_runs_experiments.json).
+                int split = n_cand;
+                if (p->runs_split > 0) split = p->runs_split < n_cand ? p->runs_split : n_cand;
+                hipLaunchKernelGGL(k_runs_corr, dim3((unsigned)((size_t)n_pairs * split), (unsigned)tiles_max), dim3(RUNS_THREADS), 0, st, dc,
+                                   n_cand, d_rv, cres, p->runs_best, tiles_max, d_flags, p->pairs_in_flight, split);
+            }
+            if (tiles_max > 1)
+                hipLaunchKernelGGL(k_runs_pick, dim3((unsigned)((n_cands + 255) / 256)), dim3(256), 0, st, dc, (int)n_cands, n_cand,
+                                   p->runs_best, tiles_max, cres, d_flags, p->pairs_in_flight);
+        }
+        // (pairs of sub-batches that go through the transforms are finished again behind those)
+        hipLaunchKernelGGL(k_finalize_pairs, dim3((n_pairs + 255) / 256), dim3(256), 0, st, cres, pres, n_pairs, n_cand,
+                           (long long)a.filter_max_offset);
+        HIP_TRY(hipGetLastError());
+        return FFS_OK;
+    }
+    int read_back_and_decide() {
+        int rc;
+        // a stream of dense calls: the transform descriptors are built while the device extracts and decides
+        // (unless a probe has built them already)
+        if (!xf_built && p->runs_prev_fft && !lists_in && (rc = build_xforms())) return rc;
+        HIP_TRY(hipEventSynchronize(p->runs_ev));  // k_runs_corr keeps the device busy meanwhile
+        mark(&ht3);
+        bool bad = false;
+        for (int ch = 0; ch < n_chunks; ++ch) {
+            const int f = p->runs_flags_host[ch];
+            if (f == 2) bad = true;
+            if (f) chunk_fft[ch] = 1, any_fft = true;
+        }
+        memcpy(&p->runs_last_boundaries, (char*)p->runs_flags_host + flag_bytes - 16, 8);
+        // A plan-owned list filled its slot: the call is solved again with four times the room (at most twice from the
+        // default: 4096 -> 16 384 -> 32 768 entries; what the first attempt wrote is overwritten in stream order), and the
+        // plan keeps the longer stride.  Which path solves what therefore does not depend on the stride.
+        long long longest = 0;
+        memcpy(&longest, (char*)p->runs_flags_host + flag_bytes - 8, 8);
+        if (need_extract && longest >= p->runs_stride && p->runs_stride < RUNS_CAP) {
+            p->runs_stride = p->runs_stride * 4 < RUNS_CAP ? p->runs_stride * 4 : RUNS_CAP;
+            p->runs_calls -= 1;
+            p->runs_chunks -= n_chunks;
+            retry = true;
+            return FFS_OK;
+        }
+        if (bad)
+            return fail(FFS_E_INVALID, "a boundary list of the call is truncated (more entries than its block holds): "
+                        "nothing can solve it -- pass the vector as bits");
+        p->runs_prev_fft = any_fft;
+        return any_fft ? upload_for_fallback() : FFS_OK;
+    }
+    // Some sub-batches go through the transforms after all: complete and upload what those need.
+    int upload_for_fallback() {
+        int rc;
+        for (int ch = 0; ch < n_chunks; ++ch) p->runs_fft_chunks += chunk_fft[ch];
+        if (lists_in) {  // the transforms read bits: expand the list-only vectors, point the descriptors at them
+            if ((rc = expand_list_vectors(p, a, st, &expanded))) return rc;
+            xptr = expanded.data();
+            const int tm = tiles_max;
+            if ((rc = fill_all_cands(xptr))) return rc;
+            tiles_max = tm;
+        }
+        if (!xf_built && (rc = build_xforms())) return rc;  // also completes the candidate descriptors (tie margins)
+        if ((rc = upload(L.refresh_at(), L.refresh_bytes(n_xf), false))) return rc;
+        for (int ch = 0; ch < n_chunks; ++ch) {  // clean accumulators for the sub-batches that are solved again
+            if (!chunk_fft[ch]) continue;
+            const size_t c0 = (size_t)ch * p->pairs_in_flight * n_cand;
+            const size_t c1 = c0 + (size_t)p->pairs_in_flight * n_cand < n_cands ? c0 + (size_t)p->pairs_in_flight * n_cand : n_cands;
+            HIP_TRY(hipMemsetAsync(da + c0 * KNOM, 0, L.acc_bytes(c1 - c0), st));
+            HIP_TRY(hipMemsetAsync(dpb + c0, 0, (c1 - c0) * sizeof(PoolBest), st));
+        }
+        return FFS_OK;
+    }
+    int clear_accumulators() {
+        HIP_TRY(hipMemsetAsync(da, 0, L.acc_and_best_bytes(), st));
+        return FFS_OK;
+    }
+
+    // ---- transform path ----------------------------------------------------------------------------------------------
+    // The pipeline of one sub-batch on plan `q`: the call's plan, or in block-segmented mode its length-M sub-plan (3x
+    // shorter transforms, the blocks' spectrum products are added in the mid pass, last pass over one third of the data).
+    // `slot_map`: see slot_stride()/cand_slot() in ffs_kernels.h.
+    int launch_transform_chunk(ffs_plan* q, int flags, int slot_map, int seg_shift, int p0) {
+        int rc = FFS_OK;
+        const int blocks = seg ? seg_blocks : 1;
+        const int np = (n_pairs - p0) < p->pairs_in_flight ? (n_pairs - p0) : p->pairs_in_flight;
+        const int first_cand = p0 * n_cand, nx = np * blocks * n_slots;
+        const int sel_ref = 0 | (1 << 16), sel_cand = 1 | ((n_slots - 1) << 16);  // row_sel of the two first-pass launches when mixed
+        const XformDesc* dxs = dx + (size_t)p0 * blocks * n_slots;
+        const bool full3 = !pruned && col3r_ok(q);  // full last pass over radix-3 columns: k_pass_c3's (wider) tiles
+        PoolArgs qa = pa;
+        qa.half_last = (flags & HALF_LAST) ? 1 : 0;
+        {
+            ProfSpan span(p, st, FFS_K_PASS_A);
+            if (mixed) {  // the reference slot of every group in its own type, then the candidate slots in theirs
+                FFS_BY_DTYPE(t_ref_dt, rc = launch_pass_a<DT>(q, dxs, nx, n_slots, n_slots, flags, st, sel_ref));
+                if (!rc) FFS_BY_DTYPE(t_dtype, rc = launch_pass_a<DT>(q, dxs, nx, n_slots, n_slots, flags, st, sel_cand));
+            } else {
+                FFS_BY_DTYPE(t_dtype, rc = launch_pass_a<DT>(q, dxs, nx, n_slots, n_slots, flags, st));
+            }
+        }
+        if (rc) return rc;
+        {
+            ProfSpan span(p, st, FFS_K_MID);
+            rc = seg ? launch_mid_seg(q, np, n_slots, seg_blocks, flags, st) : launch_mid(q, np, n_slots, flags, st);
+        }
+        if (rc) return rc;
+        {
+            ProfSpan span(p, st, FFS_K_PASS_C);
+            rc = pruned  ? launch_pass_c_pruned<false>(q, dc, first_cand, n_cand, n_packed, slot_map, np, bins, qa, st, seg ? 1 : 0, seg_shift)
+                 : full3 ? launch_pass_c3(q, dc, first_cand, n_cand, n_packed, slot_map, np, qa.half_last, st)
+                         : launch_pass_c<0>(q, dc, first_cand, n_cand, n_packed, slot_map, np, nullptr, nullptr, qa, st);
+        }
+        if (rc) return rc;
+        HIP_TRY(hipMemsetAsync(q->xlist, 0, sizeof(int), st));
+        {
+            ProfSpan span(p, st, FFS_K_NOMINEES);
+            hipLaunchKernelGGL(k_nominees, dim3(np * n_cand), dim3(64), 0, st, q->bnom, full3 ? q->N2 / col3r_cols(q) : q->N2 / q->C, n_cand,
+                               n_packed, dc, dn, first_cand, q->xlist);
+        }
+        HIP_TRY(hipGetLastError());
+        // candidates whose nominee lists overflowed (listed by k_nominees): sweep their transforms again,
+        // exhaustively; with an empty list the few blocks of this launch exit at once
+        rc = pruned ? launch_pass_c_pruned<true>(q, dc, first_cand, n_cand, n_packed, slot_map, np, bins, qa, st, seg ? 1 : 0, seg_shift)
+                    : launch_pass_c<2>(q, dc, first_cand, n_cand, n_packed, slot_map, np, nullptr, nullptr, qa, st);
+        if (rc) return rc;
+        {
+            ProfSpan span(p, st, FFS_K_RESCORE);
+            FFS_BY_RESCORE_DTYPE(mixed, t_dtype, hipLaunchKernelGGL((k_rescore<DT>), dim3(DT == 2 ? 4 : RSEG, np * n_cand), dim3(256), 0, st,
+                                                                  dc, dn, da, first_cand));
+        }
+        HIP_TRY(hipGetLastError());
+        return FFS_OK;
+    }
+    int run_transform_chunks() {
+        if (!any_fft) return FFS_OK;
+        int rc;
+        if ((rc = ensure_workspace(p))) return rc;
+        pa.entries = p->pool_entries;
+        const int sflags = seg ? half_flags_of(p->seg, true) : 0;
+        for (int p0 = 0; p0 < n_pairs; p0 += p->pairs_in_flight) {
+            if (!chunk_fft[p0 / p->pairs_in_flight]) continue;
+            rc = seg ? launch_transform_chunk(p->seg, sflags, seg_blocks * n_slots, (int)seg_lo, p0)
+                     : launch_transform_chunk(p, hflags, n_slots, 0, p0);
+            if (rc) return rc;
+        }
+        FFS_BY_RESCORE_DTYPE(mixed, t_dtype, hipLaunchKernelGGL((k_pool_rescore<DT>), dim3(2048), dim3(256), 0, st, dc, pa.header, pa.entries, dpb));
+        hipLaunchKernelGGL(k_pool_pick, dim3(256), dim3(256), 0, st, pa.header, pa.entries, dpb);
+        return FFS_OK;
+    }
+    // candidate and pair records of everything the transforms solved (the run-boundary kernels wrote their own)
+    void finalize_range(size_t c0, size_t c1, int p0, int p1) {
+        hipLaunchKernelGGL(k_finalize_cands, dim3((unsigned)((c1 - c0 + 255) / 256)), dim3(256), 0, st, dc + c0, dn + c0, da + c0 * KNOM,
+                           cres + c0, (int)(c1 - c0), mixed ? 4 : t_dtype, pa.header, dpb + c0);
+        hipLaunchKernelGGL(k_finalize_pairs, dim3((unsigned)((p1 - p0 + 255) / 256)), dim3(256), 0, st, cres + (size_t)p0 * n_cand, pres + p0,
+                           p1 - p0, n_cand, (long long)a.filter_max_offset);
+    }
+    int finalize_transformed() {
+        if (!runs_ok) finalize_range(0, n_cands, 0, n_pairs);
+        for (int ch = 0; runs_ok && ch < n_chunks; ++ch) {
+            if (!chunk_fft[ch]) continue;
+            const int p0 = ch * p->pairs_in_flight, p1 = (p0 + p->pairs_in_flight) < n_pairs ? (p0 + p->pairs_in_flight) : n_pairs;
+            finalize_range((size_t)p0 * n_cand, (size_t)p1 * n_cand, p0, p1);
+        }
+        HIP_TRY(hipGetLastError());
+        return FFS_OK;
+    }
+    // the ONE leave_stream of a solve that reaches its end (`leave` covers the error returns)
+    int finish() {
+        leave.armed = false;
+        const int rc = leave_stream(p, st);
+        if (p->host_timing && runs_ok && !retry) {
+            const double ht4 = now_ns();
+            p->ht_vec += ht1 - ht0, p->ht_cand += ht2 - ht1, p->ht_wait += ht3 - ht2, p->ht_decide += ht4 - ht3, p->ht_total += ht4 - ht0;
+        }
+        return rc;
+    }
+};
+
+// One solve, as the order of events.  *retry: a plan-owned list filled its slot -- the plan's stride has grown, solve again.
+int solve_call(ffs_plan* p, const AlignArgs& a, bool* retry) {
+    static_assert(sizeof(CandResult) == sizeof(ffs_cand_result), "ABI struct mismatch");
+    static_assert(sizeof(PairResult) == sizeof(ffs_pair_result), "ABI struct mismatch");
+    *retry = false;
+    HIP_TRY(hipSetDevice(p->device));
+    int rc;
+    AlignCall c(p, a);
+    if ((rc = enter_stream(p, c.st))) return rc;  // left by c.finish(), or by c.leave on an error return
+    c.ht0 = c.ht1 = c.ht2 = c.ht3 = p->host_timing ? now_ns() : 0.0;
+    if ((rc = c.prepare())) return rc;
+    if (c.runs_ok) {
+        if ((rc = c.fill_runs_table())) return rc;
+        if ((rc = c.start_extraction_early())) return rc;
+    }
+    c.mark(&c.ht1);
+    if ((rc = c.fill_all_cands(a.vec_ptr))) return rc;
+    if (!c.runs_ok && (rc = c.build_xforms())) return rc;
+    if ((rc = c.upload_descriptors())) return rc;
+    if (p->direct_only) {
+        if ((rc = c.run_direct())) return rc;
+        return c.finish();
+    }
+    if ((rc = c.runs_ok ? c.run_boundary_path() : c.clear_accumulators())) return rc;
+    if (c.retry) {
+        *retry = true;
+        return c.finish();
+    }
+    if ((rc = c.run_transform_chunks())) return rc;
+    if ((rc = c.finalize_transformed())) return rc;
+    return c.finish();
+}
+
+// The driver of every ffs_align_batch* call: check once, bring the inputs into a form the solve takes, split, solve.
+int align_impl(ffs_plan* p, const AlignArgs& in) {
+    int rc;
+    if ((rc = check_align_args(p, in))) return rc;
+    if (in.n_pairs == 0) return FFS_OK;
+    AlignArgs a = in;
+    std::vector<const void*> bits_ptr;  // the rewritten pointer table, when the inputs are rewritten
+    const bool may_run = p->algo != FFS_ALGO_FFT && !p->direct_only;
+    const bool lists_in = a.dtype == FFS_DTYPE_RUNS || a.ref_dt == FFS_DTYPE_RUNS;
+    if (may_run && a.dtype == FFS_DTYPE_U8 && a.ref_dt == FFS_DTYPE_U8)
+        rc = pack_byte_vectors(p, &a, &bits_ptr);
+    else if (lists_in && !(may_run && runs_able(a.dtype) && runs_able(a.ref_dt)))
+        rc = lists_to_bits(p, &a, &bits_ptr);
+    if (rc) return rc;
+    // The plan-owned boundary lists take 256 KiB per vector: a call with more than 65 536 vectors of bit-packed
+    // two-level samples is solved as consecutive sub-calls (results land where one call would put them).
+    // (a multi-level float reference brings three threshold planes of its own)
+    const int64_t stride = 1 + a.n_cand;
+    const bool ml_split = (a.ref_dt == FFS_DTYPE_F64 || a.ref_dt == FFS_DTYPE_F32) && runs_able(a.dtype);
+    const int64_t per_pair = stride + (ml_split ? 3 : 0);
+    const int64_t max_pairs = (int64_t(1) << 16) / per_pair > 0 ? (int64_t(1) << 16) / per_pair : 1;
+    const bool split = may_run && runs_able(a.dtype) && (runs_able(a.ref_dt) || ml_split) && a.n_pairs > max_pairs;
+    const int64_t step = split ? max_pairs : a.n_pairs;
+    for (int64_t p0 = 0; p0 < a.n_pairs; p0 += step) {
+        AlignArgs s = a;
+        s.n_pairs = (int)((a.n_pairs - p0) < step ? (a.n_pairs - p0) : step);
+        s.vec_ptr += p0 * stride, s.vec_len += p0 * stride, s.vec_lo += p0 * stride, s.vec_hi += p0 * stride;
+        if (s.vec_bound) s.vec_bound += p0 * stride;
+        s.cand_out_dev += p0 * a.n_cand, s.pair_out_dev += p0;
+        // (solve_call asks again only while the stride can still grow: RUNS_CAP bounds the loop, two retries from the default)
+        bool again = true;
+        while (again)
+            if ((rc = solve_call(p, s, &again))) return rc;
     }
     return FFS_OK;
-    };
-    if (!runs_ok && (rc = build_xforms())) return rc;
-    // one upload when the transforms run anyway; with the run-boundary path [header, candidates] (+ the vector table
-    // when no extraction was launched ahead of it)
-    if (runs_ok && late_extract && use_copy) {  // the whole block on the copy stream: it passes the previous call's kernels
-        if (p->half_used[p->cur_half]) HIP_TRY(hipStreamWaitEvent(p->copy_stream, p->half_done[p->cur_half], 0));
-        HIP_TRY(hipMemcpyAsync(db, hb, o_rv + n_rr * sizeof(RunsRef), hipMemcpyHostToDevice, p->copy_stream));
-        HIP_TRY(hipEventRecord(p->upload_done, p->copy_stream));
-        HIP_TRY(hipStreamWaitEvent(st, p->upload_done, 0));
-    } else if (runs_ok && (!need_extract || late_extract)) {
-        HIP_TRY(hipMemcpyAsync(db, hb, o_rv + n_rr * sizeof(RunsRef), hipMemcpyHostToDevice, st));
-    } else if (runs_ok && use_copy) {  // (beside the extraction of this call)
-        HIP_TRY(hipMemcpyAsync(db, hb, o_rv, hipMemcpyHostToDevice, p->copy_stream));
-        HIP_TRY(hipEventRecord(p->upload_done, p->copy_stream));
-        HIP_TRY(hipStreamWaitEvent(st, p->upload_done, 0));
-    } else {
-        HIP_TRY(hipMemcpyAsync(db, hb, runs_ok ? o_rv : o_xf + n_xf * sizeof(XformDesc), hipMemcpyHostToDevice, st));
-    }
-    leave.armed = true;
-    if (!(runs_ok && use_copy))
-        HIP_TRY(hipEventRecord(p->upload_done, st));  // (recorded again should a fallback upload more: the next call waits for the latest)
-    if (late_extract) {
-        ProfSpan span(p, st, FFS_K_RUNS_EXTRACT);
-        runs_extract_launch((const RunsRef*)(db + o_rv), n_vec, false, st, p->runs_flags, (int)(flag_bytes / sizeof(int)), (int)stride, (int)n_vec);
-        flags_cleared = true;
-        HIP_TRY(hipGetLastError());
-    }
-    const CandDesc* dc = (const CandDesc*)(db + o_cand);
-    const XformDesc* dx = (const XformDesc*)(db + o_xf);
-    NomList* dn = (NomList*)(db + o_nom);
-    RescoreAcc* da = (RescoreAcc*)(db + o_acc);
-    PoolBest* dpb = (PoolBest*)(db + o_pbest);
-    PoolArgs pa{dn, (PoolHeader*)(db + o_pool), nullptr, dpb,  // .entries: once the transform workspace exists
-                (n_pairs + p->pairs_in_flight - 1) / p->pairs_in_flight};
-    pa.half_last = (hflags & HALF_LAST) ? 1 : 0;
-    CandResult* cres = (CandResult*)cand_out_dev;
-    PairResult* pres = (PairResult*)pair_out_dev;
-    const int dt = t_dtype;  // (the transform kernels' element type of the candidates)
-
-    std::vector<char> chunk_fft((size_t)n_chunks, runs_ok ? 0 : 1);
-    bool any_fft = !runs_ok;
-    if (p->direct_only) {
-        FFS_BY_RESCORE_DTYPE(mixed, dt, hipLaunchKernelGGL((k_direct<DT>), dim3((unsigned)n_cands), dim3(256), 0, st, dc, cres));
-        HIP_TRY(hipGetLastError());
-    } else {
-        // ---- run-boundary path: exact correlation of every candidate whose lists are short enough, candidate and pair
-        // records written by the kernel itself; which sub-batches need the transforms instead is decided on the device
-        // (k_runs_chunk_flags) and read back as one int per sub-batch -- after everything else of the call is queued
-        if (runs_ok) {
-            if ((rc = ensure_runs(p, need_extract ? n_rr : 0, tiles_max > 1 ? n_cands * (size_t)tiles_max : 0, (size_t)n_chunks)))
-                return rc;
-            const long long budget = p->algo == FFS_ALGO_RUNS ? INT64_MAX / 4
-                                     : p->runs_budget >= 0 ? p->runs_budget
-                                                           : kRunsBudgetPerPoint * (long long)p->N * (n_cand + 1) / (2 * n_cand);
-            // Lists that arrive with host-known length bounds (the rasteriser's: two entries per subtitle) settle the
-            // question on the host: within budget even at the bounds -> no flags kernel, no copy back, no wait.  A bound of
-            // RUNS_CAP or more (16-bit histogram cells, as in k_runs_chunk_flags) proves nothing: the device decides.
-            bool proven = !need_extract && vec_bound != nullptr;
-            for (int pi = 0; proven && pi < n_pairs; ++pi) {
-                const size_t bq = (size_t)pi * stride;
-                if (vec_bound[bq] <= 0) proven = false;
-                for (int j = 0; proven && j < n_cand; ++j) {
-                    const CandDesc& cd = hc[(size_t)pi * n_cand + j];
-                    if (vec_bound[bq + 1 + j] <= 0 ||
-                        (!(cd.flags & CAND_NO_LAGS) &&
-                         runs_over_budget(vec_bound[bq + 1 + j], vec_bound[bq], RUNS_CAP, RUNS_CAP, (long long)cd.d_hi - cd.d_lo + 1, cd.R, budget)))
-                        proven = false;
-                }
-            }
-            unsigned long long* d_stats = (unsigned long long*)((char*)p->runs_flags + flag_bytes - 16);  // [boundaries, longest list]
-            const int* d_flags = proven ? p->runs_zero_flags : p->runs_flags;
-            bool skip_runs = false;  // the probe says every sub-batch is dense: transforms only, nothing extracted
-            if (probe_first) {
-                // flags from the ESTIMATED counts against the budget (the estimate's sampling error is a few per cent of a
-                // count whose square enters: a sub-batch within that of the break-even costs the same either way)
-                HIP_TRY(hipMemsetAsync(p->runs_flags, 0, flag_bytes, st));
-                hipLaunchKernelGGL(k_runs_chunk_flags, dim3((unsigned)n_chunks, runs_flag_split((long long)p->pairs_in_flight * n_cand)), dim3(256), 0, st, dc, n_pairs, n_cand,
-                                   p->pairs_in_flight, (const RunsRef*)(db + o_rv), budget, p->runs_flags, d_stats, 1);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipMemcpyAsync(p->runs_flags_host, p->runs_flags, flag_bytes, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipEventRecord(p->runs_ev, st));
-                if ((rc = build_xforms())) return rc;  // (while the probe runs: needed in either case of a dense stream)
-                HIP_TRY(hipEventSynchronize(p->runs_ev));
-                skip_runs = true;
-                for (int ch = 0; ch < n_chunks; ++ch) skip_runs = skip_runs && p->runs_flags_host[ch] == 1;
-                if (!skip_runs) {  // not (any more) a dense stream: the usual order from here on
-                    ProfSpan span(p, st, FFS_K_RUNS_EXTRACT);
-                    runs_extract_launch((const RunsRef*)(db + o_rv), n_vec, false, st, nullptr, 0, (int)stride, (int)n_vec);
-                }
-                HIP_TRY(hipGetLastError());
-            }
-            if (skip_runs) {
-                for (int ch = 0; ch < n_chunks; ++ch) chunk_fft[ch] = 1;
-                any_fft = true;
-                p->runs_calls += 1;
-                p->runs_chunks += n_chunks;
-                p->runs_fft_chunks += n_chunks;
-                p->runs_last_boundaries = -1;
-                HIP_TRY(hipMemcpyAsync(db + o_cand, hb + o_cand, o_xf + n_xf * sizeof(XformDesc) - o_cand, hipMemcpyHostToDevice, st));
-                HIP_TRY(hipMemsetAsync(da, 0, n_cands * KNOM * sizeof(RescoreAcc) + n_cands * sizeof(PoolBest), st));
-                HIP_TRY(hipEventRecord(p->upload_done, st));
-            } else {
-            if (!proven) {
-                // (flags + the statistics behind them: cleared by the extraction kernel of this call unless a probe has
-                // written estimates into them since, or no extraction ran)
-                if (!flags_cleared || probe_first) HIP_TRY(hipMemsetAsync(p->runs_flags, 0, flag_bytes, st));
-                if (ml_on)
-                    hipLaunchKernelGGL(k_runs_chunk_flags_ml, dim3((unsigned)n_chunks), dim3(256), 0, st, dc, n_pairs, n_cand,
-                                       p->pairs_in_flight, (const RunsRef*)(db + o_rv), (const LevelInfo*)(db + o_li), (int)n_vec, budget,
-                                       p->runs_flags, d_stats);
-                else
-                hipLaunchKernelGGL(k_runs_chunk_flags, dim3((unsigned)n_chunks, runs_flag_split((long long)p->pairs_in_flight * n_cand)), dim3(256), 0, st, dc, n_pairs, n_cand,
-                                   p->pairs_in_flight, (const RunsRef*)(db + o_rv), budget, p->runs_flags, d_stats, 0);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipMemcpyAsync(p->runs_flags_host, p->runs_flags, flag_bytes, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipEventRecord(p->runs_ev, st));
-            }
-            {
-                ProfSpan span(p, st, FFS_K_RUNS_CORR);
-                if (ml_on)
-                    hipLaunchKernelGGL(k_runs_corr_ml, dim3((unsigned)n_cands, (unsigned)tiles_max), dim3(RUNS_THREADS), 0, st, dc, n_cand,
-                                       (const RunsRef*)(db + o_rv), cres, p->runs_best, tiles_max, d_flags, p->pairs_in_flight,
-                                       (const LevelInfo*)(db + o_li), (int)n_vec);
-                else {
-                    // One workgroup per candidate.  The kernel can also walk several candidates of a pair in one workgroup
-                    // (FFS_RUNS_SPLIT = workgroups per pair; the reference's list is then staged once for them), measured in
-                    // round 6: 7 x fewer stagings, but the 7 x longer workgroups leave the chip idle longer at the end of a
-                    // launch -- 0.248 against 0.238 us per pair at 4096 pairs (profiles/r06_runs_experiments.json).
-                    int split = n_cand;
-                    if (p->runs_split > 0) split = p->runs_split < n_cand ? p->runs_split : n_cand;
-                    hipLaunchKernelGGL(k_runs_corr, dim3((unsigned)((size_t)n_pairs * split), (unsigned)tiles_max), dim3(RUNS_THREADS), 0, st,
-                                       dc, n_cand, (const RunsRef*)(db + o_rv), cres, p->runs_best, tiles_max, d_flags, p->pairs_in_flight,
-                                       split);
-                }
-                if (tiles_max > 1)
-                    hipLaunchKernelGGL(k_runs_pick, dim3((unsigned)((n_cands + 255) / 256)), dim3(256), 0, st, dc, (int)n_cands, n_cand,
-                                       p->runs_best, tiles_max, cres, d_flags, p->pairs_in_flight);
-            }
-            // (pairs of sub-batches that go through the transforms are finished again behind those)
-            hipLaunchKernelGGL(k_finalize_pairs, dim3((n_pairs + 255) / 256), dim3(256), 0, st, cres, pres, n_pairs, n_cand,
-                               (long long)filter_max_offset);
-            HIP_TRY(hipGetLastError());
-            if (p->host_timing) ht2 = now_ns();
-            p->runs_calls += 1;
-            p->runs_chunks += n_chunks;
-            p->runs_last_boundaries = -1;  // (not known on the host when nothing was copied back)
-            if (!proven) {
-                // a stream of dense calls: the transform descriptors are built while the device extracts and decides
-                bool built = probe_first;  // (a probe has built them already)
-                if (!built && p->runs_prev_fft && !lists_in) {
-                    if ((rc = build_xforms())) return rc;
-                    built = true;
-                }
-                HIP_TRY(hipEventSynchronize(p->runs_ev));  // k_runs_corr keeps the device busy meanwhile
-                if (p->host_timing) ht3 = now_ns();
-                bool bad = false;
-                for (int ch = 0; ch < n_chunks; ++ch) {
-                    const int f = p->runs_flags_host[ch];
-                    if (f == 2) bad = true;
-                    if (f) chunk_fft[ch] = 1, any_fft = true;
-                }
-                memcpy(&p->runs_last_boundaries, (char*)p->runs_flags_host + flag_bytes - 16, 8);
-                {
-                    // A plan-owned list filled its slot: the call is solved again with four times the room (at most twice:
-                    // 4096 -> 16 384 -> 32 768 entries; what the first attempt wrote is overwritten in stream order), and the
-                    // plan keeps the longer stride.  Which path solves what therefore does not depend on the stride.
-                    long long longest = 0;
-                    memcpy(&longest, (char*)p->runs_flags_host + flag_bytes - 8, 8);
-                    if (need_extract && longest >= p->runs_stride && p->runs_stride < RUNS_CAP) {
-                        p->runs_stride = p->runs_stride * 4 < RUNS_CAP ? p->runs_stride * 4 : RUNS_CAP;
-                        p->runs_calls -= 1;
-                        p->runs_chunks -= n_chunks;
-                        leave.armed = false;
-                        if ((rc = leave_stream(p, st))) return rc;
-                        return align_impl(p, n_pairs, n_cand, ref_dt, dtype, vec_ptr, vec_len, vec_lo, vec_hi, vec_bound, max_offset_samples,
-                                          filter_max_offset, cand_out_dev, pair_out_dev, hip_stream);
-                    }
-                }
-                if (bad)
-                    return fail(FFS_E_INVALID, "a boundary list of the call is truncated (more entries than its block holds): "
-                                "nothing can solve it -- pass the vector as bits");
-                p->runs_prev_fft = any_fft;
-                if (any_fft) {
-                    for (int ch = 0; ch < n_chunks; ++ch) p->runs_fft_chunks += chunk_fft[ch];
-                    if (lists_in) {  // the transforms read bits: expand the list-only vectors, point the descriptors at them
-                        if ((rc = expand_lists(&expanded))) return rc;
-                        xptr = expanded.data();
-                        int tm = tiles_max;
-                        if ((rc = fill_all_cands(xptr, t_ref_dt, t_dtype))) return rc;
-                        tiles_max = tm;
-                    }
-                    if (!built && (rc = build_xforms())) return rc;  // also completes the candidate descriptors (tie margins)
-                    HIP_TRY(hipMemcpyAsync(db + o_cand, hb + o_cand, o_xf + n_xf * sizeof(XformDesc) - o_cand, hipMemcpyHostToDevice, st));
-                    for (int ch = 0; ch < n_chunks; ++ch) {  // clean accumulators for the sub-batches that are solved again
-                        if (!chunk_fft[ch]) continue;
-                        const size_t c0 = (size_t)ch * p->pairs_in_flight * n_cand;
-                        const size_t c1 = c0 + (size_t)p->pairs_in_flight * n_cand < n_cands ? c0 + (size_t)p->pairs_in_flight * n_cand : n_cands;
-                        HIP_TRY(hipMemsetAsync(da + c0 * KNOM, 0, (c1 - c0) * KNOM * sizeof(RescoreAcc), st));
-                        HIP_TRY(hipMemsetAsync(dpb + c0, 0, (c1 - c0) * sizeof(PoolBest), st));
-                    }
-                    HIP_TRY(hipEventRecord(p->upload_done, st));
-                }
-            }
-            }  // !skip_runs
-        } else {
-            HIP_TRY(hipMemsetAsync(da, 0, n_cands * KNOM * sizeof(RescoreAcc) + n_cands * sizeof(PoolBest), st));
-        }
-        if (any_fft) {
-            if ((rc = ensure_workspace(p))) return rc;
-            pa.entries = p->pool_entries;
-        }
-        const int tiles = p->N2 / p->C;
-        const bool full3 = !pruned && col3r_ok(p);  // full last pass over radix-3 columns: k_pass_c3's (wider) tiles
-        for (int p0 = 0; seg && p0 < n_pairs; p0 += p->pairs_in_flight) {
-            if (!chunk_fft[p0 / p->pairs_in_flight]) continue;
-            // block-segmented pipeline on the length-M sub-plan: 3x shorter transforms, the blocks'
-            // spectrum products are added in the mid pass, last pass over one third of the data
-            ffs_plan* sp = p->seg;
-            const int sflags = half_flags_of(sp, true);
-            PoolArgs spa = pa;
-            spa.half_last = (sflags & HALF_LAST) ? 1 : 0;
-            const int np = (n_pairs - p0) < p->pairs_in_flight ? (n_pairs - p0) : p->pairs_in_flight;
-            const int first_cand = p0 * n_cand;
-            const int tiles_s = sp->N2 / sp->C;
-            const XformDesc* dxs = dx + (size_t)p0 * seg_blocks * n_slots;
-            {
-                ProfSpan span(p, st, FFS_K_PASS_A);
-                if (mixed) {  // the reference slot of every group in its own type, then the candidate slots in theirs
-                    FFS_BY_DTYPE(t_ref_dt, rc = launch_pass_a<DT>(sp, dxs, np * seg_blocks * n_slots, n_slots, n_slots, sflags, st, sel_ref));
-                    if (!rc) FFS_BY_DTYPE(t_dtype, rc = launch_pass_a<DT>(sp, dxs, np * seg_blocks * n_slots, n_slots, n_slots, sflags, st, sel_cand));
-                } else {
-                    FFS_BY_DTYPE(t_dtype, rc = launch_pass_a<DT>(sp, dxs, np * seg_blocks * n_slots, n_slots, n_slots, sflags, st));
-                }
-            }
-            if (rc) return rc;
-            {
-                ProfSpan span(p, st, FFS_K_MID);
-                rc = launch_mid_seg(sp, np, n_slots, seg_blocks, sflags, st);
-            }
-            if (rc) return rc;
-            {
-                ProfSpan span(p, st, FFS_K_PASS_C);
-                rc = launch_pass_c_pruned<false>(sp, dc, first_cand, n_cand, n_packed, seg_blocks * n_slots, np, bins, spa, st, 1,
-                                                 (int)seg_lo);
-            }
-            if (rc) return rc;
-            HIP_TRY(hipMemsetAsync(sp->xlist, 0, sizeof(int), st));
-            {
-                ProfSpan span(p, st, FFS_K_NOMINEES);
-                hipLaunchKernelGGL(k_nominees, dim3(np * n_cand), dim3(64), 0, st, sp->bnom, tiles_s, n_cand, n_packed, dc, dn,
-                                   first_cand, sp->xlist);
-            }
-            HIP_TRY(hipGetLastError());
-            if ((rc = launch_pass_c_pruned<true>(sp, dc, first_cand, n_cand, n_packed, seg_blocks * n_slots, np, bins, spa, st, 1,
-                                                 (int)seg_lo)))
-                return rc;
-            {
-                ProfSpan span(p, st, FFS_K_RESCORE);
-                FFS_BY_RESCORE_DTYPE(mixed, t_dtype, hipLaunchKernelGGL((k_rescore<DT>), dim3(DT == 2 ? 4 : RSEG, np * n_cand), dim3(256), 0,
-                                                                      st, dc, dn, da, first_cand));
-            }
-            HIP_TRY(hipGetLastError());
-        }
-        for (int p0 = 0; !seg && any_fft && p0 < n_pairs; p0 += p->pairs_in_flight) {
-            if (!chunk_fft[p0 / p->pairs_in_flight]) continue;
-            const int np = (n_pairs - p0) < p->pairs_in_flight ? (n_pairs - p0) : p->pairs_in_flight;
-            const int first_cand = p0 * n_cand;
-            {
-                ProfSpan sp(p, st, FFS_K_PASS_A);
-                if (mixed) {
-                    FFS_BY_DTYPE(t_ref_dt, rc = launch_pass_a<DT>(p, dx + (size_t)p0 * xf_per_pair, np * xf_per_pair, xf_per_pair,
-                                                                n_slots, hflags, st, sel_ref));
-                    if (!rc) FFS_BY_DTYPE(t_dtype, rc = launch_pass_a<DT>(p, dx + (size_t)p0 * xf_per_pair, np * xf_per_pair,
-                                                                        xf_per_pair, n_slots, hflags, st, sel_cand));
-                } else {
-                    FFS_BY_DTYPE(t_dtype, rc = launch_pass_a<DT>(p, dx + (size_t)p0 * xf_per_pair, np * xf_per_pair, xf_per_pair,
-                                                               n_slots, hflags, st));
-                }
-            }
-            if (rc) return rc;
-            {
-                ProfSpan sp(p, st, FFS_K_MID);
-                rc = launch_mid(p, np, n_slots, hflags, st);
-            }
-            if (rc) return rc;
-            {
-                ProfSpan sp(p, st, FFS_K_PASS_C);
-                rc = pruned ? launch_pass_c_pruned<false>(p, dc, first_cand, n_cand, n_packed, slot_map, np, bins, pa, st)
-                     : full3 ? launch_pass_c3(p, dc, first_cand, n_cand, n_packed, slot_map, np, pa.half_last, st)
-                             : launch_pass_c<0>(p, dc, first_cand, n_cand, n_packed, slot_map, np, nullptr, nullptr, pa, st);
-            }
-            if (rc) return rc;
-            HIP_TRY(hipMemsetAsync(p->xlist, 0, sizeof(int), st));
-            {
-                ProfSpan sp(p, st, FFS_K_NOMINEES);
-                hipLaunchKernelGGL(k_nominees, dim3(np * n_cand), dim3(64), 0, st, p->bnom, full3 ? p->N2 / col3r_cols(p) : tiles,
-                                   n_cand, n_packed, dc, dn, first_cand, p->xlist);
-            }
-            HIP_TRY(hipGetLastError());
-            // candidates whose nominee lists overflowed (listed by k_nominees): sweep their transforms again,
-            // exhaustively; with an empty list the few blocks of this launch exit at once
-            rc = pruned ? launch_pass_c_pruned<true>(p, dc, first_cand, n_cand, n_packed, slot_map, np, bins, pa, st)
-                        : launch_pass_c<2>(p, dc, first_cand, n_cand, n_packed, slot_map, np, nullptr, nullptr, pa, st);
-            if (rc) return rc;
-            {
-                ProfSpan sp(p, st, FFS_K_RESCORE);
-                FFS_BY_RESCORE_DTYPE(mixed, t_dtype, hipLaunchKernelGGL((k_rescore<DT>), dim3(DT == 2 ? 4 : RSEG, np * n_cand), dim3(256), 0,
-                                                                      st, dc, dn, da, first_cand));
-            }
-            HIP_TRY(hipGetLastError());
-        }
-        if (any_fft) {
-            FFS_BY_RESCORE_DTYPE(mixed, t_dtype, hipLaunchKernelGGL((k_pool_rescore<DT>), dim3(2048), dim3(256), 0, st, dc, pa.header, pa.entries, dpb));
-            hipLaunchKernelGGL(k_pool_pick, dim3(256), dim3(256), 0, st, pa.header, pa.entries, dpb);
-        }
-        // candidate and pair records of everything the transforms solved (the run-boundary kernels wrote their own)
-        auto finalize_range = [&](size_t c0, size_t c1, int p0, int p1) {
-            hipLaunchKernelGGL(k_finalize_cands, dim3((unsigned)((c1 - c0 + 255) / 256)), dim3(256), 0, st, dc + c0, dn + c0,
-                               da + c0 * KNOM, cres + c0, (int)(c1 - c0), mixed ? 4 : t_dtype, pa.header, dpb + c0);
-            hipLaunchKernelGGL(k_finalize_pairs, dim3((unsigned)((p1 - p0 + 255) / 256)), dim3(256), 0, st, cres + (size_t)p0 * n_cand,
-                               pres + p0, p1 - p0, n_cand, (long long)filter_max_offset);
-        };
-        if (!runs_ok) {
-            finalize_range(0, n_cands, 0, n_pairs);
-        } else {
-            for (int ch = 0; ch < n_chunks; ++ch) {
-                if (!chunk_fft[ch]) continue;
-                const int p0 = ch * p->pairs_in_flight, p1 = (p0 + p->pairs_in_flight) < n_pairs ? (p0 + p->pairs_in_flight) : n_pairs;
-                finalize_range((size_t)p0 * n_cand, (size_t)p1 * n_cand, p0, p1);
-            }
-        }
-        HIP_TRY(hipGetLastError());
-    }
-    if (p->direct_only) {
-        hipLaunchKernelGGL(k_finalize_pairs, dim3((n_pairs + 255) / 256), dim3(256), 0, st, cres, pres, n_pairs, n_cand,
-                           (long long)filter_max_offset);
-        HIP_TRY(hipGetLastError());
-    }
-    leave.armed = false;
-    rc = leave_stream(p, st);
-    if (p->host_timing && runs_ok) {
-        const double ht4 = now_ns();
-        p->ht_vec += ht1 - ht0, p->ht_cand += ht2 - ht1, p->ht_wait += ht3 - ht2, p->ht_decide += ht4 - ht3, p->ht_total += ht4 - ht0;
-    }
-    return rc;
 }
+
+}  // namespace
+
+extern "C" {
 
 int ffs_align_batch(ffs_plan* p, int n_pairs, int n_cand, int dtype, const void* const* vec_ptr,
                     const int64_t* vec_len, const double* vec_lo, const double* vec_hi, int64_t max_offset_samples,
                     int64_t filter_max_offset, ffs_cand_result* cand_out_dev, ffs_pair_result* pair_out_dev,
                     void* hip_stream) {
-    return align_impl(p, n_pairs, n_cand, dtype, dtype, vec_ptr, vec_len, vec_lo, vec_hi, nullptr, max_offset_samples,
-                      filter_max_offset, cand_out_dev, pair_out_dev, hip_stream);
+    return align_impl(p, AlignArgs{n_pairs, n_cand, dtype, dtype, vec_ptr, vec_len, vec_lo, vec_hi, nullptr, max_offset_samples,
+                                   filter_max_offset, cand_out_dev, pair_out_dev, hip_stream});
 }
 
 int ffs_align_batch_runs(ffs_plan* p, int n_pairs, int n_cand, const int32_t* vec_dtype, const void* const* vec_ptr,
@@ -2103,8 +2236,8 @@ int ffs_align_batch_runs(ffs_plan* p, int n_pairs, int n_cand, const int32_t* ve
         if (vec_dtype[i] != (i % stride == 0 ? ref_dt : cand_dt))
             return fail(FFS_E_INVALID, "vector %zu has element type %d: within one call all references must share one type "
                         "and all candidates one type (split the call)", i, (int)vec_dtype[i]);
-    return align_impl(p, n_pairs, n_cand, ref_dt, cand_dt, vec_ptr, vec_len, vec_lo, vec_hi, vec_max_boundaries, max_offset_samples,
-                      filter_max_offset, cand_out_dev, pair_out_dev, hip_stream);
+    return align_impl(p, AlignArgs{n_pairs, n_cand, ref_dt, cand_dt, vec_ptr, vec_len, vec_lo, vec_hi, vec_max_boundaries,
+                                   max_offset_samples, filter_max_offset, cand_out_dev, pair_out_dev, hip_stream});
 }
 
 int ffs_align_batch_typed(ffs_plan* p, int n_pairs, int n_cand, const int32_t* vec_dtype, const void* const* vec_ptr,

@@ -406,3 +406,105 @@ def test_byte_inputs_are_packed_on_the_device_and_take_the_same_path(headline):
     assert st == (1, 3, 0) and st_c == (0, 0, 0)
     _same_records(a, b)
     _same_records(a, c)
+
+
+# ---- error returns and list growth leave the plan as it should be: records against tests/exact_reference.py ------------
+def _pack_bits(torch, probs):
+    """Bit-packed DeviceBatch of host problems [(ref01, [cand01 ...])]; levels (0, 1) everywhere."""
+    from ffsubsync_amd import _native
+    from ffsubsync_amd.batch import DeviceBatch, _layout
+
+    vecs = [v for ref, cands in probs for v in [ref] + list(cands)]
+    lens = np.array([v.size for v in vecs], np.int64).reshape(len(probs), -1)
+    offs, total = _layout(lens, (lens + 31) // 32 * 4)
+    host = np.zeros(total, np.uint8)
+    for v, o in zip(vecs, offs.ravel()):
+        pk = np.packbits(np.asarray(v) != 0, bitorder="little")
+        host[o:o + pk.size] = pk
+    return DeviceBatch(torch.from_numpy(host).cuda(), offs, lens, np.zeros(lens.shape), np.ones(lens.shape), _native.FFS_DTYPE_U1)
+
+
+def _exact_records(probs, max_off):
+    import exact_reference as er
+
+    return [er.solve(ref, cands, (0.0, 1.0), [(0.0, 1.0)] * len(cands), max_off, max_off) for ref, cands in probs]
+
+
+def _equal_exact(out, want):
+    """Every candidate and pair record equals the exact reference's, scores bit for bit (an exact zero of either sign)."""
+    cres, pres = out
+    assert len(pres) == len(want)
+    bad = []
+    for i, (recs, win) in enumerate(want):
+        for j, r in enumerate(recs):
+            c = cres[i, j]
+            if (int(c["offset"]), float(c["score"]), int(c["flags"])) != (r["offset"], r["score"], r["flags"]):
+                bad.append((i, j, (int(c["offset"]), float(c["score"]), int(c["flags"])), r))
+        p = pres[i]
+        if (int(p["best_cand"]), int(p["offset"]), float(p["score"])) != (win["best_cand"], win["offset"], win["score"]):
+            bad.append((i, "pair", (int(p["best_cand"]), int(p["offset"]), float(p["score"])), win))
+    assert not bad, (len(bad), bad[:4])
+
+
+def _sparse(rng, n, mean_run=40):
+    runs = rng.geometric(1.0 / mean_run, size=2 * n // mean_run + 8)
+    return np.repeat(np.arange(runs.size) % 2 == rng.randint(2), runs)[:n]
+
+
+def test_error_after_early_extraction_leaves_the_plan_usable(torch):
+    """A call of more than 4096 candidates queues its vector table and the extraction BEFORE the candidate descriptors are
+    built.  When building them then refuses a candidate (the last one is too long for the plan: FFS_E_TOO_LONG), the call
+    returns the error with that work queued -- and the plan must be as usable as before: the same 600 pairs with a valid
+    last candidate, then a small call (one upload, extraction behind it), both equal to the exact reference."""
+    from ffsubsync_amd import _native, batch
+
+    rng = np.random.RandomState(5)
+    R, n_fft, n_cand = 3000, 8192, 7
+    base = []
+    for _ in range(12):  # twelve distinct problems, repeated: 600 pairs x 7 = 4200 candidates
+        ref = _sparse(rng, R, 50)  # (short lists: ~60 x ~130 boundaries, far inside the coincidence budget of the plan)
+        base.append((ref, [np.roll(ref, int(s)) ^ (_sparse(rng, R, 300) & _sparse(rng, R, 60)) for s in rng.randint(-900, 900, n_cand)]))
+    probs = [base[i % 12] for i in range(600)]
+    too_long = next(s for s in range(R, 3 * n_fft) if _native.plan_length(R, s, None) > n_fft)
+    assert too_long < 1 << 20
+    refused = probs[:-1] + [(probs[-1][0], probs[-1][1][:-1] + [_sparse(rng, too_long)])]
+    want12 = _exact_records(base, None)
+    al = batch.BatchAligner(n_fft, n_cand, None, pairs_in_flight=64, algorithm="auto")
+    try:
+        with pytest.raises(_native.NativeError) as err:
+            al.solve(_pack_bits(torch, refused))
+        assert err.value.code == -4  # FFS_E_TOO_LONG
+        _equal_exact(al.solve(_pack_bits(torch, probs)), [want12[i % 12] for i in range(600)])
+        _equal_exact(al.solve(_pack_bits(torch, probs[:4])), want12[:4])
+        assert al.plan.runs_stats() == (2, 10 + 1, 0)  # both on the run-boundary path; the refused call counts nowhere
+    finally:
+        al.close()
+
+
+def test_stride_growth_keeps_the_vector_capacity(torch):
+    """A small call whose lists outgrow the plan's stride (vectors that alternate every sample: 9000 boundaries against
+    4096 entries) makes the plan reallocate its lists at the longer stride -- for as many vectors as it had room for: the
+    128-vector call that came before it runs again without another reallocation.  Records of all three calls equal the
+    exact reference."""
+    from ffsubsync_amd import batch
+
+    rng = np.random.RandomState(6)
+    n = 9000
+    wide = []
+    for _ in range(64):
+        ref = _sparse(rng, n, 60)
+        wide.append((ref, [np.roll(ref, int(rng.randint(-2000, 2000))) ^ (rng.rand(n) < 0.01)]))
+    alt = np.arange(n + 8) % 2 == 1
+    dense = [(alt[:n], [alt[k:k + n - 3 * k]]) for k in range(4)]
+    want_wide, want_dense = _exact_records(wide, None), _exact_records(dense, None)
+    db_wide, db_dense = _pack_bits(torch, wide), _pack_bits(torch, dense)
+    al = batch.BatchAligner(db_wide.required_fft_length(None), 1, None, pairs_in_flight=64, algorithm="runs")
+    try:
+        _equal_exact(al.solve(db_wide), want_wide)
+        _equal_exact(al.solve(db_dense), want_dense)
+        assert al.plan.runs_boundaries_last_call() > 8 * 2 * 4096  # every list of the call was longer than the first stride
+        after_dense = al.plan.workspace_bytes
+        _equal_exact(al.solve(db_wide), want_wide)
+        assert al.plan.workspace_bytes == after_dense
+    finally:
+        al.close()
