@@ -73,6 +73,7 @@ SMOOTH_SEGMENT_DTYPE = np.dtype(
 )
 SMOOTH_SEGMENT_BYTES = 32
 assert SMOOTH_SEGMENT_DTYPE.itemsize == SMOOTH_SEGMENT_BYTES
+SMOOTH_MAX_STATES = 33 * 33  # (2 * SMOOTH_MAX_RADIUS + 1) ** 2
 SMOOTH_BLOCK_BYTES = 33 * 33 * 9 + 36  # smooth workspace per block of a pair in flight: line scores, back-pointers, tables
 # ffs_break_refine (include/ffsubsync_amd.h; static size 88 bytes)
 REFINE_MAX_RADIUS = 131072  # FFS_REFINE_MAX_RADIUS
@@ -145,6 +146,7 @@ EXPORTED_SYMBOLS = (
     "ffs_drift_range_plan_destroy",
     "ffs_drift_range_plan_workspace_bytes",
     "ffs_align_drift_range_batch",
+    "ffs_align_drift_range_smooth_batch",
     "ffs_quality_plan_create",
     "ffs_quality_plan_destroy",
     "ffs_quality_plan_workspace_bytes",
@@ -386,6 +388,13 @@ def load():
                                                     c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p,
                                                     c.c_void_p, c.c_double, c.c_int, c.c_double, c.c_void_p, c.c_void_p,
                                                     c.c_void_p, c.c_void_p, c.c_void_p]
+        lib.ffs_align_drift_range_smooth_batch.restype = c.c_int
+        lib.ffs_align_drift_range_smooth_batch.argtypes = [c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p,
+                                                           c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                                                           c.c_int64, c.c_void_p, c.c_void_p, c.c_double, c.c_int,
+                                                           c.c_double, c.c_int, c.c_int, c.c_double, c.c_void_p,
+                                                           c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                                                           c.c_void_p, c.c_void_p, c.c_void_p]
         lib.ffs_quality_plan_create.restype = c.c_int
         lib.ffs_quality_plan_create.argtypes = [c.c_int, c.c_int, c.c_int64, c.c_int64, c.POINTER(c.c_void_p)]
         lib.ffs_quality_plan_destroy.restype = c.c_int
@@ -1022,6 +1031,12 @@ class SplitPlan(_SidePlan):
                                               n_breaks_out.data_ptr(), self._stream(stream)))
 
 
+def range_band_row(max_step: int, knot_blocks: int, radius: int) -> int:
+    """uint16 cells of one block's band row in the range smooth fit (``range_band_row`` of
+    csrc/ffs_drift_range_smooth.h)."""
+    return int(max_step) * ((3 * int(knot_blocks) + 1) // 2) + 2 * int(radius) + 1
+
+
 MAX_DRIFT_STEP = 7  # DRIFT_MAX_STEP (csrc/ffs_drift.h): the 4-bit code holds STAY, 14 moves and JUMP
 
 
@@ -1150,6 +1165,36 @@ class DriftRangePlan(_SidePlan):
                                                    float(split_penalty), int(max_step), float(step_cost),
                                                    offsets_out.data_ptr(), scores_out.data_ptr(), jumps_out.data_ptr(),
                                                    totals_out.data_ptr(), self._stream(stream)))
+
+    def smooth_bytes(self) -> int:
+        """What the first ``smooth`` call adds to ``workspace_bytes``: ``SMOOTH_BLOCK_BYTES`` of fit tables and a band
+        row of ``range_band_row(max_step_cap, 256, 16)`` uint16 counts per block (``max_blocks`` rounded up to 16) and
+        pair in flight, the back-pointers and the interval counts each padded to 64 bytes."""
+        n, mb = self.pairs_in_flight, -(-self.max_blocks // 16) * 16
+        pad64 = lambda x: -(-x // 64) * 64
+        return (n * mb * (SMOOTH_MAX_STATES * 8 + 36 + 2 * range_band_row(self.max_step_cap, SMOOTH_MAX_KNOT_BLOCKS,
+                                                                          SMOOTH_MAX_RADIUS))
+                + pad64(n * mb * SMOOTH_MAX_STATES) + pad64(n * 4))
+
+    def smooth(self, ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, block_samples: int, lag_lo,
+               lag_hi, split_penalty: float, max_step: int, step_cost: float, knot_blocks: int, radius: int,
+               bend_cost: float, offsets_out, scores_out, jumps_out, totals_out, smooth_out, knot_out, segments_out,
+               n_segments_out, stream: Optional[int] = None) -> None:
+        """``ffs_align_drift_range_smooth_batch``: ``align``'s outputs plus int32 smooth offsets and uint8 knot flags of
+        n_pairs * max_b entries, a CUDA tensor of n_pairs * max_b * 32 bytes of segment records and an int32 one of
+        n_pairs segment counts (asynchronous)."""
+        n, ptrs, _bufs = _pair_buffers(ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, lag_lo, lag_hi)
+        if (n_segments_out.numel() < n or smooth_out.numel() < offsets_out.numel() or knot_out.numel() < offsets_out.numel()
+                or segments_out.numel() * segments_out.element_size() < offsets_out.numel() * SMOOTH_SEGMENT_BYTES):
+            raise ValueError("output buffer too small")
+        check(self.lib.ffs_align_drift_range_smooth_batch(self.handle, n, *ptrs[:8], int(block_samples), *ptrs[8:],
+                                                          float(split_penalty), int(max_step), float(step_cost),
+                                                          int(knot_blocks), int(radius), float(bend_cost),
+                                                          offsets_out.data_ptr(), scores_out.data_ptr(),
+                                                          jumps_out.data_ptr(), totals_out.data_ptr(),
+                                                          smooth_out.data_ptr(), knot_out.data_ptr(),
+                                                          segments_out.data_ptr(), n_segments_out.data_ptr(),
+                                                          self._stream(stream)))
 
 
 class QualityPlan(_SidePlan):

@@ -36,6 +36,7 @@
 #include "ffs_drift_report.h"
 #include "ffs_drift_smooth.h"
 #include "ffs_drift_range.h"
+#include "ffs_drift_range_smooth.h"
 
 using namespace ffsa;
 
@@ -1012,7 +1013,7 @@ void fill_xform(XformDesc* x, const VecView* a, const VecView* b, const void* sa
 extern "C" {
 
 const char* ffs_last_error(void) { return g_err.c_str(); }
-int ffs_version(void) { return 380; }
+int ffs_version(void) { return 390; }
 
 int64_t ffs_fft_length(int64_t ref_len, int64_t sub_len) {
     if (ref_len <= 0 || sub_len <= 0) return 0;
@@ -3878,27 +3879,47 @@ struct DriftSmoothArgs {  // the smooth fit of ffs_align_drift_smooth_batch
     int32_t* n_segments;
 };
 
-// the smooth workspace of a plan, made by its first smooth call: segment / interval tables, line scores, back-pointers
-int drift_smooth_workspace(ffs_drift_plan* plan) {
-    if (plan->smooth_mem) return FFS_OK;
-    const int64_t n = plan->pairs_in_flight, mb = split_align_up(plan->max_blocks, 16);
+// the smooth workspace of a plan, made by its first smooth call: segment / interval tables, line scores, back-pointers,
+// then `extra_bytes` more for the caller (*extra points at them)
+int smooth_workspace(int64_t pairs_in_flight, int64_t max_blocks, void** mem, ffsa::SmoothWs* sw, int64_t* bytes_out,
+                     int64_t extra_bytes, char** extra) {
+    if (*mem) return FFS_OK;
+    const int64_t n = pairs_in_flight, mb = split_align_up(max_blocks, 16);
     const int64_t b_t = n * mb * ffsa::SMOOTH_MAX_STATES * 8, b_back = split_align_up(n * mb * ffsa::SMOOTH_MAX_STATES, 64),
                   b_seg = n * mb * (int64_t)sizeof(ffsa::SmoothSeg), b_iv = n * mb * (int64_t)sizeof(ffsa::SmoothInt),
                   b_of = n * mb * 4, b_n = split_align_up(n * 4, 64);
-    const int64_t bytes = b_t + b_back + b_seg + b_iv + b_of + b_n;
-    if (hipMalloc(&plan->smooth_mem, bytes) != hipSuccess) {
-        plan->smooth_mem = nullptr;
+    const int64_t tables = b_t + b_back + b_seg + b_iv + b_of + b_n, bytes = tables + extra_bytes;
+    if (hipMalloc(mem, bytes) != hipSuccess) {
+        *mem = nullptr;
         return fail(FFS_E_NOMEM, "drift plan: %lld smooth workspace bytes", (long long)bytes);
     }
-    char* w = (char*)plan->smooth_mem;
-    plan->sw.T = (double*)w;
-    plan->sw.back = (uint8_t*)(w + b_t);
-    plan->sw.seg = (ffsa::SmoothSeg*)(w + b_t + b_back);
-    plan->sw.iv = (ffsa::SmoothInt*)(w + b_t + b_back + b_seg);
-    plan->sw.seg_of = (int32_t*)(w + b_t + b_back + b_seg + b_iv);
-    plan->sw.n_int = (int32_t*)(w + b_t + b_back + b_seg + b_iv + b_of);
-    plan->sw.stride = mb;
-    plan->smooth_bytes = bytes;
+    char* w = (char*)*mem;
+    sw->T = (double*)w;
+    sw->back = (uint8_t*)(w + b_t);
+    sw->seg = (ffsa::SmoothSeg*)(w + b_t + b_back);
+    sw->iv = (ffsa::SmoothInt*)(w + b_t + b_back + b_seg);
+    sw->seg_of = (int32_t*)(w + b_t + b_back + b_seg + b_iv);
+    sw->n_int = (int32_t*)(w + b_t + b_back + b_seg + b_iv + b_of);
+    sw->stride = mb;
+    if (extra) *extra = w + tables;
+    *bytes_out = bytes;
+    return FFS_OK;
+}
+int drift_smooth_workspace(ffs_drift_plan* plan) {
+    return smooth_workspace(plan->pairs_in_flight, plan->max_blocks, &plan->smooth_mem, &plan->sw, &plan->smooth_bytes, 0,
+                            nullptr);
+}
+
+// the parameter and output checks of a smooth fit
+int check_smooth_args(const DriftSmoothArgs& fit) {
+    if (fit.knot_blocks < 1 || fit.knot_blocks > ffsa::SMOOTH_MAX_KNOT_BLOCKS)
+        return fail(FFS_E_INVALID, "knot_blocks=%d outside [1, %d]", fit.knot_blocks, ffsa::SMOOTH_MAX_KNOT_BLOCKS);
+    if (fit.radius < 0 || fit.radius > ffsa::SMOOTH_MAX_RADIUS)
+        return fail(FFS_E_INVALID, "radius=%d outside [0, %d]", fit.radius, ffsa::SMOOTH_MAX_RADIUS);
+    if (!(fit.bend_cost >= 0.0) || !std::isfinite(fit.bend_cost)) return fail(FFS_E_INVALID, "bend_cost must be finite and >= 0");
+    if (!fit.smooth_offset || !fit.knot || !fit.out || !fit.n_segments) return fail(FFS_E_INVALID, "null argument");
+    if (((uintptr_t)fit.smooth_offset & 3) || ((uintptr_t)fit.out & 7) || ((uintptr_t)fit.n_segments & 3))
+        return fail(FFS_E_INVALID, "misaligned smooth outputs");
     return FFS_OK;
 }
 
@@ -3928,17 +3949,8 @@ int drift_batch(ffs_drift_plan* plan, int n_pairs, const Pairs& a, int64_t block
         if (!rep->out || !rep->n_segments) return fail(FFS_E_INVALID, "null argument");
         if (((uintptr_t)rep->out & 7) || ((uintptr_t)rep->n_segments & 3)) return fail(FFS_E_INVALID, "misaligned report outputs");
     }
-    if (fit) {
-        if (fit->knot_blocks < 1 || fit->knot_blocks > ffsa::SMOOTH_MAX_KNOT_BLOCKS)
-            return fail(FFS_E_INVALID, "knot_blocks=%d outside [1, %d]", fit->knot_blocks, ffsa::SMOOTH_MAX_KNOT_BLOCKS);
-        if (fit->radius < 0 || fit->radius > ffsa::SMOOTH_MAX_RADIUS)
-            return fail(FFS_E_INVALID, "radius=%d outside [0, %d]", fit->radius, ffsa::SMOOTH_MAX_RADIUS);
-        if (!(fit->bend_cost >= 0.0) || !std::isfinite(fit->bend_cost))
-            return fail(FFS_E_INVALID, "bend_cost must be finite and >= 0");
-        if (!fit->smooth_offset || !fit->knot || !fit->out || !fit->n_segments) return fail(FFS_E_INVALID, "null argument");
-        if (((uintptr_t)fit->smooth_offset & 3) || ((uintptr_t)fit->out & 7) || ((uintptr_t)fit->n_segments & 3))
-            return fail(FFS_E_INVALID, "misaligned smooth outputs");
-    }
+    if (fit)
+        if (int rc = check_smooth_args(*fit)) return rc;
     int64_t max_b = 0;
     for (int p = 0; p < n_pairs; ++p) {
         if (int rc = a.check(p)) return rc;
@@ -4079,6 +4091,10 @@ struct ffs_drift_range_plan : PlanCore {
     ffsa::RangeWs ws;           // stay = the code planes (max_step_cap's count), V = two rows per slot
     int32_t* pre;               // [slot][2 * pw]: s, then r
     DescStaging desc;           // SplitDesc[pairs_in_flight], then RangeLag[pairs_in_flight]
+    void* smooth_mem;           // smooth calls only, made by the first: the tables of ffsa::SmoothWs, then the band rows
+    ffsa::SmoothWs sw;
+    uint16_t* band;             // [slot][sw.stride][range_band_row(max_step_cap, 256, 16)]
+    int64_t smooth_bytes;
 };
 
 int ffs_drift_range_plan_create(int device, int pairs_in_flight, int64_t max_blocks, int64_t max_lags, int64_t max_samples,
@@ -4134,19 +4150,21 @@ int ffs_drift_range_plan_destroy(ffs_drift_range_plan* plan) {
     if (!plan) return FFS_OK;
     plan->close();
     plan->desc.release();
+    if (plan->smooth_mem) (void)hipFree(plan->smooth_mem);
     delete plan;
     return FFS_OK;
 }
 
-int64_t ffs_drift_range_plan_workspace_bytes(const ffs_drift_range_plan* plan) { return plan ? plan->work_bytes : 0; }
+int64_t ffs_drift_range_plan_workspace_bytes(const ffs_drift_range_plan* plan) {
+    return plan ? plan->work_bytes + plan->smooth_bytes : 0;
+}
 
-int ffs_align_drift_range_batch(ffs_drift_range_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
-                                const double* ref_lo, const double* ref_hi, const void* const* sub_ptr,
-                                const int64_t* sub_len, const double* sub_lo, const double* sub_hi, int64_t block_samples,
-                                const int64_t* lag_lo, const int64_t* lag_hi, double split_penalty, int max_step,
-                                double step_cost, int32_t* block_offset_out_dev, double* block_score_out_dev,
-                                uint8_t* block_jump_out_dev, double* total_out_dev, void* hip_stream) {
-    const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
+namespace {
+// ffs_align_drift_range_batch; with `fit` the smooth fit after each sub-batch's scores
+int drift_range_batch(ffs_drift_range_plan* plan, int n_pairs, const Pairs& a, int64_t block_samples, const int64_t* lag_lo,
+                      const int64_t* lag_hi, double split_penalty, int max_step, double step_cost,
+                      int32_t* block_offset_out_dev, double* block_score_out_dev, uint8_t* block_jump_out_dev,
+                      double* total_out_dev, const DriftSmoothArgs* fit, void* hip_stream) {
     if (!plan) return fail(FFS_E_INVALID, "null drift range plan");
     if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
     if (n_pairs == 0) return FFS_OK;
@@ -4161,12 +4179,24 @@ int ffs_align_drift_range_batch(ffs_drift_range_plan* plan, int n_pairs, const v
     if (max_step < 0 || max_step > plan->max_step_cap)
         return fail(FFS_E_INVALID, "max_step=%d outside [0, %d] (the plan's max_step_cap)", max_step, plan->max_step_cap);
     if (!(step_cost >= 0.0) || !std::isfinite(step_cost)) return fail(FFS_E_INVALID, "step_cost must be finite and >= 0");
+    if (fit)
+        if (int rc = check_smooth_args(*fit)) return rc;
     int64_t max_b = 0;
     if (int rc = range_limits_check(plan->max_samples, plan->max_blocks, plan->max_lags, n_pairs, a, K, lag_lo, lag_hi,
                                     &max_b))
         return rc;
     hipStream_t st = (hipStream_t)hip_stream;
     if (int rc = plan->begin(st)) return rc;
+    ffsa::RangeBand band{nullptr, 0};
+    if (fit) {  // the first smooth call: the fit's tables and band rows wide enough for every later call
+        const int64_t cap_row = ffsa::range_band_row(plan->max_step_cap, ffsa::SMOOTH_MAX_KNOT_BLOCKS, ffsa::SMOOTH_MAX_RADIUS);
+        const int64_t b_band = (int64_t)plan->pairs_in_flight * split_align_up(plan->max_blocks, 16) * cap_row * 2;
+        if (int rc = smooth_workspace(plan->pairs_in_flight, plan->max_blocks, &plan->smooth_mem, &plan->sw,
+                                      &plan->smooth_bytes, b_band, (char**)&plan->band))
+            return rc;
+        band.cells = plan->band;
+        band.row = ffsa::range_band_row(max_step, fit->knot_blocks, fit->radius);
+    }
     const int planes = ffsa::drift_range_planes(max_step);
     const int64_t pre_slot = split_align_up(2 * plan->pw, 64);
     const int pif = plan->pairs_in_flight;
@@ -4199,9 +4229,55 @@ int ffs_align_drift_range_batch(ffs_drift_range_plan* plan, int n_pairs, const v
         hipLaunchKernelGGL(ffsa::k_range_scores, dim3((unsigned)((max_b + waves - 1) / waves), (unsigned)np),
                            dim3(ffsa::RANGE_SCORE_THREADS), 0, st, dd, dl, (int)K, max_b, block_offset_out_dev,
                            block_score_out_dev);
+        if (fit) {
+            ffsa::SmoothSegment* out = (ffsa::SmoothSegment*)fit->out;
+            hipLaunchKernelGGL(ffsa::k_smooth_intervals, dim3(np), dim3(ffsa::SMOOTH_INT_THREADS), 0, st, dd, plan->sw, (int)K,
+                               fit->knot_blocks, max_b, (const int32_t*)block_offset_out_dev,
+                               (const uint8_t*)block_jump_out_dev, fit->smooth_offset, fit->knot, out, fit->n_segments);
+            hipLaunchKernelGGL(ffsa::k_range_band_counts, dim3((unsigned)chunk_b, (unsigned)np), dim3(ffsa::RBAND_THREADS), 0,
+                               st, dd, plan->sw, band, (int)K, fit->knot_blocks, fit->radius, max_b,
+                               (const int32_t*)block_offset_out_dev);
+            hipLaunchKernelGGL(ffsa::k_range_line_sums, dim3((unsigned)(np * ffsa::SMOOTH_LINE_GROUPS)),
+                               dim3(ffsa::SMOOTH_LINE_THREADS), 0, st, dd, dl, plan->sw, band, (int)K, fit->radius, max_b,
+                               (const int32_t*)block_offset_out_dev);
+            hipLaunchKernelGGL(ffsa::k_drift_knot_dp, dim3((unsigned)(np * ffsa::SMOOTH_DP_GROUPS)),
+                               dim3(ffsa::SMOOTH_DP_THREADS), 0, st, dd, plan->sw, fit->knot_blocks, fit->radius,
+                               fit->bend_cost, max_b, (const int32_t*)block_offset_out_dev,
+                               (const int32_t*)fit->n_segments, fit->smooth_offset, out);
+        }
         HIP_TRY(hipGetLastError());
     }
     return plan->end(st);
+}
+}  // namespace
+
+int ffs_align_drift_range_batch(ffs_drift_range_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
+                                const double* ref_lo, const double* ref_hi, const void* const* sub_ptr,
+                                const int64_t* sub_len, const double* sub_lo, const double* sub_hi, int64_t block_samples,
+                                const int64_t* lag_lo, const int64_t* lag_hi, double split_penalty, int max_step,
+                                double step_cost, int32_t* block_offset_out_dev, double* block_score_out_dev,
+                                uint8_t* block_jump_out_dev, double* total_out_dev, void* hip_stream) {
+    const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
+    return drift_range_batch(plan, n_pairs, a, block_samples, lag_lo, lag_hi, split_penalty, max_step, step_cost,
+                             block_offset_out_dev, block_score_out_dev, block_jump_out_dev, total_out_dev, nullptr,
+                             hip_stream);
+}
+
+int ffs_align_drift_range_smooth_batch(ffs_drift_range_plan* plan, int n_pairs, const void* const* ref_ptr,
+                                       const int64_t* ref_len, const double* ref_lo, const double* ref_hi,
+                                       const void* const* sub_ptr, const int64_t* sub_len, const double* sub_lo,
+                                       const double* sub_hi, int64_t block_samples, const int64_t* lag_lo,
+                                       const int64_t* lag_hi, double split_penalty, int max_step, double step_cost,
+                                       int knot_blocks, int radius, double bend_cost, int32_t* block_offset_out_dev,
+                                       double* block_score_out_dev, uint8_t* block_jump_out_dev, double* total_out_dev,
+                                       int32_t* smooth_offset_out_dev, uint8_t* knot_out_dev,
+                                       ffs_smooth_segment* segment_out_dev, int32_t* n_segments_out_dev, void* hip_stream) {
+    const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
+    const DriftSmoothArgs fit{knot_blocks, radius, bend_cost, smooth_offset_out_dev, knot_out_dev, segment_out_dev,
+                              n_segments_out_dev};
+    return drift_range_batch(plan, n_pairs, a, block_samples, lag_lo, lag_hi, split_penalty, max_step, step_cost,
+                             block_offset_out_dev, block_score_out_dev, block_jump_out_dev, total_out_dev, &fit,
+                             hip_stream);
 }
 
 /* ---- alignment quality report (csrc/ffs_quality.h) ------------------------------------------------------------- */

@@ -879,6 +879,42 @@ int ffs_align_drift_smooth_batch(ffs_drift_plan* plan, int n_pairs, const void* 
                                  int32_t* smooth_offset_out_dev, uint8_t* knot_out_dev, ffs_smooth_segment* segment_out_dev,
                                  int32_t* n_segments_out_dev, void* hip_stream);
 
+/* ---- smooth drift fit over any lag range (csrc/ffs_drift_range_smooth.h) --------------------------------------------
+ * Replaces: nothing in the reference.  The contract below is pinned against the numpy model
+ * tests/drift_range_smooth_model.py, bit for bit.
+ *
+ * ffs_align_drift_range_batch (same arguments, same four outputs bit for bit) followed, in the same sub-batch, by
+ * ffs_align_drift_smooth_batch's fit of every segment, with ONE change: a knot candidate c_i = o_{k_i} + u is valid
+ * where lag_lo_p <= c_i <= lag_hi_p (the pair's range) instead of -W + 1 <= c_i <= W.  Segments, knot blocks, digital
+ * lines, the uint32 sums of ov / n11 / n1x / nx1 scored once, 0.0 for an empty overlap, -inf for an invalid end, the
+ * bend cost, the Viterbi pass, its tie rule and fit_total are as stated there; the block terms are the range path's
+ * (absent samples; a block whose lag leaves it no overlap contributes nothing).  At [-W+1, W] all eight outputs equal
+ * ffs_align_drift_smooth_batch's bit for bit.  knot_blocks in [1, FFS_SMOOTH_MAX_KNOT_BLOCKS], radius in
+ * [0, FFS_SMOOTH_MAX_RADIUS], bend_cost finite and >= 0, max_step <= the plan's max_step_cap.  Outputs as
+ * ffs_align_drift_smooth_batch (smooth offsets are lags in samples, 0 past B_p; records past the segment count are
+ * zero).  Nothing is read back: the call is asynchronous.
+ *
+ * The range solve stores no (block, lag) counts; the fit counts n11 again in a band around the path: per block
+ * max_step * ceil(3 knot_blocks / 2) + 2 radius + 1 uint16 cells (81 at max_step 2, knot_blocks 16, radius 16).  The
+ * first smooth call on a plan adds pairs_in_flight * max_blocks' (max_blocks rounded up to 16) *
+ * (9837 + 2 * (max_step_cap * 384 + 33)) bytes -- ffs_align_drift_smooth_batch's tables and band rows for the plan's
+ * max_step_cap at knot_blocks 256, radius 16, so later calls need nothing more -- plus fewer than 128 bytes of padding:
+ * 8.1 MB per pair at 2 h, K = 1024 and max_step_cap 2 (704 blocks; 10.8 MB at max_step_cap 7) against 403 MB of codes
+ * and rows.  ffs_drift_range_plan_workspace_bytes counts it from then on; plans that never call it keep their size, and
+ * drift results after it stay bit-identical.
+ * FFS_E_INVALID / FFS_E_EMPTY as ffs_align_drift_range_batch, and FFS_E_INVALID for knot_blocks, radius or bend_cost
+ * outside the ranges above or a null / misaligned output (smooth offsets and counts 4-byte, records 8-byte aligned); all
+ * before any launch, the outputs untouched. */
+int ffs_align_drift_range_smooth_batch(ffs_drift_range_plan* plan, int n_pairs, const void* const* ref_ptr,
+                                       const int64_t* ref_len, const double* ref_lo, const double* ref_hi,
+                                       const void* const* sub_ptr, const int64_t* sub_len, const double* sub_lo,
+                                       const double* sub_hi, int64_t block_samples, const int64_t* lag_lo,
+                                       const int64_t* lag_hi, double split_penalty, int max_step, double step_cost,
+                                       int knot_blocks, int radius, double bend_cost, int32_t* block_offset_out_dev,
+                                       double* block_score_out_dev, uint8_t* block_jump_out_dev, double* total_out_dev,
+                                       int32_t* smooth_offset_out_dev, uint8_t* knot_out_dev,
+                                       ffs_smooth_segment* segment_out_dev, int32_t* n_segments_out_dev, void* hip_stream);
+
 /* Thread-local description of the last error returned on this thread ("" if none). */
 const char* ffs_last_error(void);
 
