@@ -1923,8 +1923,9 @@ FFS_DEV void bit_counts(const void* sp, const void* rp, int R, int d, int a, int
         const unsigned sh = (unsigned)bit0 & 31u;
         unsigned rw[5];
         if (jr >= 0 && jr + 4 <= wr_max && w0 > w_first && w0 + 3 < w_last) {
-            // interior: four whole s-words (one 16-byte load; vectors start on 64-byte boundaries) against five r-words
-            // (a 4-byte aligned 16-byte load + one dword), no edge masks
+            // interior: four whole s-words against five r-words, no edge masks.  Both 16-byte loads need no more than the
+            // 4-byte alignment FFS_DTYPE_U1 grants: w0 starts at any word of the overlap and the r side is shifted by the
+            // lag, so they are memcpy loads (global_load_dwordx4 takes any dword address), never uint4 dereferences
             uint4 sv, rv4;
             __builtin_memcpy(&sv, s + w0, 16);
             __builtin_memcpy(&rv4, r + jr, 16);

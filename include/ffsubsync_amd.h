@@ -58,6 +58,17 @@ extern "C" {
                            `len`); e[k].ones_before = upper-level samples in front of it; e[n] = (INT32_MAX, ones).
                            Producers: ffs_rasterize_batch_runs, ffs_runs_from_bits.  A list with n >= cap is truncated
                            and unusable.  ffs_runs_list_bytes(cap) = 16 + 8 * cap. */
+/* What every entry point keeps to, for vectors of all these types (pinned by tests/test_gpu_layout.py on vectors at
+ * exactly these alignments, with 0xFF -- ones, NaNs -- in every byte around them and other vectors right behind them):
+ *   - alignment: FFS_DTYPE_U8 pointers need none, FFS_DTYPE_U1 and FFS_DTYPE_F32 4 bytes, FFS_DTYPE_F64 and
+ *     `ffs_runs_list` blocks 8 bytes; nothing assumes more (no 16- or 64-byte alignment, no padding behind a vector);
+ *   - the bits of the last FFS_DTYPE_U1 word at positions >= len, and all bytes outside a vector, are never
+ *     interpreted: they may hold anything, the neighbouring vector's samples included (a kernel may load them, inside
+ *     the words the vector covers, but no result depends on them);
+ *   - the entries of a list block behind the sentinel e[n] are never read;
+ *   - inputs are never written;
+ *   - outputs are written only inside their documented extent: ceil(len/32) words of a bit-packed output (its unused
+ *     last bits are written as 0), ffs_runs_list_bytes(cap) bytes of a list block, n records of a record array. */
 
 /* result flags */
 #define FFS_FLAG_EMPTY_WINDOW 1 /* every lag masked: score=-inf, offset=N-1-S (aligners.py:45-48) */
