@@ -131,6 +131,7 @@ EXPORTED_SYMBOLS = (
     "ffs_align_split_batch",
     "ffs_align_split_report_batch",
     "ffs_split_refine_batch",
+    "ffs_drift_refine_batch",
     "ffs_split_range_plan_create",
     "ffs_split_range_plan_destroy",
     "ffs_split_range_plan_workspace_bytes",
@@ -337,6 +338,10 @@ def load():
         lib.ffs_split_refine_batch.argtypes = [c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
                                                c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p,
                                                c.c_int64, c.c_double, c.c_void_p, c.c_void_p, c.c_void_p]
+        lib.ffs_drift_refine_batch.restype = c.c_int
+        lib.ffs_drift_refine_batch.argtypes = [c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                                               c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p,
+                                               c.c_void_p, c.c_int64, c.c_double, c.c_void_p, c.c_void_p, c.c_void_p]
         lib.ffs_split_range_plan_create.restype = c.c_int
         lib.ffs_split_range_plan_create.argtypes = [c.c_int, c.c_int, c.c_int64, c.c_int64, c.c_int64,
                                                     c.POINTER(c.c_void_p)]
@@ -1029,6 +1034,20 @@ class SplitPlan(_SidePlan):
         check(self.lib.ffs_split_refine_batch(self.handle, n, *ptrs, int(block_samples), offsets.data_ptr(),
                                               int(radius_samples), float(unmatched_margin), refine_out.data_ptr(),
                                               n_breaks_out.data_ptr(), self._stream(stream)))
+
+    def drift_refine(self, ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, block_samples: int,
+                     offsets, jumps, radius_samples: int, unmatched_margin: float, refine_out, n_jumps_out,
+                     stream: Optional[int] = None) -> None:
+        """``ffs_drift_refine_batch``: ``refine`` along a drift path -- the int32 CUDA tensor of n_pairs * max_b block
+        offsets and the uint8 one of as many jump flags (as ``DriftPlan.align`` or a smooth fit wrote them) into break
+        records at the jumps and an int32 tensor of n_pairs jump counts (asynchronous)."""
+        n, ptrs, _bufs = _pair_buffers(ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi)
+        if (n_jumps_out.numel() < n or jumps.numel() < offsets.numel()
+                or refine_out.numel() * refine_out.element_size() < offsets.numel() * BREAK_REFINE_BYTES):
+            raise ValueError("buffer too small")
+        check(self.lib.ffs_drift_refine_batch(self.handle, n, *ptrs, int(block_samples), offsets.data_ptr(),
+                                              jumps.data_ptr(), int(radius_samples), float(unmatched_margin),
+                                              refine_out.data_ptr(), n_jumps_out.data_ptr(), self._stream(stream)))
 
 
 def range_band_row(max_step: int, knot_blocks: int, radius: int) -> int:

@@ -30,6 +30,7 @@
 #include "ffs_match.h"
 #include "ffs_split_report.h"
 #include "ffs_split_refine.h"
+#include "ffs_drift_refine.h"
 #include "ffs_split_range.h"
 #include "ffs_cut_report.h"
 #include "ffs_drift.h"
@@ -3402,16 +3403,19 @@ int ffs_align_split_report_batch(ffs_split_plan* plan, int n_pairs, const void* 
 
 /* ---- sample-exact break refinement (csrc/ffs_split_refine.h) -------------------------------------------------- */
 
-int ffs_split_refine_batch(ffs_split_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
-                           const double* ref_lo, const double* ref_hi, const void* const* sub_ptr, const int64_t* sub_len,
-                           const double* sub_lo, const double* sub_hi, int64_t block_samples,
-                           const int32_t* block_offset_dev, int64_t radius_samples, double unmatched_margin,
-                           ffs_break_refine* out_dev, int32_t* n_breaks_out_dev, void* hip_stream) {
-    const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
+namespace {
+// ffs_split_refine_batch (the breaks are the changes of offset, two constant lags per break), and with `drift`
+// ffs_drift_refine_batch (the breaks are the jump flags of block_jump_dev, the lags follow the path)
+int refine_batch(ffs_split_plan* plan, int n_pairs, const Pairs& a, int64_t block_samples,
+                 const int32_t* block_offset_dev, bool drift, const uint8_t* block_jump_dev, int64_t radius_samples,
+                 double unmatched_margin, ffs_break_refine* out_dev, int32_t* n_breaks_out_dev, void* hip_stream) {
+    const int64_t* ref_len = a.ref_len;
+    const int64_t* sub_len = a.sub_len;
     if (!plan) return fail(FFS_E_INVALID, "null split plan");
     if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
     if (n_pairs == 0) return FFS_OK;
-    if (a.any_null() || !block_offset_dev || !out_dev || !n_breaks_out_dev) return fail(FFS_E_INVALID, "null argument");
+    if (a.any_null() || !block_offset_dev || !out_dev || !n_breaks_out_dev || (drift && !block_jump_dev))
+        return fail(FFS_E_INVALID, "null argument");
     if (((uintptr_t)block_offset_dev & 3) || ((uintptr_t)out_dev & 7) || ((uintptr_t)n_breaks_out_dev & 3))
         return fail(FFS_E_INVALID, "misaligned block offsets or refine outputs");
     const int64_t K = block_samples, Rr = radius_samples;
@@ -3448,8 +3452,8 @@ int ffs_split_refine_batch(ffs_split_plan* plan, int n_pairs, const void* const*
             const int p = p0 + i;
             const Levels v = a.levels(p);
             ffsa::RefineDesc& d = hd[i];
-            d.r = (const uint32_t*)ref_ptr[p];
-            d.s = (const uint32_t*)sub_ptr[p];
+            d.r = (const uint32_t*)a.ref_ptr[p];
+            d.s = (const uint32_t*)a.sub_ptr[p];
             d.R = ref_len[p];
             d.S = sub_len[p];
             d.r0 = v.r0;
@@ -3465,16 +3469,50 @@ int ffs_split_refine_batch(ffs_split_plan* plan, int n_pairs, const void* const*
             chunk_b = std::max(chunk_b, (d.S + K - 1) / K);
         }
         if (int rc = plan->refine.upload(sizeof(ffsa::RefineDesc) * np, st)) return rc;
-        hipLaunchKernelGGL(ffsa::k_refine_breaks, dim3(np), dim3(ffsa::REFINE_TABLE_THREADS), 0, st, dd, (int)K, max_b, Rr,
-                           unmatched_margin, block_offset_dev, (ffsa::BreakRefine*)out_dev, n_breaks_out_dev);
+        if (drift)
+            hipLaunchKernelGGL(ffsa::k_drift_refine_jumps, dim3(np), dim3(ffsa::REFINE_TABLE_THREADS), 0, st, dd, (int)K,
+                               max_b, Rr, unmatched_margin, block_offset_dev, block_jump_dev, (ffsa::BreakRefine*)out_dev,
+                               n_breaks_out_dev);
+        else
+            hipLaunchKernelGGL(ffsa::k_refine_breaks, dim3(np), dim3(ffsa::REFINE_TABLE_THREADS), 0, st, dd, (int)K, max_b,
+                               Rr, unmatched_margin, block_offset_dev, (ffsa::BreakRefine*)out_dev, n_breaks_out_dev);
         if (chunk_b > 1) {  // one workgroup per possible break (at most one per block after the first)
             const int n_slots = (int)(chunk_b - 1);
-            hipLaunchKernelGGL(ffsa::k_refine_cut, dim3((unsigned)((int64_t)n_slots * np)), dim3(ffsa::REFINE_THREADS), 0,
-                               st, dd, n_slots, max_b, single, (const int32_t*)n_breaks_out_dev, (ffsa::BreakRefine*)out_dev);
+            const dim3 grid((unsigned)((int64_t)n_slots * np));
+            if (drift)
+                hipLaunchKernelGGL(ffsa::k_drift_refine_cut, grid, dim3(ffsa::REFINE_THREADS), 0, st, dd, n_slots, (int)K,
+                                   max_b, single, block_offset_dev, (const int32_t*)n_breaks_out_dev,
+                                   (ffsa::BreakRefine*)out_dev);
+            else
+                hipLaunchKernelGGL(ffsa::k_refine_cut, grid, dim3(ffsa::REFINE_THREADS), 0, st, dd, n_slots, max_b, single,
+                                   (const int32_t*)n_breaks_out_dev, (ffsa::BreakRefine*)out_dev);
         }
         HIP_TRY(hipGetLastError());
     }
     return plan->end(st);
+}
+}  // namespace
+
+int ffs_split_refine_batch(ffs_split_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
+                           const double* ref_lo, const double* ref_hi, const void* const* sub_ptr, const int64_t* sub_len,
+                           const double* sub_lo, const double* sub_hi, int64_t block_samples,
+                           const int32_t* block_offset_dev, int64_t radius_samples, double unmatched_margin,
+                           ffs_break_refine* out_dev, int32_t* n_breaks_out_dev, void* hip_stream) {
+    const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
+    return refine_batch(plan, n_pairs, a, block_samples, block_offset_dev, false, nullptr, radius_samples, unmatched_margin,
+                        out_dev, n_breaks_out_dev, hip_stream);
+}
+
+/* ---- sample-exact jumps of a drift solve (csrc/ffs_drift_refine.h) --------------------------------------------- */
+
+int ffs_drift_refine_batch(ffs_split_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
+                           const double* ref_lo, const double* ref_hi, const void* const* sub_ptr, const int64_t* sub_len,
+                           const double* sub_lo, const double* sub_hi, int64_t block_samples,
+                           const int32_t* block_offset_dev, const uint8_t* block_jump_dev, int64_t radius_samples,
+                           double unmatched_margin, ffs_break_refine* out_dev, int32_t* n_jumps_out_dev, void* hip_stream) {
+    const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
+    return refine_batch(plan, n_pairs, a, block_samples, block_offset_dev, true, block_jump_dev, radius_samples,
+                        unmatched_margin, out_dev, n_jumps_out_dev, hip_stream);
 }
 
 /* ---- split-aware alignment over a lag range (csrc/ffs_split_range.h) ------------------------------------------- */

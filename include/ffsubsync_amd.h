@@ -641,6 +641,34 @@ int ffs_split_refine_batch(ffs_split_plan* plan, int n_pairs, const void* const*
                            const int32_t* block_offset_dev, int64_t radius_samples, double unmatched_margin,
                            ffs_break_refine* out_dev, int32_t* n_breaks_out_dev, void* hip_stream);
 
+/* ---- sample-exact jumps of a drift solve (csrc/ffs_drift_refine.h) ------------------------------------------------
+ * Replaces: nothing in the reference.  The contract below is pinned against the numpy model tests/drift_refine_model.py.
+ *
+ * ffs_split_refine_batch's contract (the windows, N, F, G, beta = NaN for a single cut, the tie rules,
+ * coarse_score = A(c) + B(c), the flags, the 88-byte record, the zeroed tail, the count, the refusals) for a path that
+ * changes offset inside its segments -- the block offsets o_b and jump flags of ffs_align_drift_batch,
+ * ffs_align_drift_range_batch or a smooth fit (block_jump_dev[p * max_b + b], uint8) -- with two changes:
+ *   Jumps, not offset changes.  The refined positions are the blocks f_j >= 1 with block_jump[f_j] != 0, whether or not
+ *   the offset changes there (a fitted path may have equal offsets on both sides); block_jump[0] is ignored.
+ *   Lags follow the path.  For a subtitle sample x of the window, b(x) = floor(x / K): lag_a(x) = o[min(b(x), f_j - 1)]
+ *   and lag_b(x) = o[max(b(x), f_j)] -- each segment's own per-block lag where the segment exists, held at the segment's
+ *   last (first) block's value on the far side of the coarse cut.  The windows are clipped at the midpoints to the
+ *   neighbouring jumps, so only these two segments' blocks are read.  A(t) = split_mix of the integer sums
+ *   (ov, n11, n1x, nx1) over x in [L, t) at lag_a(x), B(t) the same over [t, U) at lag_b(x); a sample whose partner
+ *   x + lag(x) lies outside [0, R) is absent.
+ * In the record offset_prev = o[f_j - 1] and offset_next = o[f_j].  Lags are any int32; the call takes no window, so it
+ * serves the windowed and the range solves alike.  For block offsets that are constant inside every segment, with
+ * block_jump set exactly where the offset changes, records and counts are byte-identical to ffs_split_refine_batch's.
+ *
+ * The call runs on the split plan as ffs_split_refine_batch does (its pairs_in_flight and the same few hundred bytes per
+ * pair in flight, made by the first call of either kind; none of the split workspace).  FFS_E_INVALID / FFS_E_EMPTY as
+ * ffs_split_refine_batch, and FFS_E_INVALID for a null block_jump_dev; all before any launch, the outputs untouched. */
+int ffs_drift_refine_batch(ffs_split_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
+                           const double* ref_lo, const double* ref_hi, const void* const* sub_ptr, const int64_t* sub_len,
+                           const double* sub_lo, const double* sub_hi, int64_t block_samples,
+                           const int32_t* block_offset_dev, const uint8_t* block_jump_dev, int64_t radius_samples,
+                           double unmatched_margin, ffs_break_refine* out_dev, int32_t* n_jumps_out_dev, void* hip_stream);
+
 /* ---- split-aware alignment over any lag range: subtitles for another cut of the video (csrc/ffs_split_range.h) -----
  * Replaces: nothing in the reference.  The contract below is pinned against the numpy model tests/cut_model.py.
  *
