@@ -1,6 +1,9 @@
 """Drift-tolerant alignment on the device (csrc/ffs_drift.h via ffsubsync_amd.drift_align): bit for bit against the numpy
 model tests/drift_model.py on block offsets, jump flags, block scores and totals; max_step = 0 against split_align_batch;
-long pairs, batching, drift_sync end to end against split_sync, and the C entry point's error returns."""
+long pairs, batching, drift_sync end to end against split_sync, and the C entry point's error returns.  That the model's
+path IS the maximum over all lag paths, and that the device reaches it at the shapes this module does not run (W = 1 and
+2, 2W = 262 144, K off the powers of two, K = 32 768), is pinned in tests/test_gpu_drift_optimum.py against
+tests/drift_path_reference.py, which shares nothing with the model."""
 import ctypes
 
 import numpy as np

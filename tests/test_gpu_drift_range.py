@@ -1,7 +1,9 @@
 """Drift-tolerant alignment over a lag range on the device (csrc/ffs_drift_range.h via ffsubsync_amd.drift_range): bit
 for bit against the numpy model tests/drift_range_model.py, a path that steps across a tile edge, bit for bit against
 ffs_align_split_range_batch at max_step = 0 and against ffs_align_drift_batch at [-W+1, W], the error paths, and
-cut_drift_sync on subtitles for another cut that also drift."""
+cut_drift_sync on subtitles for another cut that also drift.  That the model's path IS the maximum over all lag paths,
+and that the device reaches it at the shapes this module does not run, is pinned in tests/test_gpu_drift_optimum.py
+against tests/drift_path_reference.py, which shares nothing with the model."""
 import ctypes
 import json
 import os
