@@ -123,6 +123,7 @@ EXPORTED_SYMBOLS = (
     "ffs_comm_destroy",
     "ffs_plan_set_algorithm",
     "ffs_plan_runs_stats",
+    "ffs_plan_dispatch_report",
     "ffs_plan_profile",
     "ffs_plan_profile_read",
     "ffs_split_plan_create",
@@ -159,6 +160,12 @@ EXPORTED_SYMBOLS = (
     "ffs_last_error",
     "ffs_version",
 )
+# ffs_dispatch_report: twelve int32 fields, in the header's order
+DISPATCH_FIELDS = ("transform_sub_batches", "transform_length", "n1", "n2", "seg_blocks", "half_flags", "pass_a_family",
+                   "pass_a_ref_family", "pass_a_paired", "mid_family", "last_family", "sweep_family")
+FFS_DISPATCH_PASS_A, FFS_DISPATCH_PASS_A3 = 1, 2
+FFS_DISPATCH_MID, FFS_DISPATCH_MID_SEG_ONE_1, FFS_DISPATCH_MID_SEG_ONE_4, FFS_DISPATCH_MID_SEG_PIPE = 1, 2, 3, 4
+FFS_DISPATCH_LAST_FULL, FFS_DISPATCH_LAST_C3, FFS_DISPATCH_LAST_PRUNED = 1, 2, 3
 KERNEL_NAMES = ("pass_a", "mid", "pass_c", "nominees", "rescore", "runs_extract", "runs_corr", "levels")
 FFS_ALGO_AUTO, FFS_ALGO_FFT, FFS_ALGO_RUNS = 0, 1, 2
 ALGORITHMS = {"auto": FFS_ALGO_AUTO, "fft": FFS_ALGO_FFT, "runs": FFS_ALGO_RUNS}
@@ -315,6 +322,8 @@ def load():
         lib.ffs_plan_set_algorithm.argtypes = [c.c_void_p, c.c_int]
         lib.ffs_plan_runs_stats.restype = c.c_int
         lib.ffs_plan_runs_stats.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
+        lib.ffs_plan_dispatch_report.restype = c.c_int
+        lib.ffs_plan_dispatch_report.argtypes = [c.c_void_p, c.c_void_p]
         lib.ffs_plan_profile.restype = c.c_int
         lib.ffs_plan_profile.argtypes = [c.c_void_p, c.c_int]
         lib.ffs_plan_profile_read.restype = c.c_int
@@ -509,6 +518,13 @@ class Plan:
         v = ctypes.c_int64()
         check(self.lib.ffs_plan_runs_stats(self.handle, None, None, None, ctypes.byref(v)))
         return int(v.value)
+
+    def dispatch_report(self) -> dict:
+        """What the most recent solve launched for its transform sub-batches (``ffs_plan_dispatch_report``): a dict of
+        DISPATCH_FIELDS, all zero when nothing went through the transforms."""
+        v = (ctypes.c_int32 * len(DISPATCH_FIELDS))()
+        check(self.lib.ffs_plan_dispatch_report(self.handle, ctypes.byref(v)))
+        return {k: int(v[i]) for i, k in enumerate(DISPATCH_FIELDS)}
 
     def profile(self, enable: bool) -> None:
         check(self.lib.ffs_plan_profile(self.handle, 1 if enable else 0))

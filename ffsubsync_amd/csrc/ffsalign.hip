@@ -266,6 +266,10 @@ struct ffs_plan {
     size_t lvl_bytes = 0;
     hipEvent_t runs_ev = nullptr;
     int64_t runs_calls = 0, runs_fft_chunks = 0, runs_chunks = 0, runs_last_boundaries = 0;  // statistics (ffs_plan_runs_stats)
+    // What the most recent ffs_align_batch* call launched for its transform sub-batches (ffs_plan_dispatch_report): every
+    // launch function notes its choice here, on the plan whose kernels it starts (the sub-plan in block-segmented mode;
+    // launch_transform_chunk copies that to the call's plan).
+    mutable ffs_dispatch_report dispatch = {};
     // FFS_HOST_TIMING=1: host nanoseconds of the run-boundary calls by section, printed when the plan is destroyed
     bool host_timing = false;
     double ht_vec = 0, ht_cand = 0, ht_wait = 0, ht_decide = 0, ht_total = 0;
@@ -544,6 +548,9 @@ int launch_pass_a_inst(const ffs_plan* p, const XformDesc* descs, int n_xf, int 
                         xf_per_pair <= FFS_PAIR_MAX_XF && xf_per_pair == slots_per_pair;
     const int grid_rows = row_sel ? (n_xf / xf_per_pair) * (row_sel >> 16) : n_xf;
     const int flags = ref_half | STORE_8B | (p->lab_flags & (31 << 10));
+    ffs_dispatch_report& rep = p->dispatch;
+    (row_sel && (row_sel & 0xffff) == 0 ? rep.pass_a_ref_family : rep.pass_a_family) = FFS_DISPATCH_PASS_A;
+    rep.pass_a_paired = !paired ? 0 : xf_per_pair == 2 ? 1 : 2;
     if constexpr (CAN_PAIR) {
         if (paired) {
             const size_t lds_p = lds > (size_t)L * C * sizeof(cf) ? lds : (size_t)L * C * sizeof(cf);  // the whole column tile
@@ -589,6 +596,9 @@ int launch_pass_a3_inst(const ffs_plan* p, const XformDesc* descs, int n_xf, int
     const int flags = ref_half | (ahead << 16);
     const dim3 gx(nt + (ahead ? 8 : 0));
     const int groups_y = n_xf / xf_per_pair;
+    ffs_dispatch_report& rep = p->dispatch;
+    (row_sel && (row_sel & 0xffff) == 0 ? rep.pass_a_ref_family : rep.pass_a_family) = FFS_DISPATCH_PASS_A3;
+    rep.pass_a_paired = !paired ? 0 : xf_per_pair == 2 ? 1 : 2;
 #define FFS_A3_LAUNCH(PM, GY)                                                                                              \
     do {                                                                                                                   \
         if ((rc_lds = ensure_lds(p, (const void*)k_pass_a3<NS, LI, C, PM>, lds))) return rc_lds;                          \
@@ -615,6 +625,7 @@ int launch_pass_c3_inst(const ffs_plan* p, const CandDesc* cands, int first_cand
     const cf* tw = NS == 2 ? p->tw1h : p->tw1;
     const int tiles = p->N2 / C;
     const int plain = n_packed - (half_last ? 1 : 0);  // slots with two candidates (or all of them without HALF_LAST)
+    p->dispatch.last_family = FFS_DISPATCH_LAST_C3;
     if (plain > 0) {
         if ((rc_lds = ensure_lds(p, (const void*)k_pass_c3<NS, LI, C, false>, lds))) return rc_lds;
         hipLaunchKernelGGL((k_pass_c3<NS, LI, C, false>), dim3(tiles, n_pairs * plain), dim3(256), lds, st, p->work, p->N2,
@@ -676,6 +687,7 @@ int launch_mid_inst(const ffs_plan* p, int n_pairs, int n_slots, int ref_half, h
     if ((rc_lds = ensure_lds(p, (const void*)k_mid<L, SEP>, lds))) return rc_lds;
     constexpr int ROWS = 256 / (L / 16);
     dim3 grid(p->N1 / ROWS, n_pairs);
+    p->dispatch.mid_family = FFS_DISPATCH_MID;
     hipLaunchKernelGGL((k_mid<L, SEP>), grid, dim3(256), lds, st, p->work, p->N1, p->log2CL, (long long)p->N, n_slots,
                        (float)(1.0 / (double)p->N), p->tw2, p->tbM, p->tsM, ref_half);
     HIP_TRY(hipGetLastError());
@@ -691,6 +703,7 @@ int launch_mid(const ffs_plan* p, int n_pairs, int n_slots, int ref_half, hipStr
         const size_t lds = row_lds_bytes(4096);
         int rc_lds;
         if ((rc_lds = ensure_lds(p, (const void*)k_mid<4096, true, true>, lds))) return rc_lds;
+        p->dispatch.mid_family = FFS_DISPATCH_MID;
         hipLaunchKernelGGL((k_mid<4096, true, true>), dim3(p->N1, n_pairs), dim3(256), lds, st, p->work, p->N1, p->log2CL,
                            (long long)p->N, n_slots, (float)(1.0 / (double)p->N), p->tw2, p->tbM, p->tsM, ref_half);
         HIP_TRY(hipGetLastError());
@@ -717,14 +730,17 @@ int launch_mid_seg(const ffs_plan* sp, int n_pairs, int n_slots, int n_blocks, i
     const int flags = ref_half | PAIR_ROWS;
     const int mid_lab = sp->lab_flags & (DBG_NO_FFT | DBG_HOT_MEM | DBG_NO_STORE);
     if (n_slots - 1 == 1) {  // one packed slot (every FFTAligner.fit): one accumulator row, three blocks per CU
+        sp->dispatch.mid_family = FFS_DISPATCH_MID_SEG_ONE_1;
         if ((rc_lds = ensure_lds(sp, (const void*)k_mid_seg_one<4096, false, 1>, lds))) return rc_lds;
         hipLaunchKernelGGL((k_mid_seg_one<4096, false, 1>), dim3(sp->N1, n_pairs), dim3(256), lds, st, sp->work, sp->N1,
                            sp->log2CL, (long long)sp->N, n_slots, n_blocks, inv_n, sp->tw2, sp->tbM, sp->tsM, flags | mid_lab);
     } else if (n_slots - 1 <= 4) {  // single sweep: all (<= 4) candidate slots accumulate at once
+        sp->dispatch.mid_family = FFS_DISPATCH_MID_SEG_ONE_4;
         if ((rc_lds = ensure_lds(sp, (const void*)k_mid_seg_one<4096, true>, ldsp))) return rc_lds;
         hipLaunchKernelGGL((k_mid_seg_one<4096, true>), dim3(sp->N1, n_pairs), dim3(256), ldsp, st, sp->work, sp->N1,
                            sp->log2CL, (long long)sp->N, n_slots, n_blocks, inv_n, sp->tw2, sp->tbM, sp->tsM, flags | mid_lab);
     } else {  // nine or more candidates: two slots per sweep
+        sp->dispatch.mid_family = FFS_DISPATCH_MID_SEG_PIPE;
         if ((rc_lds = ensure_lds(sp, (const void*)k_mid_seg_pipe<4096>, ldsp))) return rc_lds;
         hipLaunchKernelGGL((k_mid_seg_pipe<4096>), dim3(sp->N1, n_pairs), dim3(256), ldsp, st, sp->work, sp->N1, sp->log2CL,
                            (long long)sp->N, n_slots, n_blocks, inv_n, sp->tw2, sp->tbM, sp->tsM, flags);
@@ -749,6 +765,8 @@ int launch_pass_c_inst(const ffs_plan* p, const CandDesc* cands, int first_cand,
     int rc_lds;
     if ((rc_lds = ensure_lds(p, (const void*)k_pass_c<L, C, MODE>, lds))) return rc_lds;
     dim3 grid(p->N2 / C, MODE == 2 ? kCollectRows : n_pairs * n_packed);
+    if (MODE == 0) p->dispatch.last_family = FFS_DISPATCH_LAST_FULL;
+    if (MODE == 2) p->dispatch.sweep_family = FFS_DISPATCH_LAST_FULL;
     hipLaunchKernelGGL((k_pass_c<L, C, MODE>), grid, dim3((L / 16) * C), lds, st, p->work, p->N2, (long long)p->N, p->tw1,
                        cands, first_cand, n_cand, n_packed, n_slots, p->bnom, out_a, out_b, pa.noms, pa.header, pa.entries, p->log2CL,
                        p->twn1, p->xlist, pa.best, pa.shares, pa.half_last);
@@ -794,6 +812,7 @@ int launch_pass_c_pruned_inst(const ffs_plan* p, const CandDesc* cands, int firs
     int rc_lds;
     if ((rc_lds = ensure_lds(p, (const void*)k_pass_c_pruned<L, C, EXH>, lds))) return rc_lds;
     dim3 grid(p->N2 / C, EXH ? kCollectRows : n_pairs * n_packed);
+    (EXH ? p->dispatch.sweep_family : p->dispatch.last_family) = FFS_DISPATCH_LAST_PRUNED;
     hipLaunchKernelGGL((k_pass_c_pruned<L, C, EXH>), grid, dim3((L / 16) * C), lds, st, p->work, p->N2, (long long)p->N,
                        p->twn1, cands, first_cand, n_cand, n_packed, n_slots, p->bnom, bins, pa.noms, pa.header, pa.entries, p->log2CL,
                        p->xlist, seg, seg_shift, pa.best, pa.shares, pa.half_last);
@@ -2056,6 +2075,8 @@ struct AlignCall {
         const bool full3 = !pruned && col3r_ok(q);  // full last pass over radix-3 columns: k_pass_c3's (wider) tiles
         PoolArgs qa = pa;
         qa.half_last = (flags & HALF_LAST) ? 1 : 0;
+        const int done = p->dispatch.transform_sub_batches;  // (q may be p)
+        q->dispatch = ffs_dispatch_report{};
         {
             ProfSpan span(p, st, FFS_K_PASS_A);
             if (mixed) {  // the reference slot of every group in its own type, then the candidate slots in theirs
@@ -2096,6 +2117,13 @@ struct AlignCall {
                                                                   dc, dn, da, first_cand));
         }
         HIP_TRY(hipGetLastError());
+        p->dispatch = q->dispatch;
+        p->dispatch.transform_sub_batches = done + 1;
+        p->dispatch.transform_length = (int32_t)q->N;
+        p->dispatch.n1 = q->N1;
+        p->dispatch.n2 = q->N2;
+        p->dispatch.seg_blocks = seg ? seg_blocks : 0;
+        p->dispatch.half_flags = flags & (HALF_REF | HALF_LAST);
         return FFS_OK;
     }
     int run_transform_chunks() {
@@ -2150,6 +2178,7 @@ int solve_call(ffs_plan* p, const AlignArgs& a, bool* retry) {
     *retry = false;
     HIP_TRY(hipSetDevice(p->device));
     int rc;
+    p->dispatch = ffs_dispatch_report{};
     AlignCall c(p, a);
     if ((rc = enter_stream(p, c.st))) return rc;  // left by c.finish(), or by c.leave on an error return
     c.ht0 = c.ht1 = c.ht2 = c.ht3 = p->host_timing ? now_ns() : 0.0;
@@ -2960,6 +2989,12 @@ int ffs_plan_runs_stats(ffs_plan* p, int64_t* calls, int64_t* sub_batches, int64
     if (sub_batches) *sub_batches = p->runs_chunks;
     if (sub_batches_through_transforms) *sub_batches_through_transforms = p->runs_fft_chunks;
     if (boundaries_last_call) *boundaries_last_call = p->runs_last_boundaries;
+    return FFS_OK;
+}
+
+int ffs_plan_dispatch_report(ffs_plan* p, ffs_dispatch_report* out) {
+    if (!p || !out) return fail(FFS_E_INVALID, "plan and out must not be null");
+    *out = p->dispatch;
     return FFS_OK;
 }
 

@@ -222,6 +222,47 @@ int ffs_plan_set_algorithm(ffs_plan* plan, int algorithm);
  * (what k_runs_extract wrote: 8 bytes each).  Any pointer may be NULL. */
 int ffs_plan_runs_stats(ffs_plan* plan, int64_t* calls, int64_t* sub_batches, int64_t* sub_batches_through_transforms,
                         int64_t* boundaries_last_call);
+/* What the most recent ffs_align_batch* call on the plan launched for the sub-batches it sent through the transforms
+ * (read-only; noted by the launch functions themselves, no device work, no synchronisation).  All zero when no
+ * sub-batch took the transforms (run-boundary path, direct kernel).  The sub-batches of one call share every choice.
+ *   transform_sub_batches  sub-batches that went through the transforms
+ *   transform_length       length the transform kernels ran at: the plan's N, or N/3 in block-segmented mode
+ *   n1, n2                 its column and row lengths (transform_length = n1 * n2)
+ *   seg_blocks             blocks per vector in block-segmented mode (2 or 3), 0 otherwise
+ *   half_flags             1: the reference slot holds half of its rows, 2: so does a single-candidate last slot
+ *   pass_a_family          first pass of the candidate slots: FFS_DISPATCH_PASS_A (k_pass_a) or _PASS_A3 (k_pass_a3)
+ *   pass_a_ref_family      the same for the reference slots when they are launched on their own (reference and
+ *                          candidates of different element types), 0 otherwise
+ *   pass_a_paired          0: one column transform per slot; 1: reference and the only candidate slot paired;
+ *                          2: reference and the single-candidate last slot paired
+ *   mid_family             FFS_DISPATCH_MID (k_mid), _MID_SEG_ONE_1 / _MID_SEG_ONE_4 (k_mid_seg_one with one / four
+ *                          accumulator rows), _MID_SEG_PIPE (k_mid_seg_pipe)
+ *   last_family            FFS_DISPATCH_LAST_FULL (k_pass_c), _LAST_C3 (k_pass_c3), _LAST_PRUNED (k_pass_c_pruned)
+ *   sweep_family           the exhaustive sweep over flagged candidates: _LAST_FULL or _LAST_PRUNED (whether any
+ *                          candidate was flagged is known on the device only) */
+#define FFS_DISPATCH_PASS_A 1
+#define FFS_DISPATCH_PASS_A3 2
+#define FFS_DISPATCH_MID 1
+#define FFS_DISPATCH_MID_SEG_ONE_1 2
+#define FFS_DISPATCH_MID_SEG_ONE_4 3
+#define FFS_DISPATCH_MID_SEG_PIPE 4
+#define FFS_DISPATCH_LAST_FULL 1
+#define FFS_DISPATCH_LAST_C3 2
+#define FFS_DISPATCH_LAST_PRUNED 3
+typedef struct ffs_dispatch_report {
+    int32_t transform_sub_batches;
+    int32_t transform_length;
+    int32_t n1, n2;
+    int32_t seg_blocks;
+    int32_t half_flags;
+    int32_t pass_a_family;
+    int32_t pass_a_ref_family;
+    int32_t pass_a_paired;
+    int32_t mid_family;
+    int32_t last_family;
+    int32_t sweep_family;
+} ffs_dispatch_report;
+int ffs_plan_dispatch_report(ffs_plan* plan, ffs_dispatch_report* out);
 
 /* Full correlation of one reference with one or two candidates (b_dev may be NULL):
  *   out_x_dev[m] = sum_i x'[i] * ref'[(i + m) mod n_fft],  m in [0, n_fft)
