@@ -1,7 +1,8 @@
 // ffs_cut_report.h -- per-piece quality report of a split solve over any lag range [lag_lo, lag_hi], up to the full
 // overlap range (gfx950).  The contract is ffs_split_report.h's with the lag set d = lag_lo + j, j in [0, L),
 // L = lag_hi - lag_lo + 1 (lags without overlap score exactly 0.0 and count in the moments); at [-W+1, W] the records
-// are bit-identical to k_split_piece_report's.  Pinned against the numpy model tests/cut_report_model.py.
+// are bit-identical to k_split_piece_report's.  Pinned against the numpy model tests/cut_report_model.py and against the
+// independent reference tests/report_reference.py (interval correlations from their definition).
 //
 // k_split_piece_sums sums the split's stored block counts; the range split stores none (3.8), and storing them at the
 // full range would take 4 GB per 2 h pair.  Here each piece's n11 row is counted from the bits instead, for the pieces

@@ -2,7 +2,8 @@
 // correlation curve of the segment's own subtitle samples over every SHIFT of its whole path that stays inside the lag
 // window, its moments and greedy peaks, the curve at the shifts that would continue a neighbouring segment without a
 // jump (jump evidence) and the best CONSTANT lag among those the path visits (drift evidence).  The contract is this
-// library's own, pinned against the numpy model tests/drift_report_model.py.
+// library's own, pinned against the numpy model tests/drift_report_model.py and, independently of the count table and the
+// row indexing below, against tests/report_reference.py (sums of block scores from their definition).
 //
 // Segment i of a pair: a maximal run [f_i, e_i) of blocks with no jump inside (block_jump of k_drift_dp), subtitle samples
 // [f_i K, min(e_i K, S)), block offsets o_b with o_min / o_max over the run.  Shift set delta in [-W+1-o_min, W-o_max]

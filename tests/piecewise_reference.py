@@ -101,12 +101,19 @@ class Reference:
             np.cumsum(rows, axis=0, out=pre[1:])  # integers below 2^53: exact
             self.prefix.append(pre)
         self.rows = np.stack([self.interval(b, b + 1) for b in range(self.B)])
-        self.M = np.full((self.B + 1, self.B + 1), -np.inf)
-        for a in range(self.B):
-            for c in range(a + 1, self.B + 1):
-                self.M[a, c] = float(np.max(self.interval(a, c)))
+        self._M = None
         # bound of |sum of the products| of any slice at any lag: the scale of fp64 rounding on the tolerance path
         self.abs_terms = float(np.sum(np.abs(self.s))) * float(np.max(np.abs(self.r)))
+
+    @property
+    def M(self):
+        """M(a, c) of every interval, built on first use (the report reference needs the rows alone)."""
+        if self._M is None:
+            self._M = np.full((self.B + 1, self.B + 1), -np.inf)
+            for a in range(self.B):
+                for c in range(a + 1, self.B + 1):
+                    self._M[a, c] = float(np.max(self.interval(a, c)))
+        return self._M
 
     def lag_index(self, d):
         return int(d) - self.lo
