@@ -64,6 +64,7 @@ SEGMENT_REPORT_DTYPE = np.dtype(
      ("peak_shift", "<i8", (QUALITY_MAX_PEAKS,)), ("n_peaks", "<i4"), ("flags", "<i4")], align=True
 )
 SEGMENT_REPORT_BYTES = 264
+RPATH_ROUND_SEGMENTS, RPATH_CHUNK_WORDS = 8, 512  # csrc/ffs_drift_range_sched.h
 assert SEGMENT_REPORT_DTYPE.itemsize == SEGMENT_REPORT_BYTES
 # ffs_smooth_segment (include/ffsubsync_amd.h; static size 32 bytes) and the limits of the smooth fit
 SMOOTH_MAX_KNOT_BLOCKS = 256  # FFS_SMOOTH_MAX_KNOT_BLOCKS
@@ -149,6 +150,7 @@ EXPORTED_SYMBOLS = (
     "ffs_drift_range_plan_workspace_bytes",
     "ffs_align_drift_range_batch",
     "ffs_align_drift_range_smooth_batch",
+    "ffs_drift_range_report_batch",
     "ffs_quality_plan_create",
     "ffs_quality_plan_destroy",
     "ffs_quality_plan_workspace_bytes",
@@ -409,6 +411,11 @@ def load():
                                                            c.c_double, c.c_int, c.c_int, c.c_double, c.c_void_p,
                                                            c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
                                                            c.c_void_p, c.c_void_p, c.c_void_p]
+        lib.ffs_drift_range_report_batch.restype = c.c_int
+        lib.ffs_drift_range_report_batch.argtypes = [c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                                                     c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p,
+                                                     c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_int64, c.c_void_p,
+                                                     c.c_void_p, c.c_void_p]
         lib.ffs_quality_plan_create.restype = c.c_int
         lib.ffs_quality_plan_create.argtypes = [c.c_int, c.c_int, c.c_int64, c.c_int64, c.POINTER(c.c_void_p)]
         lib.ffs_quality_plan_destroy.restype = c.c_int
@@ -1230,6 +1237,30 @@ class DriftRangePlan(_SidePlan):
                                                           smooth_out.data_ptr(), knot_out.data_ptr(),
                                                           segments_out.data_ptr(), n_segments_out.data_ptr(),
                                                           self._stream(stream)))
+
+    def report_bytes(self) -> int:
+        """What the first ``report`` call adds to ``workspace_bytes``: 8 rows of ``max_lags`` + 1 cells (padded to 64)
+        of 12 bytes per pair in flight, and the work-item table."""
+        lpad = -(-(self.max_lags + 1) // 64) * 64
+        words = -(-self.max_samples // 32)
+        items = 2 * (-(-words // RPATH_CHUNK_WORDS) + self.max_blocks)
+        return self.pairs_in_flight * (RPATH_ROUND_SEGMENTS * lpad * 12 + items * 32)
+
+    def report(self, ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, block_samples: int, lag_lo,
+               lag_hi, offsets, jumps, top_k: int, exclusion_samples: int, report_out, n_segments_out,
+               stream: Optional[int] = None) -> None:
+        """``ffs_drift_range_report_batch``: the segment path reports of the int32 / uint8 CUDA tensors of
+        n_pairs * max_b block offsets and jump flags (as ``align`` wrote them) over each pair's range into a CUDA
+        tensor of n_pairs * max_b * 264 bytes and an int32 one of n_pairs segment counts.  The call waits for the
+        stream's earlier work (it reads the path back)."""
+        n, ptrs, _bufs = _pair_buffers(ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, lag_lo, lag_hi)
+        if (n_segments_out.numel() < n or jumps.numel() < offsets.numel()
+                or report_out.numel() * report_out.element_size() < offsets.numel() * SEGMENT_REPORT_BYTES):
+            raise ValueError("output buffer too small")
+        check(self.lib.ffs_drift_range_report_batch(self.handle, n, *ptrs[:8], int(block_samples), *ptrs[8:],
+                                                    offsets.data_ptr(), jumps.data_ptr(), int(top_k),
+                                                    int(exclusion_samples), report_out.data_ptr(),
+                                                    n_segments_out.data_ptr(), self._stream(stream)))
 
 
 class QualityPlan(_SidePlan):

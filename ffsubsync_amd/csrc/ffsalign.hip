@@ -38,6 +38,7 @@
 #include "ffs_drift_smooth.h"
 #include "ffs_drift_range.h"
 #include "ffs_drift_range_smooth.h"
+#include "ffs_drift_range_report.h"
 
 using namespace ffsa;
 
@@ -1033,7 +1034,7 @@ void fill_xform(XformDesc* x, const VecView* a, const VecView* b, const void* sa
 extern "C" {
 
 const char* ffs_last_error(void) { return g_err.c_str(); }
-int ffs_version(void) { return 390; }
+int ffs_version(void) { return 400; }
 
 int64_t ffs_fft_length(int64_t ref_len, int64_t sub_len) {
     if (ref_len <= 0 || sub_len <= 0) return 0;
@@ -4168,6 +4169,13 @@ struct ffs_drift_range_plan : PlanCore {
     ffsa::SmoothWs sw;
     uint16_t* band;             // [slot][sw.stride][range_band_row(max_step_cap, 256, 16)]
     int64_t smooth_bytes;
+    void* report_mem = nullptr; // report calls only, made by the first: the fp64 score rows, then the uint32 n11 rows
+    double* rep_scores = nullptr;   // [slot][RPATH_ROUND_SEGMENTS][rep_lpad]
+    uint32_t* rep_rows = nullptr;   // [slot][RPATH_ROUND_SEGMENTS][rep_lpad]
+    int64_t rep_lpad = 0;       // max_lags + 1 cells, padded to 64
+    DescStaging rep_items;      // report calls only: RangePathItem[rep_item_cap]
+    int64_t rep_item_cap = 0;
+    int64_t report_bytes = 0;
 };
 
 int ffs_drift_range_plan_create(int device, int pairs_in_flight, int64_t max_blocks, int64_t max_lags, int64_t max_samples,
@@ -4224,12 +4232,14 @@ int ffs_drift_range_plan_destroy(ffs_drift_range_plan* plan) {
     plan->close();
     plan->desc.release();
     if (plan->smooth_mem) (void)hipFree(plan->smooth_mem);
+    if (plan->report_mem) (void)hipFree(plan->report_mem);
+    plan->rep_items.release();
     delete plan;
     return FFS_OK;
 }
 
 int64_t ffs_drift_range_plan_workspace_bytes(const ffs_drift_range_plan* plan) {
-    return plan ? plan->work_bytes + plan->smooth_bytes : 0;
+    return plan ? plan->work_bytes + plan->smooth_bytes + plan->report_bytes : 0;
 }
 
 namespace {
@@ -4351,6 +4361,149 @@ int ffs_align_drift_range_smooth_batch(ffs_drift_range_plan* plan, int n_pairs, 
     return drift_range_batch(plan, n_pairs, a, block_samples, lag_lo, lag_hi, split_penalty, max_step, step_cost,
                              block_offset_out_dev, block_score_out_dev, block_jump_out_dev, total_out_dev, &fit,
                              hip_stream);
+}
+
+/* ---- per-segment path report over a lag range (csrc/ffs_drift_range_report.h) ---------------------------------- */
+
+int ffs_drift_range_report_batch(ffs_drift_range_plan* plan, int n_pairs, const void* const* ref_ptr,
+                                 const int64_t* ref_len, const double* ref_lo, const double* ref_hi,
+                                 const void* const* sub_ptr, const int64_t* sub_len, const double* sub_lo,
+                                 const double* sub_hi, int64_t block_samples, const int64_t* lag_lo,
+                                 const int64_t* lag_hi, const int32_t* block_offset_dev, const uint8_t* block_jump_dev,
+                                 int top_k, int64_t exclusion_samples, ffs_segment_report* report_out_dev,
+                                 int32_t* n_segments_out_dev, void* hip_stream) {
+    const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
+    if (!plan) return fail(FFS_E_INVALID, "null drift range plan");
+    if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
+    if (n_pairs == 0) return FFS_OK;
+    if (a.any_null() || !lag_lo || !lag_hi || !block_offset_dev || !block_jump_dev || !report_out_dev || !n_segments_out_dev)
+        return fail(FFS_E_INVALID, "null argument");
+    if (((uintptr_t)block_offset_dev & 3) || ((uintptr_t)report_out_dev & 7) || ((uintptr_t)n_segments_out_dev & 3))
+        return fail(FFS_E_INVALID, "misaligned block offsets or report outputs");
+    const int64_t K = block_samples;
+    if (int rc = check_block_samples(K)) return rc;
+    if (top_k < 1 || top_k > ffsa::QUAL_MAX_PEAKS) return fail(FFS_E_INVALID, "top_k=%d outside [1, 8]", top_k);
+    if (exclusion_samples < 1) return fail(FFS_E_INVALID, "exclusion_samples=%lld: need >= 1", (long long)exclusion_samples);
+    int64_t max_b = 0;
+    if (int rc = range_limits_check(plan->max_samples, plan->max_blocks, plan->max_lags, n_pairs, a, K, lag_lo, lag_hi,
+                                    &max_b))
+        return rc;
+    // the path on the host (after the stream's earlier work): the offsets checked against the ranges, then the rounds'
+    // work items are made from its segments and their runs
+    hipStream_t st = (hipStream_t)hip_stream;
+    std::vector<int32_t> offs((size_t)n_pairs * max_b);
+    std::vector<uint8_t> jumps((size_t)n_pairs * max_b);
+    HIP_TRY(hipSetDevice(plan->device));
+    HIP_TRY(hipMemcpyAsync(offs.data(), block_offset_dev, offs.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(jumps.data(), block_jump_dev, jumps.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int p = 0; p < n_pairs; ++p) {
+        const int64_t B = (sub_len[p] + K - 1) / K;
+        for (int64_t b = 0; b < B; ++b) {
+            const int64_t o = offs[(size_t)p * max_b + b];
+            if (o < lag_lo[p] || o > lag_hi[p])
+                return fail(FFS_E_INVALID, "pair %d: block %lld offset %lld outside the lag range [%lld, %lld]", p,
+                            (long long)b, (long long)o, (long long)lag_lo[p], (long long)lag_hi[p]);
+        }
+    }
+    if (int rc = plan->begin(st)) return rc;
+    const int pif = plan->pairs_in_flight;
+    constexpr int G = ffsa::RPATH_ROUND_SEGMENTS;
+    if (!plan->report_mem) {  // the first report call: G score and n11 rows per pair in flight, one sub-batch's items
+        const int64_t lpad = split_align_up(plan->max_lags + 1, 64);
+        const int64_t cells = (int64_t)pif * G * lpad;
+        const int64_t item_cap = (int64_t)pif * ffsa::range_path_item_cap(plan->max_samples, plan->max_blocks);
+        const int64_t item_bytes = item_cap * (int64_t)sizeof(ffsa::RangePathItem);
+        void* mem = nullptr;
+        if (hipMalloc(&mem, (size_t)(cells * 12)) != hipSuccess)
+            return fail(FFS_E_NOMEM, "drift range plan: %lld report workspace bytes", (long long)(cells * 12));
+        if (int rc = plan->rep_items.create((size_t)item_bytes)) {
+            (void)hipFree(mem);
+            return fail(rc, "drift range plan: report work items");
+        }
+        plan->report_mem = mem;
+        plan->rep_scores = (double*)mem;
+        plan->rep_rows = (uint32_t*)((char*)mem + cells * 8);
+        plan->rep_lpad = lpad;
+        plan->rep_item_cap = item_cap;
+        plan->report_bytes = cells * 12 + item_bytes;
+    }
+    const int64_t lpad = plan->rep_lpad;
+    const int64_t pre_slot = split_align_up(2 * plan->pw, 64);
+    ffsa::SplitDesc* hd = (ffsa::SplitDesc*)plan->desc.host;
+    ffsa::RangeLag* hl = (ffsa::RangeLag*)(hd + pif);
+    const ffsa::SplitDesc* dd = (const ffsa::SplitDesc*)plan->desc.dev;
+    const ffsa::RangeLag* dl = (const ffsa::RangeLag*)(dd + pif);
+    const ffsa::RangePathItem* di_items = (const ffsa::RangePathItem*)plan->rep_items.dev;
+    ffsa::SegmentReport* out = (ffsa::SegmentReport*)report_out_dev;
+    std::vector<std::vector<ffsa::RangePathSegment>> segs;
+    std::vector<ffsa::RangePathItem> items;
+    std::vector<int64_t> round_start;  // per round: its first work item (+ the end)
+    for (int p0 = 0; p0 < n_pairs; p0 += pif) {
+        const int np = std::min(pif, n_pairs - p0);
+        if (int rc = plan->desc.wait_free()) return rc;
+        int64_t max_l = 0;
+        for (int i = 0; i < np; ++i) {
+            const int p = p0 + i;
+            int32_t* pre_s = plan->pre + (int64_t)i * pre_slot;
+            hd[i] = a.split_desc(p, pre_s, pre_s + plan->pw);
+            hl[i].lag_lo = lag_lo[p];
+            hl[i].L = lag_hi[p] - lag_lo[p] + 1;
+            max_l = std::max(max_l, hl[i].L);
+        }
+        if (int rc = plan->desc.upload(sizeof(ffsa::SplitDesc) * pif + sizeof(ffsa::RangeLag) * np, st)) return rc;
+        // the segments of each pair (as k_drift_segments forms them) -> work items, round by round: round r holds the
+        // segments r*G .. r*G + G - 1 of every pair
+        segs.resize((size_t)np);
+        int64_t most = 0;
+        for (int i = 0; i < np; ++i) {
+            const int p = p0 + i;
+            ffsa::range_path_segments(offs.data() + (size_t)p * max_b, jumps.data() + (size_t)p * max_b,
+                                      (sub_len[p] + K - 1) / K, segs[i]);
+            most = std::max(most, (int64_t)segs[i].size());
+        }
+        const int64_t n_rounds = (most + G - 1) / G;
+        items.clear();
+        round_start.assign(1, 0);
+        for (int64_t r = 0; r < n_rounds; ++r) {
+            for (int i = 0; i < np; ++i) {
+                const int p = p0 + i;
+                for (int g = 0; g < G && r * G + g < (int64_t)segs[i].size(); ++g)
+                    ffsa::range_path_items(offs.data() + (size_t)p * max_b, segs[i][(size_t)(r * G + g)], K, sub_len[p],
+                                           lag_lo[p], hl[i].L, i * G + g, items);
+            }
+            round_start.push_back((int64_t)items.size());
+        }
+        if ((int64_t)items.size() > plan->rep_item_cap)
+            return fail(FFS_E_INVALID, "drift range report: %lld work items exceed the table of %lld",
+                        (long long)items.size(), (long long)plan->rep_item_cap);
+        if (int rc = plan->rep_items.wait_free()) return rc;
+        memcpy(plan->rep_items.host, items.data(), items.size() * sizeof(ffsa::RangePathItem));
+        if (int rc = plan->rep_items.upload(sizeof(ffsa::RangePathItem) * items.size(), st)) return rc;
+        hipLaunchKernelGGL(ffsa::k_split_prefix, dim3(2 * np), dim3(ffsa::SPLIT_PREFIX_THREADS), 0, st, dd,
+                           (int64_t)plan->max_samples);
+        hipLaunchKernelGGL(ffsa::k_drift_segments, dim3(np), dim3(ffsa::DRIFT_SEG_THREADS), 0, st, dd, (int)K, max_b,
+                           block_offset_dev, block_jump_dev, out, n_segments_out_dev);
+        const int64_t n_tiles = (max_l + ffsa::QUAL_TILE - 1) / ffsa::QUAL_TILE;
+        const int n_sum_tiles = (int)((max_l + ffsa::DRIFT_SUM_TILE - 1) / ffsa::DRIFT_SUM_TILE);
+        for (int64_t r = 0; r < n_rounds; ++r) {
+            HIP_TRY(hipMemsetAsync(plan->rep_rows, 0, (size_t)np * G * lpad * 4, st));
+            for (int64_t q = round_start[r]; q < round_start[r + 1]; q += ffsa::RPATH_MAX_ITEMS) {
+                const int64_t nq = std::min<int64_t>(ffsa::RPATH_MAX_ITEMS, round_start[r + 1] - q);
+                hipLaunchKernelGGL(ffsa::k_range_path_counts, dim3((unsigned)n_tiles, (unsigned)nq),
+                                   dim3(ffsa::QUAL_CNT_THREADS), 0, st, dd, di_items + q, plan->rep_rows, lpad);
+            }
+            hipLaunchKernelGGL(ffsa::k_range_path_scores, dim3((unsigned)((int64_t)n_sum_tiles * G * np)),
+                               dim3(ffsa::DRIFT_SUM_THREADS), 0, st, dd, dl, (const uint32_t*)plan->rep_rows,
+                               plan->rep_scores, lpad, (int)K, n_sum_tiles, (int)(r * G), max_b, block_offset_dev,
+                               (const int32_t*)n_segments_out_dev, (const ffsa::SegmentReport*)out);
+            hipLaunchKernelGGL(ffsa::k_range_segment_report, dim3((unsigned)(np * G)), dim3(ffsa::QUAL_PEAK_THREADS), 0, st,
+                               dd, dl, (const uint32_t*)plan->rep_rows, (const double*)plan->rep_scores, lpad,
+                               (int)(r * G), max_b, top_k, exclusion_samples, (const int32_t*)n_segments_out_dev, out);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    return plan->end(st);
 }
 
 /* ---- alignment quality report (csrc/ffs_quality.h) ------------------------------------------------------------- */

@@ -8,8 +8,9 @@ with one constant per piece.  ``drift_align`` follows the ramp, inside +-131 072
 ``csrc/ffs_drift_range.h`` -- one launch per block step, the lag row spread over many workgroups.
 
 ``cut_drift_sync`` chains the seven-ratio solve with no window, the range drift solve and the per-cue output at block
-granularity; ``drift_range_smooth.smooth_cut_sync`` adds the polyline fit over a range.  Sample-exact
-breaks, a segment report and unmatched-cue detection over a range are not part of it.
+granularity; ``drift_range_smooth.smooth_cut_sync`` adds the polyline fit over a range,
+``drift_refine.refined_cut_drift_sync`` sample-exact jumps and unmatched cues (3.16) and
+``drift_range_report.checked_cut_drift_sync`` the segment report over a range and a decision per file (3.17).
 
 Parity is against the in-repo numpy model ``tests/drift_range_model.py``, bit for bit; at ``max_step`` = 0 offsets,
 scores and total equal ``split_align_range_batch``'s, at [-W+1, W] every output equals ``drift_align_batch``'s.

@@ -995,6 +995,45 @@ int ffs_align_drift_range_smooth_batch(ffs_drift_range_plan* plan, int n_pairs, 
                                        int32_t* smooth_offset_out_dev, uint8_t* knot_out_dev,
                                        ffs_smooth_segment* segment_out_dev, int32_t* n_segments_out_dev, void* hip_stream);
 
+/* ---- per-segment path report of a drift solve over any lag range (csrc/ffs_drift_range_report.h) --------------------
+ * Replaces: nothing in the reference.  The contract below is pinned against the numpy model
+ * tests/drift_range_report_model.py and the independent reference tests/report_reference.py.
+ *
+ * ffs_align_drift_report_batch's segment records (ffs_segment_report, unchanged, the same flags) for a finished path
+ * -- block_offset_dev[p * max_b + b] and block_jump_dev[p * max_b + b] as ffs_align_drift_range_batch writes them,
+ * every o_b inside [lag_lo_p, lag_hi_p] -- over the lag set d in [lag_lo_p, lag_hi_p], L = lag_hi - lag_lo + 1, instead
+ * of [-W+1, W].  Segments are formed from block_jump as there.  Shift set delta in [lag_lo - o_min, lag_hi - o_max]:
+ * n_lags = L - (o_max - o_min) >= 1, shift index t puts block b at the lag lag_lo + t + (o_b - o_min).  Per block and
+ * lag d: a = max(bK, -d), e = min((b+1)K, S, R-d); where e > a, ov / n1x / nx1 as there and n11 counted exactly from the
+ * bits; where e <= a all four are 0.  The four are summed over the segment's blocks as exact integers and scored once
+ * (split_mix, no FMA); the score is exactly 0.0 where the summed overlap is 0, and such shifts count in the moments.
+ * Moments and greedy peaks over the n_lags shifts as there (peaks reported as shifts, 0 the path itself); own = p(0),
+ * prev = p(last_offset_{i-1} - first_offset_i), next = p(first_offset_{i+1} - last_offset_i), NaN without that neighbour
+ * or outside the shift set; flat_score / flat_offset the maximum over d in [o_min, o_max] of the constant-lag score of
+ * the segment's samples on their exact n11, the largest d on ties.  At [-W+1, W], given ffs_align_drift_batch's path,
+ * the records are bit-identical to ffs_align_drift_report_batch's; at max_step = 0 they equal
+ * ffs_split_range_report_batch's in the shared fields.  report_out_dev: n_pairs * max_b records (8-byte aligned;
+ * records past the count zero); n_segments_out_dev: n_pairs int32.
+ *
+ * The range solve stores no counts, so the report neither needs nor touches the DP: it is a post-pass.  The call reads
+ * the offsets and jump flags back once (it waits for hip_stream's earlier work) to check them and to schedule its
+ * rounds; the kernels run on hip_stream.  Segments are reported 8 per pair and round.  The first report call on a plan
+ * adds pairs_in_flight * 8 rows of max_lags + 1 cells (padded to 64) of 12 bytes -- a uint32 n11 row, whose last
+ * o_max - o_min + 1 cells hold the constant-lag counts, and an fp64 score row -- plus a work-item table of
+ * pairs_in_flight * 2 * (ceil(ceil(max_samples / 32) / 512) + max_blocks) * 32 bytes: 138 MB per pair at 2 h over the
+ * full range (1 439 999 lags).  ffs_drift_range_plan_workspace_bytes counts it from then on; a plan that never reports
+ * keeps its size, and drift results after a report stay bit-identical.
+ * FFS_E_INVALID / FFS_E_EMPTY for everything ffs_align_drift_range_batch refuses of these arguments, and FFS_E_INVALID
+ * for top_k outside [1, 8], exclusion_samples < 1, a null or misaligned offset, jump or output pointer, or a block
+ * offset outside its pair's range; all before any launch, the outputs untouched. */
+int ffs_drift_range_report_batch(ffs_drift_range_plan* plan, int n_pairs, const void* const* ref_ptr,
+                                 const int64_t* ref_len, const double* ref_lo, const double* ref_hi,
+                                 const void* const* sub_ptr, const int64_t* sub_len, const double* sub_lo,
+                                 const double* sub_hi, int64_t block_samples, const int64_t* lag_lo,
+                                 const int64_t* lag_hi, const int32_t* block_offset_dev, const uint8_t* block_jump_dev,
+                                 int top_k, int64_t exclusion_samples, ffs_segment_report* report_out_dev,
+                                 int32_t* n_segments_out_dev, void* hip_stream);
+
 /* Thread-local description of the last error returned on this thread ("" if none). */
 const char* ffs_last_error(void);
 
