@@ -88,6 +88,26 @@ BREAK_REFINE_DTYPE = np.dtype(
 )
 BREAK_REFINE_BYTES = 88
 assert BREAK_REFINE_DTYPE.itemsize == BREAK_REFINE_BYTES
+# ffs_cue / ffs_cue_report (include/ffsubsync_amd.h; static sizes 24 and 120 bytes)
+CUE_MAX_RADIUS = 4096  # FFS_CUE_MAX_RADIUS
+CUE_MAX_CONTEXT = 65536  # FFS_CUE_MAX_CONTEXT
+CUE_EMPTY = 1  # FFS_CUE_EMPTY: the cue holds no sample of the subtitle vector
+CUE_INVALID = 2  # FFS_CUE_INVALID: |lag| > 2^31
+CUE_NO_OVERLAP = 4  # FFS_CUE_NO_OVERLAP: no sample of the window has a partner at the applied lag
+CUE_BEST_AT_EDGE = 8  # FFS_CUE_BEST_AT_EDGE: |best_delta| = radius > 0
+CUE_FLAT = 16  # FFS_CUE_FLAT: every lag within the radius scores the same
+CUE_SILENT = 32  # FFS_CUE_SILENT: no reference speech under the cue at any lag within the radius
+CUE_DTYPE = np.dtype([("start", "<i8"), ("end", "<i8"), ("lag", "<i8")], align=True)
+CUE_BYTES = 24
+assert CUE_DTYPE.itemsize == CUE_BYTES
+CUE_REPORT_DTYPE = np.dtype(
+    [("start", "<i8"), ("end", "<i8"), ("lo", "<i8"), ("hi", "<i8"), ("lag", "<i8"), ("own", "<i4", (4,)),
+     ("best", "<i4", (4,)), ("own_score", "<f8"), ("best_score", "<f8"), ("best_delta", "<i4"), ("n_best", "<i4"),
+     ("cue_own_n11", "<i4"), ("cue_own_ov", "<i4"), ("cue_max_n11", "<i4"), ("cue_max_delta", "<i4"), ("flags", "<i4"),
+     ("reserved", "<i4")], align=True
+)
+CUE_REPORT_BYTES = 120
+assert CUE_REPORT_DTYPE.itemsize == CUE_REPORT_BYTES
 
 # every symbol include/ffsubsync_amd.h declares (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = (
@@ -134,6 +154,7 @@ EXPORTED_SYMBOLS = (
     "ffs_align_split_report_batch",
     "ffs_split_refine_batch",
     "ffs_drift_refine_batch",
+    "ffs_cue_report_batch",
     "ffs_split_range_plan_create",
     "ffs_split_range_plan_destroy",
     "ffs_split_range_plan_workspace_bytes",
@@ -349,6 +370,9 @@ def load():
         lib.ffs_split_refine_batch.argtypes = [c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
                                                c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p,
                                                c.c_int64, c.c_double, c.c_void_p, c.c_void_p, c.c_void_p]
+        lib.ffs_cue_report_batch.restype = c.c_int
+        lib.ffs_cue_report_batch.argtypes = [c.c_void_p, c.c_int] + [c.c_void_p] * 8 + [
+            c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_void_p]
         lib.ffs_drift_refine_batch.restype = c.c_int
         lib.ffs_drift_refine_batch.argtypes = [c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
                                                c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p,
@@ -1071,6 +1095,20 @@ class SplitPlan(_SidePlan):
         check(self.lib.ffs_drift_refine_batch(self.handle, n, *ptrs, int(block_samples), offsets.data_ptr(),
                                               jumps.data_ptr(), int(radius_samples), float(unmatched_margin),
                                               refine_out.data_ptr(), n_jumps_out.data_ptr(), self._stream(stream)))
+
+    def cue_report(self, ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, cues, cue_first, cue_count,
+                   radius_samples: int, context_samples: int, report_out, stream: Optional[int] = None) -> None:
+        """``ffs_cue_report_batch``: the uint8 CUDA tensor ``cues`` of 24-byte ``CUE_DTYPE`` entries, pair p's being the
+        ``cue_count[p]`` entries from ``cue_first[p]`` on, into a uint8 CUDA tensor of one 120-byte record per table
+        entry (asynchronous)."""
+        n_cues = cues.numel() * cues.element_size() // CUE_BYTES
+        n, ptrs, _bufs = _pair_buffers(ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, cue_first,
+                                       cue_count)
+        if report_out.numel() * report_out.element_size() < n_cues * CUE_REPORT_BYTES:
+            raise ValueError("output buffer too small")
+        check(self.lib.ffs_cue_report_batch(self.handle, n, *ptrs[:8], cues.data_ptr(), n_cues, ptrs[8], ptrs[9],
+                                            int(radius_samples), int(context_samples), report_out.data_ptr(),
+                                            self._stream(stream)))
 
 
 def range_band_row(max_step: int, knot_blocks: int, radius: int) -> int:

@@ -35,6 +35,7 @@
 #include "ffs_cut_report.h"
 #include "ffs_drift.h"
 #include "ffs_drift_report.h"
+#include "ffs_cue_report.h"
 #include "ffs_drift_smooth.h"
 #include "ffs_drift_range.h"
 #include "ffs_drift_range_smooth.h"
@@ -3260,6 +3261,8 @@ struct ffs_split_plan : PlanCore {
     DescStaging refine;        // refine calls only, made by the first: RefineDesc[pairs_in_flight], then on the device
     double* refine_scratch;    // the null-score scratch [pairs_in_flight][4]
     int64_t refine_bytes;
+    DescStaging cue;           // cue report calls only, made by the first: CueDesc[pairs_in_flight]
+    int64_t cue_bytes;
 };
 
 int ffs_split_plan_create(int device, int pairs_in_flight, int64_t max_blocks, int64_t max_lags, int64_t max_samples,
@@ -3316,12 +3319,13 @@ int ffs_split_plan_destroy(ffs_split_plan* plan) {
     plan->desc.release();
     if (plan->curves) (void)hipFree(plan->curves);
     plan->refine.release();
+    plan->cue.release();
     delete plan;
     return FFS_OK;
 }
 
 int64_t ffs_split_plan_workspace_bytes(const ffs_split_plan* plan) {
-    return plan ? plan->work_bytes + plan->curve_bytes + plan->refine_bytes : 0;
+    return plan ? plan->work_bytes + plan->curve_bytes + plan->refine_bytes + plan->cue_bytes : 0;
 }
 
 namespace {
@@ -3549,6 +3553,89 @@ int ffs_drift_refine_batch(ffs_split_plan* plan, int n_pairs, const void* const*
     const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
     return refine_batch(plan, n_pairs, a, block_samples, block_offset_dev, true, block_jump_dev, radius_samples,
                         unmatched_margin, out_dev, n_jumps_out_dev, hip_stream);
+}
+
+/* ---- per-cue evidence report (csrc/ffs_cue_report.h) ------------------------------------------------------------ */
+
+int ffs_cue_report_batch(ffs_split_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
+                         const double* ref_lo, const double* ref_hi, const void* const* sub_ptr, const int64_t* sub_len,
+                         const double* sub_lo, const double* sub_hi, const ffs_cue* cue_dev, int64_t n_cues,
+                         const int64_t* cue_first, const int64_t* cue_count, int64_t radius_samples,
+                         int64_t context_samples, ffs_cue_report* out_dev, void* hip_stream) {
+    const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
+    if (!plan) return fail(FFS_E_INVALID, "null split plan");
+    if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
+    if (n_pairs == 0) return FFS_OK;
+    if (a.any_null() || !cue_first || !cue_count) return fail(FFS_E_INVALID, "null argument");
+    if (radius_samples < 0 || radius_samples > ffsa::CUE_MAX_RADIUS)
+        return fail(FFS_E_INVALID, "radius_samples=%lld: need 0 <= radius <= %lld", (long long)radius_samples,
+                    (long long)ffsa::CUE_MAX_RADIUS);
+    if (context_samples < 0 || context_samples > ffsa::CUE_MAX_CONTEXT)
+        return fail(FFS_E_INVALID, "context_samples=%lld: need 0 <= context <= %lld", (long long)context_samples,
+                    (long long)ffsa::CUE_MAX_CONTEXT);
+    if (n_cues < 0 || n_cues > INT32_MAX / 2) return fail(FFS_E_INVALID, "n_cues=%lld: need 0 <= n_cues <= 2^30", (long long)n_cues);
+    int64_t total = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+        if (int rc = a.check(p)) return rc;
+        if (ref_len[p] > INT32_MAX / 2 || sub_len[p] > INT32_MAX / 2)
+            return fail(FFS_E_INVALID, "pair %d: vectors longer than 2^30 samples", p);
+        if (cue_count[p] < 0) return fail(FFS_E_INVALID, "pair %d: cue_count=%lld < 0", p, (long long)cue_count[p]);
+        if (cue_first[p] < 0 || cue_first[p] > n_cues || cue_count[p] > n_cues - cue_first[p])
+            return fail(FFS_E_INVALID, "pair %d: cues [%lld, +%lld) outside the table of %lld", p, (long long)cue_first[p],
+                        (long long)cue_count[p], (long long)n_cues);
+        total += cue_count[p];
+    }
+    if (total == 0) return FFS_OK;
+    if (!cue_dev || !out_dev || ((uintptr_t)cue_dev & 7) || ((uintptr_t)out_dev & 7))
+        return fail(FFS_E_INVALID, "null or misaligned cue table or report output");
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (int rc = plan->begin(st)) return rc;
+    const int pif = plan->pairs_in_flight;
+    if (!plan->cue.dev) {  // the first cue report call: descriptors and their staging
+        const size_t desc_bytes = sizeof(ffsa::CueDesc) * (size_t)pif;
+        if (int rc = plan->cue.create(desc_bytes)) return fail(rc, "split plan: cue report workspace");
+        plan->cue_bytes = (int64_t)desc_bytes;
+    }
+    ffsa::CueDesc* hd = (ffsa::CueDesc*)plan->cue.host;
+    const ffsa::CueDesc* dd = (const ffsa::CueDesc*)plan->cue.dev;
+    for (int p0 = 0; p0 < n_pairs; p0 += pif) {
+        const int np = std::min(pif, n_pairs - p0);
+        int nd = 0;
+        int64_t grid = 0;
+        for (int i = 0; i < np; ++i) grid += cue_count[p0 + i];
+        if (grid == 0) continue;
+        if (int rc = plan->cue.wait_free()) return rc;
+        grid = 0;
+        for (int i = 0; i < np; ++i) {  // pairs without cues get no descriptor
+            const int p = p0 + i;
+            if (cue_count[p] == 0) continue;
+            const Levels v = a.levels(p);
+            ffsa::CueDesc& c = hd[nd++];
+            c.v.r = (const uint32_t*)a.ref_ptr[p];
+            c.v.s = (const uint32_t*)a.sub_ptr[p];
+            c.v.R = ref_len[p];
+            c.v.S = sub_len[p];
+            c.v.r0 = v.r0;
+            c.v.r1 = v.r1;
+            c.v.s0 = v.s0;
+            c.v.s1 = v.s1;
+            c.v.c00 = v.c00;
+            c.v.c01 = v.c01;
+            c.v.c10 = v.c10;
+            c.v.c11 = v.c11;
+            c.v.pair_ws = nullptr;
+            c.v.out_row = p;
+            c.cue_first = cue_first[p];
+            c.grid_first = grid;
+            c.cue_count = cue_count[p];
+            grid += cue_count[p];
+        }
+        if (int rc = plan->cue.upload(sizeof(ffsa::CueDesc) * nd, st)) return rc;
+        hipLaunchKernelGGL(ffsa::k_cue_report, dim3((unsigned)grid), dim3(ffsa::CUE_THREADS), 0, st, dd, nd,
+                           (const ffsa::Cue*)cue_dev, (int)radius_samples, (int)context_samples, (ffsa::CueReport*)out_dev);
+        HIP_TRY(hipGetLastError());
+    }
+    return plan->end(st);
 }
 
 /* ---- split-aware alignment over a lag range (csrc/ffs_split_range.h) ------------------------------------------- */

@@ -710,6 +710,73 @@ int ffs_drift_refine_batch(ffs_split_plan* plan, int n_pairs, const void* const*
                            const int32_t* block_offset_dev, const uint8_t* block_jump_dev, int64_t radius_samples,
                            double unmatched_margin, ffs_break_refine* out_dev, int32_t* n_jumps_out_dev, void* hip_stream);
 
+/* ---- per-cue evidence report (csrc/ffs_cue_report.h) ----------------------------------------------------------------
+ * Replaces: nothing in the reference.  The contract below is pinned against the numpy model tests/cue_model.py.
+ *
+ * Every sync ends in cue times; this call reports on each cue by itself.  Per pair: the vectors as
+ * ffs_split_refine_batch takes them, and cue_count[p] entries of the device table cue_dev from entry cue_first[p] on:
+ * start / end in samples of s, lag = the offset the sync applied to that cue.  Cues may be unsorted, may overlap and may
+ * number zero; their contents are not validated on the host and may be any int64.  Per cue: a = clamp(start, 0, S),
+ * e = clamp(end, 0, S); e <= a sets FFS_CUE_EMPTY, |lag| > 2^31 sets FFS_CUE_INVALID, and in both cases the record
+ * holds start, end, lag and the flags, everything else zero.  Otherwise the window is L = max(0, a - m),
+ * U = min(S, e + m), m = context_samples in [0, FFS_CUE_MAX_CONTEXT], and for every delta in [-rho, rho],
+ * rho = radius_samples in [0, FFS_CUE_MAX_RADIUS], with d = lag + delta:
+ *   window counts ov, n11, n1x (s = 1), nx1 (r = 1) over subtitle samples i in [L, U) whose partner i + d lies in
+ *   [0, R) (other samples are absent, as in the split); c(delta) = ((n00*c00 + n01*c01) + n10*c10) + n11*c11, fp64, each
+ *   operation rounded on its own;
+ *   cue counts cov(delta), c11(delta): the partners inside the reference and the reference ones over i in [a, e).
+ * best_delta maximises c, cue_max_delta maximises c11; ties go to the smallest |delta|, then to +delta over -delta.
+ * n_best = the number of delta with c(delta) equal to the maximum (fp64 equality).
+ *
+ * Records: out_dev[k] for table entry k, for every entry inside a pair's range (other entries are not written).  The
+ * call uses the split plan's pairs_in_flight for its sub-batches and none of its split workspace; the first cue report
+ * call on a plan adds one descriptor block per pair in flight, counted by ffs_split_plan_workspace_bytes from then on. */
+#define FFS_CUE_MAX_RADIUS 4096
+#define FFS_CUE_MAX_CONTEXT 65536
+#define FFS_CUE_EMPTY 1        /* e <= a */
+#define FFS_CUE_INVALID 2      /* |lag| > 2^31 */
+#define FFS_CUE_NO_OVERLAP 4   /* ov = 0 at delta = 0 */
+#define FFS_CUE_BEST_AT_EDGE 8 /* rho > 0 and |best_delta| = rho */
+#define FFS_CUE_FLAT 16        /* rho > 0 and n_best = 2 rho + 1 */
+#define FFS_CUE_SILENT 32      /* cue_max_n11 = 0: no reference speech under the cue at any lag within rho */
+
+typedef struct ffs_cue {
+    int64_t start, end; /* [start, end) in samples of s */
+    int64_t lag;        /* the offset applied to the cue (samples) */
+} ffs_cue;
+
+typedef struct ffs_cue_report {
+    int64_t start, end;        /* as given */
+    int64_t lo, hi;            /* the window [L, U) */
+    int64_t lag;               /* as given */
+    int32_t own[4];            /* ov, n11, n1x, nx1 at delta = 0 */
+    int32_t best[4];           /* the same at best_delta */
+    double own_score;          /* c(0) */
+    double best_score;         /* c(best_delta) */
+    int32_t best_delta, n_best;
+    int32_t cue_own_n11, cue_own_ov;      /* c11(0), cov(0) */
+    int32_t cue_max_n11, cue_max_delta;   /* max c11 and where */
+    int32_t flags, reserved;   /* flags: FFS_CUE_*; reserved = 0 */
+} ffs_cue_report;
+#ifdef __cplusplus
+static_assert(sizeof(ffs_cue) == 24, "ffs_cue is 24 bytes");
+static_assert(sizeof(ffs_cue_report) == 120, "ffs_cue_report is 120 bytes");
+#else
+_Static_assert(sizeof(ffs_cue) == 24, "ffs_cue is 24 bytes");
+_Static_assert(sizeof(ffs_cue_report) == 120, "ffs_cue_report is 120 bytes");
+#endif
+
+/* Report on the cues of n_pairs pairs on hip_stream (host arrays of n_pairs entries; ref_ptr / sub_ptr, cue_dev and
+ * out_dev are DEVICE pointers, 8-byte aligned; n_cues = the entries of the table and of out_dev).  FFS_E_INVALID /
+ * FFS_E_EMPTY as ffs_split_refine_batch, and FFS_E_INVALID for a radius or context out of range, a negative count, a
+ * range outside the table, or a null / misaligned table or output when there is a cue to report; all before any launch,
+ * the output untouched.  n_pairs = 0 or zero cues in total is not an error. */
+int ffs_cue_report_batch(ffs_split_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
+                         const double* ref_lo, const double* ref_hi, const void* const* sub_ptr, const int64_t* sub_len,
+                         const double* sub_lo, const double* sub_hi, const ffs_cue* cue_dev, int64_t n_cues,
+                         const int64_t* cue_first, const int64_t* cue_count, int64_t radius_samples,
+                         int64_t context_samples, ffs_cue_report* out_dev, void* hip_stream);
+
 /* ---- split-aware alignment over any lag range: subtitles for another cut of the video (csrc/ffs_split_range.h) -----
  * Replaces: nothing in the reference.  The contract below is pinned against the numpy model tests/cut_model.py.
  *
