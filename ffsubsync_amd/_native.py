@@ -108,6 +108,35 @@ CUE_REPORT_DTYPE = np.dtype(
 )
 CUE_REPORT_BYTES = 120
 assert CUE_REPORT_DTYPE.itemsize == CUE_REPORT_BYTES
+# ffs_cue_retime / ffs_retime_summary (include/ffsubsync_amd.h; static sizes 64 and 40 bytes)
+RETIME_MAX_RADIUS = 1024  # FFS_RETIME_MAX_RADIUS
+RETIME_Q = 64  # FFS_RETIME_Q: penalty_q and jump_q are in 64ths of a score sample
+RETIME_NO_JUMP = -1  # FFS_RETIME_NO_JUMP: the linear link cost is not capped
+RETIME_MAX_PENALTY_Q = 1 << 20
+RETIME_MAX_JUMP_Q = 1 << 40
+RETIME_WORK_CAP = 256 << 20  # FFS_RETIME_WORK_CAP: bytes of retime workspace one sub-batch may use
+RETIME_CELL_BYTES = 6  # int32 profile + int16 backpointer per (cue, delta)
+RETIME_DESC_BYTES = 72  # the descriptor a retime call keeps per pair in flight
+RETIME_KEEP_ORDER = 1  # FFS_RETIME_KEEP_ORDER (call flag)
+RETIME_EMPTY = 1  # FFS_RETIME_EMPTY
+RETIME_INVALID = 2  # FFS_RETIME_INVALID
+RETIME_MOVED = 4  # FFS_RETIME_MOVED: delta != 0
+RETIME_JUMP = 8  # FFS_RETIME_JUMP: the incoming link paid jump_q instead of the linear cost
+RETIME_UNORDERED = 16  # FFS_RETIME_UNORDERED: the cue starts before its predecessor in the input
+RETIME_ORDER_TIGHT = 32  # FFS_RETIME_ORDER_TIGHT: the order constraint holds with equality
+RETIME_AT_EDGE = 64  # FFS_RETIME_AT_EDGE: |delta| = radius > 0
+CUE_RETIME_DTYPE = np.dtype(
+    [("start", "<i8"), ("end", "<i8"), ("lag", "<i8"), ("delta", "<i4"), ("flags", "<i4"), ("own", "<i4"), ("at", "<i4"),
+     ("best", "<i4"), ("best_delta", "<i4"), ("link", "<i8"), ("reserved", "<i4", (2,))], align=True
+)
+CUE_RETIME_BYTES = 64
+assert CUE_RETIME_DTYPE.itemsize == CUE_RETIME_BYTES
+RETIME_SUMMARY_DTYPE = np.dtype(
+    [("total", "<i8"), ("own_total", "<i8"), ("best_total", "<i8"), ("n_live", "<i4"), ("n_moved", "<i4"),
+     ("n_jumps", "<i4"), ("reserved", "<i4")], align=True
+)
+RETIME_SUMMARY_BYTES = 40
+assert RETIME_SUMMARY_DTYPE.itemsize == RETIME_SUMMARY_BYTES
 
 # every symbol include/ffsubsync_amd.h declares (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = (
@@ -155,6 +184,7 @@ EXPORTED_SYMBOLS = (
     "ffs_split_refine_batch",
     "ffs_drift_refine_batch",
     "ffs_cue_report_batch",
+    "ffs_cue_retime_batch",
     "ffs_split_range_plan_create",
     "ffs_split_range_plan_destroy",
     "ffs_split_range_plan_workspace_bytes",
@@ -373,6 +403,10 @@ def load():
         lib.ffs_cue_report_batch.restype = c.c_int
         lib.ffs_cue_report_batch.argtypes = [c.c_void_p, c.c_int] + [c.c_void_p] * 8 + [
             c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_void_p]
+        lib.ffs_cue_retime_batch.restype = c.c_int
+        lib.ffs_cue_retime_batch.argtypes = [c.c_void_p, c.c_int] + [c.c_void_p] * 8 + [
+            c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_int64, c.c_int64, c.c_int,
+            c.c_void_p, c.c_void_p, c.c_void_p]
         lib.ffs_drift_refine_batch.restype = c.c_int
         lib.ffs_drift_refine_batch.argtypes = [c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
                                                c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p,
@@ -1109,6 +1143,23 @@ class SplitPlan(_SidePlan):
         check(self.lib.ffs_cue_report_batch(self.handle, n, *ptrs[:8], cues.data_ptr(), n_cues, ptrs[8], ptrs[9],
                                             int(radius_samples), int(context_samples), report_out.data_ptr(),
                                             self._stream(stream)))
+
+    def cue_retime(self, ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, cues, cue_first, cue_count,
+                   radius_samples: int, context_samples: int, penalty_q: int, jump_q: int, flags: int, retime_out,
+                   summary_out, stream: Optional[int] = None) -> None:
+        """``ffs_cue_retime_batch``: the cue table as ``cue_report`` takes it, into a uint8 CUDA tensor of one 64-byte
+        ``CUE_RETIME_DTYPE`` record per table entry and one of a 40-byte ``RETIME_SUMMARY_DTYPE`` record per pair
+        (asynchronous)."""
+        n_cues = cues.numel() * cues.element_size() // CUE_BYTES
+        n, ptrs, _bufs = _pair_buffers(ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, cue_first,
+                                       cue_count)
+        if (retime_out.numel() * retime_out.element_size() < n_cues * CUE_RETIME_BYTES
+                or summary_out.numel() * summary_out.element_size() < n * RETIME_SUMMARY_BYTES):
+            raise ValueError("output buffer too small")
+        check(self.lib.ffs_cue_retime_batch(self.handle, n, *ptrs[:8], cues.data_ptr() if n_cues else None, n_cues,
+                                            ptrs[8], ptrs[9], int(radius_samples), int(context_samples), int(penalty_q),
+                                            int(jump_q), int(flags), retime_out.data_ptr() if n_cues else None,
+                                            summary_out.data_ptr(), self._stream(stream)))
 
 
 def range_band_row(max_step: int, knot_blocks: int, radius: int) -> int:

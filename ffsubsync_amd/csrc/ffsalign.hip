@@ -36,6 +36,7 @@
 #include "ffs_drift.h"
 #include "ffs_drift_report.h"
 #include "ffs_cue_report.h"
+#include "ffs_cue_retime.h"
 #include "ffs_drift_smooth.h"
 #include "ffs_drift_range.h"
 #include "ffs_drift_range_smooth.h"
@@ -3263,6 +3264,10 @@ struct ffs_split_plan : PlanCore {
     int64_t refine_bytes;
     DescStaging cue;           // cue report calls only, made by the first: CueDesc[pairs_in_flight]
     int64_t cue_bytes;
+    DescStaging retime;        // cue retime calls only, made by the first: RetimeDesc[pairs_in_flight]
+    int64_t retime_bytes;
+    void* retime_ws = nullptr; // profiles and backpointers of one sub-batch, 6 bytes per (cue, delta); grows on demand
+    int64_t retime_ws_bytes;
 };
 
 int ffs_split_plan_create(int device, int pairs_in_flight, int64_t max_blocks, int64_t max_lags, int64_t max_samples,
@@ -3320,12 +3325,16 @@ int ffs_split_plan_destroy(ffs_split_plan* plan) {
     if (plan->curves) (void)hipFree(plan->curves);
     plan->refine.release();
     plan->cue.release();
+    plan->retime.release();
+    if (plan->retime_ws) (void)hipFree(plan->retime_ws);
     delete plan;
     return FFS_OK;
 }
 
 int64_t ffs_split_plan_workspace_bytes(const ffs_split_plan* plan) {
-    return plan ? plan->work_bytes + plan->curve_bytes + plan->refine_bytes + plan->cue_bytes : 0;
+    return plan ? plan->work_bytes + plan->curve_bytes + plan->refine_bytes + plan->cue_bytes + plan->retime_bytes +
+                      plan->retime_ws_bytes
+                : 0;
 }
 
 namespace {
@@ -3634,6 +3643,129 @@ int ffs_cue_report_batch(ffs_split_plan* plan, int n_pairs, const void* const* r
         hipLaunchKernelGGL(ffsa::k_cue_report, dim3((unsigned)grid), dim3(ffsa::CUE_THREADS), 0, st, dd, nd,
                            (const ffsa::Cue*)cue_dev, (int)radius_samples, (int)context_samples, (ffsa::CueReport*)out_dev);
         HIP_TRY(hipGetLastError());
+    }
+    return plan->end(st);
+}
+
+/* ---- joint cue retiming (csrc/ffs_cue_retime.h) ------------------------------------------------------------------ */
+
+namespace {
+// the pairs [p0, p0 + np) of the next sub-batch: at most pairs_in_flight of them, their cells within the workspace cap
+// (every pair alone fits: checked before); returns np and the sub-batch's cues
+int retime_cut(const int64_t* cue_count, int n_pairs, int p0, int pif, int64_t n_delta, int64_t* rows_out) {
+    int np = 0;
+    int64_t rows = 0;
+    while (p0 + np < n_pairs && np < pif) {
+        const int64_t c = cue_count[p0 + np];
+        if (np > 0 && (rows + c) * n_delta * ffsa::RETIME_CELL_BYTES > ffsa::RETIME_WORK_CAP) break;
+        rows += c;
+        ++np;
+    }
+    *rows_out = rows;
+    return np;
+}
+}  // namespace
+
+int ffs_cue_retime_batch(ffs_split_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
+                         const double* ref_lo, const double* ref_hi, const void* const* sub_ptr, const int64_t* sub_len,
+                         const double* sub_lo, const double* sub_hi, const ffs_cue* cue_dev, int64_t n_cues,
+                         const int64_t* cue_first, const int64_t* cue_count, int64_t radius_samples,
+                         int64_t context_samples, int64_t penalty_q, int64_t jump_q, int flags, ffs_cue_retime* out_dev,
+                         ffs_retime_summary* summary_out_dev, void* hip_stream) {
+    const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
+    if (!plan) return fail(FFS_E_INVALID, "null split plan");
+    if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
+    if (n_pairs == 0) return FFS_OK;
+    if (a.any_null() || !cue_first || !cue_count) return fail(FFS_E_INVALID, "null argument");
+    if (radius_samples < 0 || radius_samples > ffsa::RETIME_MAX_RADIUS)
+        return fail(FFS_E_INVALID, "radius_samples=%lld: need 0 <= radius <= %lld", (long long)radius_samples,
+                    (long long)ffsa::RETIME_MAX_RADIUS);
+    if (context_samples < 0 || context_samples > ffsa::CUE_MAX_CONTEXT)
+        return fail(FFS_E_INVALID, "context_samples=%lld: need 0 <= context <= %lld", (long long)context_samples,
+                    (long long)ffsa::CUE_MAX_CONTEXT);
+    if (penalty_q < 0 || penalty_q > ffsa::RETIME_MAX_PENALTY_Q)
+        return fail(FFS_E_INVALID, "penalty_q=%lld: need 0 <= penalty_q <= 2^20", (long long)penalty_q);
+    if (jump_q < ffsa::RETIME_NO_JUMP || jump_q > ffsa::RETIME_MAX_JUMP_Q)
+        return fail(FFS_E_INVALID, "jump_q=%lld: need -1 (no jump) or 0 <= jump_q <= 2^40", (long long)jump_q);
+    if (flags & ~ffsa::RETIME_KEEP_ORDER) return fail(FFS_E_INVALID, "flags=%d: unknown bits", flags);
+    if (n_cues < 0 || n_cues > INT32_MAX / 2) return fail(FFS_E_INVALID, "n_cues=%lld: need 0 <= n_cues <= 2^30", (long long)n_cues);
+    const int64_t n_delta = 2 * radius_samples + 1;
+    int64_t total = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+        if (int rc = a.check(p)) return rc;
+        if (ref_len[p] > INT32_MAX / 2 || sub_len[p] > INT32_MAX / 2)
+            return fail(FFS_E_INVALID, "pair %d: vectors longer than 2^30 samples", p);
+        if (cue_count[p] < 0) return fail(FFS_E_INVALID, "pair %d: cue_count=%lld < 0", p, (long long)cue_count[p]);
+        if (cue_first[p] < 0 || cue_first[p] > n_cues || cue_count[p] > n_cues - cue_first[p])
+            return fail(FFS_E_INVALID, "pair %d: cues [%lld, +%lld) outside the table of %lld", p, (long long)cue_first[p],
+                        (long long)cue_count[p], (long long)n_cues);
+        if (cue_count[p] * n_delta * ffsa::RETIME_CELL_BYTES > ffsa::RETIME_WORK_CAP)
+            return fail(FFS_E_INVALID, "pair %d: %lld cues x %lld shifts x 6 bytes exceed the retime workspace cap of %lld bytes",
+                        p, (long long)cue_count[p], (long long)n_delta, (long long)ffsa::RETIME_WORK_CAP);
+        total += cue_count[p];
+    }
+    if (!summary_out_dev || ((uintptr_t)summary_out_dev & 7)) return fail(FFS_E_INVALID, "null or misaligned summary output");
+    if (total > 0 && (!cue_dev || !out_dev || ((uintptr_t)cue_dev & 7) || ((uintptr_t)out_dev & 7)))
+        return fail(FFS_E_INVALID, "null or misaligned cue table or retime output");
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (int rc = plan->begin(st)) return rc;
+    const int pif = plan->pairs_in_flight;
+    if (!plan->retime.dev) {  // the first retime call: descriptors and their staging
+        const size_t desc_bytes = sizeof(ffsa::RetimeDesc) * (size_t)pif;
+        if (int rc = plan->retime.create(desc_bytes)) return fail(rc, "split plan: cue retime descriptors");
+        plan->retime_bytes = (int64_t)desc_bytes;
+    }
+    int64_t need = 0;  // the largest sub-batch's cells
+    for (int p0 = 0; p0 < n_pairs;) {
+        int64_t rows;
+        p0 += retime_cut(cue_count, n_pairs, p0, pif, n_delta, &rows);
+        need = std::max(need, split_align_up(rows * n_delta * ffsa::RETIME_CELL_BYTES, 256));
+    }
+    if (need > plan->retime_ws_bytes) {  // grow: no earlier call may still use the old block
+        HIP_TRY(hipEventSynchronize(plan->done));
+        if (plan->retime_ws) (void)hipFree(plan->retime_ws);
+        plan->retime_ws = nullptr;
+        plan->retime_ws_bytes = 0;
+        if (hipMalloc(&plan->retime_ws, (size_t)need) != hipSuccess) {
+            plan->retime_ws = nullptr;
+            return fail(FFS_E_NOMEM, "split plan: %lld cue retime workspace bytes", (long long)need);
+        }
+        plan->retime_ws_bytes = need;
+    }
+    ffsa::RetimeDesc* hd = (ffsa::RetimeDesc*)plan->retime.host;
+    const ffsa::RetimeDesc* dd = (const ffsa::RetimeDesc*)plan->retime.dev;
+    const int n_rounds = (int)((n_delta + 63) / 64);
+    for (int p0 = 0; p0 < n_pairs;) {
+        int64_t rows;
+        const int np = retime_cut(cue_count, n_pairs, p0, pif, n_delta, &rows);
+        if (int rc = plan->retime.wait_free()) return rc;
+        int64_t row = 0;
+        for (int i = 0; i < np; ++i) {  // every pair gets a descriptor: one without cues still gets its summary
+            const int p = p0 + i;
+            ffsa::RetimeDesc& c = hd[i];
+            c.r = (const uint32_t*)a.ref_ptr[p];
+            c.s = (const uint32_t*)a.sub_ptr[p];
+            c.R = ref_len[p];
+            c.S = sub_len[p];
+            c.cue_first = cue_first[p];
+            c.cue_count = cue_count[p];
+            c.grid_first = row * n_rounds;
+            c.ws_first = row;
+            c.out_row = p;
+            row += cue_count[p];
+        }
+        if (int rc = plan->retime.upload(sizeof(ffsa::RetimeDesc) * np, st)) return rc;
+        int32_t* prof = (int32_t*)plan->retime_ws;
+        int16_t* bp = (int16_t*)((char*)plan->retime_ws + rows * n_delta * 4);
+        if (rows > 0)
+            hipLaunchKernelGGL(ffsa::k_retime_profile, dim3((unsigned)(rows * n_rounds)), dim3(ffsa::RETIME_PROFILE_THREADS),
+                               0, st, dd, np, (const ffsa::Cue*)cue_dev, (int)radius_samples, (int)context_samples,
+                               n_rounds, prof);
+        hipLaunchKernelGGL(ffsa::k_retime_dp, dim3(np), dim3(ffsa::RETIME_DP_THREADS), 0, st, dd,
+                           (const ffsa::Cue*)cue_dev, (int)radius_samples, penalty_q, jump_q, flags, (const int32_t*)prof, bp,
+                           (ffsa::RetimeRec*)out_dev, (ffsa::RetimeSummary*)summary_out_dev);
+        HIP_TRY(hipGetLastError());
+        p0 += np;
     }
     return plan->end(st);
 }

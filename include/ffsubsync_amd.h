@@ -777,6 +777,95 @@ int ffs_cue_report_batch(ffs_split_plan* plan, int n_pairs, const void* const* r
                          const int64_t* cue_first, const int64_t* cue_count, int64_t radius_samples,
                          int64_t context_samples, ffs_cue_report* out_dev, void* hip_stream);
 
+/* ---- joint cue retiming: order-preserving per-cue shifts (csrc/ffs_cue_retime.h) -----------------------------------
+ * Replaces: nothing in the reference.  The contract below is pinned against the numpy model tests/retime_model.py and
+ * the enumeration of every path in tests/retime_reference.py.
+ *
+ * One residual shift delta_k in [-rho, rho] per cue, chosen jointly by a Viterbi pass over (cue x shift).  Inputs per
+ * pair exactly as ffs_cue_report_batch; THE TABLE ORDER IS THE CHAIN ORDER (pass cues in file order).  Everything is
+ * exact integer arithmetic.  Live and skipped cues: a = clamp(start, 0, S), e = clamp(end, 0, S); e <= a sets
+ * FFS_RETIME_EMPTY, |lag| > 2^31 sets FFS_RETIME_INVALID; such a cue is skipped (its record holds start, end, lag and
+ * the flag, everything else zero; it takes no part in the chain; its neighbours link to each other).  The other cues
+ * are live, 1..K in table order.  Node score: the window and the counts ov, n11, n1x, nx1 at d = lag + delta are
+ * ffs_cue_report_batch's (m = context_samples), and A_k(delta) = ov - 2 n1x - 2 nx1 + 4 n11, the agreeing minus the
+ * disagreeing samples that have a partner: c(delta) at levels (0,1)/(0,1).  THE PAIR'S LEVELS DO NOT ENTER THE RETIME
+ * (they are checked as ffs_cue_report_batch checks them and otherwise unused): a max-plus recurrence over a thousand
+ * fp64 sums cannot be pinned against an independent optimum, integers can.  u_k(delta) = 64 A_k(delta).
+ * Link from live cue k-1 (shift d') to live cue k (shift d): w = penalty_q |d - d'|, and with jump_q >= 0
+ * w = min(w, jump_q) (both in 64ths of a score sample, FFS_RETIME_Q); g_k = (a_k + lag_k) - (a_{k-1} + lag_{k-1}); with
+ * FFS_RETIME_KEEP_ORDER and g_k >= 0 only d' <= d + g_k is admissible (the shifted start of cue k is not before that of
+ * cue k-1); with g_k < 0 or without the flag every d' is; with the flag, g_k < 0 sets FFS_RETIME_UNORDERED on cue k.
+ *   V_1(d) = u_1(d);  V_k(d) = u_k(d) + max over admissible d' of (V_{k-1}(d') - w(d', d))   (int64)
+ * The backpointer is the maximising d'; delta_K = argmax V_K; every tie goes to the option order on the candidate
+ * itself: the smallest |.|, then + over -.  The path delta_1..delta_K is the backtrack from delta_K.
+ * Invariants: own_total <= total <= best_total, and total = 64 * sum(at) - sum(link).
+ *
+ * Records: out_dev[k] for table entry k, for every entry inside a pair's range (other entries are not written);
+ * summary_out_dev[p] for every pair (all zeros for a pair without a live cue).
+ *
+ * Stream and workspace: the call runs on the split plan as ffs_cue_report_batch does (asynchronous on hip_stream; the
+ * plan orders its calls among themselves).  It uses none of the split workspace.  The first retime call adds one
+ * descriptor block per pair in flight; every call whose largest sub-batch needs more than the plan holds grows the
+ * retime workspace to 6 bytes per (cue, delta) of that sub-batch (an int32 profile and an int16 backpointer), rounded
+ * up to 256 bytes: growing waits for the plan's earlier calls and allocates, so such a call cannot be captured into a
+ * graph.  Both are counted by ffs_split_plan_workspace_bytes from then on.  Sub-batches are cut so that the pair count
+ * stays within pairs_in_flight and the workspace within FFS_RETIME_WORK_CAP (a sub-batch takes pairs in order while
+ * both hold). */
+#define FFS_RETIME_MAX_RADIUS 1024
+#define FFS_RETIME_Q 64
+#define FFS_RETIME_NO_JUMP (-1)
+#define FFS_RETIME_WORK_CAP (256ll << 20) /* bytes of retime workspace one sub-batch may use (256 MiB) */
+#define FFS_RETIME_KEEP_ORDER 1   /* call flag */
+#define FFS_RETIME_EMPTY 1        /* e <= a */
+#define FFS_RETIME_INVALID 2      /* |lag| > 2^31 */
+#define FFS_RETIME_MOVED 4        /* delta != 0 */
+#define FFS_RETIME_JUMP 8         /* jump_q >= 0 and penalty_q |delta - delta'| > jump_q on the incoming link */
+#define FFS_RETIME_UNORDERED 16   /* KEEP_ORDER and g_k < 0 */
+#define FFS_RETIME_ORDER_TIGHT 32 /* the order constraint is active and delta_{k-1} = delta_k + g_k */
+#define FFS_RETIME_AT_EDGE 64     /* rho > 0 and |delta| = rho */
+
+typedef struct ffs_cue_retime {
+    int64_t start, end, lag;   /* the cue as given */
+    int32_t delta;             /* delta_k */
+    int32_t flags;             /* FFS_RETIME_* */
+    int32_t own;               /* A_k(0) */
+    int32_t at;                /* A_k(delta_k) */
+    int32_t best;              /* max over delta of A_k */
+    int32_t best_delta;        /* where, in the option order */
+    int64_t link;              /* w paid on the link into this cue; 0 for the first live cue */
+    int32_t reserved[2];       /* zero */
+} ffs_cue_retime;
+
+typedef struct ffs_retime_summary {
+    int64_t total;             /* V_K(delta_K) */
+    int64_t own_total;         /* 64 * sum of A_k(0) */
+    int64_t best_total;        /* 64 * sum of max A_k */
+    int32_t n_live, n_moved, n_jumps, reserved;
+} ffs_retime_summary;
+#ifdef __cplusplus
+static_assert(sizeof(ffs_cue_retime) == 64, "ffs_cue_retime is 64 bytes");
+static_assert(sizeof(ffs_retime_summary) == 40, "ffs_retime_summary is 40 bytes");
+#else
+_Static_assert(sizeof(ffs_cue_retime) == 64, "ffs_cue_retime is 64 bytes");
+_Static_assert(sizeof(ffs_retime_summary) == 40, "ffs_retime_summary is 40 bytes");
+#endif
+
+/* Retime the cues of n_pairs pairs on hip_stream (host arrays of n_pairs entries; ref_ptr / sub_ptr, cue_dev, out_dev and
+ * summary_out_dev are DEVICE pointers, 8-byte aligned; n_cues = the entries of the table and of out_dev;
+ * summary_out_dev holds n_pairs entries).  radius_samples in [0, FFS_RETIME_MAX_RADIUS], context_samples in
+ * [0, FFS_CUE_MAX_CONTEXT], penalty_q in [0, 2^20], jump_q = FFS_RETIME_NO_JUMP or in [0, 2^40], flags = 0 or
+ * FFS_RETIME_KEEP_ORDER.  Refusals, all before any launch with both outputs untouched: everything
+ * ffs_cue_report_batch refuses; FFS_E_INVALID for a radius, context, penalty_q or jump_q out of range, unknown flag
+ * bits, a null or misaligned summary output, and a pair whose own cue_count * (2 radius + 1) * 6 bytes exceed
+ * FFS_RETIME_WORK_CAP (named in the message).  Cue contents are never validated on the host.  n_pairs = 0 is not an
+ * error; with zero cues in total the summaries are still written (cue_dev and out_dev may then be null). */
+int ffs_cue_retime_batch(ffs_split_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
+                         const double* ref_lo, const double* ref_hi, const void* const* sub_ptr, const int64_t* sub_len,
+                         const double* sub_lo, const double* sub_hi, const ffs_cue* cue_dev, int64_t n_cues,
+                         const int64_t* cue_first, const int64_t* cue_count, int64_t radius_samples,
+                         int64_t context_samples, int64_t penalty_q, int64_t jump_q, int flags, ffs_cue_retime* out_dev,
+                         ffs_retime_summary* summary_out_dev, void* hip_stream);
+
 /* ---- split-aware alignment over any lag range: subtitles for another cut of the video (csrc/ffs_split_range.h) -----
  * Replaces: nothing in the reference.  The contract below is pinned against the numpy model tests/cut_model.py.
  *
