@@ -133,6 +133,13 @@ def drift_align_batch(batch, max_offset_samples: int, block_samples: int = DEFAU
     jumps = torch.empty(n * max_b, dtype=torch.uint8, device=dev)
     plan.align(*batch.pair_arrays(), k, w, float(split_penalty), int(max_step), float(step_cost), offs, scores, jumps,
                totals)
+    return drift_results(offs, scores, jumps, totals, n_blocks, k, sub_len)
+
+
+def drift_results(offs, scores, jumps, totals, n_blocks, block_samples: int, sub_len) -> List[DriftResult]:
+    """One ``DriftResult`` per pair from the device outputs of a drift call (n_pairs * max_b block offsets, scores and
+    jump flags, n_pairs totals) after the call."""
+    n, max_b = len(n_blocks), int(max(n_blocks))
     offs_h = offs.cpu().numpy().reshape(n, max_b)
     scores_h = scores.cpu().numpy().reshape(n, max_b)
     jumps_h = jumps.cpu().numpy().reshape(n, max_b)
@@ -141,7 +148,7 @@ def drift_align_batch(batch, max_offset_samples: int, block_samples: int = DEFAU
     for p in range(n):
         nb = int(n_blocks[p])
         bo, bs, bj = offs_h[p, :nb].copy(), scores_h[p, :nb].copy(), jumps_h[p, :nb].copy()
-        out.append(DriftResult(segments_from_blocks(bo, bs, bj, k, int(sub_len[p])), float(totals_h[p]), bo, bs, bj))
+        out.append(DriftResult(segments_from_blocks(bo, bs, bj, block_samples, int(sub_len[p])), float(totals_h[p]), bo, bs, bj))
     return out
 
 

@@ -25,7 +25,7 @@ from . import _native
 from .constants import SAMPLE_RATE, candidate_ratios
 from .cut_align import (DEFAULT_CUT_PENALTY, full_range, lag_arrays, solve_ratios_windowless, validate_args,
                         validate_range)
-from .drift_align import DEFAULT_MAX_STEP, DriftResult, Segment, map_cues_drift, segments_from_blocks, validate_drift_args
+from .drift_align import DEFAULT_MAX_STEP, DriftResult, Segment, drift_results, map_cues_drift, validate_drift_args
 from .split_align import DEFAULT_BLOCK_SAMPLES, _check_batch, split_outputs
 
 # Chosen on the CPU model over the full range by profiles/drift_range_calibration.py over workloads/cut_drift.py
@@ -97,16 +97,7 @@ def drift_align_range_batch(batch, lag_ranges=None, block_samples: int = DEFAULT
     jumps = torch.empty(n * max_b, dtype=torch.uint8, device=dev)
     plan.align(*batch.pair_arrays(), k, lo, hi, float(split_penalty), int(max_step), float(step_cost), offs, scores,
                jumps, totals)
-    offs_h = offs.cpu().numpy().reshape(n, max_b)
-    scores_h = scores.cpu().numpy().reshape(n, max_b)
-    jumps_h = jumps.cpu().numpy().reshape(n, max_b)
-    totals_h = totals.cpu().numpy()
-    out = []
-    for p in range(n):
-        nb = int(n_blocks[p])
-        bo, bs, bj = offs_h[p, :nb].copy(), scores_h[p, :nb].copy(), jumps_h[p, :nb].copy()
-        out.append(DriftResult(segments_from_blocks(bo, bs, bj, k, int(sub_len[p])), float(totals_h[p]), bo, bs, bj))
-    return out
+    return drift_results(offs, scores, jumps, totals, n_blocks, k, sub_len)
 
 
 def cut_drift_sync(problems, lag_range=None, block_samples: int = DEFAULT_BLOCK_SAMPLES,

@@ -24,7 +24,7 @@ from . import _native, cut_report, quality, split_refine
 from .constants import SAMPLE_RATE, candidate_ratios
 from .cut_align import DEFAULT_CUT_PENALTY, full_range, lag_arrays, solve_ratios_windowless, validate_range
 from .cut_align import validate_args as validate_cut_args
-from .drift_align import DEFAULT_MAX_STEP, DriftResult, Segment, map_cues_drift, segments_from_blocks, validate_drift_args
+from .drift_align import DEFAULT_MAX_STEP, DriftResult, Segment, drift_results, map_cues_drift, validate_drift_args
 from .drift_range import DEFAULT_RANGE_STEP_COST, code_planes
 from .drift_report import DriftReport, SegmentQuality, assess_drift, from_record, jump_support
 from .split_align import DEFAULT_BLOCK_SAMPLES, _check_batch, split_outputs
@@ -170,15 +170,7 @@ def drift_range_report_batch(batch, lag_ranges=None, block_samples: int = DEFAUL
     plan.align(*batch.pair_arrays(), k, lo, hi, float(split_penalty), int(max_step), float(step_cost), offs, scores,
                jumps, totals)
     recs, counts = _records(batch, lo, hi, offs, jumps, k, top_k, exclusion_samples, plan, max_b)
-    offs_h = offs.cpu().numpy().reshape(n, max_b)
-    scores_h = scores.cpu().numpy().reshape(n, max_b)
-    jumps_h = jumps.cpu().numpy().reshape(n, max_b)
-    totals_h = totals.cpu().numpy()
-    res = []
-    for p in range(n):
-        nb = int(n_blocks[p])
-        bo, bs, bj = offs_h[p, :nb].copy(), scores_h[p, :nb].copy(), jumps_h[p, :nb].copy()
-        res.append(DriftResult(segments_from_blocks(bo, bs, bj, k, int(sub_len[p])), float(totals_h[p]), bo, bs, bj))
+    res = drift_results(offs, scores, jumps, totals, n_blocks, k, sub_len)
     if raw:
         return res, recs, counts
     return [DriftReport(r, [from_record(x) for x in recs[p, :int(counts[p])]]) for p, r in enumerate(res)]

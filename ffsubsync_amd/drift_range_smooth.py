@@ -22,7 +22,7 @@ from . import _native
 from .constants import SAMPLE_RATE, candidate_ratios
 from .cut_align import (DEFAULT_CUT_PENALTY, full_range, lag_arrays, solve_ratios_windowless, validate_args,
                         validate_range)
-from .drift_align import DEFAULT_MAX_STEP, DriftResult, segments_from_blocks, validate_drift_args
+from .drift_align import DEFAULT_MAX_STEP, drift_results, validate_drift_args
 from .drift_range import DEFAULT_RANGE_STEP_COST, CutDriftSyncResult, code_planes
 from .drift_smooth import (SmoothResult, SmoothSegment, map_cues_smooth, smooth_segments_from_blocks,
                            validate_smooth_args)
@@ -97,19 +97,11 @@ def smooth_align_range_batch(batch, lag_ranges=None, block_samples: int = DEFAUL
     counts = torch.empty(n, dtype=torch.int32, device=dev)
     plan.smooth(*batch.pair_arrays(), k, lo, hi, float(split_penalty), int(max_step), float(step_cost), int(knot_blocks),
                 int(radius), float(bend_cost), offs, scores, jumps, totals, smooth, knot, rec, counts)
-    offs_h = offs.cpu().numpy().reshape(n, max_b)
-    scores_h = scores.cpu().numpy().reshape(n, max_b)
-    jumps_h = jumps.cpu().numpy().reshape(n, max_b)
-    totals_h = totals.cpu().numpy()
+    res = drift_results(offs, scores, jumps, totals, n_blocks, k, sub_len)
     smooth_h = smooth.cpu().numpy().reshape(n, max_b)
     knot_h = knot.cpu().numpy().reshape(n, max_b)
     recs = rec.cpu().numpy().view(_native.SMOOTH_SEGMENT_DTYPE).reshape(n, max_b)
     counts_h = counts.cpu().numpy()
-    res = []
-    for p in range(n):
-        nb = int(n_blocks[p])
-        bo, bs, bj = offs_h[p, :nb].copy(), scores_h[p, :nb].copy(), jumps_h[p, :nb].copy()
-        res.append(DriftResult(segments_from_blocks(bo, bs, bj, k, int(sub_len[p])), float(totals_h[p]), bo, bs, bj))
     if raw:
         return res, smooth_h, knot_h, recs, counts_h
     out = []

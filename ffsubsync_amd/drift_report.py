@@ -33,8 +33,8 @@ import numpy as np
 
 from . import _native, quality, split_report
 from .constants import SAMPLE_RATE, candidate_ratios
-from .drift_align import (DEFAULT_MAX_STEP, DEFAULT_STEP_COST, DriftResult, Segment, map_cues_drift,
-                          segments_from_blocks, validate_drift_args)
+from .drift_align import (DEFAULT_MAX_STEP, DEFAULT_STEP_COST, DriftResult, Segment, drift_results, map_cues_drift,
+                          validate_drift_args)
 from .split_align import DEFAULT_BLOCK_SAMPLES, DEFAULT_SPLIT_PENALTY, _check_batch, solve_ratios, split_outputs
 
 DEFAULT_TOP_K = quality.DEFAULT_TOP_K
@@ -207,17 +207,9 @@ def drift_report_batch(batch, max_offset_samples: int, block_samples: int = DEFA
     counts = torch.empty(n, dtype=torch.int32, device=dev)
     plan.report(*batch.pair_arrays(), k, w, float(split_penalty), int(max_step), float(step_cost), int(top_k),
                 int(exclusion_samples), offs, scores, jumps, totals, rep, counts)
-    offs_h = offs.cpu().numpy().reshape(n, max_b)
-    scores_h = scores.cpu().numpy().reshape(n, max_b)
-    jumps_h = jumps.cpu().numpy().reshape(n, max_b)
-    totals_h = totals.cpu().numpy()
+    res = drift_results(offs, scores, jumps, totals, n_blocks, k, sub_len)
     recs = rep.cpu().numpy().view(_native.SEGMENT_REPORT_DTYPE).reshape(n, max_b)
     counts_h = counts.cpu().numpy()
-    res = []
-    for p in range(n):
-        nb = int(n_blocks[p])
-        bo, bs, bj = offs_h[p, :nb].copy(), scores_h[p, :nb].copy(), jumps_h[p, :nb].copy()
-        res.append(DriftResult(segments_from_blocks(bo, bs, bj, k, int(sub_len[p])), float(totals_h[p]), bo, bs, bj))
     if raw:
         return res, recs, counts_h
     return [DriftReport(r, [from_record(x) for x in recs[p, :int(counts_h[p])]]) for p, r in enumerate(res)]

@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _native
 from .constants import SAMPLE_RATE, candidate_ratios
-from .drift_align import (DEFAULT_MAX_STEP, DEFAULT_STEP_COST, DriftResult, DriftSyncResult, segments_from_blocks,
+from .drift_align import (DEFAULT_MAX_STEP, DEFAULT_STEP_COST, DriftResult, DriftSyncResult, drift_results,
                           validate_drift_args)
 from .split_align import (DEFAULT_BLOCK_SAMPLES, DEFAULT_SPLIT_PENALTY, _check_batch, _scaled_us, solve_ratios,
                           split_outputs, validate_args)
@@ -143,19 +143,11 @@ def smooth_align_batch(batch, max_offset_samples: int, block_samples: int = DEFA
     counts = torch.empty(n, dtype=torch.int32, device=dev)
     plan.smooth(*batch.pair_arrays(), k, w, float(split_penalty), int(max_step), float(step_cost), int(knot_blocks),
                 int(radius), float(bend_cost), offs, scores, jumps, totals, smooth, knot, rec, counts)
-    offs_h = offs.cpu().numpy().reshape(n, max_b)
-    scores_h = scores.cpu().numpy().reshape(n, max_b)
-    jumps_h = jumps.cpu().numpy().reshape(n, max_b)
-    totals_h = totals.cpu().numpy()
+    res = drift_results(offs, scores, jumps, totals, n_blocks, k, sub_len)
     smooth_h = smooth.cpu().numpy().reshape(n, max_b)
     knot_h = knot.cpu().numpy().reshape(n, max_b)
     recs = rec.cpu().numpy().view(_native.SMOOTH_SEGMENT_DTYPE).reshape(n, max_b)
     counts_h = counts.cpu().numpy()
-    res = []
-    for p in range(n):
-        nb = int(n_blocks[p])
-        bo, bs, bj = offs_h[p, :nb].copy(), scores_h[p, :nb].copy(), jumps_h[p, :nb].copy()
-        res.append(DriftResult(segments_from_blocks(bo, bs, bj, k, int(sub_len[p])), float(totals_h[p]), bo, bs, bj))
     if raw:
         return res, smooth_h, knot_h, recs, counts_h
     out = []

@@ -189,6 +189,59 @@ def test_gaps_at_the_windowed_maximum_seams():
     _check(db, probs, cues, 600, 10, 2, 900, True, "wide")  # every gap below 2 rho
 
 
+LONG_N = 70000
+# (start, end, lag): windows at context 0 of exactly 256 words from a word boundary, 257 words off one, 512 words from a
+# boundary, a short cue, 513 words off a boundary (three slices), 907 words (four slices) and a cue whose partners run
+# past the end of the reference; at context 65536 every window is the whole vector (2188 words, nine slices)
+LONG_CUES = ((3200, 3200 + 8192, 30), (12005, 12005 + 8192, 45), (20480, 20480 + 16384, 5), (36900, 36950, -3),
+             (37001, 37001 + 16384, -20), (40000, 69000, -45), (60000, 69990, 900))
+
+
+def _long_problem():
+    """One pair of 70 000 samples: the subtitle follows the reference at +37 up to sample 36 000 and at -25 behind it,
+    5 % of its samples flipped."""
+    if "long" not in _batches:
+        rng = np.random.RandomState(313)
+        r = speechy(rng, LONG_N, 150)
+        i = np.arange(LONG_N)
+        src = np.clip(i + np.where(i < 36000, 37, -25), 0, LONG_N - 1)
+        s = r[src] ^ (rng.rand(LONG_N) < 0.05).astype(np.uint8)
+        probs = [_pair(r, s, LEVELS[1])]
+        cues = [tuple(np.array([c[k] for c in LONG_CUES], np.int64) for k in range(3))]
+        _batches["long"] = (probs, cues, _device_batch(probs))
+    return _batches["long"]
+
+
+def _window_words(cue, context, S=LONG_N):
+    lo, hi = max(cue[0] - context, 0), min(cue[1] + context, S)
+    return lo >> 5, (hi + 31) >> 5
+
+
+def test_the_long_cues_span_the_slice_seams():
+    """(host data only) The shapes test_long_windows_are_staged_slice_by_slice relies on: CUE_SLICE = 256 window words."""
+    words = [b - a for a, b in (_window_words(c, 0) for c in LONG_CUES)]
+    assert words == [256, 257, 512, 2, 513, 907, 313]
+    assert [c[0] % 32 == 0 for c in LONG_CUES[:5]] == [True, False, True, False, False]
+    assert any(c[1] - c[0] > 3 * 8192 for c in LONG_CUES)  # a window of more than 3 x 8192 samples at any context
+    assert all(_window_words(c, 65536) == (0, (LONG_N + 31) >> 5) for c in LONG_CUES)
+    assert {np.sign(c[2]) for c in LONG_CUES} == {-1, 1} and LONG_CUES[6][1] + LONG_CUES[6][2] > LONG_N
+
+
+@pytest.mark.parametrize("keep_order", [True, False])
+@pytest.mark.parametrize("context", [0, 8192, 65536])
+@pytest.mark.parametrize("radius", [33, 100, 1024])
+def test_long_windows_are_staged_slice_by_slice(radius, context, keep_order):
+    """k_retime_profile stages the reference 256 window words at a time: windows of exactly one slice, one word more, two
+    slices, one word more, four and nine slices, from and off a word boundary, a short cue between them, lags of both
+    signs and partners past the end of the reference -- the second and later iterations of the slice loop (the barrier
+    between slices, the carried bit offset, the clamps far from word 0, the first staged word) under the byte-exact
+    check against retime_model.retime_fast."""
+    probs, cues, db = _long_problem()
+    got, _, sums = _check(db, probs, cues, radius, context, 16, 2000 if keep_order else -1, keep_order, "long windows")
+    assert max(int(e - s) for s, e in zip(got["start"], got["end"])) > 3 * 8192
+    assert sums["n_live"].tolist() == sums["n_moved"].tolist() == [len(LONG_CUES)]  # every cue live and moved
+
+
 def test_constant_profiles_and_ties():
     from ffsubsync_amd import cue_retime as ct
 

@@ -488,9 +488,14 @@ def _row(db, p):
     return DeviceBatch(db.data, db.offs[p:p + 1], db.lens[p:p + 1], db.lo[p:p + 1], db.hi[p:p + 1], db.dtype)
 
 
+FAMILY_MODELS = {}  # family: (model, same) as ``_families`` assembles them (tests/stream_cases.py reads them too)
+
+
 def _family(name, call, model, same):
     """One block family: ``call(row, pr)`` on the one-pair view of every problem in the hostile image, ``model(pr)`` its
     numpy model, ``same(got, want, pr)`` the family's own comparison (None or true when equal)."""
+    FAMILY_MODELS[name] = (model, same)
+
     def run(layout):
         probs = _family_problems(name)
         img, db = _family_image(probs, layout)
