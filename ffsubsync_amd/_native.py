@@ -1028,18 +1028,33 @@ def _pair_buffers(ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, su
     return n, [b.ctypes.data for b in bufs], bufs
 
 
+def _nbytes(tensor) -> int:
+    return tensor.numel() * tensor.element_size()
+
+
+def _check_block_records(n, counts_out, records_out, record_bytes, offsets, *per_block, what="output buffer too small"):
+    """The size tests of a call that writes ``n`` counts and one record of ``record_bytes`` per entry of ``offsets`` (the
+    n_pairs * max_b block offsets), and reads or writes the ``per_block`` tensors at as many entries."""
+    if (counts_out.numel() < n or _nbytes(records_out) < offsets.numel() * record_bytes
+            or any(t.numel() < offsets.numel() for t in per_block)):
+        raise ValueError(what)
+
+
 class _SidePlan:
     """Handle lifetime of the plans beside the headline aligner.  A subclass names its C entry points (``_create``,
-    ``_destroy``, ``_workspace``) and passes its size limits in the order ``_create`` takes them; ``fits`` takes the
-    same limits in the same order."""
+    ``_destroy``, ``_workspace``) and its size limits (``_limits``) in the order ``_create`` takes them: they become
+    attributes, and ``fits`` takes them in the same order."""
 
     _create = _destroy = _workspace = ""
+    _limits: Tuple[str, ...] = ()
 
     def __init__(self, dims, device: Optional[int]) -> None:
+        self._dims = tuple(int(d) for d in dims)
+        for name, value in zip(self._limits, self._dims):
+            setattr(self, name, value)
         torch = require_gpu()
         self.lib = load()
         self.device = torch.cuda.current_device() if device is None else int(device)
-        self._dims = tuple(int(d) for d in dims)
         handle = ctypes.c_void_p()
         check(getattr(self.lib, self._create)(self.device, *self._dims, ctypes.byref(handle)))
         self.handle = handle
@@ -1067,18 +1082,22 @@ class _SidePlan:
             pass
 
 
-class SplitPlan(_SidePlan):
+class _BlockPlan(_SidePlan):
+    """A side plan sized by pairs in flight, blocks, lags and samples."""
+
+    _limits = ("pairs_in_flight", "max_blocks", "max_lags", "max_samples")
+
+    def __init__(self, pairs_in_flight: int, max_blocks: int, max_lags: int, max_samples: int,
+                 device: Optional[int] = None) -> None:
+        super().__init__((pairs_in_flight, max_blocks, max_lags, max_samples), device)
+
+
+class SplitPlan(_BlockPlan):
     """Owns one ``ffs_split_plan``: the workspace of the split-aware aligner (``split_align.py``) for
     ``pairs_in_flight`` problems of up to ``max_samples`` subtitle samples, ``max_blocks`` blocks and ``max_lags`` = 2W
     lags."""
 
     _create, _destroy, _workspace = "ffs_split_plan_create", "ffs_split_plan_destroy", "ffs_split_plan_workspace_bytes"
-
-    def __init__(self, pairs_in_flight: int, max_blocks: int, max_lags: int, max_samples: int,
-                 device: Optional[int] = None) -> None:
-        self.pairs_in_flight, self.max_blocks = int(pairs_in_flight), int(max_blocks)
-        self.max_lags, self.max_samples = int(max_lags), int(max_samples)
-        super().__init__((pairs_in_flight, max_blocks, max_lags, max_samples), device)
 
     def align(self, ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, block_samples: int,
               max_offset_samples: int, split_penalty: float, offsets_out, scores_out, totals_out,
@@ -1096,8 +1115,7 @@ class SplitPlan(_SidePlan):
         """``ffs_align_split_report_batch``: ``align``'s outputs plus a uint8 CUDA tensor of n_pairs * max_b * 224 bytes
         of piece reports and an int32 one of n_pairs piece counts (asynchronous)."""
         n, ptrs, _bufs = _pair_buffers(ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi)
-        if n_pieces_out.numel() < n or report_out.numel() * report_out.element_size() < offsets_out.numel() * PIECE_REPORT_BYTES:
-            raise ValueError("output buffer too small")
+        _check_block_records(n, n_pieces_out, report_out, PIECE_REPORT_BYTES, offsets_out)
         check(self.lib.ffs_align_split_report_batch(self.handle, n, *ptrs, int(block_samples), int(max_offset_samples),
                                                     float(split_penalty), int(top_k), int(exclusion_samples),
                                                     offsets_out.data_ptr(), scores_out.data_ptr(), totals_out.data_ptr(),
@@ -1110,8 +1128,7 @@ class SplitPlan(_SidePlan):
         into a uint8 CUDA tensor of n_pairs * max_b * 88 bytes of break records and an int32 one of n_pairs break counts
         (asynchronous); ``unmatched_margin`` NaN = a single cut."""
         n, ptrs, _bufs = _pair_buffers(ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi)
-        if n_breaks_out.numel() < n or refine_out.numel() * refine_out.element_size() < offsets.numel() * BREAK_REFINE_BYTES:
-            raise ValueError("output buffer too small")
+        _check_block_records(n, n_breaks_out, refine_out, BREAK_REFINE_BYTES, offsets)
         check(self.lib.ffs_split_refine_batch(self.handle, n, *ptrs, int(block_samples), offsets.data_ptr(),
                                               int(radius_samples), float(unmatched_margin), refine_out.data_ptr(),
                                               n_breaks_out.data_ptr(), self._stream(stream)))
@@ -1123,9 +1140,7 @@ class SplitPlan(_SidePlan):
         offsets and the uint8 one of as many jump flags (as ``DriftPlan.align`` or a smooth fit wrote them) into break
         records at the jumps and an int32 tensor of n_pairs jump counts (asynchronous)."""
         n, ptrs, _bufs = _pair_buffers(ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi)
-        if (n_jumps_out.numel() < n or jumps.numel() < offsets.numel()
-                or refine_out.numel() * refine_out.element_size() < offsets.numel() * BREAK_REFINE_BYTES):
-            raise ValueError("buffer too small")
+        _check_block_records(n, n_jumps_out, refine_out, BREAK_REFINE_BYTES, offsets, jumps, what="buffer too small")
         check(self.lib.ffs_drift_refine_batch(self.handle, n, *ptrs, int(block_samples), offsets.data_ptr(),
                                               jumps.data_ptr(), int(radius_samples), float(unmatched_margin),
                                               refine_out.data_ptr(), n_jumps_out.data_ptr(), self._stream(stream)))
@@ -1138,7 +1153,7 @@ class SplitPlan(_SidePlan):
         n_cues = cues.numel() * cues.element_size() // CUE_BYTES
         n, ptrs, _bufs = _pair_buffers(ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, cue_first,
                                        cue_count)
-        if report_out.numel() * report_out.element_size() < n_cues * CUE_REPORT_BYTES:
+        if _nbytes(report_out) < n_cues * CUE_REPORT_BYTES:
             raise ValueError("output buffer too small")
         check(self.lib.ffs_cue_report_batch(self.handle, n, *ptrs[:8], cues.data_ptr(), n_cues, ptrs[8], ptrs[9],
                                             int(radius_samples), int(context_samples), report_out.data_ptr(),
@@ -1153,8 +1168,7 @@ class SplitPlan(_SidePlan):
         n_cues = cues.numel() * cues.element_size() // CUE_BYTES
         n, ptrs, _bufs = _pair_buffers(ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, cue_first,
                                        cue_count)
-        if (retime_out.numel() * retime_out.element_size() < n_cues * CUE_RETIME_BYTES
-                or summary_out.numel() * summary_out.element_size() < n * RETIME_SUMMARY_BYTES):
+        if _nbytes(retime_out) < n_cues * CUE_RETIME_BYTES or _nbytes(summary_out) < n * RETIME_SUMMARY_BYTES:
             raise ValueError("output buffer too small")
         check(self.lib.ffs_cue_retime_batch(self.handle, n, *ptrs[:8], cues.data_ptr() if n_cues else None, n_cues,
                                             ptrs[8], ptrs[9], int(radius_samples), int(context_samples), int(penalty_q),
@@ -1171,18 +1185,12 @@ def range_band_row(max_step: int, knot_blocks: int, radius: int) -> int:
 MAX_DRIFT_STEP = 7  # DRIFT_MAX_STEP (csrc/ffs_drift.h): the 4-bit code holds STAY, 14 moves and JUMP
 
 
-class DriftPlan(_SidePlan):
+class DriftPlan(_BlockPlan):
     """Owns one ``ffs_drift_plan``: the workspace of the drift-tolerant aligner (``drift_align.py``) for
     ``pairs_in_flight`` problems of up to ``max_samples`` subtitle samples, ``max_blocks`` blocks and ``max_lags`` = 2W
     lags."""
 
     _create, _destroy, _workspace = "ffs_drift_plan_create", "ffs_drift_plan_destroy", "ffs_drift_plan_workspace_bytes"
-
-    def __init__(self, pairs_in_flight: int, max_blocks: int, max_lags: int, max_samples: int,
-                 device: Optional[int] = None) -> None:
-        self.pairs_in_flight, self.max_blocks = int(pairs_in_flight), int(max_blocks)
-        self.max_lags, self.max_samples = int(max_lags), int(max_samples)
-        super().__init__((pairs_in_flight, max_blocks, max_lags, max_samples), device)
 
     def align(self, ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, block_samples: int,
               max_offset_samples: int, split_penalty: float, max_step: int, step_cost: float, offsets_out, scores_out,
@@ -1203,9 +1211,7 @@ class DriftPlan(_SidePlan):
         bytes of segment reports and an int32 one of n_pairs segment counts.  The call reads each sub-batch's segment
         counts back, so it waits for the stream."""
         n, ptrs, _bufs = _pair_buffers(ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi)
-        if (n_segments_out.numel() < n
-                or report_out.numel() * report_out.element_size() < offsets_out.numel() * SEGMENT_REPORT_BYTES):
-            raise ValueError("output buffer too small")
+        _check_block_records(n, n_segments_out, report_out, SEGMENT_REPORT_BYTES, offsets_out)
         check(self.lib.ffs_align_drift_report_batch(self.handle, n, *ptrs, int(block_samples), int(max_offset_samples),
                                                     float(split_penalty), int(max_step), float(step_cost), int(top_k),
                                                     int(exclusion_samples), offsets_out.data_ptr(),
@@ -1221,9 +1227,7 @@ class DriftPlan(_SidePlan):
         n_pairs * max_b entries, a CUDA tensor of n_pairs * max_b * 32 bytes of segment records and an int32 one of
         n_pairs segment counts (asynchronous)."""
         n, ptrs, _bufs = _pair_buffers(ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi)
-        if (n_segments_out.numel() < n or smooth_out.numel() < offsets_out.numel() or knot_out.numel() < offsets_out.numel()
-                or segments_out.numel() * segments_out.element_size() < offsets_out.numel() * SMOOTH_SEGMENT_BYTES):
-            raise ValueError("output buffer too small")
+        _check_block_records(n, n_segments_out, segments_out, SMOOTH_SEGMENT_BYTES, offsets_out, smooth_out, knot_out)
         check(self.lib.ffs_align_drift_smooth_batch(self.handle, n, *ptrs, int(block_samples), int(max_offset_samples),
                                                     float(split_penalty), int(max_step), float(step_cost),
                                                     int(knot_blocks), int(radius), float(bend_cost),
@@ -1233,19 +1237,13 @@ class DriftPlan(_SidePlan):
                                                     self._stream(stream)))
 
 
-class SplitRangePlan(_SidePlan):
+class SplitRangePlan(_BlockPlan):
     """Owns one ``ffs_split_range_plan``: the workspace of the lag-range split aligner (``cut_align.py``) for
     ``pairs_in_flight`` problems of up to ``max_samples`` samples per vector, ``max_blocks`` blocks and ``max_lags``
     lags."""
 
     _create = "ffs_split_range_plan_create"
     _destroy, _workspace = "ffs_split_range_plan_destroy", "ffs_split_range_plan_workspace_bytes"
-
-    def __init__(self, pairs_in_flight: int, max_blocks: int, max_lags: int, max_samples: int,
-                 device: Optional[int] = None) -> None:
-        self.pairs_in_flight, self.max_blocks = int(pairs_in_flight), int(max_blocks)
-        self.max_lags, self.max_samples = int(max_lags), int(max_samples)
-        super().__init__((pairs_in_flight, max_blocks, max_lags, max_samples), device)
 
     def align(self, ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, block_samples: int, lag_lo,
               lag_hi, split_penalty: float, offsets_out, scores_out, totals_out, stream: Optional[int] = None) -> None:
@@ -1264,8 +1262,7 @@ class SplitRangePlan(_SidePlan):
         (as ``align`` wrote them) over each pair's range into a uint8 CUDA tensor of n_pairs * max_b * 224 bytes and an
         int32 one of n_pairs piece counts.  The call waits for the stream's earlier work (it reads the offsets back)."""
         n, ptrs, _bufs = _pair_buffers(ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, lag_lo, lag_hi)
-        if n_pieces_out.numel() < n or report_out.numel() * report_out.element_size() < offsets.numel() * PIECE_REPORT_BYTES:
-            raise ValueError("output buffer too small")
+        _check_block_records(n, n_pieces_out, report_out, PIECE_REPORT_BYTES, offsets)
         check(self.lib.ffs_split_range_report_batch(self.handle, n, *ptrs[:8], int(block_samples), *ptrs[8:],
                                                     offsets.data_ptr(), int(top_k), int(exclusion_samples),
                                                     report_out.data_ptr(), n_pieces_out.data_ptr(), self._stream(stream)))
@@ -1278,11 +1275,10 @@ class DriftRangePlan(_SidePlan):
 
     _create = "ffs_drift_range_plan_create"
     _destroy, _workspace = "ffs_drift_range_plan_destroy", "ffs_drift_range_plan_workspace_bytes"
+    _limits = _BlockPlan._limits + ("max_step_cap",)
 
     def __init__(self, pairs_in_flight: int, max_blocks: int, max_lags: int, max_samples: int, max_step_cap: int,
                  device: Optional[int] = None) -> None:
-        self.pairs_in_flight, self.max_blocks = int(pairs_in_flight), int(max_blocks)
-        self.max_lags, self.max_samples, self.max_step_cap = int(max_lags), int(max_samples), int(max_step_cap)
         super().__init__((pairs_in_flight, max_blocks, max_lags, max_samples, max_step_cap), device)
 
     def align(self, ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, block_samples: int, lag_lo,
@@ -1315,9 +1311,7 @@ class DriftRangePlan(_SidePlan):
         n_pairs * max_b entries, a CUDA tensor of n_pairs * max_b * 32 bytes of segment records and an int32 one of
         n_pairs segment counts (asynchronous)."""
         n, ptrs, _bufs = _pair_buffers(ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, lag_lo, lag_hi)
-        if (n_segments_out.numel() < n or smooth_out.numel() < offsets_out.numel() or knot_out.numel() < offsets_out.numel()
-                or segments_out.numel() * segments_out.element_size() < offsets_out.numel() * SMOOTH_SEGMENT_BYTES):
-            raise ValueError("output buffer too small")
+        _check_block_records(n, n_segments_out, segments_out, SMOOTH_SEGMENT_BYTES, offsets_out, smooth_out, knot_out)
         check(self.lib.ffs_align_drift_range_smooth_batch(self.handle, n, *ptrs[:8], int(block_samples), *ptrs[8:],
                                                           float(split_penalty), int(max_step), float(step_cost),
                                                           int(knot_blocks), int(radius), float(bend_cost),
@@ -1343,9 +1337,7 @@ class DriftRangePlan(_SidePlan):
         tensor of n_pairs * max_b * 264 bytes and an int32 one of n_pairs segment counts.  The call waits for the
         stream's earlier work (it reads the path back)."""
         n, ptrs, _bufs = _pair_buffers(ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi, lag_lo, lag_hi)
-        if (n_segments_out.numel() < n or jumps.numel() < offsets.numel()
-                or report_out.numel() * report_out.element_size() < offsets.numel() * SEGMENT_REPORT_BYTES):
-            raise ValueError("output buffer too small")
+        _check_block_records(n, n_segments_out, report_out, SEGMENT_REPORT_BYTES, offsets, jumps)
         check(self.lib.ffs_drift_range_report_batch(self.handle, n, *ptrs[:8], int(block_samples), *ptrs[8:],
                                                     offsets.data_ptr(), jumps.data_ptr(), int(top_k),
                                                     int(exclusion_samples), report_out.data_ptr(),
@@ -1359,8 +1351,9 @@ class QualityPlan(_SidePlan):
 
     _create, _destroy, _workspace = "ffs_quality_plan_create", "ffs_quality_plan_destroy", "ffs_quality_plan_workspace_bytes"
 
+    _limits = ("pairs_in_flight", "max_lags", "max_samples")
+
     def __init__(self, pairs_in_flight: int, max_lags: int, max_samples: int, device: Optional[int] = None) -> None:
-        self.pairs_in_flight, self.max_lags, self.max_samples = int(pairs_in_flight), int(max_lags), int(max_samples)
         self.scratch = None  # int32 CUDA tensor: FFS_DTYPE_U1 images of FFS_DTYPE_RUNS vectors
         super().__init__((pairs_in_flight, max_lags, max_samples), device)
 
@@ -1376,7 +1369,7 @@ class QualityPlan(_SidePlan):
         """``ffs_align_quality_batch`` on host descriptor arrays (one entry per pair) into a uint8 CUDA tensor of
         n_pairs * 160 bytes (asynchronous).  ``max_offset_samples`` None = no window."""
         n, ptrs, _bufs = _pair_buffers(ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi)
-        if out.numel() * out.element_size() < n * QUALITY_RESULT_BYTES:
+        if _nbytes(out) < n * QUALITY_RESULT_BYTES:
             raise ValueError("output buffer too small")
         mo = -1 if max_offset_samples is None else int(max_offset_samples)
         check(self.lib.ffs_align_quality_batch(self.handle, n, *ptrs, mo, int(top_k), int(exclusion_samples),
@@ -1404,10 +1397,10 @@ class MatchPlan(_SidePlan):
 
     _create, _destroy, _workspace = "ffs_match_plan_create", "ffs_match_plan_destroy", "ffs_match_plan_workspace_bytes"
 
+    _limits = ("pairs_in_flight", "max_lags", "max_samples", "max_vectors")
+
     def __init__(self, pairs_in_flight: int, max_lags: int, max_samples: int, max_vectors: int,
                  device: Optional[int] = None) -> None:
-        self.pairs_in_flight, self.max_lags = int(pairs_in_flight), int(max_lags)
-        self.max_samples, self.max_vectors = int(max_samples), int(max_vectors)
         super().__init__((pairs_in_flight, max_lags, max_samples, max_vectors), device)
 
     def report(self, ref_list, ref_len, ref_lo, ref_hi, sub_list, sub_len, sub_lo, sub_hi, pair_ref, pair_sub,
@@ -1425,7 +1418,7 @@ class MatchPlan(_SidePlan):
         ps = np.ascontiguousarray(pair_sub, dtype=np.int32)
         if pr.size != ps.size:
             raise ValueError("one reference index and one subtitle index per pair")
-        if out.numel() * out.element_size() < pr.size * QUALITY_RESULT_BYTES:
+        if _nbytes(out) < pr.size * QUALITY_RESULT_BYTES:
             raise ValueError("output buffer too small")
         mo = -1 if max_offset_samples is None else int(max_offset_samples)
         check(self.lib.ffs_match_quality_batch(self.handle, rt[0].size, *[b.ctypes.data for b in rt], stb[0].size,

@@ -3137,13 +3137,64 @@ struct DescStaging {
     }
 };
 
-// What every plan holds: its device, the pairs one sub-batch solves, the workspace and the `done` event.
+// A workspace laid out as a byte count that hands out typed blocks.  A plan states its layout once, as a function of a
+// Carver, and runs it twice: over no memory to sum the bytes, then over the allocation to place the same blocks.
+extern "C++" {  // (a member template, inside this file's extern "C" block)
+struct Carver {
+    char* base;  // nullptr: only count
+    int64_t used = 0;
+
+    // `count` elements, the block's bytes rounded up to a multiple of `pad`
+    template <typename T>
+    T* take(int64_t count, int64_t pad = 1) {
+        T* at = base ? (T*)(base + used) : nullptr;
+        used += split_align_up(count * (int64_t)sizeof(T), pad);
+        return at;
+    }
+};
+}
+
+// What every plan holds: its device, the pairs one sub-batch solves, the workspace, the `done` event, and the blocks
+// that calls made on first use.
 struct PlanCore {
     int device = 0;
     int pairs_in_flight = 0;
     void* work = nullptr;
     int64_t work_bytes = 0;
     hipEvent_t done = nullptr;  // the plan's last call has finished with the workspace
+    DescStaging desc;           // the descriptors of one sub-batch, made at create (each plan says what they are)
+    std::vector<void*> blocks;            // device blocks made after open()
+    std::vector<DescStaging*> stagings;   // descriptor blocks made after open()
+    int64_t extra_bytes = 0;              // device bytes of both
+
+    int64_t workspace_bytes() const { return work_bytes + extra_bytes; }
+
+    // A block made by the first call that needs it, after that call's checks: "<plan>: <bytes> <kind> workspace bytes"
+    // when the device refuses it.
+    int add_block(void** out, int64_t bytes, const char* plan, const char* kind) {
+        void* mem = nullptr;
+        if (hipMalloc(&mem, (size_t)bytes) != hipSuccess)
+            return fail(FFS_E_NOMEM, "%s: %lld %s workspace bytes", plan, (long long)bytes, kind);
+        blocks.push_back(mem);
+        extra_bytes += bytes;
+        *out = mem;
+        return FFS_OK;
+    }
+    // the retime workspace before it is made again larger (the caller has waited for `done`)
+    void drop_block(void* block, int64_t bytes) {
+        const auto at = std::find(blocks.begin(), blocks.end(), block);
+        if (at == blocks.end()) return;
+        (void)hipFree(block);
+        blocks.erase(at);
+        extra_bytes -= bytes;
+    }
+    // descriptors (and `dev_extra` bytes of device scratch behind them) made by the first call that needs them
+    int add_staging(DescStaging* s, size_t bytes, size_t dev_extra, const char* what) {
+        if (int rc = s->create(bytes, dev_extra)) return fail(rc, "%s", what);
+        stagings.push_back(s);
+        extra_bytes += (int64_t)(bytes + dev_extra);
+        return FFS_OK;
+    }
 
     // at create: the workspace, then `done`; on failure the caller destroys the plan
     int open(int dev, int pif, int64_t bytes, const char* what) {
@@ -3160,7 +3211,7 @@ struct PlanCore {
         }
         return FFS_OK;
     }
-    // at destroy, before anything else is freed: wait for the last call, then free the workspace
+    // at destroy, before anything else is freed: wait for the last call, then free the workspace and every later block
     void close() {
         (void)hipSetDevice(device);
         if (done) {
@@ -3168,6 +3219,9 @@ struct PlanCore {
             (void)hipEventDestroy(done);
         }
         if (work) (void)hipFree(work);
+        for (void* b : blocks) (void)hipFree(b);
+        for (DescStaging* s : stagings) s->release();
+        desc.release();
     }
     // every batch call, after its checks: on the plan's device, `st` waits until the previous call (any stream) is done
     int begin(hipStream_t st) {
@@ -3208,6 +3262,13 @@ struct Pairs {
             return fail(FFS_E_INVALID, "pair %d: levels must be finite", p);
         return FFS_OK;
     }
+    // ... and for the kernels that index samples with an int32
+    int check_short(int p) const {
+        if (int rc = check(p)) return rc;
+        if (ref_len[p] > INT32_MAX / 2 || sub_len[p] > INT32_MAX / 2)
+            return fail(FFS_E_INVALID, "pair %d: vectors longer than 2^30 samples", p);
+        return FFS_OK;
+    }
 
     Levels levels(int p) const {
 #pragma clang fp contract(off)
@@ -3240,79 +3301,202 @@ struct Pairs {
         d.out_row = p;
         return d;
     }
+
+    // pair p's RefineDesc, its null-score scratch at pair_ws (or none), its outputs at row p
+    ffsa::RefineDesc refine_desc(int p, double* pair_ws) const {
+        const Levels v = levels(p);
+        ffsa::RefineDesc d;
+        d.r = (const uint32_t*)ref_ptr[p];
+        d.s = (const uint32_t*)sub_ptr[p];
+        d.R = ref_len[p];
+        d.S = sub_len[p];
+        d.r0 = v.r0;
+        d.r1 = v.r1;
+        d.s0 = v.s0;
+        d.s1 = v.s1;
+        d.c00 = v.c00;
+        d.c01 = v.c01;
+        d.c10 = v.c10;
+        d.c11 = v.c11;
+        d.pair_ws = pair_ws;
+        d.out_row = p;
+        return d;
+    }
 };
+
+/* The opening of every batch call: FFS_E_INVALID for a null plan ("null <name> plan"), n_pairs < 0 or, with pairs to
+   solve, a null argument; FFS_OK when there are no pairs (the call is done); CALL_GO_ON otherwise. */
+constexpr int CALL_GO_ON = 1;
+int check_call(const void* plan, const char* name, int n_pairs, bool null_argument) {
+    if (!plan) return fail(FFS_E_INVALID, "null %s plan", name);
+    if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
+    if (n_pairs == 0) return FFS_OK;
+    if (null_argument) return fail(FFS_E_INVALID, "null argument");
+    return CALL_GO_ON;
+}
 
 int check_block_samples(int64_t K) {
     if (K < 256 || K > ffsa::SPLIT_MAX_K || K % 32 != 0)
         return fail(FFS_E_INVALID, "block_samples=%lld: need a multiple of 32 in [256, 32768]", (long long)K);
     return FFS_OK;
 }
+
+// W = max_offset_samples of the window family, against the kernels' limit and the plan's
+int check_window(int64_t W, int64_t plan_max_lags) {
+    if (W < 1 || 2 * W > 262144) return fail(FFS_E_INVALID, "max_offset_samples=%lld: need 1 <= W, 2W <= 262144", (long long)W);
+    if (2 * W > plan_max_lags)
+        return fail(FFS_E_INVALID, "2 * max_offset_samples = %lld exceeds the plan's max_lags %lld", (long long)(2 * W),
+                    (long long)plan_max_lags);
+    return FFS_OK;
+}
+
+int check_split_penalty(double split_penalty) {
+    if (!(split_penalty >= 0.0)) return fail(FFS_E_INVALID, "split_penalty must be >= 0 (not NaN)");
+    return FFS_OK;
+}
+
+// `cap_note` names the cap where it is the plan's own
+int check_step(int max_step, int cap, const char* cap_note, double step_cost) {
+    if (max_step < 0 || max_step > cap) return fail(FFS_E_INVALID, "max_step=%d outside [0, %d]%s", max_step, cap, cap_note);
+    if (!(step_cost >= 0.0) || !std::isfinite(step_cost)) return fail(FFS_E_INVALID, "step_cost must be finite and >= 0");
+    return FFS_OK;
+}
+
+int check_peaks(int top_k, int64_t exclusion_samples) {
+    if (top_k < 1 || top_k > ffsa::QUAL_MAX_PEAKS) return fail(FFS_E_INVALID, "top_k=%d outside [1, 8]", top_k);
+    if (exclusion_samples < 1) return fail(FFS_E_INVALID, "exclusion_samples=%lld: need >= 1", (long long)exclusion_samples);
+    return FFS_OK;
+}
+
+// pair p's blocks of K samples against the plan's limit; keeps the largest count
+int check_blocks(int p, int64_t S, int64_t K, int64_t plan_max_blocks, int64_t* max_b) {
+    const int64_t B = (S + K - 1) / K;
+    if (B > plan_max_blocks)
+        return fail(FFS_E_INVALID, "pair %d: %lld blocks exceed the plan's max_blocks %lld", p, (long long)B,
+                    (long long)plan_max_blocks);
+    *max_b = std::max(*max_b, B);
+    return FFS_OK;
+}
 }  // namespace
 
 /* ---- split-aware alignment (csrc/ffs_split.h) ---------------------------------------------------------------- */
 
-struct ffs_split_plan : PlanCore {
+namespace {
+// What the split plan and the drift plan share: counts over a window of max_lags = 2W lags, the DP's tables, prefixes.
+// The split DP keeps one stay bit per (block, lag) and one V row; the drift DP keeps DRIFT_PLANES code bits and two V rows.
+struct WindowPlan : PlanCore {
     int64_t max_blocks, max_lags, max_samples;
-    int64_t lpad, pw_s, pw_r;  // padded lag row, prefix words per vector
-    ffsa::SplitWs ws;
-    int32_t* pre;              // [slot][pw_s + pw_r]
-    DescStaging desc;          // SplitDesc[pairs_in_flight]
-    uint32_t* curves;          // report calls only, made by the first: per-piece n11 rows, [slot][max_blocks][lpad]
-    int64_t curve_bytes;
-    DescStaging refine;        // refine calls only, made by the first: RefineDesc[pairs_in_flight], then on the device
-    double* refine_scratch;    // the null-score scratch [pairs_in_flight][4]
-    int64_t refine_bytes;
-    DescStaging cue;           // cue report calls only, made by the first: CueDesc[pairs_in_flight]
-    int64_t cue_bytes;
-    DescStaging retime;        // cue retime calls only, made by the first: RetimeDesc[pairs_in_flight]
-    int64_t retime_bytes;
-    void* retime_ws = nullptr; // profiles and backpointers of one sub-batch, 6 bytes per (cue, delta); grows on demand
-    int64_t retime_ws_bytes;
+    int64_t lpad, pw_s, pw_r, pre_slot;  // padded lag row, prefix words per vector and per slot
+    ffsa::SplitWs ws;            // counts, stay bits (split only), V, arg
+    unsigned long long* codes;   // drift only: [slot][max_blocks][lpad / 64][DRIFT_PLANES]
+    int64_t codes_slot;
+    int32_t* pre;                // [slot][pw_s + pw_r]
+                                 // desc: SplitDesc[pairs_in_flight]
+
+    void carve(Carver& c, bool drift) {
+        const int64_t n = pairs_in_flight;
+        ws.counts = c.take<uint16_t>(n * ws.counts_slot);
+        ws.stay = drift ? nullptr : c.take<unsigned long long>(n * ws.stay_slot);
+        codes = drift ? c.take<unsigned long long>(n * codes_slot) : nullptr;
+        ws.V = c.take<double>(n * ws.v_slot);
+        ws.arg = c.take<int32_t>(n * ws.arg_slot);
+        pre = c.take<int32_t>(n * pre_slot);
+    }
 };
 
-int ffs_split_plan_create(int device, int pairs_in_flight, int64_t max_blocks, int64_t max_lags, int64_t max_samples,
-                          ffs_split_plan** out) {
-    if (!out) return fail(FFS_E_INVALID, "null output handle");
-    *out = nullptr;
+int window_plan_dims_check(const char* what, int pairs_in_flight, int64_t max_blocks, int64_t max_lags, int64_t max_samples) {
     if (pairs_in_flight < 1 || max_blocks < 1 || max_lags < 2 || max_lags > 262144 || max_samples < 1)
-        return fail(FFS_E_INVALID, "split plan: need pairs_in_flight >= 1, max_blocks >= 1, 2 <= max_lags <= 262144, "
-                                   "max_samples >= 1");
-    HIP_TRY(hipSetDevice(device));
-    ffs_split_plan* p = new (std::nothrow) ffs_split_plan();
-    if (!p) return fail(FFS_E_NOMEM, "split plan");
+        return fail(FFS_E_INVALID, "%s: need pairs_in_flight >= 1, max_blocks >= 1, 2 <= max_lags <= 262144, "
+                                   "max_samples >= 1", what);
+    return FFS_OK;
+}
+
+// the sizes, the workspace and the descriptors of a new window plan; on failure the caller destroys the plan
+int window_plan_open(WindowPlan* p, const char* what, bool drift, int device, int pairs_in_flight, int64_t max_blocks,
+                     int64_t max_lags, int64_t max_samples) {
+    p->pairs_in_flight = pairs_in_flight;
     p->max_blocks = max_blocks;
     p->max_lags = max_lags;
     p->max_samples = max_samples;
     p->lpad = split_align_up(max_lags, 64);
     p->pw_s = max_samples / 32 + 2;
     p->pw_r = (max_samples + max_lags / 2) / 32 + 2;
-    const int64_t counts_slot = split_align_up(max_blocks * p->lpad, 128);       // uint16
-    const int64_t stay_slot = split_align_up(max_blocks * (p->lpad / 64), 32);   // uint64
-    const int64_t v_slot = split_align_up(p->lpad, 32);                          // double
-    const int64_t arg_slot = split_align_up(max_blocks, 64);                     // int32
-    const int64_t pre_slot = split_align_up(p->pw_s + p->pw_r, 64);              // int32
-    const int64_t n = pairs_in_flight;
-    const int64_t b_counts = n * counts_slot * 2, b_stay = n * stay_slot * 8, b_v = n * v_slot * 8, b_arg = n * arg_slot * 4,
-                  b_pre = n * pre_slot * 4;
-    if (int rc = p->open(device, pairs_in_flight, b_counts + b_stay + b_v + b_arg + b_pre, "split plan")) {
-        ffs_split_plan_destroy(p);
-        return rc;
-    }
-    char* w = (char*)p->work;
-    p->ws.counts = (uint16_t*)w;
-    p->ws.stay = (unsigned long long*)(w + b_counts);
-    p->ws.V = (double*)(w + b_counts + b_stay);
-    p->ws.arg = (int32_t*)(w + b_counts + b_stay + b_v);
-    p->pre = (int32_t*)(w + b_counts + b_stay + b_v + b_arg);
+    p->pre_slot = split_align_up(p->pw_s + p->pw_r, 64);                                          // int32
     p->ws.counts_row = p->lpad;
     p->ws.stay_row = p->lpad / 64;
-    p->ws.counts_slot = counts_slot;
-    p->ws.stay_slot = stay_slot;
-    p->ws.v_slot = v_slot;
-    p->ws.arg_slot = arg_slot;
-    if (p->desc.create(sizeof(ffsa::SplitDesc) * (size_t)pairs_in_flight) != FFS_OK) {
+    p->ws.counts_slot = split_align_up(max_blocks * p->lpad, 128);                                // uint16
+    p->ws.stay_slot = drift ? 0 : split_align_up(max_blocks * (p->lpad / 64), 32);                // uint64
+    p->codes_slot = drift ? split_align_up(max_blocks * (p->lpad / 64) * ffsa::DRIFT_PLANES, 32) : 0;  // uint64
+    p->ws.v_slot = (drift ? 2 : 1) * split_align_up(p->lpad, 32);                                 // double
+    p->ws.arg_slot = split_align_up(max_blocks, 64);                                              // int32
+    Carver size{nullptr};
+    p->carve(size, drift);
+    if (int rc = p->open(device, pairs_in_flight, size.used, what)) return rc;
+    Carver place{(char*)p->work};
+    p->carve(place, drift);
+    if (p->desc.create(sizeof(ffsa::SplitDesc) * (size_t)pairs_in_flight) != FFS_OK)
+        return fail(FFS_E_HIP, "%s: descriptor buffers / events", what);
+    return FFS_OK;
+}
+
+// the per-pair checks of the window calls: the subtitle's length and blocks against the plan; the largest block count
+int window_limits_check(const WindowPlan* plan, int n_pairs, const Pairs& a, int64_t K, int64_t* max_b) {
+    *max_b = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+        if (int rc = a.check(p)) return rc;
+        if (a.sub_len[p] > plan->max_samples)
+            return fail(FFS_E_INVALID, "pair %d: subtitle length %lld exceeds the plan's max_samples %lld", p,
+                        (long long)a.sub_len[p], (long long)plan->max_samples);
+        if (int rc = check_blocks(p, a.sub_len[p], K, plan->max_blocks, max_b)) return rc;
+    }
+    return FFS_OK;
+}
+
+// the SplitDesc rows of the sub-batch [p0, p0 + np) filled and uploaded; its largest block count
+int window_stage(WindowPlan* plan, const Pairs& a, int p0, int np, int64_t K, hipStream_t st, int64_t* chunk_b) {
+    if (int rc = plan->desc.wait_free()) return rc;
+    ffsa::SplitDesc* hd = (ffsa::SplitDesc*)plan->desc.host;
+    *chunk_b = 0;
+    for (int i = 0; i < np; ++i) {
+        int32_t* pre_s = plan->pre + (int64_t)i * plan->pre_slot;
+        hd[i] = a.split_desc(p0 + i, pre_s, pre_s + plan->pw_s);
+        *chunk_b = std::max(*chunk_b, (hd[i].S + K - 1) / K);
+    }
+    return plan->desc.upload(sizeof(ffsa::SplitDesc) * np, st);
+}
+
+// the prefixes and the per-(block, lag) counts of a staged sub-batch of np pairs and at most chunk_b blocks
+void window_counts(const WindowPlan* plan, int np, int64_t K, int64_t W, int64_t chunk_b, hipStream_t st) {
+    const ffsa::SplitDesc* dd = (const ffsa::SplitDesc*)plan->desc.dev;
+    const int n_tiles = (int)((2 * W + ffsa::SPLIT_TILE - 1) / ffsa::SPLIT_TILE);
+    const int n_bgroups = (int)((chunk_b + ffsa::SPLIT_BPW - 1) / ffsa::SPLIT_BPW);
+    hipLaunchKernelGGL(ffsa::k_split_prefix, dim3(2 * np), dim3(ffsa::SPLIT_PREFIX_THREADS), 0, st, dd, (int64_t)W);
+    hipLaunchKernelGGL(ffsa::k_split_counts, dim3((unsigned)((int64_t)n_tiles * n_bgroups * np)),
+                       dim3(ffsa::SPLIT_CNT_THREADS), 0, st, dd, plan->ws, (int)K, (int64_t)W, n_tiles, n_bgroups);
+}
+}  // namespace
+
+struct ffs_split_plan : WindowPlan {
+    uint32_t* curves = nullptr;        // report calls only, made by the first: per-piece n11 rows, [slot][max_blocks][lpad]
+    DescStaging refine;                // refine calls only, made by the first: RefineDesc[pairs_in_flight], then on the device
+    double* refine_scratch = nullptr;  // the null-score scratch [pairs_in_flight][4]
+    DescStaging cue;                   // cue report calls only, made by the first: CueDesc[pairs_in_flight]
+    DescStaging retime;                // cue retime calls only, made by the first: RetimeDesc[pairs_in_flight]
+    void* retime_ws = nullptr;  // profiles and backpointers of one sub-batch, 6 bytes per (cue, delta); grows on demand
+    int64_t retime_ws_bytes = 0;
+};
+
+int ffs_split_plan_create(int device, int pairs_in_flight, int64_t max_blocks, int64_t max_lags, int64_t max_samples,
+                          ffs_split_plan** out) {
+    if (!out) return fail(FFS_E_INVALID, "null output handle");
+    *out = nullptr;
+    if (int rc = window_plan_dims_check("split plan", pairs_in_flight, max_blocks, max_lags, max_samples)) return rc;
+    HIP_TRY(hipSetDevice(device));
+    ffs_split_plan* p = new (std::nothrow) ffs_split_plan();
+    if (!p) return fail(FFS_E_NOMEM, "split plan");
+    if (int rc = window_plan_open(p, "split plan", false, device, pairs_in_flight, max_blocks, max_lags, max_samples)) {
         ffs_split_plan_destroy(p);
-        return fail(FFS_E_HIP, "split plan: descriptor buffers / events");
+        return rc;
     }
     *out = p;
     return FFS_OK;
@@ -3321,21 +3505,11 @@ int ffs_split_plan_create(int device, int pairs_in_flight, int64_t max_blocks, i
 int ffs_split_plan_destroy(ffs_split_plan* plan) {
     if (!plan) return FFS_OK;
     plan->close();
-    plan->desc.release();
-    if (plan->curves) (void)hipFree(plan->curves);
-    plan->refine.release();
-    plan->cue.release();
-    plan->retime.release();
-    if (plan->retime_ws) (void)hipFree(plan->retime_ws);
     delete plan;
     return FFS_OK;
 }
 
-int64_t ffs_split_plan_workspace_bytes(const ffs_split_plan* plan) {
-    return plan ? plan->work_bytes + plan->curve_bytes + plan->refine_bytes + plan->cue_bytes + plan->retime_bytes +
-                      plan->retime_ws_bytes
-                : 0;
-}
+int64_t ffs_split_plan_workspace_bytes(const ffs_split_plan* plan) { return plan ? plan->workspace_bytes() : 0; }
 
 namespace {
 struct SplitReportArgs {  // the per-piece report of ffs_align_split_report_batch
@@ -3349,65 +3523,33 @@ struct SplitReportArgs {  // the per-piece report of ffs_align_split_report_batc
 int split_batch(ffs_split_plan* plan, int n_pairs, const Pairs& a, int64_t block_samples, int64_t max_offset_samples,
                 double split_penalty, int32_t* block_offset_out_dev, double* block_score_out_dev, double* total_out_dev,
                 const SplitReportArgs* rep, void* hip_stream) {
-    if (!plan) return fail(FFS_E_INVALID, "null split plan");
-    if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
-    if (n_pairs == 0) return FFS_OK;
-    if (a.any_null() || !block_offset_out_dev || !block_score_out_dev || !total_out_dev)
-        return fail(FFS_E_INVALID, "null argument");
+    if (int rc = check_call(plan, "split", n_pairs, a.any_null() || !block_offset_out_dev || !block_score_out_dev || !total_out_dev);
+        rc != CALL_GO_ON)
+        return rc;
     const int64_t K = block_samples, W = max_offset_samples;
     if (int rc = check_block_samples(K)) return rc;
-    if (W < 1 || 2 * W > 262144) return fail(FFS_E_INVALID, "max_offset_samples=%lld: need 1 <= W, 2W <= 262144", (long long)W);
-    if (2 * W > plan->max_lags)
-        return fail(FFS_E_INVALID, "2 * max_offset_samples = %lld exceeds the plan's max_lags %lld", (long long)(2 * W),
-                    (long long)plan->max_lags);
-    if (!(split_penalty >= 0.0)) return fail(FFS_E_INVALID, "split_penalty must be >= 0 (not NaN)");
+    if (int rc = check_window(W, plan->max_lags)) return rc;
+    if (int rc = check_split_penalty(split_penalty)) return rc;
     if (rep) {
-        if (rep->top_k < 1 || rep->top_k > ffsa::QUAL_MAX_PEAKS) return fail(FFS_E_INVALID, "top_k=%d outside [1, 8]", rep->top_k);
-        if (rep->exclusion < 1) return fail(FFS_E_INVALID, "exclusion_samples=%lld: need >= 1", (long long)rep->exclusion);
+        if (int rc = check_peaks(rep->top_k, rep->exclusion)) return rc;
         if (!rep->out || !rep->n_pieces) return fail(FFS_E_INVALID, "null argument");
         if (((uintptr_t)rep->out & 7) || ((uintptr_t)rep->n_pieces & 3)) return fail(FFS_E_INVALID, "misaligned report outputs");
     }
     int64_t max_b = 0;
-    for (int p = 0; p < n_pairs; ++p) {
-        if (int rc = a.check(p)) return rc;
-        if (a.sub_len[p] > plan->max_samples)
-            return fail(FFS_E_INVALID, "pair %d: subtitle length %lld exceeds the plan's max_samples %lld", p,
-                        (long long)a.sub_len[p], (long long)plan->max_samples);
-        const int64_t B = (a.sub_len[p] + K - 1) / K;
-        if (B > plan->max_blocks)
-            return fail(FFS_E_INVALID, "pair %d: %lld blocks exceed the plan's max_blocks %lld", p, (long long)B,
-                        (long long)plan->max_blocks);
-        max_b = std::max(max_b, B);
-    }
+    if (int rc = window_limits_check(plan, n_pairs, a, K, &max_b)) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
     if (int rc = plan->begin(st)) return rc;
-    if (rep && !plan->curves) {  // the first report call: one uint32 n11 row per (slot, block)
-        const int64_t bytes = (int64_t)plan->pairs_in_flight * plan->ws.counts_slot * 4;
-        if (hipMalloc((void**)&plan->curves, bytes) != hipSuccess) {
-            plan->curves = nullptr;
-            return fail(FFS_E_NOMEM, "split plan: %lld report workspace bytes", (long long)bytes);
-        }
-        plan->curve_bytes = bytes;
-    }
+    if (rep && !plan->curves)  // the first report call: one uint32 n11 row per (slot, block)
+        if (int rc = plan->add_block((void**)&plan->curves, (int64_t)plan->pairs_in_flight * plan->ws.counts_slot * 4,
+                                     "split plan", "report"))
+            return rc;
     const int64_t L = 2 * W;
-    const int n_tiles = (int)((L + ffsa::SPLIT_TILE - 1) / ffsa::SPLIT_TILE);
-    const int64_t pre_slot = split_align_up(plan->pw_s + plan->pw_r, 64);
-    ffsa::SplitDesc* hd = (ffsa::SplitDesc*)plan->desc.host;
     const ffsa::SplitDesc* dd = (const ffsa::SplitDesc*)plan->desc.dev;
     for (int p0 = 0; p0 < n_pairs; p0 += plan->pairs_in_flight) {
         const int np = std::min(plan->pairs_in_flight, n_pairs - p0);
-        if (int rc = plan->desc.wait_free()) return rc;
         int64_t chunk_b = 0;
-        for (int i = 0; i < np; ++i) {
-            int32_t* pre_s = plan->pre + (int64_t)i * pre_slot;
-            hd[i] = a.split_desc(p0 + i, pre_s, pre_s + plan->pw_s);
-            chunk_b = std::max(chunk_b, (hd[i].S + K - 1) / K);
-        }
-        if (int rc = plan->desc.upload(sizeof(ffsa::SplitDesc) * np, st)) return rc;
-        const int n_bgroups = (int)((chunk_b + ffsa::SPLIT_BPW - 1) / ffsa::SPLIT_BPW);
-        hipLaunchKernelGGL(ffsa::k_split_prefix, dim3(2 * np), dim3(ffsa::SPLIT_PREFIX_THREADS), 0, st, dd, (int64_t)W);
-        hipLaunchKernelGGL(ffsa::k_split_counts, dim3((unsigned)((int64_t)n_tiles * n_bgroups * np)),
-                           dim3(ffsa::SPLIT_CNT_THREADS), 0, st, dd, plan->ws, (int)K, (int64_t)W, n_tiles, n_bgroups);
+        if (int rc = window_stage(plan, a, p0, np, K, st, &chunk_b)) return rc;
+        window_counts(plan, np, K, W, chunk_b, st);
         hipLaunchKernelGGL(ffsa::k_split_dp, dim3(np), dim3(ffsa::SPLIT_DP_THREADS), 0, st, dd, plan->ws, (int)K, (int64_t)W,
                            split_penalty, max_b, block_offset_out_dev, block_score_out_dev, total_out_dev);
         if (rep) {
@@ -3458,13 +3600,10 @@ namespace {
 int refine_batch(ffs_split_plan* plan, int n_pairs, const Pairs& a, int64_t block_samples,
                  const int32_t* block_offset_dev, bool drift, const uint8_t* block_jump_dev, int64_t radius_samples,
                  double unmatched_margin, ffs_break_refine* out_dev, int32_t* n_breaks_out_dev, void* hip_stream) {
-    const int64_t* ref_len = a.ref_len;
-    const int64_t* sub_len = a.sub_len;
-    if (!plan) return fail(FFS_E_INVALID, "null split plan");
-    if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
-    if (n_pairs == 0) return FFS_OK;
-    if (a.any_null() || !block_offset_dev || !out_dev || !n_breaks_out_dev || (drift && !block_jump_dev))
-        return fail(FFS_E_INVALID, "null argument");
+    if (int rc = check_call(plan, "split", n_pairs,
+                            a.any_null() || !block_offset_dev || !out_dev || !n_breaks_out_dev || (drift && !block_jump_dev));
+        rc != CALL_GO_ON)
+        return rc;
     if (((uintptr_t)block_offset_dev & 3) || ((uintptr_t)out_dev & 7) || ((uintptr_t)n_breaks_out_dev & 3))
         return fail(FFS_E_INVALID, "misaligned block offsets or refine outputs");
     const int64_t K = block_samples, Rr = radius_samples;
@@ -3477,19 +3616,16 @@ int refine_batch(ffs_split_plan* plan, int n_pairs, const Pairs& a, int64_t bloc
         return fail(FFS_E_INVALID, "unmatched_margin must be finite and >= 0, or NaN for a single cut");
     int64_t max_b = 0;
     for (int p = 0; p < n_pairs; ++p) {
-        if (int rc = a.check(p)) return rc;
-        if (ref_len[p] > INT32_MAX / 2 || sub_len[p] > INT32_MAX / 2)
-            return fail(FFS_E_INVALID, "pair %d: vectors longer than 2^30 samples", p);
-        max_b = std::max(max_b, (sub_len[p] + K - 1) / K);
+        if (int rc = a.check_short(p)) return rc;
+        max_b = std::max(max_b, (a.sub_len[p] + K - 1) / K);
     }
     hipStream_t st = (hipStream_t)hip_stream;
     if (int rc = plan->begin(st)) return rc;
     const int pif = plan->pairs_in_flight;
     if (!plan->refine.dev) {  // the first refine call: descriptors, their staging and the null-score scratch
         const size_t desc_bytes = sizeof(ffsa::RefineDesc) * (size_t)pif, scratch_bytes = sizeof(double) * 4 * (size_t)pif;
-        if (int rc = plan->refine.create(desc_bytes, scratch_bytes)) return fail(rc, "split plan: refine workspace");
+        if (int rc = plan->add_staging(&plan->refine, desc_bytes, scratch_bytes, "split plan: refine workspace")) return rc;
         plan->refine_scratch = (double*)((char*)plan->refine.dev + desc_bytes);
-        plan->refine_bytes = (int64_t)(desc_bytes + scratch_bytes);
     }
     ffsa::RefineDesc* hd = (ffsa::RefineDesc*)plan->refine.host;
     const ffsa::RefineDesc* dd = (const ffsa::RefineDesc*)plan->refine.dev;
@@ -3498,24 +3634,8 @@ int refine_batch(ffs_split_plan* plan, int n_pairs, const Pairs& a, int64_t bloc
         if (int rc = plan->refine.wait_free()) return rc;
         int64_t chunk_b = 0;
         for (int i = 0; i < np; ++i) {
-            const int p = p0 + i;
-            const Levels v = a.levels(p);
-            ffsa::RefineDesc& d = hd[i];
-            d.r = (const uint32_t*)a.ref_ptr[p];
-            d.s = (const uint32_t*)a.sub_ptr[p];
-            d.R = ref_len[p];
-            d.S = sub_len[p];
-            d.r0 = v.r0;
-            d.r1 = v.r1;
-            d.s0 = v.s0;
-            d.s1 = v.s1;
-            d.c00 = v.c00;
-            d.c01 = v.c01;
-            d.c10 = v.c10;
-            d.c11 = v.c11;
-            d.pair_ws = plan->refine_scratch + 4 * (int64_t)i;
-            d.out_row = p;
-            chunk_b = std::max(chunk_b, (d.S + K - 1) / K);
+            hd[i] = a.refine_desc(p0 + i, plan->refine_scratch + 4 * (int64_t)i);
+            chunk_b = std::max(chunk_b, (hd[i].S + K - 1) / K);
         }
         if (int rc = plan->refine.upload(sizeof(ffsa::RefineDesc) * np, st)) return rc;
         if (drift)
@@ -3566,32 +3686,45 @@ int ffs_drift_refine_batch(ffs_split_plan* plan, int n_pairs, const void* const*
 
 /* ---- per-cue evidence report (csrc/ffs_cue_report.h) ------------------------------------------------------------ */
 
-int ffs_cue_report_batch(ffs_split_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
+namespace {
+// the checks the cue report and the cue retime calls share
+int check_cue_window(int64_t radius_samples, int64_t max_radius, int64_t context_samples) {
+    if (radius_samples < 0 || radius_samples > max_radius)
+        return fail(FFS_E_INVALID, "radius_samples=%lld: need 0 <= radius <= %lld", (long long)radius_samples, (long long)max_radius);
+    if (context_samples < 0 || context_samples > ffsa::CUE_MAX_CONTEXT)
+        return fail(FFS_E_INVALID, "context_samples=%lld: need 0 <= context <= %lld", (long long)context_samples,
+                    (long long)ffsa::CUE_MAX_CONTEXT);
+    return FFS_OK;
+}
+
+int check_cue_table_size(int64_t n_cues) {
+    if (n_cues < 0 || n_cues > INT32_MAX / 2) return fail(FFS_E_INVALID, "n_cues=%lld: need 0 <= n_cues <= 2^30", (long long)n_cues);
+    return FFS_OK;
+}
+
+// pair p's vectors and its slice of the cue table
+int check_cue_pair(int p, const Pairs& a, const int64_t* cue_first, const int64_t* cue_count, int64_t n_cues) {
+    if (int rc = a.check_short(p)) return rc;
+    if (cue_count[p] < 0) return fail(FFS_E_INVALID, "pair %d: cue_count=%lld < 0", p, (long long)cue_count[p]);
+    if (cue_first[p] < 0 || cue_first[p] > n_cues || cue_count[p] > n_cues - cue_first[p])
+        return fail(FFS_E_INVALID, "pair %d: cues [%lld, +%lld) outside the table of %lld", p, (long long)cue_first[p],
+                    (long long)cue_count[p], (long long)n_cues);
+    return FFS_OK;
+}
+}  // namespace
+
+int ffs_cue_report_batch(ffs_split_plan* plan, int n_pairs,const void* const* ref_ptr, const int64_t* ref_len,
                          const double* ref_lo, const double* ref_hi, const void* const* sub_ptr, const int64_t* sub_len,
                          const double* sub_lo, const double* sub_hi, const ffs_cue* cue_dev, int64_t n_cues,
                          const int64_t* cue_first, const int64_t* cue_count, int64_t radius_samples,
                          int64_t context_samples, ffs_cue_report* out_dev, void* hip_stream) {
     const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
-    if (!plan) return fail(FFS_E_INVALID, "null split plan");
-    if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
-    if (n_pairs == 0) return FFS_OK;
-    if (a.any_null() || !cue_first || !cue_count) return fail(FFS_E_INVALID, "null argument");
-    if (radius_samples < 0 || radius_samples > ffsa::CUE_MAX_RADIUS)
-        return fail(FFS_E_INVALID, "radius_samples=%lld: need 0 <= radius <= %lld", (long long)radius_samples,
-                    (long long)ffsa::CUE_MAX_RADIUS);
-    if (context_samples < 0 || context_samples > ffsa::CUE_MAX_CONTEXT)
-        return fail(FFS_E_INVALID, "context_samples=%lld: need 0 <= context <= %lld", (long long)context_samples,
-                    (long long)ffsa::CUE_MAX_CONTEXT);
-    if (n_cues < 0 || n_cues > INT32_MAX / 2) return fail(FFS_E_INVALID, "n_cues=%lld: need 0 <= n_cues <= 2^30", (long long)n_cues);
+    if (int rc = check_call(plan, "split", n_pairs, a.any_null() || !cue_first || !cue_count); rc != CALL_GO_ON) return rc;
+    if (int rc = check_cue_window(radius_samples, ffsa::CUE_MAX_RADIUS, context_samples)) return rc;
+    if (int rc = check_cue_table_size(n_cues)) return rc;
     int64_t total = 0;
     for (int p = 0; p < n_pairs; ++p) {
-        if (int rc = a.check(p)) return rc;
-        if (ref_len[p] > INT32_MAX / 2 || sub_len[p] > INT32_MAX / 2)
-            return fail(FFS_E_INVALID, "pair %d: vectors longer than 2^30 samples", p);
-        if (cue_count[p] < 0) return fail(FFS_E_INVALID, "pair %d: cue_count=%lld < 0", p, (long long)cue_count[p]);
-        if (cue_first[p] < 0 || cue_first[p] > n_cues || cue_count[p] > n_cues - cue_first[p])
-            return fail(FFS_E_INVALID, "pair %d: cues [%lld, +%lld) outside the table of %lld", p, (long long)cue_first[p],
-                        (long long)cue_count[p], (long long)n_cues);
+        if (int rc = check_cue_pair(p, a, cue_first, cue_count, n_cues)) return rc;
         total += cue_count[p];
     }
     if (total == 0) return FFS_OK;
@@ -3600,11 +3733,9 @@ int ffs_cue_report_batch(ffs_split_plan* plan, int n_pairs, const void* const* r
     hipStream_t st = (hipStream_t)hip_stream;
     if (int rc = plan->begin(st)) return rc;
     const int pif = plan->pairs_in_flight;
-    if (!plan->cue.dev) {  // the first cue report call: descriptors and their staging
-        const size_t desc_bytes = sizeof(ffsa::CueDesc) * (size_t)pif;
-        if (int rc = plan->cue.create(desc_bytes)) return fail(rc, "split plan: cue report workspace");
-        plan->cue_bytes = (int64_t)desc_bytes;
-    }
+    if (!plan->cue.dev)  // the first cue report call: descriptors and their staging
+        if (int rc = plan->add_staging(&plan->cue, sizeof(ffsa::CueDesc) * (size_t)pif, 0, "split plan: cue report workspace"))
+            return rc;
     ffsa::CueDesc* hd = (ffsa::CueDesc*)plan->cue.host;
     const ffsa::CueDesc* dd = (const ffsa::CueDesc*)plan->cue.dev;
     for (int p0 = 0; p0 < n_pairs; p0 += pif) {
@@ -3618,22 +3749,8 @@ int ffs_cue_report_batch(ffs_split_plan* plan, int n_pairs, const void* const* r
         for (int i = 0; i < np; ++i) {  // pairs without cues get no descriptor
             const int p = p0 + i;
             if (cue_count[p] == 0) continue;
-            const Levels v = a.levels(p);
             ffsa::CueDesc& c = hd[nd++];
-            c.v.r = (const uint32_t*)a.ref_ptr[p];
-            c.v.s = (const uint32_t*)a.sub_ptr[p];
-            c.v.R = ref_len[p];
-            c.v.S = sub_len[p];
-            c.v.r0 = v.r0;
-            c.v.r1 = v.r1;
-            c.v.s0 = v.s0;
-            c.v.s1 = v.s1;
-            c.v.c00 = v.c00;
-            c.v.c01 = v.c01;
-            c.v.c10 = v.c10;
-            c.v.c11 = v.c11;
-            c.v.pair_ws = nullptr;
-            c.v.out_row = p;
+            c.v = a.refine_desc(p, nullptr);
             c.cue_first = cue_first[p];
             c.grid_first = grid;
             c.cue_count = cue_count[p];
@@ -3673,32 +3790,18 @@ int ffs_cue_retime_batch(ffs_split_plan* plan, int n_pairs, const void* const* r
                          int64_t context_samples, int64_t penalty_q, int64_t jump_q, int flags, ffs_cue_retime* out_dev,
                          ffs_retime_summary* summary_out_dev, void* hip_stream) {
     const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
-    if (!plan) return fail(FFS_E_INVALID, "null split plan");
-    if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
-    if (n_pairs == 0) return FFS_OK;
-    if (a.any_null() || !cue_first || !cue_count) return fail(FFS_E_INVALID, "null argument");
-    if (radius_samples < 0 || radius_samples > ffsa::RETIME_MAX_RADIUS)
-        return fail(FFS_E_INVALID, "radius_samples=%lld: need 0 <= radius <= %lld", (long long)radius_samples,
-                    (long long)ffsa::RETIME_MAX_RADIUS);
-    if (context_samples < 0 || context_samples > ffsa::CUE_MAX_CONTEXT)
-        return fail(FFS_E_INVALID, "context_samples=%lld: need 0 <= context <= %lld", (long long)context_samples,
-                    (long long)ffsa::CUE_MAX_CONTEXT);
+    if (int rc = check_call(plan, "split", n_pairs, a.any_null() || !cue_first || !cue_count); rc != CALL_GO_ON) return rc;
+    if (int rc = check_cue_window(radius_samples, ffsa::RETIME_MAX_RADIUS, context_samples)) return rc;
     if (penalty_q < 0 || penalty_q > ffsa::RETIME_MAX_PENALTY_Q)
         return fail(FFS_E_INVALID, "penalty_q=%lld: need 0 <= penalty_q <= 2^20", (long long)penalty_q);
     if (jump_q < ffsa::RETIME_NO_JUMP || jump_q > ffsa::RETIME_MAX_JUMP_Q)
         return fail(FFS_E_INVALID, "jump_q=%lld: need -1 (no jump) or 0 <= jump_q <= 2^40", (long long)jump_q);
     if (flags & ~ffsa::RETIME_KEEP_ORDER) return fail(FFS_E_INVALID, "flags=%d: unknown bits", flags);
-    if (n_cues < 0 || n_cues > INT32_MAX / 2) return fail(FFS_E_INVALID, "n_cues=%lld: need 0 <= n_cues <= 2^30", (long long)n_cues);
+    if (int rc = check_cue_table_size(n_cues)) return rc;
     const int64_t n_delta = 2 * radius_samples + 1;
     int64_t total = 0;
     for (int p = 0; p < n_pairs; ++p) {
-        if (int rc = a.check(p)) return rc;
-        if (ref_len[p] > INT32_MAX / 2 || sub_len[p] > INT32_MAX / 2)
-            return fail(FFS_E_INVALID, "pair %d: vectors longer than 2^30 samples", p);
-        if (cue_count[p] < 0) return fail(FFS_E_INVALID, "pair %d: cue_count=%lld < 0", p, (long long)cue_count[p]);
-        if (cue_first[p] < 0 || cue_first[p] > n_cues || cue_count[p] > n_cues - cue_first[p])
-            return fail(FFS_E_INVALID, "pair %d: cues [%lld, +%lld) outside the table of %lld", p, (long long)cue_first[p],
-                        (long long)cue_count[p], (long long)n_cues);
+        if (int rc = check_cue_pair(p, a, cue_first, cue_count, n_cues)) return rc;
         if (cue_count[p] * n_delta * ffsa::RETIME_CELL_BYTES > ffsa::RETIME_WORK_CAP)
             return fail(FFS_E_INVALID, "pair %d: %lld cues x %lld shifts x 6 bytes exceed the retime workspace cap of %lld bytes",
                         p, (long long)cue_count[p], (long long)n_delta, (long long)ffsa::RETIME_WORK_CAP);
@@ -3710,11 +3813,9 @@ int ffs_cue_retime_batch(ffs_split_plan* plan, int n_pairs, const void* const* r
     hipStream_t st = (hipStream_t)hip_stream;
     if (int rc = plan->begin(st)) return rc;
     const int pif = plan->pairs_in_flight;
-    if (!plan->retime.dev) {  // the first retime call: descriptors and their staging
-        const size_t desc_bytes = sizeof(ffsa::RetimeDesc) * (size_t)pif;
-        if (int rc = plan->retime.create(desc_bytes)) return fail(rc, "split plan: cue retime descriptors");
-        plan->retime_bytes = (int64_t)desc_bytes;
-    }
+    if (!plan->retime.dev)  // the first retime call: descriptors and their staging
+        if (int rc = plan->add_staging(&plan->retime, sizeof(ffsa::RetimeDesc) * (size_t)pif, 0, "split plan: cue retime descriptors"))
+            return rc;
     int64_t need = 0;  // the largest sub-batch's cells
     for (int p0 = 0; p0 < n_pairs;) {
         int64_t rows;
@@ -3723,13 +3824,10 @@ int ffs_cue_retime_batch(ffs_split_plan* plan, int n_pairs, const void* const* r
     }
     if (need > plan->retime_ws_bytes) {  // grow: no earlier call may still use the old block
         HIP_TRY(hipEventSynchronize(plan->done));
-        if (plan->retime_ws) (void)hipFree(plan->retime_ws);
+        plan->drop_block(plan->retime_ws, plan->retime_ws_bytes);
         plan->retime_ws = nullptr;
         plan->retime_ws_bytes = 0;
-        if (hipMalloc(&plan->retime_ws, (size_t)need) != hipSuccess) {
-            plan->retime_ws = nullptr;
-            return fail(FFS_E_NOMEM, "split plan: %lld cue retime workspace bytes", (long long)need);
-        }
+        if (int rc = plan->add_block(&plan->retime_ws, need, "split plan", "cue retime")) return rc;
         plan->retime_ws_bytes = need;
     }
     ffsa::RetimeDesc* hd = (ffsa::RetimeDesc*)plan->retime.host;
@@ -3772,62 +3870,166 @@ int ffs_cue_retime_batch(ffs_split_plan* plan, int n_pairs, const void* const* r
 
 /* ---- split-aware alignment over a lag range (csrc/ffs_split_range.h) ------------------------------------------- */
 
-struct ffs_split_range_plan : PlanCore {
+namespace {
+// What the split range plan and the drift range plan share: the DP's tables over up to max_lags lags, prefixes over whole
+// vectors, SplitDesc and RangeLag rows.  `ws.stay` holds one bit plane per (block, lag) in the split range plan and
+// drift_range_planes(max_step_cap) of them in the drift range plan, which also keeps two V rows.
+struct RangePlan : PlanCore {
     int64_t max_blocks, max_lags, max_samples;
-    int64_t pw;                 // prefix words per vector
+    int64_t pw, pre_slot;       // prefix words per vector and per slot
     ffsa::RangeWs ws;
     int32_t* pre;               // [slot][2 * pw]: s, then r
-    DescStaging desc;           // SplitDesc[pairs_in_flight], then RangeLag[pairs_in_flight]
+                                // desc: SplitDesc[pairs_in_flight], then RangeLag[pairs_in_flight]
+
+    const ffsa::SplitDesc* dd() const { return (const ffsa::SplitDesc*)desc.dev; }
+    const ffsa::RangeLag* dl() const { return (const ffsa::RangeLag*)(dd() + pairs_in_flight); }
+
+    void carve(Carver& c) {
+        const int64_t n = pairs_in_flight;
+        ws.stay = c.take<unsigned long long>(n * ws.stay_slot);
+        ws.V = c.take<double>(n * ws.v_slot);
+        ws.pv = c.take<double>(n * 2 * ws.part_row);
+        ws.pj = c.take<int32_t>(n * 2 * ws.part_row);
+        ws.arg = c.take<int32_t>(n * ws.arg_slot);
+        pre = c.take<int32_t>(n * pre_slot);
+    }
+};
+
+// `more_need`: what the drift range plan's message adds about max_step_cap
+int range_plan_dims_check(const char* what, const char* more_need, int pairs_in_flight, int64_t max_blocks, int64_t max_lags,
+                          int64_t max_samples, int max_step_cap) {
+    if (pairs_in_flight < 1 || pairs_in_flight > 65535 || max_blocks < 1 || max_lags < 1 || max_lags > INT32_MAX ||
+        max_samples < 1 || max_samples > INT32_MAX / 2 || max_step_cap < 0 || max_step_cap > ffsa::DRIFT_RANGE_MAX_STEP)
+        return fail(FFS_E_INVALID, "%s: need 1 <= pairs_in_flight <= 65535, max_blocks >= 1, "
+                                   "1 <= max_lags <= 2^31 - 1, 1 <= max_samples <= 2^30 - 1%s", what, more_need);
+    return FFS_OK;
+}
+
+// the sizes, the workspace and the descriptors of a new range plan of `planes` bit planes per (block, lag) and `v_rows`
+// V rows; on failure the caller destroys the plan
+int range_plan_open(RangePlan* p, const char* what, int planes, int v_rows, int device, int pairs_in_flight,
+                    int64_t max_blocks, int64_t max_lags, int64_t max_samples) {
+    p->pairs_in_flight = pairs_in_flight;
+    p->max_blocks = max_blocks;
+    p->max_lags = max_lags;
+    p->max_samples = max_samples;
+    p->pw = max_samples / 32 + 2;
+    p->pre_slot = split_align_up(2 * p->pw, 64);                                                  // int32
+    p->ws.stay_row = (max_lags + 63) / 64;  // 64-lag words per block row and plane
+    p->ws.part_row = split_align_up((max_lags + ffsa::RANGE_TILE - 1) / ffsa::RANGE_TILE, 32);
+    p->ws.stay_slot = split_align_up(max_blocks * p->ws.stay_row * planes, 32);                   // uint64
+    p->ws.v_slot = v_rows * split_align_up(p->ws.stay_row * 64, 32);                              // double
+    p->ws.arg_slot = split_align_up(max_blocks, 64);                                              // int32
+    Carver size{nullptr};
+    p->carve(size);
+    if (int rc = p->open(device, pairs_in_flight, size.used, what)) return rc;
+    Carver place{(char*)p->work};
+    p->carve(place);
+    if (p->desc.create((sizeof(ffsa::SplitDesc) + sizeof(ffsa::RangeLag)) * (size_t)pairs_in_flight) != FFS_OK)
+        return fail(FFS_E_HIP, "%s: descriptor buffers / events", what);
+    return FFS_OK;
+}
+
+// the per-pair checks of the range calls: lengths and blocks against the plan, the lag ranges; the largest block count
+int range_limits_check(const RangePlan* plan, int n_pairs, const Pairs& a, int64_t K, const int64_t* lag_lo,
+                       const int64_t* lag_hi, int64_t* max_b) {
+    *max_b = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+        if (int rc = a.check(p)) return rc;
+        if (a.sub_len[p] > plan->max_samples || a.ref_len[p] > plan->max_samples)
+            return fail(FFS_E_INVALID, "pair %d: lengths %lld / %lld exceed the plan's max_samples %lld", p,
+                        (long long)a.ref_len[p], (long long)a.sub_len[p], (long long)plan->max_samples);
+        if (int rc = check_blocks(p, a.sub_len[p], K, plan->max_blocks, max_b)) return rc;
+        if (lag_lo[p] > lag_hi[p] || lag_lo[p] < -(int64_t)INT32_MAX || lag_hi[p] > INT32_MAX)
+            return fail(FFS_E_INVALID, "pair %d: lag range [%lld, %lld]: need -(2^31 - 1) <= lag_lo <= lag_hi <= 2^31 - 1", p,
+                        (long long)lag_lo[p], (long long)lag_hi[p]);
+        if (lag_hi[p] - lag_lo[p] + 1 > plan->max_lags)
+            return fail(FFS_E_INVALID, "pair %d: %lld lags exceed the plan's max_lags %lld", p,
+                        (long long)(lag_hi[p] - lag_lo[p] + 1), (long long)plan->max_lags);
+    }
+    return FFS_OK;
+}
+
+struct RangeChunk {  // of one staged sub-batch: its largest block count, tile count and lag range
+    int64_t chunk_b, max_tiles, max_l;
+};
+
+// the SplitDesc and RangeLag rows of the sub-batch [p0, p0 + np) filled and uploaded in one copy (the RangeLag half is at
+// a fixed offset: the whole used span goes)
+int range_stage(RangePlan* plan, const Pairs& a, const int64_t* lag_lo, const int64_t* lag_hi, int p0, int np, int64_t K,
+                hipStream_t st, RangeChunk* chunk) {
+    if (int rc = plan->desc.wait_free()) return rc;
+    const int pif = plan->pairs_in_flight;
+    ffsa::SplitDesc* hd = (ffsa::SplitDesc*)plan->desc.host;
+    ffsa::RangeLag* hl = (ffsa::RangeLag*)(hd + pif);
+    *chunk = RangeChunk{0, 0, 0};
+    for (int i = 0; i < np; ++i) {
+        const int p = p0 + i;
+        int32_t* pre_s = plan->pre + (int64_t)i * plan->pre_slot;
+        hd[i] = a.split_desc(p, pre_s, pre_s + plan->pw);
+        hl[i].lag_lo = lag_lo[p];
+        hl[i].L = lag_hi[p] - lag_lo[p] + 1;
+        chunk->chunk_b = std::max(chunk->chunk_b, (hd[i].S + K - 1) / K);
+        chunk->max_tiles = std::max(chunk->max_tiles, (hl[i].L + ffsa::RANGE_TILE - 1) / ffsa::RANGE_TILE);
+        chunk->max_l = std::max(chunk->max_l, hl[i].L);
+    }
+    return plan->desc.upload(sizeof(ffsa::SplitDesc) * pif + sizeof(ffsa::RangeLag) * np, st);
+}
+
+// prefixes over every sample of both vectors of a staged sub-batch (W = max_samples: min(R, S + W) = R)
+void range_prefixes(const RangePlan* plan, int np, hipStream_t st) {
+    hipLaunchKernelGGL(ffsa::k_split_prefix, dim3(2 * np), dim3(ffsa::SPLIT_PREFIX_THREADS), 0, st, plan->dd(),
+                       (int64_t)plan->max_samples);
+}
+
+// A solved path on the host for the two range reports: the block offsets, and with `jump_dev` the jump flags, copied
+// behind the stream's earlier work, one synchronise, then every block's offset against its pair's lag range.
+int read_path(const RangePlan* plan, int n_pairs, const Pairs& a, int64_t K, int64_t max_b, const int64_t* lag_lo,
+              const int64_t* lag_hi, const int32_t* offset_dev, const uint8_t* jump_dev, std::vector<int32_t>* offs,
+              std::vector<uint8_t>* jumps, hipStream_t st) {
+    offs->resize((size_t)n_pairs * max_b);
+    HIP_TRY(hipSetDevice(plan->device));
+    HIP_TRY(hipMemcpyAsync(offs->data(), offset_dev, offs->size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (jump_dev) {
+        jumps->resize((size_t)n_pairs * max_b);
+        HIP_TRY(hipMemcpyAsync(jumps->data(), jump_dev, jumps->size(), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int p = 0; p < n_pairs; ++p) {
+        const int64_t B = (a.sub_len[p] + K - 1) / K;
+        for (int64_t b = 0; b < B; ++b) {
+            const int64_t o = (*offs)[(size_t)p * max_b + b];
+            if (o < lag_lo[p] || o > lag_hi[p])
+                return fail(FFS_E_INVALID, "pair %d: block %lld offset %lld outside the lag range [%lld, %lld]", p,
+                            (long long)b, (long long)o, (long long)lag_lo[p], (long long)lag_hi[p]);
+        }
+    }
+    return FFS_OK;
+}
+}  // namespace
+
+struct ffs_split_range_plan : RangePlan {
     uint32_t* rows = nullptr;   // report calls only, made by the first: piece n11 rows, [slot][CUT_ROUND_PIECES][lpad]
-    int64_t lpad = 0;
-    DescStaging items;          // report calls only: CutItem[item_cap]
-    int64_t item_cap = 0;
-    int64_t report_bytes = 0;
+    int64_t lpad;               // max_lags padded to 64
+    DescStaging items;          // report calls only, made by the first: CutItem[item_cap]
+    int64_t item_cap;
 };
 
 int ffs_split_range_plan_create(int device, int pairs_in_flight, int64_t max_blocks, int64_t max_lags, int64_t max_samples,
                                 ffs_split_range_plan** out) {
     if (!out) return fail(FFS_E_INVALID, "null output handle");
     *out = nullptr;
-    if (pairs_in_flight < 1 || pairs_in_flight > 65535 || max_blocks < 1 || max_lags < 1 || max_lags > INT32_MAX ||
-        max_samples < 1 || max_samples > INT32_MAX / 2)
-        return fail(FFS_E_INVALID, "split range plan: need 1 <= pairs_in_flight <= 65535, max_blocks >= 1, "
-                                   "1 <= max_lags <= 2^31 - 1, 1 <= max_samples <= 2^30 - 1");
+    if (int rc = range_plan_dims_check("split range plan", "", pairs_in_flight, max_blocks, max_lags, max_samples, 0)) return rc;
     HIP_TRY(hipSetDevice(device));
     ffs_split_range_plan* p = new (std::nothrow) ffs_split_range_plan();
     if (!p) return fail(FFS_E_NOMEM, "split range plan");
-    p->max_blocks = max_blocks;
-    p->max_lags = max_lags;
-    p->max_samples = max_samples;
-    p->pw = max_samples / 32 + 2;
-    const int64_t stay_row = (max_lags + 63) / 64;
-    const int64_t part_row = split_align_up((max_lags + ffsa::RANGE_TILE - 1) / ffsa::RANGE_TILE, 32);
-    const int64_t stay_slot = split_align_up(max_blocks * stay_row, 32);   // uint64
-    const int64_t v_slot = split_align_up(stay_row * 64, 32);             // double
-    const int64_t arg_slot = split_align_up(max_blocks, 64);               // int32
-    const int64_t pre_slot = split_align_up(2 * p->pw, 64);                // int32
-    const int64_t n = pairs_in_flight;
-    const int64_t b_stay = n * stay_slot * 8, b_v = n * v_slot * 8, b_pv = n * 2 * part_row * 8, b_pj = n * 2 * part_row * 4,
-                  b_arg = n * arg_slot * 4, b_pre = n * pre_slot * 4;
-    if (int rc = p->open(device, pairs_in_flight, b_stay + b_v + b_pv + b_pj + b_arg + b_pre, "split range plan")) {
+    p->lpad = split_align_up(max_lags, 64);
+    // a pair's report items over all its rounds: sum of ceil(piece words / CW) <= ceil(words / CW) + pieces
+    constexpr int CW = ffsa::CUT_CHUNK_WORDS;
+    p->item_cap = (int64_t)pairs_in_flight * ((max_samples / 32 + 1 + CW - 1) / CW + max_blocks);
+    if (int rc = range_plan_open(p, "split range plan", 1, 1, device, pairs_in_flight, max_blocks, max_lags, max_samples)) {
         ffs_split_range_plan_destroy(p);
         return rc;
-    }
-    char* w = (char*)p->work;
-    p->ws.stay = (unsigned long long*)w;
-    p->ws.V = (double*)(w + b_stay);
-    p->ws.pv = (double*)(w + b_stay + b_v);
-    p->ws.pj = (int32_t*)(w + b_stay + b_v + b_pv);
-    p->ws.arg = (int32_t*)(w + b_stay + b_v + b_pv + b_pj);
-    p->pre = (int32_t*)(w + b_stay + b_v + b_pv + b_pj + b_arg);
-    p->ws.stay_row = stay_row;
-    p->ws.stay_slot = stay_slot;
-    p->ws.v_slot = v_slot;
-    p->ws.part_row = part_row;
-    p->ws.arg_slot = arg_slot;
-    if (p->desc.create((sizeof(ffsa::SplitDesc) + sizeof(ffsa::RangeLag)) * (size_t)pairs_in_flight) != FFS_OK) {
-        ffs_split_range_plan_destroy(p);
-        return fail(FFS_E_HIP, "split range plan: descriptor buffers / events");
     }
     *out = p;
     return FFS_OK;
@@ -3836,48 +4038,11 @@ int ffs_split_range_plan_create(int device, int pairs_in_flight, int64_t max_blo
 int ffs_split_range_plan_destroy(ffs_split_range_plan* plan) {
     if (!plan) return FFS_OK;
     plan->close();
-    plan->desc.release();
-    if (plan->rows) (void)hipFree(plan->rows);
-    plan->items.release();
     delete plan;
     return FFS_OK;
 }
 
-int64_t ffs_split_range_plan_workspace_bytes(const ffs_split_range_plan* plan) {
-    return plan ? plan->work_bytes + plan->report_bytes : 0;
-}
-
-namespace {
-// the per-pair checks of the range calls (lengths and blocks against the plan, the lag ranges); the largest block count
-// against explicit limits (the split range and drift range plans share them)
-int range_limits_check(int64_t plan_max_samples, int64_t plan_max_blocks, int64_t plan_max_lags, int n_pairs,
-                       const Pairs& a, int64_t K, const int64_t* lag_lo, const int64_t* lag_hi, int64_t* max_b) {
-    *max_b = 0;
-    for (int p = 0; p < n_pairs; ++p) {
-        if (int rc = a.check(p)) return rc;
-        if (a.sub_len[p] > plan_max_samples || a.ref_len[p] > plan_max_samples)
-            return fail(FFS_E_INVALID, "pair %d: lengths %lld / %lld exceed the plan's max_samples %lld", p,
-                        (long long)a.ref_len[p], (long long)a.sub_len[p], (long long)plan_max_samples);
-        const int64_t B = (a.sub_len[p] + K - 1) / K;
-        if (B > plan_max_blocks)
-            return fail(FFS_E_INVALID, "pair %d: %lld blocks exceed the plan's max_blocks %lld", p, (long long)B,
-                        (long long)plan_max_blocks);
-        if (lag_lo[p] > lag_hi[p] || lag_lo[p] < -(int64_t)INT32_MAX || lag_hi[p] > INT32_MAX)
-            return fail(FFS_E_INVALID, "pair %d: lag range [%lld, %lld]: need -(2^31 - 1) <= lag_lo <= lag_hi <= 2^31 - 1", p,
-                        (long long)lag_lo[p], (long long)lag_hi[p]);
-        if (lag_hi[p] - lag_lo[p] + 1 > plan_max_lags)
-            return fail(FFS_E_INVALID, "pair %d: %lld lags exceed the plan's max_lags %lld", p,
-                        (long long)(lag_hi[p] - lag_lo[p] + 1), (long long)plan_max_lags);
-        *max_b = std::max(*max_b, B);
-    }
-    return FFS_OK;
-}
-
-int range_pairs_check(const ffs_split_range_plan* plan, int n_pairs, const Pairs& a, int64_t K, const int64_t* lag_lo,
-                      const int64_t* lag_hi, int64_t* max_b) {
-    return range_limits_check(plan->max_samples, plan->max_blocks, plan->max_lags, n_pairs, a, K, lag_lo, lag_hi, max_b);
-}
-}  // namespace
+int64_t ffs_split_range_plan_workspace_bytes(const ffs_split_range_plan* plan) { return plan ? plan->workspace_bytes() : 0; }
 
 int ffs_align_split_range_batch(ffs_split_range_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
                                 const double* ref_lo, const double* ref_hi, const void* const* sub_ptr,
@@ -3886,46 +4051,29 @@ int ffs_align_split_range_batch(ffs_split_range_plan* plan, int n_pairs, const v
                                 int32_t* block_offset_out_dev, double* block_score_out_dev, double* total_out_dev,
                                 void* hip_stream) {
     const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
-    if (!plan) return fail(FFS_E_INVALID, "null split range plan");
-    if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
-    if (n_pairs == 0) return FFS_OK;
-    if (a.any_null() || !lag_lo || !lag_hi || !block_offset_out_dev || !block_score_out_dev || !total_out_dev)
-        return fail(FFS_E_INVALID, "null argument");
+    if (int rc = check_call(plan, "split range", n_pairs,
+                            a.any_null() || !lag_lo || !lag_hi || !block_offset_out_dev || !block_score_out_dev || !total_out_dev);
+        rc != CALL_GO_ON)
+        return rc;
     if (((uintptr_t)block_offset_out_dev & 3) || ((uintptr_t)block_score_out_dev & 7) || ((uintptr_t)total_out_dev & 7))
         return fail(FFS_E_INVALID, "misaligned outputs");
     const int64_t K = block_samples;
     if (int rc = check_block_samples(K)) return rc;
-    if (!(split_penalty >= 0.0)) return fail(FFS_E_INVALID, "split_penalty must be >= 0 (not NaN)");
+    if (int rc = check_split_penalty(split_penalty)) return rc;
     int64_t max_b = 0;
-    if (int rc = range_pairs_check(plan, n_pairs, a, K, lag_lo, lag_hi, &max_b)) return rc;
+    if (int rc = range_limits_check(plan, n_pairs, a, K, lag_lo, lag_hi, &max_b)) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
     if (int rc = plan->begin(st)) return rc;
-    const int64_t pre_slot = split_align_up(2 * plan->pw, 64);
     const int pif = plan->pairs_in_flight;
-    ffsa::SplitDesc* hd = (ffsa::SplitDesc*)plan->desc.host;
-    ffsa::RangeLag* hl = (ffsa::RangeLag*)(hd + pif);
-    const ffsa::SplitDesc* dd = (const ffsa::SplitDesc*)plan->desc.dev;
-    const ffsa::RangeLag* dl = (const ffsa::RangeLag*)(dd + pif);
+    const ffsa::SplitDesc* dd = plan->dd();
+    const ffsa::RangeLag* dl = plan->dl();
     for (int p0 = 0; p0 < n_pairs; p0 += pif) {
         const int np = std::min(pif, n_pairs - p0);
-        if (int rc = plan->desc.wait_free()) return rc;
-        int64_t chunk_b = 0, max_tiles = 0;
-        for (int i = 0; i < np; ++i) {
-            const int p = p0 + i;
-            int32_t* pre_s = plan->pre + (int64_t)i * pre_slot;
-            hd[i] = a.split_desc(p, pre_s, pre_s + plan->pw);
-            hl[i].lag_lo = lag_lo[p];
-            hl[i].L = lag_hi[p] - lag_lo[p] + 1;
-            chunk_b = std::max(chunk_b, (hd[i].S + K - 1) / K);
-            max_tiles = std::max(max_tiles, (hl[i].L + ffsa::RANGE_TILE - 1) / ffsa::RANGE_TILE);
-        }
-        // one upload of both arrays (the RangeLag half is at a fixed offset: copy the whole used span)
-        if (int rc = plan->desc.upload(sizeof(ffsa::SplitDesc) * pif + sizeof(ffsa::RangeLag) * np, st)) return rc;
-        // prefixes over every sample of both vectors (W = max_samples: min(R, S + W) = R)
-        hipLaunchKernelGGL(ffsa::k_split_prefix, dim3(2 * np), dim3(ffsa::SPLIT_PREFIX_THREADS), 0, st, dd,
-                           (int64_t)plan->max_samples);
-        for (int64_t b = 0; b < chunk_b; ++b)
-            hipLaunchKernelGGL(ffsa::k_range_step, dim3((unsigned)max_tiles, (unsigned)np), dim3(ffsa::RANGE_THREADS), 0, st,
+        RangeChunk c;
+        if (int rc = range_stage(plan, a, lag_lo, lag_hi, p0, np, K, st, &c)) return rc;
+        range_prefixes(plan, np, st);
+        for (int64_t b = 0; b < c.chunk_b; ++b)
+            hipLaunchKernelGGL(ffsa::k_range_step, dim3((unsigned)c.max_tiles, (unsigned)np), dim3(ffsa::RANGE_THREADS), 0, st,
                                dd, dl, plan->ws, (int)K, b, split_penalty);
         hipLaunchKernelGGL(ffsa::k_range_backtrack, dim3(np), dim3(ffsa::RANGE_THREADS), 0, st, dd, dl, plan->ws, (int)K,
                            max_b, block_offset_out_dev, total_out_dev);
@@ -3948,76 +4096,41 @@ int ffs_split_range_report_batch(ffs_split_range_plan* plan, int n_pairs, const 
                                  int64_t exclusion_samples, ffs_piece_report* out_dev, int32_t* n_pieces_out_dev,
                                  void* hip_stream) {
     const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
-    if (!plan) return fail(FFS_E_INVALID, "null split range plan");
-    if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
-    if (n_pairs == 0) return FFS_OK;
-    if (a.any_null() || !lag_lo || !lag_hi || !block_offset_dev || !out_dev || !n_pieces_out_dev)
-        return fail(FFS_E_INVALID, "null argument");
+    if (int rc = check_call(plan, "split range", n_pairs,
+                            a.any_null() || !lag_lo || !lag_hi || !block_offset_dev || !out_dev || !n_pieces_out_dev);
+        rc != CALL_GO_ON)
+        return rc;
     if (((uintptr_t)block_offset_dev & 3) || ((uintptr_t)out_dev & 7) || ((uintptr_t)n_pieces_out_dev & 3))
         return fail(FFS_E_INVALID, "misaligned block offsets or report outputs");
     const int64_t K = block_samples;
     if (int rc = check_block_samples(K)) return rc;
-    if (top_k < 1 || top_k > ffsa::QUAL_MAX_PEAKS) return fail(FFS_E_INVALID, "top_k=%d outside [1, 8]", top_k);
-    if (exclusion_samples < 1) return fail(FFS_E_INVALID, "exclusion_samples=%lld: need >= 1", (long long)exclusion_samples);
+    if (int rc = check_peaks(top_k, exclusion_samples)) return rc;
     int64_t max_b = 0;
-    if (int rc = range_pairs_check(plan, n_pairs, a, K, lag_lo, lag_hi, &max_b)) return rc;
-    // the block offsets on the host (after the stream's earlier work): checked against the ranges, then the rounds'
-    // work items are made from their pieces
+    if (int rc = range_limits_check(plan, n_pairs, a, K, lag_lo, lag_hi, &max_b)) return rc;
+    // the block offsets on the host: the rounds' work items are made from their pieces
     hipStream_t st = (hipStream_t)hip_stream;
-    std::vector<int32_t> offs((size_t)n_pairs * max_b);
-    HIP_TRY(hipSetDevice(plan->device));
-    HIP_TRY(hipMemcpyAsync(offs.data(), block_offset_dev, offs.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (int p = 0; p < n_pairs; ++p) {
-        const int64_t B = (sub_len[p] + K - 1) / K;
-        for (int64_t b = 0; b < B; ++b) {
-            const int64_t o = offs[(size_t)p * max_b + b];
-            if (o < lag_lo[p] || o > lag_hi[p])
-                return fail(FFS_E_INVALID, "pair %d: block %lld offset %lld outside the lag range [%lld, %lld]", p,
-                            (long long)b, (long long)o, (long long)lag_lo[p], (long long)lag_hi[p]);
-        }
-    }
+    std::vector<int32_t> offs;
+    if (int rc = read_path(plan, n_pairs, a, K, max_b, lag_lo, lag_hi, block_offset_dev, nullptr, &offs, nullptr, st)) return rc;
     if (int rc = plan->begin(st)) return rc;
     const int pif = plan->pairs_in_flight;
     constexpr int G = ffsa::CUT_ROUND_PIECES, CW = ffsa::CUT_CHUNK_WORDS;
-    if (!plan->rows) {  // the first report call: G n11 rows per pair in flight, and the work items of one sub-batch
-        plan->lpad = split_align_up(plan->max_lags, 64);
-        const int64_t row_bytes = (int64_t)pif * G * plan->lpad * 4;
-        // a pair's items over all its rounds: sum of ceil(piece words / CW) <= ceil(words / CW) + pieces
-        plan->item_cap = (int64_t)pif * ((plan->max_samples / 32 + 1 + CW - 1) / CW + plan->max_blocks);
-        const int64_t item_bytes = plan->item_cap * (int64_t)sizeof(ffsa::CutItem);
-        if (hipMalloc((void**)&plan->rows, row_bytes) != hipSuccess) {
-            plan->rows = nullptr;
-            return fail(FFS_E_NOMEM, "split range plan: %lld report workspace bytes", (long long)row_bytes);
-        }
-        if (int rc = plan->items.create((size_t)item_bytes)) {
-            (void)hipFree(plan->rows);
-            plan->rows = nullptr;
-            return fail(rc, "split range plan: report work items");
-        }
-        plan->report_bytes = row_bytes + item_bytes;
-    }
-    const int64_t pre_slot = split_align_up(2 * plan->pw, 64);
-    ffsa::SplitDesc* hd = (ffsa::SplitDesc*)plan->desc.host;
-    ffsa::RangeLag* hl = (ffsa::RangeLag*)(hd + pif);
-    const ffsa::SplitDesc* dd = (const ffsa::SplitDesc*)plan->desc.dev;
-    const ffsa::RangeLag* dl = (const ffsa::RangeLag*)(dd + pif);
+    // the first report call: G n11 rows per pair in flight, and the work items of one sub-batch
+    if (!plan->rows)
+        if (int rc = plan->add_block((void**)&plan->rows, (int64_t)pif * G * plan->lpad * 4, "split range plan", "report"))
+            return rc;
+    if (!plan->items.dev)
+        if (int rc = plan->add_staging(&plan->items, (size_t)plan->item_cap * sizeof(ffsa::CutItem), 0,
+                                       "split range plan: report work items"))
+            return rc;
+    const ffsa::SplitDesc* dd = plan->dd();
+    const ffsa::RangeLag* dl = plan->dl();
     ffsa::CutItem* hi_items = (ffsa::CutItem*)plan->items.host;
     const ffsa::CutItem* di_items = (const ffsa::CutItem*)plan->items.dev;
     std::vector<int64_t> round_start;  // per round: its first work item (+ the end)
     for (int p0 = 0; p0 < n_pairs; p0 += pif) {
         const int np = std::min(pif, n_pairs - p0);
-        if (int rc = plan->desc.wait_free()) return rc;
-        int64_t max_l = 0;
-        for (int i = 0; i < np; ++i) {
-            const int p = p0 + i;
-            int32_t* pre_s = plan->pre + (int64_t)i * pre_slot;
-            hd[i] = a.split_desc(p, pre_s, pre_s + plan->pw);
-            hl[i].lag_lo = lag_lo[p];
-            hl[i].L = lag_hi[p] - lag_lo[p] + 1;
-            max_l = std::max(max_l, hl[i].L);
-        }
-        if (int rc = plan->desc.upload(sizeof(ffsa::SplitDesc) * pif + sizeof(ffsa::RangeLag) * np, st)) return rc;
+        RangeChunk c;
+        if (int rc = range_stage(plan, a, lag_lo, lag_hi, p0, np, K, st, &c)) return rc;
         // the pieces of each pair (maximal runs of equal block offsets, as k_split_pieces forms them) -> work items,
         // round by round: round r holds the pieces r*G .. r*G + G - 1 of every pair
         std::vector<std::vector<int64_t>> starts(np);
@@ -4053,11 +4166,10 @@ int ffs_split_range_report_batch(ffs_split_range_plan* plan, int n_pairs, const 
             round_start.push_back(n_items);
         }
         if (int rc = plan->items.upload(sizeof(ffsa::CutItem) * n_items, st)) return rc;
-        hipLaunchKernelGGL(ffsa::k_split_prefix, dim3(2 * np), dim3(ffsa::SPLIT_PREFIX_THREADS), 0, st, dd,
-                           (int64_t)plan->max_samples);
+        range_prefixes(plan, np, st);
         hipLaunchKernelGGL(ffsa::k_split_pieces, dim3(np), dim3(ffsa::PIECE_SCAN_THREADS), 0, st, dd, (int)K, max_b,
                            block_offset_dev, (ffsa::PieceReport*)out_dev, n_pieces_out_dev);
-        const int64_t n_tiles = (max_l + ffsa::QUAL_TILE - 1) / ffsa::QUAL_TILE;
+        const int64_t n_tiles = (c.max_l + ffsa::QUAL_TILE - 1) / ffsa::QUAL_TILE;
         for (int64_t r = 0; r < n_rounds; ++r) {
             HIP_TRY(hipMemsetAsync(plan->rows, 0, (size_t)np * G * plan->lpad * 4, st));
             for (int64_t q = round_start[r]; q < round_start[r + 1]; q += ffsa::CUT_MAX_ITEMS) {
@@ -4076,66 +4188,23 @@ int ffs_split_range_report_batch(ffs_split_range_plan* plan, int n_pairs, const 
 
 /* ---- drift-tolerant alignment (csrc/ffs_drift.h) --------------------------------------------------------------- */
 
-struct ffs_drift_plan : PlanCore {
-    int64_t max_blocks, max_lags, max_samples;
-    int64_t lpad, pw_s, pw_r;    // padded lag row, prefix words per vector
-    ffsa::SplitWs ws;            // counts, two V rows per slot (v_slot = 2 rows), arg; no stay bits
-    unsigned long long* codes;   // [slot][max_blocks][lpad / 64][DRIFT_PLANES]
-    int64_t codes_slot;
-    int32_t* pre;                // [slot][pw_s + pw_r]
-    DescStaging desc;            // SplitDesc[pairs_in_flight]
-    double* rows;                // report calls only, made by the first: [slot][DRIFT_ROUND_SEGMENTS][lpad] path curves
-    int64_t row_bytes;
-    void* smooth_mem;            // smooth calls only, made by the first: the tables of ffsa::SmoothWs
+struct ffs_drift_plan : WindowPlan {
+    double* rows = nullptr;      // report calls only, made by the first: [slot][DRIFT_ROUND_SEGMENTS][lpad] path curves
+    void* smooth_mem = nullptr;  // smooth calls only, made by the first: the tables of ffsa::SmoothWs
     ffsa::SmoothWs sw;
-    int64_t smooth_bytes;
 };
 
 int ffs_drift_plan_create(int device, int pairs_in_flight, int64_t max_blocks, int64_t max_lags, int64_t max_samples,
                           ffs_drift_plan** out) {
     if (!out) return fail(FFS_E_INVALID, "null output handle");
     *out = nullptr;
-    if (pairs_in_flight < 1 || max_blocks < 1 || max_lags < 2 || max_lags > 262144 || max_samples < 1)
-        return fail(FFS_E_INVALID, "drift plan: need pairs_in_flight >= 1, max_blocks >= 1, 2 <= max_lags <= 262144, "
-                                   "max_samples >= 1");
+    if (int rc = window_plan_dims_check("drift plan", pairs_in_flight, max_blocks, max_lags, max_samples)) return rc;
     HIP_TRY(hipSetDevice(device));
     ffs_drift_plan* p = new (std::nothrow) ffs_drift_plan();
     if (!p) return fail(FFS_E_NOMEM, "drift plan");
-    p->max_blocks = max_blocks;
-    p->max_lags = max_lags;
-    p->max_samples = max_samples;
-    p->lpad = split_align_up(max_lags, 64);
-    p->pw_s = max_samples / 32 + 2;
-    p->pw_r = (max_samples + max_lags / 2) / 32 + 2;
-    const int64_t counts_slot = split_align_up(max_blocks * p->lpad, 128);                              // uint16
-    const int64_t codes_slot = split_align_up(max_blocks * (p->lpad / 64) * ffsa::DRIFT_PLANES, 32);    // uint64
-    const int64_t v_slot = 2 * split_align_up(p->lpad, 32);                                             // double, two rows
-    const int64_t arg_slot = split_align_up(max_blocks, 64);                                            // int32
-    const int64_t pre_slot = split_align_up(p->pw_s + p->pw_r, 64);                                     // int32
-    const int64_t n = pairs_in_flight;
-    const int64_t b_counts = n * counts_slot * 2, b_codes = n * codes_slot * 8, b_v = n * v_slot * 8, b_arg = n * arg_slot * 4,
-                  b_pre = n * pre_slot * 4;
-    if (int rc = p->open(device, pairs_in_flight, b_counts + b_codes + b_v + b_arg + b_pre, "drift plan")) {
+    if (int rc = window_plan_open(p, "drift plan", true, device, pairs_in_flight, max_blocks, max_lags, max_samples)) {
         ffs_drift_plan_destroy(p);
         return rc;
-    }
-    char* w = (char*)p->work;
-    p->ws.counts = (uint16_t*)w;
-    p->ws.stay = nullptr;
-    p->codes = (unsigned long long*)(w + b_counts);
-    p->ws.V = (double*)(w + b_counts + b_codes);
-    p->ws.arg = (int32_t*)(w + b_counts + b_codes + b_v);
-    p->pre = (int32_t*)(w + b_counts + b_codes + b_v + b_arg);
-    p->ws.counts_row = p->lpad;
-    p->ws.stay_row = p->lpad / 64;
-    p->ws.counts_slot = counts_slot;
-    p->ws.stay_slot = 0;
-    p->codes_slot = codes_slot;
-    p->ws.v_slot = v_slot;
-    p->ws.arg_slot = arg_slot;
-    if (p->desc.create(sizeof(ffsa::SplitDesc) * (size_t)pairs_in_flight) != FFS_OK) {
-        ffs_drift_plan_destroy(p);
-        return fail(FFS_E_HIP, "drift plan: descriptor buffers / events");
     }
     *out = p;
     return FFS_OK;
@@ -4144,16 +4213,11 @@ int ffs_drift_plan_create(int device, int pairs_in_flight, int64_t max_blocks, i
 int ffs_drift_plan_destroy(ffs_drift_plan* plan) {
     if (!plan) return FFS_OK;
     plan->close();
-    plan->desc.release();
-    if (plan->rows) (void)hipFree(plan->rows);
-    if (plan->smooth_mem) (void)hipFree(plan->smooth_mem);
     delete plan;
     return FFS_OK;
 }
 
-int64_t ffs_drift_plan_workspace_bytes(const ffs_drift_plan* plan) {
-    return plan ? plan->work_bytes + plan->row_bytes + plan->smooth_bytes : 0;
-}
+int64_t ffs_drift_plan_workspace_bytes(const ffs_drift_plan* plan) { return plan ? plan->workspace_bytes() : 0; }
 
 namespace {
 struct DriftReportArgs {  // the per-segment report of ffs_align_drift_report_batch
@@ -4172,35 +4236,27 @@ struct DriftSmoothArgs {  // the smooth fit of ffs_align_drift_smooth_batch
     int32_t* n_segments;
 };
 
-// the smooth workspace of a plan, made by its first smooth call: segment / interval tables, line scores, back-pointers,
-// then `extra_bytes` more for the caller (*extra points at them)
-int smooth_workspace(int64_t pairs_in_flight, int64_t max_blocks, void** mem, ffsa::SmoothWs* sw, int64_t* bytes_out,
-                     int64_t extra_bytes, char** extra) {
+// The smooth workspace of a plan of `max_blocks` blocks, made by its first smooth call: line scores, back-pointers,
+// segment / interval tables, and with `band` that many uint16 band cells behind them (the drift range plan's).
+int smooth_workspace(PlanCore* plan, int64_t max_blocks, void** mem, ffsa::SmoothWs* sw, int64_t band_cells, uint16_t** band) {
     if (*mem) return FFS_OK;
-    const int64_t n = pairs_in_flight, mb = split_align_up(max_blocks, 16);
-    const int64_t b_t = n * mb * ffsa::SMOOTH_MAX_STATES * 8, b_back = split_align_up(n * mb * ffsa::SMOOTH_MAX_STATES, 64),
-                  b_seg = n * mb * (int64_t)sizeof(ffsa::SmoothSeg), b_iv = n * mb * (int64_t)sizeof(ffsa::SmoothInt),
-                  b_of = n * mb * 4, b_n = split_align_up(n * 4, 64);
-    const int64_t tables = b_t + b_back + b_seg + b_iv + b_of + b_n, bytes = tables + extra_bytes;
-    if (hipMalloc(mem, bytes) != hipSuccess) {
-        *mem = nullptr;
-        return fail(FFS_E_NOMEM, "drift plan: %lld smooth workspace bytes", (long long)bytes);
-    }
-    char* w = (char*)*mem;
-    sw->T = (double*)w;
-    sw->back = (uint8_t*)(w + b_t);
-    sw->seg = (ffsa::SmoothSeg*)(w + b_t + b_back);
-    sw->iv = (ffsa::SmoothInt*)(w + b_t + b_back + b_seg);
-    sw->seg_of = (int32_t*)(w + b_t + b_back + b_seg + b_iv);
-    sw->n_int = (int32_t*)(w + b_t + b_back + b_seg + b_iv + b_of);
+    const int64_t n = plan->pairs_in_flight, mb = split_align_up(max_blocks, 16);
+    auto carve = [&](Carver& c) {
+        sw->T = c.take<double>(n * mb * ffsa::SMOOTH_MAX_STATES);
+        sw->back = c.take<uint8_t>(n * mb * ffsa::SMOOTH_MAX_STATES, 64);
+        sw->seg = c.take<ffsa::SmoothSeg>(n * mb);
+        sw->iv = c.take<ffsa::SmoothInt>(n * mb);
+        sw->seg_of = c.take<int32_t>(n * mb);
+        sw->n_int = c.take<int32_t>(n, 64);
+        if (band) *band = c.take<uint16_t>(band_cells);
+    };
+    Carver size{nullptr};
+    carve(size);
+    if (int rc = plan->add_block(mem, size.used, "drift plan", "smooth")) return rc;
+    Carver place{(char*)*mem};
+    carve(place);
     sw->stride = mb;
-    if (extra) *extra = w + tables;
-    *bytes_out = bytes;
     return FFS_OK;
-}
-int drift_smooth_workspace(ffs_drift_plan* plan) {
-    return smooth_workspace(plan->pairs_in_flight, plan->max_blocks, &plan->smooth_mem, &plan->sw, &plan->smooth_bytes, 0,
-                            nullptr);
 }
 
 // the parameter and output checks of a smooth fit
@@ -4221,74 +4277,41 @@ int drift_batch(ffs_drift_plan* plan, int n_pairs, const Pairs& a, int64_t block
                 double split_penalty, int max_step, double step_cost, int32_t* block_offset_out_dev,
                 double* block_score_out_dev, uint8_t* block_jump_out_dev, double* total_out_dev, const DriftReportArgs* rep,
                 const DriftSmoothArgs* fit, void* hip_stream) {
-    if (!plan) return fail(FFS_E_INVALID, "null drift plan");
-    if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
-    if (n_pairs == 0) return FFS_OK;
-    if (a.any_null() || !block_offset_out_dev || !block_score_out_dev || !block_jump_out_dev || !total_out_dev)
-        return fail(FFS_E_INVALID, "null argument");
+    if (int rc = check_call(plan, "drift", n_pairs,
+                            a.any_null() || !block_offset_out_dev || !block_score_out_dev || !block_jump_out_dev || !total_out_dev);
+        rc != CALL_GO_ON)
+        return rc;
     const int64_t K = block_samples, W = max_offset_samples;
     if (int rc = check_block_samples(K)) return rc;
-    if (W < 1 || 2 * W > 262144) return fail(FFS_E_INVALID, "max_offset_samples=%lld: need 1 <= W, 2W <= 262144", (long long)W);
-    if (2 * W > plan->max_lags)
-        return fail(FFS_E_INVALID, "2 * max_offset_samples = %lld exceeds the plan's max_lags %lld", (long long)(2 * W),
-                    (long long)plan->max_lags);
-    if (!(split_penalty >= 0.0)) return fail(FFS_E_INVALID, "split_penalty must be >= 0 (not NaN)");
-    if (max_step < 0 || max_step > ffsa::DRIFT_MAX_STEP)
-        return fail(FFS_E_INVALID, "max_step=%d outside [0, %d]", max_step, ffsa::DRIFT_MAX_STEP);
-    if (!(step_cost >= 0.0) || !std::isfinite(step_cost)) return fail(FFS_E_INVALID, "step_cost must be finite and >= 0");
+    if (int rc = check_window(W, plan->max_lags)) return rc;
+    if (int rc = check_split_penalty(split_penalty)) return rc;
+    if (int rc = check_step(max_step, ffsa::DRIFT_MAX_STEP, "", step_cost)) return rc;
     if (rep) {
-        if (rep->top_k < 1 || rep->top_k > ffsa::QUAL_MAX_PEAKS) return fail(FFS_E_INVALID, "top_k=%d outside [1, 8]", rep->top_k);
-        if (rep->exclusion < 1) return fail(FFS_E_INVALID, "exclusion_samples=%lld: need >= 1", (long long)rep->exclusion);
+        if (int rc = check_peaks(rep->top_k, rep->exclusion)) return rc;
         if (!rep->out || !rep->n_segments) return fail(FFS_E_INVALID, "null argument");
         if (((uintptr_t)rep->out & 7) || ((uintptr_t)rep->n_segments & 3)) return fail(FFS_E_INVALID, "misaligned report outputs");
     }
     if (fit)
         if (int rc = check_smooth_args(*fit)) return rc;
     int64_t max_b = 0;
-    for (int p = 0; p < n_pairs; ++p) {
-        if (int rc = a.check(p)) return rc;
-        if (a.sub_len[p] > plan->max_samples)
-            return fail(FFS_E_INVALID, "pair %d: subtitle length %lld exceeds the plan's max_samples %lld", p,
-                        (long long)a.sub_len[p], (long long)plan->max_samples);
-        const int64_t B = (a.sub_len[p] + K - 1) / K;
-        if (B > plan->max_blocks)
-            return fail(FFS_E_INVALID, "pair %d: %lld blocks exceed the plan's max_blocks %lld", p, (long long)B,
-                        (long long)plan->max_blocks);
-        max_b = std::max(max_b, B);
-    }
+    if (int rc = window_limits_check(plan, n_pairs, a, K, &max_b)) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
     if (int rc = plan->begin(st)) return rc;
     if (fit)
-        if (int rc = drift_smooth_workspace(plan)) return rc;
+        if (int rc = smooth_workspace(plan, plan->max_blocks, &plan->smooth_mem, &plan->sw, 0, nullptr)) return rc;
     constexpr int G = ffsa::DRIFT_ROUND_SEGMENTS;
-    if (rep && !plan->rows) {  // the first report call: G fp64 path-curve rows per slot
-        const int64_t bytes = (int64_t)plan->pairs_in_flight * G * plan->lpad * 8;
-        if (hipMalloc((void**)&plan->rows, bytes) != hipSuccess) {
-            plan->rows = nullptr;
-            return fail(FFS_E_NOMEM, "drift plan: %lld report workspace bytes", (long long)bytes);
-        }
-        plan->row_bytes = bytes;
-    }
+    if (rep && !plan->rows)  // the first report call: G fp64 path-curve rows per slot
+        if (int rc = plan->add_block((void**)&plan->rows, (int64_t)plan->pairs_in_flight * G * plan->lpad * 8, "drift plan",
+                                     "report"))
+            return rc;
     const int64_t L = 2 * W;
-    const int n_tiles = (int)((L + ffsa::SPLIT_TILE - 1) / ffsa::SPLIT_TILE);
-    const int64_t pre_slot = split_align_up(plan->pw_s + plan->pw_r, 64);
-    ffsa::SplitDesc* hd = (ffsa::SplitDesc*)plan->desc.host;
     const ffsa::SplitDesc* dd = (const ffsa::SplitDesc*)plan->desc.dev;
     std::vector<int32_t> n_seg;  // report calls: the sub-batch's segment counts, read back to size its rounds
     for (int p0 = 0; p0 < n_pairs; p0 += plan->pairs_in_flight) {
         const int np = std::min(plan->pairs_in_flight, n_pairs - p0);
-        if (int rc = plan->desc.wait_free()) return rc;
         int64_t chunk_b = 0;
-        for (int i = 0; i < np; ++i) {
-            int32_t* pre_s = plan->pre + (int64_t)i * pre_slot;
-            hd[i] = a.split_desc(p0 + i, pre_s, pre_s + plan->pw_s);
-            chunk_b = std::max(chunk_b, (hd[i].S + K - 1) / K);
-        }
-        if (int rc = plan->desc.upload(sizeof(ffsa::SplitDesc) * np, st)) return rc;
-        const int n_bgroups = (int)((chunk_b + ffsa::SPLIT_BPW - 1) / ffsa::SPLIT_BPW);
-        hipLaunchKernelGGL(ffsa::k_split_prefix, dim3(2 * np), dim3(ffsa::SPLIT_PREFIX_THREADS), 0, st, dd, (int64_t)W);
-        hipLaunchKernelGGL(ffsa::k_split_counts, dim3((unsigned)((int64_t)n_tiles * n_bgroups * np)),
-                           dim3(ffsa::SPLIT_CNT_THREADS), 0, st, dd, plan->ws, (int)K, (int64_t)W, n_tiles, n_bgroups);
+        if (int rc = window_stage(plan, a, p0, np, K, st, &chunk_b)) return rc;
+        window_counts(plan, np, K, W, chunk_b, st);
         hipLaunchKernelGGL(ffsa::k_drift_dp, dim3(np), dim3(ffsa::SPLIT_DP_THREADS), 0, st, dd, plan->ws, plan->codes,
                            plan->codes_slot, (int)K, (int64_t)W, split_penalty, max_step, step_cost, max_b,
                            block_offset_out_dev, block_score_out_dev, block_jump_out_dev, total_out_dev);
@@ -4377,70 +4400,36 @@ int ffs_align_drift_smooth_batch(ffs_drift_plan* plan, int n_pairs, const void* 
 
 /* ---- drift-tolerant alignment over a lag range (csrc/ffs_drift_range.h) ---------------------------------------- */
 
-struct ffs_drift_range_plan : PlanCore {
-    int64_t max_blocks, max_lags, max_samples;
+struct ffs_drift_range_plan : RangePlan {  // ws.stay = the code planes (max_step_cap's count), V = two rows per slot
     int max_step_cap;
-    int64_t pw;                 // prefix words per vector
-    ffsa::RangeWs ws;           // stay = the code planes (max_step_cap's count), V = two rows per slot
-    int32_t* pre;               // [slot][2 * pw]: s, then r
-    DescStaging desc;           // SplitDesc[pairs_in_flight], then RangeLag[pairs_in_flight]
-    void* smooth_mem;           // smooth calls only, made by the first: the tables of ffsa::SmoothWs, then the band rows
+    void* smooth_mem = nullptr;     // smooth calls only, made by the first: the tables of ffsa::SmoothWs, then the band rows
     ffsa::SmoothWs sw;
-    uint16_t* band;             // [slot][sw.stride][range_band_row(max_step_cap, 256, 16)]
-    int64_t smooth_bytes;
-    void* report_mem = nullptr; // report calls only, made by the first: the fp64 score rows, then the uint32 n11 rows
+    uint16_t* band = nullptr;       // [slot][sw.stride][range_band_row(max_step_cap, 256, 16)]
+    void* report_mem = nullptr;     // report calls only, made by the first: the fp64 score rows, then the uint32 n11 rows
     double* rep_scores = nullptr;   // [slot][RPATH_ROUND_SEGMENTS][rep_lpad]
     uint32_t* rep_rows = nullptr;   // [slot][RPATH_ROUND_SEGMENTS][rep_lpad]
-    int64_t rep_lpad = 0;       // max_lags + 1 cells, padded to 64
-    DescStaging rep_items;      // report calls only: RangePathItem[rep_item_cap]
-    int64_t rep_item_cap = 0;
-    int64_t report_bytes = 0;
+    int64_t rep_lpad;               // max_lags + 1 cells, padded to 64
+    DescStaging rep_items;          // report calls only, made by the first: RangePathItem[rep_item_cap]
+    int64_t rep_item_cap;
 };
 
 int ffs_drift_range_plan_create(int device, int pairs_in_flight, int64_t max_blocks, int64_t max_lags, int64_t max_samples,
                                 int max_step_cap, ffs_drift_range_plan** out) {
     if (!out) return fail(FFS_E_INVALID, "null output handle");
     *out = nullptr;
-    if (pairs_in_flight < 1 || pairs_in_flight > 65535 || max_blocks < 1 || max_lags < 1 || max_lags > INT32_MAX ||
-        max_samples < 1 || max_samples > INT32_MAX / 2 || max_step_cap < 0 || max_step_cap > ffsa::DRIFT_RANGE_MAX_STEP)
-        return fail(FFS_E_INVALID, "drift range plan: need 1 <= pairs_in_flight <= 65535, max_blocks >= 1, "
-                                   "1 <= max_lags <= 2^31 - 1, 1 <= max_samples <= 2^30 - 1, 0 <= max_step_cap <= 7");
+    if (int rc = range_plan_dims_check("drift range plan", ", 0 <= max_step_cap <= 7", pairs_in_flight, max_blocks, max_lags,
+                                       max_samples, max_step_cap))
+        return rc;
     HIP_TRY(hipSetDevice(device));
     ffs_drift_range_plan* p = new (std::nothrow) ffs_drift_range_plan();
     if (!p) return fail(FFS_E_NOMEM, "drift range plan");
-    p->max_blocks = max_blocks;
-    p->max_lags = max_lags;
-    p->max_samples = max_samples;
     p->max_step_cap = max_step_cap;
-    p->pw = max_samples / 32 + 2;
-    const int64_t row = (max_lags + 63) / 64;  // 64-lag words per block row and plane
-    const int64_t part_row = split_align_up((max_lags + ffsa::RANGE_TILE - 1) / ffsa::RANGE_TILE, 32);
-    const int64_t codes_slot = split_align_up(max_blocks * row * ffsa::drift_range_planes(max_step_cap), 32);  // uint64
-    const int64_t v_slot = 2 * split_align_up(row * 64, 32);                // double, two rows
-    const int64_t arg_slot = split_align_up(max_blocks, 64);                // int32
-    const int64_t pre_slot = split_align_up(2 * p->pw, 64);                 // int32
-    const int64_t n = pairs_in_flight;
-    const int64_t b_codes = n * codes_slot * 8, b_v = n * v_slot * 8, b_pv = n * 2 * part_row * 8,
-                  b_pj = n * 2 * part_row * 4, b_arg = n * arg_slot * 4, b_pre = n * pre_slot * 4;
-    if (int rc = p->open(device, pairs_in_flight, b_codes + b_v + b_pv + b_pj + b_arg + b_pre, "drift range plan")) {
+    p->rep_lpad = split_align_up(max_lags + 1, 64);
+    p->rep_item_cap = (int64_t)pairs_in_flight * ffsa::range_path_item_cap(max_samples, max_blocks);
+    if (int rc = range_plan_open(p, "drift range plan", ffsa::drift_range_planes(max_step_cap), 2, device, pairs_in_flight,
+                                 max_blocks, max_lags, max_samples)) {
         ffs_drift_range_plan_destroy(p);
         return rc;
-    }
-    char* w = (char*)p->work;
-    p->ws.stay = (unsigned long long*)w;
-    p->ws.V = (double*)(w + b_codes);
-    p->ws.pv = (double*)(w + b_codes + b_v);
-    p->ws.pj = (int32_t*)(w + b_codes + b_v + b_pv);
-    p->ws.arg = (int32_t*)(w + b_codes + b_v + b_pv + b_pj);
-    p->pre = (int32_t*)(w + b_codes + b_v + b_pv + b_pj + b_arg);
-    p->ws.stay_row = row;
-    p->ws.stay_slot = codes_slot;
-    p->ws.v_slot = v_slot;
-    p->ws.part_row = part_row;
-    p->ws.arg_slot = arg_slot;
-    if (p->desc.create((sizeof(ffsa::SplitDesc) + sizeof(ffsa::RangeLag)) * (size_t)pairs_in_flight) != FFS_OK) {
-        ffs_drift_range_plan_destroy(p);
-        return fail(FFS_E_HIP, "drift range plan: descriptor buffers / events");
     }
     *out = p;
     return FFS_OK;
@@ -4449,17 +4438,11 @@ int ffs_drift_range_plan_create(int device, int pairs_in_flight, int64_t max_blo
 int ffs_drift_range_plan_destroy(ffs_drift_range_plan* plan) {
     if (!plan) return FFS_OK;
     plan->close();
-    plan->desc.release();
-    if (plan->smooth_mem) (void)hipFree(plan->smooth_mem);
-    if (plan->report_mem) (void)hipFree(plan->report_mem);
-    plan->rep_items.release();
     delete plan;
     return FFS_OK;
 }
 
-int64_t ffs_drift_range_plan_workspace_bytes(const ffs_drift_range_plan* plan) {
-    return plan ? plan->work_bytes + plan->smooth_bytes + plan->report_bytes : 0;
-}
+int64_t ffs_drift_range_plan_workspace_bytes(const ffs_drift_range_plan* plan) { return plan ? plan->workspace_bytes() : 0; }
 
 namespace {
 // ffs_align_drift_range_batch; with `fit` the smooth fit after each sub-batch's scores
@@ -4467,63 +4450,44 @@ int drift_range_batch(ffs_drift_range_plan* plan, int n_pairs, const Pairs& a, i
                       const int64_t* lag_hi, double split_penalty, int max_step, double step_cost,
                       int32_t* block_offset_out_dev, double* block_score_out_dev, uint8_t* block_jump_out_dev,
                       double* total_out_dev, const DriftSmoothArgs* fit, void* hip_stream) {
-    if (!plan) return fail(FFS_E_INVALID, "null drift range plan");
-    if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
-    if (n_pairs == 0) return FFS_OK;
-    if (a.any_null() || !lag_lo || !lag_hi || !block_offset_out_dev || !block_score_out_dev || !block_jump_out_dev ||
-        !total_out_dev)
-        return fail(FFS_E_INVALID, "null argument");
+    if (int rc = check_call(plan, "drift range", n_pairs,
+                            a.any_null() || !lag_lo || !lag_hi || !block_offset_out_dev || !block_score_out_dev ||
+                                !block_jump_out_dev || !total_out_dev);
+        rc != CALL_GO_ON)
+        return rc;
     if (((uintptr_t)block_offset_out_dev & 3) || ((uintptr_t)block_score_out_dev & 7) || ((uintptr_t)total_out_dev & 7))
         return fail(FFS_E_INVALID, "misaligned outputs");
     const int64_t K = block_samples;
     if (int rc = check_block_samples(K)) return rc;
-    if (!(split_penalty >= 0.0)) return fail(FFS_E_INVALID, "split_penalty must be >= 0 (not NaN)");
-    if (max_step < 0 || max_step > plan->max_step_cap)
-        return fail(FFS_E_INVALID, "max_step=%d outside [0, %d] (the plan's max_step_cap)", max_step, plan->max_step_cap);
-    if (!(step_cost >= 0.0) || !std::isfinite(step_cost)) return fail(FFS_E_INVALID, "step_cost must be finite and >= 0");
+    if (int rc = check_split_penalty(split_penalty)) return rc;
+    if (int rc = check_step(max_step, plan->max_step_cap, " (the plan's max_step_cap)", step_cost)) return rc;
     if (fit)
         if (int rc = check_smooth_args(*fit)) return rc;
     int64_t max_b = 0;
-    if (int rc = range_limits_check(plan->max_samples, plan->max_blocks, plan->max_lags, n_pairs, a, K, lag_lo, lag_hi,
-                                    &max_b))
-        return rc;
+    if (int rc = range_limits_check(plan, n_pairs, a, K, lag_lo, lag_hi, &max_b)) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
     if (int rc = plan->begin(st)) return rc;
+    const int pif = plan->pairs_in_flight;
     ffsa::RangeBand band{nullptr, 0};
     if (fit) {  // the first smooth call: the fit's tables and band rows wide enough for every later call
         const int64_t cap_row = ffsa::range_band_row(plan->max_step_cap, ffsa::SMOOTH_MAX_KNOT_BLOCKS, ffsa::SMOOTH_MAX_RADIUS);
-        const int64_t b_band = (int64_t)plan->pairs_in_flight * split_align_up(plan->max_blocks, 16) * cap_row * 2;
-        if (int rc = smooth_workspace(plan->pairs_in_flight, plan->max_blocks, &plan->smooth_mem, &plan->sw,
-                                      &plan->smooth_bytes, b_band, (char**)&plan->band))
+        if (int rc = smooth_workspace(plan, plan->max_blocks, &plan->smooth_mem, &plan->sw,
+                                      (int64_t)pif * split_align_up(plan->max_blocks, 16) * cap_row, &plan->band))
             return rc;
         band.cells = plan->band;
         band.row = ffsa::range_band_row(max_step, fit->knot_blocks, fit->radius);
     }
     const int planes = ffsa::drift_range_planes(max_step);
-    const int64_t pre_slot = split_align_up(2 * plan->pw, 64);
-    const int pif = plan->pairs_in_flight;
-    ffsa::SplitDesc* hd = (ffsa::SplitDesc*)plan->desc.host;
-    ffsa::RangeLag* hl = (ffsa::RangeLag*)(hd + pif);
-    const ffsa::SplitDesc* dd = (const ffsa::SplitDesc*)plan->desc.dev;
-    const ffsa::RangeLag* dl = (const ffsa::RangeLag*)(dd + pif);
+    const ffsa::SplitDesc* dd = plan->dd();
+    const ffsa::RangeLag* dl = plan->dl();
     for (int p0 = 0; p0 < n_pairs; p0 += pif) {
         const int np = std::min(pif, n_pairs - p0);
-        if (int rc = plan->desc.wait_free()) return rc;
-        int64_t chunk_b = 0, max_tiles = 0;
-        for (int i = 0; i < np; ++i) {
-            const int p = p0 + i;
-            int32_t* pre_s = plan->pre + (int64_t)i * pre_slot;
-            hd[i] = a.split_desc(p, pre_s, pre_s + plan->pw);
-            hl[i].lag_lo = lag_lo[p];
-            hl[i].L = lag_hi[p] - lag_lo[p] + 1;
-            chunk_b = std::max(chunk_b, (hd[i].S + K - 1) / K);
-            max_tiles = std::max(max_tiles, (hl[i].L + ffsa::RANGE_TILE - 1) / ffsa::RANGE_TILE);
-        }
-        if (int rc = plan->desc.upload(sizeof(ffsa::SplitDesc) * pif + sizeof(ffsa::RangeLag) * np, st)) return rc;
-        hipLaunchKernelGGL(ffsa::k_split_prefix, dim3(2 * np), dim3(ffsa::SPLIT_PREFIX_THREADS), 0, st, dd,
-                           (int64_t)plan->max_samples);
+        RangeChunk c;
+        if (int rc = range_stage(plan, a, lag_lo, lag_hi, p0, np, K, st, &c)) return rc;
+        range_prefixes(plan, np, st);
+        const int64_t chunk_b = c.chunk_b;
         for (int64_t b = 0; b < chunk_b; ++b)
-            hipLaunchKernelGGL(ffsa::k_range_drift_step, dim3((unsigned)max_tiles, (unsigned)np), dim3(ffsa::RANGE_THREADS),
+            hipLaunchKernelGGL(ffsa::k_range_drift_step, dim3((unsigned)c.max_tiles, (unsigned)np), dim3(ffsa::RANGE_THREADS),
                                0, st, dd, dl, plan->ws, (int)K, b, split_penalty, max_step, step_cost, planes);
         hipLaunchKernelGGL(ffsa::k_range_drift_backtrack, dim3(np), dim3(ffsa::RANGE_THREADS), 0, st, dd, dl, plan->ws,
                            (int)K, max_b, max_step, planes, block_offset_out_dev, block_jump_out_dev, total_out_dev);
@@ -4592,67 +4556,46 @@ int ffs_drift_range_report_batch(ffs_drift_range_plan* plan, int n_pairs, const 
                                  int top_k, int64_t exclusion_samples, ffs_segment_report* report_out_dev,
                                  int32_t* n_segments_out_dev, void* hip_stream) {
     const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
-    if (!plan) return fail(FFS_E_INVALID, "null drift range plan");
-    if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
-    if (n_pairs == 0) return FFS_OK;
-    if (a.any_null() || !lag_lo || !lag_hi || !block_offset_dev || !block_jump_dev || !report_out_dev || !n_segments_out_dev)
-        return fail(FFS_E_INVALID, "null argument");
+    if (int rc = check_call(plan, "drift range", n_pairs,
+                            a.any_null() || !lag_lo || !lag_hi || !block_offset_dev || !block_jump_dev || !report_out_dev ||
+                                !n_segments_out_dev);
+        rc != CALL_GO_ON)
+        return rc;
     if (((uintptr_t)block_offset_dev & 3) || ((uintptr_t)report_out_dev & 7) || ((uintptr_t)n_segments_out_dev & 3))
         return fail(FFS_E_INVALID, "misaligned block offsets or report outputs");
     const int64_t K = block_samples;
     if (int rc = check_block_samples(K)) return rc;
-    if (top_k < 1 || top_k > ffsa::QUAL_MAX_PEAKS) return fail(FFS_E_INVALID, "top_k=%d outside [1, 8]", top_k);
-    if (exclusion_samples < 1) return fail(FFS_E_INVALID, "exclusion_samples=%lld: need >= 1", (long long)exclusion_samples);
+    if (int rc = check_peaks(top_k, exclusion_samples)) return rc;
     int64_t max_b = 0;
-    if (int rc = range_limits_check(plan->max_samples, plan->max_blocks, plan->max_lags, n_pairs, a, K, lag_lo, lag_hi,
-                                    &max_b))
-        return rc;
-    // the path on the host (after the stream's earlier work): the offsets checked against the ranges, then the rounds'
-    // work items are made from its segments and their runs
+    if (int rc = range_limits_check(plan, n_pairs, a, K, lag_lo, lag_hi, &max_b)) return rc;
+    // the path on the host: the rounds' work items are made from its segments and their runs
     hipStream_t st = (hipStream_t)hip_stream;
-    std::vector<int32_t> offs((size_t)n_pairs * max_b);
-    std::vector<uint8_t> jumps((size_t)n_pairs * max_b);
-    HIP_TRY(hipSetDevice(plan->device));
-    HIP_TRY(hipMemcpyAsync(offs.data(), block_offset_dev, offs.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(jumps.data(), block_jump_dev, jumps.size(), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (int p = 0; p < n_pairs; ++p) {
-        const int64_t B = (sub_len[p] + K - 1) / K;
-        for (int64_t b = 0; b < B; ++b) {
-            const int64_t o = offs[(size_t)p * max_b + b];
-            if (o < lag_lo[p] || o > lag_hi[p])
-                return fail(FFS_E_INVALID, "pair %d: block %lld offset %lld outside the lag range [%lld, %lld]", p,
-                            (long long)b, (long long)o, (long long)lag_lo[p], (long long)lag_hi[p]);
-        }
-    }
+    std::vector<int32_t> offs;
+    std::vector<uint8_t> jumps;
+    if (int rc = read_path(plan, n_pairs, a, K, max_b, lag_lo, lag_hi, block_offset_dev, block_jump_dev, &offs, &jumps, st))
+        return rc;
     if (int rc = plan->begin(st)) return rc;
     const int pif = plan->pairs_in_flight;
     constexpr int G = ffsa::RPATH_ROUND_SEGMENTS;
-    if (!plan->report_mem) {  // the first report call: G score and n11 rows per pair in flight, one sub-batch's items
-        const int64_t lpad = split_align_up(plan->max_lags + 1, 64);
-        const int64_t cells = (int64_t)pif * G * lpad;
-        const int64_t item_cap = (int64_t)pif * ffsa::range_path_item_cap(plan->max_samples, plan->max_blocks);
-        const int64_t item_bytes = item_cap * (int64_t)sizeof(ffsa::RangePathItem);
-        void* mem = nullptr;
-        if (hipMalloc(&mem, (size_t)(cells * 12)) != hipSuccess)
-            return fail(FFS_E_NOMEM, "drift range plan: %lld report workspace bytes", (long long)(cells * 12));
-        if (int rc = plan->rep_items.create((size_t)item_bytes)) {
-            (void)hipFree(mem);
-            return fail(rc, "drift range plan: report work items");
-        }
-        plan->report_mem = mem;
-        plan->rep_scores = (double*)mem;
-        plan->rep_rows = (uint32_t*)((char*)mem + cells * 8);
-        plan->rep_lpad = lpad;
-        plan->rep_item_cap = item_cap;
-        plan->report_bytes = cells * 12 + item_bytes;
-    }
     const int64_t lpad = plan->rep_lpad;
-    const int64_t pre_slot = split_align_up(2 * plan->pw, 64);
-    ffsa::SplitDesc* hd = (ffsa::SplitDesc*)plan->desc.host;
-    ffsa::RangeLag* hl = (ffsa::RangeLag*)(hd + pif);
-    const ffsa::SplitDesc* dd = (const ffsa::SplitDesc*)plan->desc.dev;
-    const ffsa::RangeLag* dl = (const ffsa::RangeLag*)(dd + pif);
+    // the first report call: G score and n11 rows per pair in flight, one sub-batch's items
+    if (!plan->report_mem) {
+        auto carve = [&](Carver& c) {
+            plan->rep_scores = c.take<double>((int64_t)pif * G * lpad);
+            plan->rep_rows = c.take<uint32_t>((int64_t)pif * G * lpad);
+        };
+        Carver size{nullptr};
+        carve(size);
+        if (int rc = plan->add_block(&plan->report_mem, size.used, "drift range plan", "report")) return rc;
+        Carver place{(char*)plan->report_mem};
+        carve(place);
+    }
+    if (!plan->rep_items.dev)
+        if (int rc = plan->add_staging(&plan->rep_items, (size_t)plan->rep_item_cap * sizeof(ffsa::RangePathItem), 0,
+                                       "drift range plan: report work items"))
+            return rc;
+    const ffsa::SplitDesc* dd = plan->dd();
+    const ffsa::RangeLag* dl = plan->dl();
     const ffsa::RangePathItem* di_items = (const ffsa::RangePathItem*)plan->rep_items.dev;
     ffsa::SegmentReport* out = (ffsa::SegmentReport*)report_out_dev;
     std::vector<std::vector<ffsa::RangePathSegment>> segs;
@@ -4660,17 +4603,8 @@ int ffs_drift_range_report_batch(ffs_drift_range_plan* plan, int n_pairs, const 
     std::vector<int64_t> round_start;  // per round: its first work item (+ the end)
     for (int p0 = 0; p0 < n_pairs; p0 += pif) {
         const int np = std::min(pif, n_pairs - p0);
-        if (int rc = plan->desc.wait_free()) return rc;
-        int64_t max_l = 0;
-        for (int i = 0; i < np; ++i) {
-            const int p = p0 + i;
-            int32_t* pre_s = plan->pre + (int64_t)i * pre_slot;
-            hd[i] = a.split_desc(p, pre_s, pre_s + plan->pw);
-            hl[i].lag_lo = lag_lo[p];
-            hl[i].L = lag_hi[p] - lag_lo[p] + 1;
-            max_l = std::max(max_l, hl[i].L);
-        }
-        if (int rc = plan->desc.upload(sizeof(ffsa::SplitDesc) * pif + sizeof(ffsa::RangeLag) * np, st)) return rc;
+        RangeChunk c;
+        if (int rc = range_stage(plan, a, lag_lo, lag_hi, p0, np, K, st, &c)) return rc;
         // the segments of each pair (as k_drift_segments forms them) -> work items, round by round: round r holds the
         // segments r*G .. r*G + G - 1 of every pair
         segs.resize((size_t)np);
@@ -4689,7 +4623,7 @@ int ffs_drift_range_report_batch(ffs_drift_range_plan* plan, int n_pairs, const 
                 const int p = p0 + i;
                 for (int g = 0; g < G && r * G + g < (int64_t)segs[i].size(); ++g)
                     ffsa::range_path_items(offs.data() + (size_t)p * max_b, segs[i][(size_t)(r * G + g)], K, sub_len[p],
-                                           lag_lo[p], hl[i].L, i * G + g, items);
+                                           lag_lo[p], lag_hi[p] - lag_lo[p] + 1, i * G + g, items);
             }
             round_start.push_back((int64_t)items.size());
         }
@@ -4699,12 +4633,11 @@ int ffs_drift_range_report_batch(ffs_drift_range_plan* plan, int n_pairs, const 
         if (int rc = plan->rep_items.wait_free()) return rc;
         memcpy(plan->rep_items.host, items.data(), items.size() * sizeof(ffsa::RangePathItem));
         if (int rc = plan->rep_items.upload(sizeof(ffsa::RangePathItem) * items.size(), st)) return rc;
-        hipLaunchKernelGGL(ffsa::k_split_prefix, dim3(2 * np), dim3(ffsa::SPLIT_PREFIX_THREADS), 0, st, dd,
-                           (int64_t)plan->max_samples);
+        range_prefixes(plan, np, st);
         hipLaunchKernelGGL(ffsa::k_drift_segments, dim3(np), dim3(ffsa::DRIFT_SEG_THREADS), 0, st, dd, (int)K, max_b,
                            block_offset_dev, block_jump_dev, out, n_segments_out_dev);
-        const int64_t n_tiles = (max_l + ffsa::QUAL_TILE - 1) / ffsa::QUAL_TILE;
-        const int n_sum_tiles = (int)((max_l + ffsa::DRIFT_SUM_TILE - 1) / ffsa::DRIFT_SUM_TILE);
+        const int64_t n_tiles = (c.max_l + ffsa::QUAL_TILE - 1) / ffsa::QUAL_TILE;
+        const int n_sum_tiles = (int)((c.max_l + ffsa::DRIFT_SUM_TILE - 1) / ffsa::DRIFT_SUM_TILE);
         for (int64_t r = 0; r < n_rounds; ++r) {
             HIP_TRY(hipMemsetAsync(plan->rep_rows, 0, (size_t)np * G * lpad * 4, st));
             for (int64_t q = round_start[r]; q < round_start[r + 1]; q += ffsa::RPATH_MAX_ITEMS) {
@@ -4727,13 +4660,68 @@ int ffs_drift_range_report_batch(ffs_drift_range_plan* plan, int n_pairs, const 
 
 /* ---- alignment quality report (csrc/ffs_quality.h) ------------------------------------------------------------- */
 
+namespace {
+// the window, the peak parameters and the output records of the quality and the match calls
+int check_quality_args(int64_t max_offset_samples, int top_k, int64_t exclusion_samples, const void* out_dev) {
+    if (max_offset_samples < -1) return fail(FFS_E_INVALID, "max_offset_samples=%lld: need >= 0, or -1 for none", (long long)max_offset_samples);
+    if (int rc = check_peaks(top_k, exclusion_samples)) return rc;
+    if ((uintptr_t)out_dev & 7) return fail(FFS_E_INVALID, "misaligned output records");
+    return FFS_OK;
+}
+
+// pair p's lag window (R and S samples, max_offset_samples) against the plan's lags
+int check_window_lags(int p, int64_t R, int64_t S, int64_t max_offset_samples, int64_t plan_max_lags) {
+    int64_t wl = 0, wh = -1;
+    if (lag_window(R, S, ffs_fft_length(R, S), max_offset_samples, &wl, &wh) && wh - wl + 1 > plan_max_lags)
+        return fail(FFS_E_INVALID, "pair %d: %lld lags exceed the plan's max_lags %lld", p, (long long)(wh - wl + 1),
+                    (long long)plan_max_lags);
+    return FFS_OK;
+}
+
+// the lengths of a pair and its lag window in its (zeroed) descriptor: the window's lags, and of them those with an overlap
+void qual_window(ffsa::QualDesc* q, int64_t R, int64_t S, int64_t max_offset_samples) {
+    q->R = R;
+    q->S = S;
+    int64_t wl = 0, wh = -1;
+    if (lag_window(R, S, ffs_fft_length(R, S), max_offset_samples, &wl, &wh)) {
+        q->d_lo = wl;
+        q->n_lags = wh - wl + 1;
+        const int64_t clo = std::max(wl, 1 - S), chi = std::min(wh, R - 1);
+        q->c_lo = clo;
+        q->n_count = chi >= clo ? chi - clo + 1 : 0;
+    }
+    q->cd.R = (int32_t)R;
+    q->cd.S = (int32_t)S;
+}
+
+// k_quality_counts over n descriptors of at most max_count counted lags and max_sw subtitle words, in chunks of subtitle
+// words: enough workgroups to fill the device (about 4 per CU), at least 64 words each so that the atomics stay a small
+// fraction of the work, at most QUAL_MAX_CHUNK (LDS)
+void quality_counts(const ffsa::QualDesc* dq, int n, int64_t max_count, int64_t max_sw, int n_sm, hipStream_t st) {
+    const int64_t n_tiles = (max_count + ffsa::QUAL_TILE - 1) / ffsa::QUAL_TILE;
+    const int64_t want = std::max<int64_t>(1, (int64_t)n_sm * 4);
+    int64_t cw = (n * n_tiles * max_sw + want - 1) / want;
+    cw = std::min<int64_t>(ffsa::QUAL_MAX_CHUNK, std::max<int64_t>(64, cw));
+    const int64_t n_chunks = (max_sw + cw - 1) / cw;
+    hipLaunchKernelGGL(ffsa::k_quality_counts, dim3((unsigned)(n * n_tiles * n_chunks)), dim3(ffsa::QUAL_CNT_THREADS), 0, st, dq,
+                       (int)n_tiles, (int)n_chunks, (int)cw);
+}
+}  // namespace
+
 struct ffs_quality_plan : PlanCore {
     int64_t max_lags, max_samples;
     int64_t lpad, pre_slot;     // padded curve row, prefix words per slot (both vectors)
     uint32_t* curve;            // [slot][lpad]
     double* sc;                 // [slot][lpad]
     int32_t* pre;               // [slot][pre_slot]
-    DescStaging desc;           // SplitDesc[pairs_in_flight] (k_split_prefix), then QualDesc[pairs_in_flight]
+                                // desc: SplitDesc[pairs_in_flight] (k_split_prefix), then QualDesc[pairs_in_flight]
+
+    void carve(Carver& c) {
+        const int64_t n = pairs_in_flight;
+        sc = c.take<double>(n * lpad);
+        curve = c.take<uint32_t>(n * lpad);
+        pre = c.take<int32_t>(n * pre_slot);
+    }
 };
 
 int ffs_quality_plan_create(int device, int pairs_in_flight, int64_t max_lags, int64_t max_samples, ffs_quality_plan** out) {
@@ -4748,16 +4736,15 @@ int ffs_quality_plan_create(int device, int pairs_in_flight, int64_t max_lags, i
     p->max_samples = max_samples;
     p->lpad = split_align_up(max_lags, 64);
     p->pre_slot = split_align_up(2 * (max_samples / 32 + 2), 64);
-    const int64_t n = pairs_in_flight;
-    const int64_t b_curve = n * p->lpad * 4, b_sc = n * p->lpad * 8, b_pre = n * p->pre_slot * 4;
-    if (int rc = p->open(device, pairs_in_flight, b_curve + b_sc + b_pre, "quality plan")) {
+    p->pairs_in_flight = pairs_in_flight;
+    Carver size{nullptr};
+    p->carve(size);
+    if (int rc = p->open(device, pairs_in_flight, size.used, "quality plan")) {
         ffs_quality_plan_destroy(p);
         return rc;
     }
-    char* w = (char*)p->work;
-    p->sc = (double*)w;
-    p->curve = (uint32_t*)(w + b_sc);
-    p->pre = (int32_t*)(w + b_sc + b_curve);
+    Carver place{(char*)p->work};
+    p->carve(place);
     if (p->desc.create((sizeof(ffsa::SplitDesc) + sizeof(ffsa::QualDesc)) * (size_t)pairs_in_flight) != FFS_OK) {
         ffs_quality_plan_destroy(p);
         return fail(FFS_E_HIP, "quality plan: descriptor buffers / events");
@@ -4769,37 +4756,26 @@ int ffs_quality_plan_create(int device, int pairs_in_flight, int64_t max_lags, i
 int ffs_quality_plan_destroy(ffs_quality_plan* plan) {
     if (!plan) return FFS_OK;
     plan->close();
-    plan->desc.release();
     delete plan;
     return FFS_OK;
 }
 
-int64_t ffs_quality_plan_workspace_bytes(const ffs_quality_plan* plan) { return plan ? plan->work_bytes : 0; }
+int64_t ffs_quality_plan_workspace_bytes(const ffs_quality_plan* plan) { return plan ? plan->workspace_bytes() : 0; }
 
 int ffs_align_quality_batch(ffs_quality_plan* plan, int n_pairs, const void* const* ref_ptr, const int64_t* ref_len,
                             const double* ref_lo, const double* ref_hi, const void* const* sub_ptr, const int64_t* sub_len,
                             const double* sub_lo, const double* sub_hi, int64_t max_offset_samples, int top_k,
                             int64_t exclusion_samples, ffs_quality_result* out_dev, void* hip_stream) {
     const Pairs a{ref_ptr, ref_len, ref_lo, ref_hi, sub_ptr, sub_len, sub_lo, sub_hi};
-    if (!plan) return fail(FFS_E_INVALID, "null quality plan");
-    if (n_pairs < 0) return fail(FFS_E_INVALID, "n_pairs < 0");
-    if (n_pairs == 0) return FFS_OK;
-    if (a.any_null() || !out_dev) return fail(FFS_E_INVALID, "null argument");
-    if (max_offset_samples < -1) return fail(FFS_E_INVALID, "max_offset_samples=%lld: need >= 0, or -1 for none", (long long)max_offset_samples);
-    if (top_k < 1 || top_k > ffsa::QUAL_MAX_PEAKS) return fail(FFS_E_INVALID, "top_k=%d outside [1, 8]", top_k);
-    if (exclusion_samples < 1) return fail(FFS_E_INVALID, "exclusion_samples=%lld: need >= 1", (long long)exclusion_samples);
-    if ((uintptr_t)out_dev & 7) return fail(FFS_E_INVALID, "misaligned output records");
+    if (int rc = check_call(plan, "quality", n_pairs, a.any_null() || !out_dev); rc != CALL_GO_ON) return rc;
+    if (int rc = check_quality_args(max_offset_samples, top_k, exclusion_samples, out_dev)) return rc;
     int64_t max_sw = 0;
     for (int p = 0; p < n_pairs; ++p) {
         if (int rc = a.check(p)) return rc;
         if (ref_len[p] > plan->max_samples || sub_len[p] > plan->max_samples)
             return fail(FFS_E_INVALID, "pair %d: lengths %lld / %lld exceed the plan's max_samples %lld", p,
                         (long long)ref_len[p], (long long)sub_len[p], (long long)plan->max_samples);
-        const int64_t n_ref = ffs_fft_length(ref_len[p], sub_len[p]);
-        int64_t wl = 0, wh = -1;
-        if (lag_window(ref_len[p], sub_len[p], n_ref, max_offset_samples, &wl, &wh) && wh - wl + 1 > plan->max_lags)
-            return fail(FFS_E_INVALID, "pair %d: %lld lags exceed the plan's max_lags %lld", p, (long long)(wh - wl + 1),
-                        (long long)plan->max_lags);
+        if (int rc = check_window_lags(p, ref_len[p], sub_len[p], max_offset_samples, plan->max_lags)) return rc;
         max_sw = std::max(max_sw, (sub_len[p] + 31) / 32);
     }
     hipStream_t st = (hipStream_t)hip_stream;
@@ -4826,18 +4802,7 @@ int ffs_align_quality_batch(ffs_quality_plan* plan, int n_pairs, const void* con
             memset(&q, 0, sizeof q);
             q.r = sd.r;
             q.s = sd.s;
-            q.R = R;
-            q.S = S;
-            int64_t wl = 0, wh = -1;
-            if (lag_window(R, S, ffs_fft_length(R, S), max_offset_samples, &wl, &wh)) {
-                q.d_lo = wl;
-                q.n_lags = wh - wl + 1;
-                const int64_t clo = std::max(wl, 1 - S), chi = std::min(wh, R - 1);
-                q.c_lo = clo;
-                q.n_count = chi >= clo ? chi - clo + 1 : 0;
-            }
-            q.cd.R = (int32_t)R;
-            q.cd.S = (int32_t)S;
+            qual_window(&q, R, S, max_offset_samples);
             q.cd.s0 = v.s0;
             q.cd.s1 = v.s1;
             q.cd.r0 = v.r0;
@@ -4855,17 +4820,7 @@ int ffs_align_quality_batch(ffs_quality_plan* plan, int n_pairs, const void* con
         // prefixes over every sample of both vectors (W beyond any length: k_split_prefix then covers all of r)
         hipLaunchKernelGGL(ffsa::k_split_prefix, dim3(2 * np), dim3(ffsa::SPLIT_PREFIX_THREADS), 0, st, ds,
                            (int64_t)(int64_t(1) << 40));
-        if (max_count > 0) {
-            // chunks of subtitle words: enough workgroups to fill the device (about 4 per CU), at least 64 words each so
-            // that the atomics stay a small fraction of the work, at most QUAL_MAX_CHUNK (LDS)
-            const int64_t n_tiles = (max_count + ffsa::QUAL_TILE - 1) / ffsa::QUAL_TILE;
-            const int64_t want = std::max<int64_t>(1, (int64_t)n_sm * 4);
-            int64_t cw = (np * n_tiles * max_sw + want - 1) / want;
-            cw = std::min<int64_t>(ffsa::QUAL_MAX_CHUNK, std::max<int64_t>(64, cw));
-            const int64_t n_chunks = (max_sw + cw - 1) / cw;
-            hipLaunchKernelGGL(ffsa::k_quality_counts, dim3((unsigned)(np * n_tiles * n_chunks)), dim3(ffsa::QUAL_CNT_THREADS),
-                               0, st, dq, (int)n_tiles, (int)n_chunks, (int)cw);
-        }
+        if (max_count > 0) quality_counts(dq, np, max_count, max_sw, n_sm, st);
         hipLaunchKernelGGL(ffsa::k_quality_peaks, dim3(np), dim3(ffsa::QUAL_PEAK_THREADS), 0, st, dq, top_k,
                            exclusion_samples, (ffsa::QualResult*)out_dev);
         HIP_TRY(hipGetLastError());
@@ -4885,8 +4840,17 @@ struct ffs_match_plan : PlanCore {
     ffsa::MatchHdr* hdr_dev;             // [vector]
     ffsa::MatchHdr* hdr_host;            // pinned
     DescStaging vec;                     // per call: list pointers, ExpandVec and SplitDesc tables of the vectors
-    DescStaging desc;                    // per sub-batch: QualDesc[pairs_in_flight], then MatchLists[pairs_in_flight]
+                                         // desc: QualDesc[pairs_in_flight], then MatchLists[pairs_in_flight]
     size_t off_expand, off_split, vec_bytes;
+
+    void carve(Carver& c) {
+        const int64_t n = pairs_in_flight, nv = max_vectors;
+        sc = c.take<double>(n * lpad);
+        curve = c.take<uint32_t>(n * lpad);
+        bits = c.take<uint32_t>(nv * vec_words);
+        pre = c.take<int32_t>(nv * pre_words);
+        hdr_dev = c.take<ffsa::MatchHdr>(nv, 64);
+    }
 };
 
 int ffs_match_plan_create(int device, int pairs_in_flight, int64_t max_lags, int64_t max_samples, int64_t max_vectors,
@@ -4906,19 +4870,16 @@ int ffs_match_plan_create(int device, int pairs_in_flight, int64_t max_lags, int
     p->lpad = split_align_up(max_lags, 64);
     p->vec_words = split_align_up(max_samples / 32 + 1, 16);
     p->pre_words = split_align_up(max_samples / 32 + 2, 16);
-    const int64_t n = pairs_in_flight, nv = max_vectors;
-    const int64_t b_sc = n * p->lpad * 8, b_curve = n * p->lpad * 4, b_bits = nv * p->vec_words * 4,
-                  b_pre = nv * p->pre_words * 4, b_hdr = split_align_up(nv * (int64_t)sizeof(ffsa::MatchHdr), 64);
-    if (int rc = p->open(device, pairs_in_flight, b_sc + b_curve + b_bits + b_pre + b_hdr, "match plan")) {
+    const int64_t nv = max_vectors;
+    p->pairs_in_flight = pairs_in_flight;
+    Carver size{nullptr};
+    p->carve(size);
+    if (int rc = p->open(device, pairs_in_flight, size.used, "match plan")) {
         ffs_match_plan_destroy(p);
         return rc;
     }
-    char* w = (char*)p->work;
-    p->sc = (double*)w;
-    p->curve = (uint32_t*)(w + b_sc);
-    p->bits = (uint32_t*)(w + b_sc + b_curve);
-    p->pre = (int32_t*)(w + b_sc + b_curve + b_bits);
-    p->hdr_dev = (ffsa::MatchHdr*)(w + b_sc + b_curve + b_bits + b_pre);
+    Carver place{(char*)p->work};
+    p->carve(place);
     p->off_expand = (size_t)split_align_up(nv * 8, 64);
     p->off_split = p->off_expand + (size_t)split_align_up(nv * (int64_t)sizeof(ExpandVec), 64);
     p->vec_bytes = p->off_split + sizeof(ffsa::SplitDesc) * (size_t)((nv + 1) / 2);
@@ -4940,13 +4901,12 @@ int ffs_match_plan_destroy(ffs_match_plan* plan) {
     if (!plan) return FFS_OK;
     plan->close();
     plan->vec.release();
-    plan->desc.release();
     if (plan->hdr_host) (void)hipHostFree(plan->hdr_host);
     delete plan;
     return FFS_OK;
 }
 
-int64_t ffs_match_plan_workspace_bytes(const ffs_match_plan* plan) { return plan ? plan->work_bytes : 0; }
+int64_t ffs_match_plan_workspace_bytes(const ffs_match_plan* plan) { return plan ? plan->workspace_bytes() : 0; }
 
 int ffs_match_quality_batch(ffs_match_plan* plan, int n_ref, const void* const* ref_list, const int64_t* ref_len,
                             const double* ref_lo, const double* ref_hi, int n_sub, const void* const* sub_list,
@@ -4959,10 +4919,7 @@ int ffs_match_quality_batch(ffs_match_plan* plan, int n_ref, const void* const* 
     if (!ref_list || !ref_len || !ref_lo || !ref_hi || !sub_list || !sub_len || !sub_lo || !sub_hi || !pair_ref || !pair_sub ||
         !out_dev)
         return fail(FFS_E_INVALID, "null argument");
-    if (max_offset_samples < -1) return fail(FFS_E_INVALID, "max_offset_samples=%lld: need >= 0, or -1 for none", (long long)max_offset_samples);
-    if (top_k < 1 || top_k > ffsa::QUAL_MAX_PEAKS) return fail(FFS_E_INVALID, "top_k=%d outside [1, 8]", top_k);
-    if (exclusion_samples < 1) return fail(FFS_E_INVALID, "exclusion_samples=%lld: need >= 1", (long long)exclusion_samples);
-    if ((uintptr_t)out_dev & 7) return fail(FFS_E_INVALID, "misaligned output records");
+    if (int rc = check_quality_args(max_offset_samples, top_k, exclusion_samples, out_dev)) return rc;
     if (algorithm != FFS_MATCH_AUTO && algorithm != FFS_MATCH_RUNS && algorithm != FFS_MATCH_BITS)
         return fail(FFS_E_INVALID, "algorithm=%d: need FFS_MATCH_AUTO, FFS_MATCH_RUNS or FFS_MATCH_BITS", algorithm);
     const int64_t nv = (int64_t)n_ref + n_sub;
@@ -4990,11 +4947,8 @@ int ffs_match_quality_batch(ffs_match_plan* plan, int n_ref, const void* const* 
         if (pair_ref[p] < 0 || pair_ref[p] >= n_ref || pair_sub[p] < 0 || pair_sub[p] >= n_sub)
             return fail(FFS_E_INVALID, "pair %d: index (%d, %d) outside the %d references x %d subtitle vectors", p,
                         (int)pair_ref[p], (int)pair_sub[p], n_ref, n_sub);
-        const int64_t R = ref_len[pair_ref[p]], S = sub_len[pair_sub[p]];
-        int64_t wl = 0, wh = -1;
-        if (lag_window(R, S, ffs_fft_length(R, S), max_offset_samples, &wl, &wh) && wh - wl + 1 > plan->max_lags)
-            return fail(FFS_E_INVALID, "pair %d: %lld lags exceed the plan's max_lags %lld", p, (long long)(wh - wl + 1),
-                        (long long)plan->max_lags);
+        if (int rc = check_window_lags(p, ref_len[pair_ref[p]], sub_len[pair_sub[p]], max_offset_samples, plan->max_lags))
+            return rc;
     }
     hipStream_t st = (hipStream_t)hip_stream;
     if (int rc = plan->begin(st)) return rc;
@@ -5083,18 +5037,7 @@ int ffs_match_quality_batch(ffs_match_plan* plan, int n_ref, const void* const* 
             memset(&q, 0, sizeof q);
             q.r = plan->bits + vr * plan->vec_words;
             q.s = plan->bits + vs * plan->vec_words;
-            q.R = R;
-            q.S = S;
-            int64_t wl = 0, wh = -1;
-            if (lag_window(R, S, ffs_fft_length(R, S), max_offset_samples, &wl, &wh)) {
-                q.d_lo = wl;
-                q.n_lags = wh - wl + 1;
-                const int64_t clo = std::max(wl, 1 - S), chi = std::min(wh, R - 1);
-                q.c_lo = clo;
-                q.n_count = chi >= clo ? chi - clo + 1 : 0;
-            }
-            q.cd.R = (int32_t)R;
-            q.cd.S = (int32_t)S;
+            qual_window(&q, R, S, max_offset_samples);
             q.cd.s0 = mapped(sub_lo[is]);
             q.cd.s1 = mapped(sub_hi[is]);
             q.cd.r0 = mapped(ref_lo[ir]);
@@ -5120,15 +5063,9 @@ int ffs_match_quality_batch(ffs_match_plan* plan, int n_ref, const void* const* 
             hipLaunchKernelGGL(ffsa::k_runs_curve, dim3((unsigned)(n_runs * n_tiles)), dim3(ffsa::MATCH_THREADS), 0, st, dq, dl,
                                (int)n_tiles);
         }
-        if (n_bits > 0 && max_count_bits > 0) {  // k_quality_counts as ffs_align_quality_batch launches it
+        if (n_bits > 0 && max_count_bits > 0) {
             HIP_TRY(hipMemsetAsync(plan->curve + (int64_t)n_runs * plan->lpad, 0, (size_t)n_bits * plan->lpad * 4, st));
-            const int64_t n_tiles = (max_count_bits + ffsa::QUAL_TILE - 1) / ffsa::QUAL_TILE;
-            const int64_t want = std::max<int64_t>(1, (int64_t)n_sm * 4);
-            int64_t cw = (n_bits * n_tiles * max_sw + want - 1) / want;
-            cw = std::min<int64_t>(ffsa::QUAL_MAX_CHUNK, std::max<int64_t>(64, cw));
-            const int64_t n_chunks = (max_sw + cw - 1) / cw;
-            hipLaunchKernelGGL(ffsa::k_quality_counts, dim3((unsigned)(n_bits * n_tiles * n_chunks)), dim3(ffsa::QUAL_CNT_THREADS),
-                               0, st, dq + n_runs, (int)n_tiles, (int)n_chunks, (int)cw);
+            quality_counts(dq + n_runs, n_bits, max_count_bits, max_sw, n_sm, st);
         }
         hipLaunchKernelGGL(ffsa::k_quality_peaks, dim3(np), dim3(ffsa::QUAL_PEAK_THREADS), 0, st, dq, top_k,
                            exclusion_samples, (ffsa::QualResult*)out_dev);
