@@ -1551,12 +1551,12 @@ __global__ __launch_bounds__(256) void k_runs_chunk_flags_ml(const CandDesc* __r
         const int cap_p = rs.cap > 0 ? rs.cap : ((GInts)rs.hdr)[3];
         nb += (unsigned)n_p;
         if (!li.ok || n_p >= cap_p || n_p >= RUNS_CAP) {
-            if (n_p > longest) longest = n_p;
+            if (rs.bits && n_p > longest) longest = n_p;
             over = 1;
             continue;
         }
         long long coinc = 0, cell = 0;
-        if (n_p > longest) longest = n_p;
+        if (rs.bits && n_p > longest) longest = n_p;  // (plan-owned lists only: the host sizes their stride by it)
         for (int k = 0; k < li.n_levels - 1; ++k) {
             const RunsRef rk = refs[n_vec_all + 3 * pair + k];
             const int n_q = ((GInts)rk.hdr)[0];

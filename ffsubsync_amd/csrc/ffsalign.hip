@@ -2217,16 +2217,19 @@ int align_impl(ffs_plan* p, const AlignArgs& in) {
     std::vector<const void*> bits_ptr;  // the rewritten pointer table, when the inputs are rewritten
     const bool may_run = p->algo != FFS_ALGO_FFT && !p->direct_only;
     const bool lists_in = a.dtype == FFS_DTYPE_RUNS || a.ref_dt == FFS_DTYPE_RUNS;
+    // (a multi-level float reference against two-level candidates takes the run-boundary path too: candidates that are
+    // lists stay the caller's lists there -- k_runs_corr_ml reads their edge windows from the list -- and are expanded
+    // only for a sub-batch that needs the transforms after all)
+    const bool ml_split = (a.ref_dt == FFS_DTYPE_F64 || a.ref_dt == FFS_DTYPE_F32) && runs_able(a.dtype);
     if (may_run && a.dtype == FFS_DTYPE_U8 && a.ref_dt == FFS_DTYPE_U8)
         rc = pack_byte_vectors(p, &a, &bits_ptr);
-    else if (lists_in && !(may_run && runs_able(a.dtype) && runs_able(a.ref_dt)))
+    else if (lists_in && !(may_run && runs_able(a.dtype) && (runs_able(a.ref_dt) || ml_split)))
         rc = lists_to_bits(p, &a, &bits_ptr);
     if (rc) return rc;
     // The plan-owned boundary lists take 256 KiB per vector: a call with more than 65 536 vectors of bit-packed
     // two-level samples is solved as consecutive sub-calls (results land where one call would put them).
     // (a multi-level float reference brings three threshold planes of its own)
     const int64_t stride = 1 + a.n_cand;
-    const bool ml_split = (a.ref_dt == FFS_DTYPE_F64 || a.ref_dt == FFS_DTYPE_F32) && runs_able(a.dtype);
     const int64_t per_pair = stride + (ml_split ? 3 : 0);
     const int64_t max_pairs = (int64_t(1) << 16) / per_pair > 0 ? (int64_t(1) << 16) / per_pair : 1;
     const bool split = may_run && runs_able(a.dtype) && (runs_able(a.ref_dt) || ml_split) && a.n_pairs > max_pairs;

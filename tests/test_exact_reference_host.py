@@ -99,6 +99,29 @@ def test_multilevel_reference_equals_brute_force_counting(max_off):
             assert got == _brute(None, sub01, None, sl, max_off, M=M, info=info)
 
 
+@pytest.mark.parametrize("max_off", [None, 30])
+def test_multilevel_reference_equals_brute_force_counting_on_every_level_set(max_off):
+    """Every level set the run path accepts (tests/level_cases.py: divisors 1 .. 4, multiplicities up to 8, a vanishing
+    base, levels outside [0, 1], float32 values), references built from nested planes; R < S and R > S."""
+    import level_cases as lc
+
+    for n, ls in enumerate(lc.ACCEPTED):
+        rng = np.random.RandomState(40 + n)
+        for R, S in [(397, 150), (150, 211)]:
+            planes = lc._nest(ls, *(_runs(rng, R, k) != 0 for k in (6, 5, 4)))
+            ref = lc.make(ls, planes)
+            info = er.level_info(ref)
+            assert info is not None and info[2] == ls.m and info[1] == ls.q
+            M = er.multilevel_weights(ref, info[0], info[2])
+            assert np.array_equal(M, sum(mk * pl for mk, pl in zip(ls.m, planes)))
+            sub01 = _runs(rng, S, 4)
+            for sl in [(0.0, 1.0), (0.0, 1.0 / 1.001), (-0.5, 1.25), (0.5, 1.0)]:
+                got = er.candidate_multilevel(np.asarray(ref, np.float64), sub01, sl, max_off)
+                want = _brute(None, sub01, None, sl, max_off, M=M, info=info)
+                assert got == want or (got["score"] == want["score"] == 0.0 and got["offset"] == want["offset"]
+                                       and got["n_at_max"] == want["n_at_max"]), (ls, R, S, sl, got, want)
+
+
 def test_fma_emulation_rounds_once():
     eps = 2.0 ** -30
     # a*b = 1 - 2^-60 exactly: unfused rounds the product to 1.0 first
