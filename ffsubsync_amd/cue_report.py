@@ -20,6 +20,7 @@ import numpy as np
 
 from . import _native
 from .constants import SAMPLE_RATE
+from .side_call import bits_batch, check_two_level_batch, no_workspace_split_plan
 from .split_align import _scaled_us, empty_error
 
 # Chosen on the CPU model (profiles/cue_report_calibration.py -> profiles/cue_report_calibration.json;
@@ -89,24 +90,6 @@ def validate_args(radius_samples, context_samples) -> None:
         raise ValueError("context_samples=%r: need an integer in [0, %d]" % (context_samples, _native.CUE_MAX_CONTEXT))
 
 
-def _check_batch(batch) -> None:
-    if batch.n_cand != 1:
-        raise ValueError("cue_report_batch needs one candidate per pair (DeviceBatch.select_candidates)")
-    ref_dt = batch.dtype if batch.ref_dtype is None else batch.ref_dtype
-    if ref_dt in (_native.FFS_DTYPE_F32, _native.FFS_DTYPE_F64):
-        raise ValueError("cue_report_batch needs a two-level reference: a multi-level float reference (FFS_DTYPE_%s) is "
-                         "not supported" % ("F64" if ref_dt == _native.FFS_DTYPE_F64 else "F32"))
-    if ref_dt != batch.dtype or batch.dtype not in (_native.FFS_DTYPE_U1, _native.FFS_DTYPE_U8):
-        raise ValueError("cue_report_batch needs two-level vectors: bit-packed (FFS_DTYPE_U1) or 0/1 bytes (FFS_DTYPE_U8)")
-    lens = np.asarray(batch.lens)
-    for p in range(lens.shape[0]):
-        if lens[p, 0] <= 0 or lens[p, 1] <= 0:
-            raise empty_error(max(int(lens[p, 0]), 0), max(int(lens[p, 1]), 0))
-    levels = np.concatenate([np.ravel(batch.lo), np.ravel(batch.hi)])
-    if not np.all(np.isfinite(levels)):
-        raise ValueError("two-level vectors need finite levels")
-
-
 def flat_cue_table(cues, n_pairs: int):
     """The flat ``_native.CUE_DTYPE`` table of per-pair (start, end, lag) triples, and each pair's first entry and
     count (ValueError for a wrong number of pairs or mismatched lengths)."""
@@ -136,7 +119,7 @@ _plans = _native.SidePlanCache(_native.SplitPlan)
 
 def _get_plan(n_pairs: int):
     """A split plan of this device that holds no split workspace: cue report calls use its sub-batching only."""
-    return _plans.get(int(max(1, min(n_pairs, 256))), 1, 2, 1)
+    return no_workspace_split_plan(_plans, n_pairs)
 
 
 def clear_plan_cache() -> None:
@@ -150,13 +133,12 @@ def cue_report_batch(batch, cues, radius_samples: int = DEFAULT_RADIUS, context_
     Returns one list of ``CueReport`` per pair, or with ``raw`` (the ``_native.CUE_REPORT_DTYPE`` records of the flat
     table, the per-pair slices into it)."""
     validate_args(radius_samples, context_samples)
-    _check_batch(batch)
+    check_two_level_batch(batch, "cue_report_batch", float_ref_message=True)
     n = batch.n_pairs
     table, first, count = flat_cue_table(cues, n)
     slices = [slice(int(f), int(f + c)) for f, c in zip(first, count)]
     torch = _native.require_gpu()
-    if batch.dtype == _native.FFS_DTYPE_U8:
-        batch = batch.to_bits()
+    batch = bits_batch(batch)
     dev = batch.data.device
     if table.size:
         cue_dev = torch.from_numpy(table.view(np.uint8).reshape(-1)).to(dev)

@@ -20,6 +20,7 @@ import numpy as np
 from . import _native
 from .constants import SAMPLE_RATE
 from .cue_report import _get_plan, cue_table, flat_cue_table, validate_args as _validate_report_args
+from .side_call import bits_batch, check_two_level_batch
 from .split_align import empty_error
 
 # Chosen on the CPU model (profiles/cue_retime_calibration.py -> profiles/cue_retime_calibration.json;
@@ -96,24 +97,6 @@ def validate_args(radius, context, penalty_q, jump_q) -> None:
         raise ValueError("jump_q=%r: need -1 (no cap) or an integer in [0, 2^40]" % (jump_q,))
 
 
-def _check_batch(batch) -> None:
-    if batch.n_cand != 1:
-        raise ValueError("retime_batch needs one candidate per pair (DeviceBatch.select_candidates)")
-    ref_dt = batch.dtype if batch.ref_dtype is None else batch.ref_dtype
-    if ref_dt in (_native.FFS_DTYPE_F32, _native.FFS_DTYPE_F64):
-        raise ValueError("retime_batch needs a two-level reference: a multi-level float reference (FFS_DTYPE_%s) is not "
-                         "supported" % ("F64" if ref_dt == _native.FFS_DTYPE_F64 else "F32"))
-    if ref_dt != batch.dtype or batch.dtype not in (_native.FFS_DTYPE_U1, _native.FFS_DTYPE_U8):
-        raise ValueError("retime_batch needs two-level vectors: bit-packed (FFS_DTYPE_U1) or 0/1 bytes (FFS_DTYPE_U8)")
-    lens = np.asarray(batch.lens)
-    for p in range(lens.shape[0]):
-        if lens[p, 0] <= 0 or lens[p, 1] <= 0:
-            raise empty_error(max(int(lens[p, 0]), 0), max(int(lens[p, 1]), 0))
-    levels = np.concatenate([np.ravel(batch.lo), np.ravel(batch.hi)])
-    if not np.all(np.isfinite(levels)):
-        raise ValueError("two-level vectors need finite levels")
-
-
 def workspace_bytes(cue_counts, radius: int, pairs_in_flight: int) -> int:
     """Bytes of retime workspace ``ffs_cue_retime_batch`` needs for pairs with these cue counts: 6 bytes per (cue,
     shift) of the largest sub-batch (the header's cutting rule), rounded up to 256."""
@@ -138,7 +121,7 @@ def retime_batch(batch, cues, radius: int = DEFAULT_RADIUS, context: int = DEFAU
     per pair, one ``RetimeSummary`` per pair), or with ``raw`` (the ``_native.CUE_RETIME_DTYPE`` records of the flat
     table, the per-pair slices into it, the ``_native.RETIME_SUMMARY_DTYPE`` records)."""
     validate_args(radius, context, penalty_q, jump_q)
-    _check_batch(batch)
+    check_two_level_batch(batch, "retime_batch", float_ref_message=True)
     n = batch.n_pairs
     table, first, count = flat_cue_table(cues, n)
     for p, c in enumerate(count):
@@ -147,8 +130,7 @@ def retime_batch(batch, cues, radius: int = DEFAULT_RADIUS, context: int = DEFAU
                              % (p, int(c), 2 * int(radius) + 1, _native.RETIME_WORK_CAP))
     slices = [slice(int(f), int(f + c)) for f, c in zip(first, count)]
     torch = _native.require_gpu()
-    if batch.dtype == _native.FFS_DTYPE_U8:
-        batch = batch.to_bits()
+    batch = bits_batch(batch)
     dev = batch.data.device
     cue_dev = torch.from_numpy(table.view(np.uint8).reshape(-1)).to(dev)
     rec_out = torch.empty(table.size * _native.CUE_RETIME_BYTES, dtype=torch.uint8, device=dev)

@@ -20,6 +20,7 @@ import numpy as np
 
 from . import _native, split_refine
 from .constants import SAMPLE_RATE, candidate_ratios
+from .side_call import BlockCall, pairs_for_budget
 from .split_align import (DEFAULT_BLOCK_SAMPLES, Piece, SplitResult, _check_batch, empty_error, split_outputs,
                           split_results, validate_block_samples)
 
@@ -75,10 +76,14 @@ def full_range(ref_len: int, sub_len: int) -> Tuple[int, int]:
 _plans = _native.SidePlanCache(_native.SplitRangePlan)
 
 
+def workspace_per_pair(max_blocks: int, max_lags: int, max_samples: int) -> float:
+    """Bytes of range split workspace per pair in flight: stay bits and one fp64 row, ~140 MB for a 2 h full-range pair."""
+    return max_blocks * (max_lags / 8.0 + 8) + max_lags * 8.0 + max_samples / 4.0 + 4096
+
+
 def _get_plan(n_pairs: int, max_blocks: int, max_lags: int, max_samples: int, pairs_in_flight: Optional[int]):
-    if pairs_in_flight is None:  # bound the workspace (stay bits + one fp64 row: ~140 MB per 2 h full-range pair) to ~12 GiB
-        per_pair = max_blocks * (max_lags / 8.0 + 8) + max_lags * 8.0 + max_samples / 4.0 + 4096
-        pairs_in_flight = int(max(1, min(n_pairs, 256, (12 << 30) // per_pair)))
+    if pairs_in_flight is None:  # bound the workspace to ~12 GiB
+        pairs_in_flight = pairs_for_budget(n_pairs, workspace_per_pair(max_blocks, max_lags, max_samples))
     return _plans.get(pairs_in_flight, max_blocks, max_lags, max_samples)
 
 
@@ -111,19 +116,12 @@ def split_align_range_batch(batch, lag_ranges=None, block_samples: int = DEFAULT
     every pair, a list of one per pair, or None for each pair's full overlap range [-(S-1), R-1]."""
     validate_args(block_samples, split_penalty)
     _check_batch(batch)
-    n = batch.n_pairs
-    ref_len, sub_len = batch.lens[:, 0].astype(np.int64), batch.lens[:, 1].astype(np.int64)
     lo, hi = lag_arrays(batch, lag_ranges)
-    _native.require_gpu()
-    if batch.dtype == _native.FFS_DTYPE_U8:
-        batch = batch.to_bits()
-    k = int(block_samples)
-    n_blocks = (sub_len + k - 1) // k
-    max_b = int(n_blocks.max())
-    plan = _get_plan(n, max_b, int((hi - lo + 1).max()), int(max(sub_len.max(), ref_len.max())), pairs_in_flight)
-    outs = split_outputs(n, max_b, batch.data.device)
-    plan.align(*batch.pair_arrays(), k, lo, hi, float(split_penalty), *outs)
-    return split_results(outs, n_blocks, k, sub_len)
+    call = BlockCall(batch, block_samples)
+    plan = _get_plan(call.n, call.max_b, *call.lag_dims(lo, hi), pairs_in_flight)
+    outs = split_outputs(call.n, call.max_b, call.dev)
+    plan.align(*call.pair_arrays(), call.k, lo, hi, float(split_penalty), *outs)
+    return split_results(outs, call.n_blocks, call.k, call.sub_len)
 
 
 def _device_refs(problems):

@@ -29,6 +29,7 @@ import numpy as np
 
 from . import _native, cut_align, quality, split_refine
 from .constants import SAMPLE_RATE
+from .side_call import BlockCall, pairs_for_budget, record_lists
 from .split_align import DEFAULT_BLOCK_SAMPLES, Piece, _check_batch, split_outputs, split_results
 from .split_report import DEFAULT_EXCLUSION_SAMPLES, DEFAULT_TOP_K, PieceQuality, SplitReport, from_record
 
@@ -131,9 +132,9 @@ _plans = _native.SidePlanCache(_native.SplitRangePlan)
 def _get_plan(n_pairs: int, max_blocks: int, max_lags: int, max_samples: int, pairs_in_flight: Optional[int]):
     """The report's own plan, sized for the piece rows its first report call adds (8 uint32 rows of max_lags per pair)."""
     if pairs_in_flight is None:  # the range split's workspace plus the rows: ~186 MB per 2 h full-range pair, ~12 GiB
-        per_pair = (max_blocks * (max_lags / 8.0 + 8) + max_lags * 8.0 + max_samples / 4.0 + 4096
+        per_pair = (cut_align.workspace_per_pair(max_blocks, max_lags, max_samples)
                     + ROUND_PIECES * (max_lags + 64) * 4.0 + (max_samples / 16384.0 + max_blocks) * 16.0)
-        pairs_in_flight = int(max(1, min(n_pairs, 256, (12 << 30) // per_pair)))
+        pairs_in_flight = pairs_for_budget(n_pairs, per_pair)
     return _plans.get(pairs_in_flight, max_blocks, max_lags, max_samples, role="report")
 
 
@@ -141,15 +142,12 @@ def clear_plan_cache() -> None:
     _plans.clear()
 
 
-def _records(batch, lo, hi, offsets, block_samples, top_k, exclusion_samples, plan, max_b):
-    """The device report of ``offsets`` (int32 CUDA tensor [n_pairs * max_b]): (records [n_pairs, max_b], counts)."""
-    torch = _native.require_gpu()
-    n, dev = batch.n_pairs, batch.data.device
-    rep_out = torch.empty(n * max_b * _native.PIECE_REPORT_BYTES, dtype=torch.uint8, device=dev)
-    n_out = torch.empty(n, dtype=torch.int32, device=dev)
-    plan.report(*batch.pair_arrays(), int(block_samples), lo, hi, offsets, int(top_k), int(exclusion_samples), rep_out,
-                n_out)
-    return rep_out.cpu().numpy().view(_native.PIECE_REPORT_DTYPE).reshape(n, max_b), n_out.cpu().numpy()
+def _records(call, plan, record_dtype, lo, hi, path, top_k, exclusion_samples):
+    """The device report of a range plan over ``path``, the CUDA tensors [n_pairs * max_b] it reports on (block offsets;
+    for a drift path jump flags too): (``record_dtype`` records [n_pairs, max_b], counts)."""
+    rep_out, n_out = call.records(record_dtype), call.per_pair(np.int32)
+    plan.report(*call.pair_arrays(), call.k, lo, hi, *path, int(top_k), int(exclusion_samples), rep_out, n_out)
+    return call.read_records(rep_out, record_dtype), n_out.cpu().numpy()
 
 
 def report_batch(batch, block_offsets, lag_ranges=None, block_samples: int = DEFAULT_BLOCK_SAMPLES,
@@ -161,22 +159,11 @@ def report_batch(batch, block_offsets, lag_ranges=None, block_samples: int = DEF
     validate_args(block_samples, 0.0, top_k, exclusion_samples)
     _check_batch(batch)
     lo, hi = cut_align.lag_arrays(batch, lag_ranges)
-    torch = _native.require_gpu()
-    if batch.dtype == _native.FFS_DTYPE_U8:
-        batch = batch.to_bits()
-    k = int(block_samples)
-    ref_len, sub_len = batch.lens[:, 0].astype(np.int64), batch.lens[:, 1].astype(np.int64)
-    n_blocks = (sub_len + k - 1) // k
-    n, max_b = batch.n_pairs, int(n_blocks.max())
-    offs = np.zeros((n, max_b), np.int32)
-    for p in range(n):
-        row = np.asarray(block_offsets[p], dtype=np.int64)[:int(n_blocks[p])]
-        if row.size != n_blocks[p]:
-            raise ValueError("pair %d: %d block offsets for %d blocks" % (p, row.size, n_blocks[p]))
-        offs[p, :row.size] = row
-    plan = _get_plan(n, max_b, int((hi - lo + 1).max()), int(max(sub_len.max(), ref_len.max())), pairs_in_flight)
-    dev_offs = torch.from_numpy(offs.ravel()).to(batch.data.device)
-    return _records(batch, lo, hi, dev_offs, k, top_k, exclusion_samples, plan, max_b)
+    call = BlockCall(batch, block_samples)
+    what = lambda p, size, blocks: "pair %d: %d block offsets for %d blocks" % (p, size, blocks)
+    path = call.place(what, ([np.asarray(block_offsets[p], dtype=np.int64) for p in range(call.n)], np.int32), clip=True)
+    plan = _get_plan(call.n, call.max_b, *call.lag_dims(lo, hi), pairs_in_flight)
+    return _records(call, plan, _native.PIECE_REPORT_DTYPE, lo, hi, path, top_k, exclusion_samples)
 
 
 def split_range_report_batch(batch, lag_ranges=None, block_samples: int = DEFAULT_BLOCK_SAMPLES,
@@ -189,21 +176,15 @@ def split_range_report_batch(batch, lag_ranges=None, block_samples: int = DEFAUL
     validate_args(block_samples, split_penalty, top_k, exclusion_samples)
     _check_batch(batch)
     lo, hi = cut_align.lag_arrays(batch, lag_ranges)
-    _native.require_gpu()
-    if batch.dtype == _native.FFS_DTYPE_U8:
-        batch = batch.to_bits()
-    k = int(block_samples)
-    ref_len, sub_len = batch.lens[:, 0].astype(np.int64), batch.lens[:, 1].astype(np.int64)
-    n_blocks = (sub_len + k - 1) // k
-    n, max_b = batch.n_pairs, int(n_blocks.max())
-    plan = _get_plan(n, max_b, int((hi - lo + 1).max()), int(max(sub_len.max(), ref_len.max())), pairs_in_flight)
-    outs = split_outputs(n, max_b, batch.data.device)
-    plan.align(*batch.pair_arrays(), k, lo, hi, float(split_penalty), *outs)
-    recs, counts = _records(batch, lo, hi, outs[0], k, top_k, exclusion_samples, plan, max_b)
-    res = split_results(outs, n_blocks, k, sub_len)
+    call = BlockCall(batch, block_samples)
+    plan = _get_plan(call.n, call.max_b, *call.lag_dims(lo, hi), pairs_in_flight)
+    outs = split_outputs(call.n, call.max_b, call.dev)
+    plan.align(*call.pair_arrays(), call.k, lo, hi, float(split_penalty), *outs)
+    recs, counts = _records(call, plan, _native.PIECE_REPORT_DTYPE, lo, hi, outs[:1], top_k, exclusion_samples)
+    res = split_results(outs, call.n_blocks, call.k, call.sub_len)
     if raw:
         return res, recs, counts
-    return [SplitReport(r, [from_record(x) for x in recs[p, :int(counts[p])]]) for p, r in enumerate(res)]
+    return [SplitReport(r, q) for r, q in zip(res, record_lists(recs, counts, from_record))]
 
 
 def checked_cut_sync(problems, lag_range=None, block_samples: int = DEFAULT_BLOCK_SAMPLES,

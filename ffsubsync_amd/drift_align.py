@@ -18,6 +18,7 @@ import numpy as np
 
 from . import _native
 from .constants import SAMPLE_RATE, candidate_ratios
+from .side_call import BlockCall, pairs_for_budget
 from .split_align import (DEFAULT_BLOCK_SAMPLES, DEFAULT_SPLIT_PENALTY, _check_batch, map_cues, pieces_from_blocks,
                           solve_ratios, split_outputs, validate_args)
 
@@ -101,7 +102,7 @@ def _get_plan(n_pairs: int, max_blocks: int, max_lags: int, max_samples: int, pa
     """The cached drift plan of this device."""
     if pairs_in_flight is None:  # ~2.5 bytes per (block, lag): uint16 counts and a 4-bit code; bound it to ~12 GiB
         per_pair = max_blocks * (max_lags + 64) * 2.7 + 1
-        pairs_in_flight = int(max(1, min(n_pairs, 256, (12 << 30) // per_pair)))
+        pairs_in_flight = pairs_for_budget(n_pairs, per_pair)
     return _plans.get(pairs_in_flight, max_blocks, max_lags, max_samples)
 
 
@@ -119,21 +120,20 @@ def drift_align_batch(batch, max_offset_samples: int, block_samples: int = DEFAU
     validate_args(block_samples, max_offset_samples, split_penalty)
     validate_drift_args(max_step, step_cost)
     _check_batch(batch)
-    torch = _native.require_gpu()
-    if batch.dtype == _native.FFS_DTYPE_U8:
-        batch = batch.to_bits()
-    k, w = int(block_samples), int(max_offset_samples)
-    n = batch.n_pairs
-    sub_len = batch.lens[:, 1].astype(np.int64)
-    n_blocks = (sub_len + k - 1) // k
-    max_b = int(n_blocks.max())
-    plan = _get_plan(n, max_b, 2 * w, int(sub_len.max()), pairs_in_flight)
-    dev = batch.data.device
-    offs, scores, totals = split_outputs(n, max_b, dev)
-    jumps = torch.empty(n * max_b, dtype=torch.uint8, device=dev)
-    plan.align(*batch.pair_arrays(), k, w, float(split_penalty), int(max_step), float(step_cost), offs, scores, jumps,
+    call = BlockCall(batch, block_samples)
+    w = int(max_offset_samples)
+    plan = _get_plan(call.n, call.max_b, 2 * w, int(call.sub_len.max()), pairs_in_flight)
+    offs, scores, jumps, totals = drift_outputs(call)
+    plan.align(*call.pair_arrays(), call.k, w, float(split_penalty), int(max_step), float(step_cost), offs, scores, jumps,
                totals)
-    return drift_results(offs, scores, jumps, totals, n_blocks, k, sub_len)
+    return drift_results(offs, scores, jumps, totals, call.n_blocks, call.k, call.sub_len)
+
+
+def drift_outputs(call: BlockCall):
+    """The device outputs of a drift call: ``split_outputs``' block offsets and scores, jump flags (n * max_b each)
+    and totals (n), in the order the drift plans take them."""
+    offs, scores, totals = split_outputs(call.n, call.max_b, call.dev)
+    return offs, scores, call.per_block(np.uint8), totals
 
 
 def drift_results(offs, scores, jumps, totals, n_blocks, block_samples: int, sub_len) -> List[DriftResult]:

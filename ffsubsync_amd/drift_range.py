@@ -25,8 +25,10 @@ from . import _native
 from .constants import SAMPLE_RATE, candidate_ratios
 from .cut_align import (DEFAULT_CUT_PENALTY, full_range, lag_arrays, solve_ratios_windowless, validate_args,
                         validate_range)
-from .drift_align import DEFAULT_MAX_STEP, DriftResult, Segment, drift_results, map_cues_drift, validate_drift_args
-from .split_align import DEFAULT_BLOCK_SAMPLES, _check_batch, split_outputs
+from .drift_align import (DEFAULT_MAX_STEP, DriftResult, Segment, drift_outputs, drift_results, map_cues_drift,
+                          validate_drift_args)
+from .side_call import BlockCall, pairs_for_budget
+from .split_align import DEFAULT_BLOCK_SAMPLES, _check_batch
 
 # Chosen on the CPU model over the full range by profiles/drift_range_calibration.py over workloads/cut_drift.py
 # (profiles/drift_range_calibration.json): the smallest power-of-two step cost at which every clean
@@ -57,12 +59,16 @@ def code_planes(max_step: int) -> int:
     return (2 * int(max_step) + 1).bit_length()
 
 
+def workspace_per_pair(max_blocks: int, max_lags: int, max_samples: int, max_step: int) -> float:
+    """Bytes of range drift workspace per pair in flight: code planes and two fp64 rows, ~400 MB for a 2 h full-range
+    pair at max_step 2.  The smooth fit and the report add their own on top."""
+    return max_blocks * (code_planes(max_step) * max_lags / 8.0 + 8) + max_lags * 16.0 + max_samples / 4.0 + 4096
+
+
 def _get_plan(n_pairs: int, max_blocks: int, max_lags: int, max_samples: int, max_step: int,
               pairs_in_flight: Optional[int]):
-    if pairs_in_flight is None:  # bound the workspace (code planes + two fp64 rows: ~400 MB per 2 h full-range pair at
-        # max_step 2) to ~12 GiB
-        per_pair = max_blocks * (code_planes(max_step) * max_lags / 8.0 + 8) + max_lags * 16.0 + max_samples / 4.0 + 4096
-        pairs_in_flight = int(max(1, min(n_pairs, 256, (12 << 30) // per_pair)))
+    if pairs_in_flight is None:  # bound the workspace to ~12 GiB
+        pairs_in_flight = pairs_for_budget(n_pairs, workspace_per_pair(max_blocks, max_lags, max_samples, max_step))
     return _plans.get(pairs_in_flight, max_blocks, max_lags, max_samples, max_step)
 
 
@@ -81,23 +87,12 @@ def drift_align_range_batch(batch, lag_ranges=None, block_samples: int = DEFAULT
     validate_args(block_samples, split_penalty)
     validate_drift_args(max_step, step_cost)
     _check_batch(batch)
-    n = batch.n_pairs
-    ref_len, sub_len = batch.lens[:, 0].astype(np.int64), batch.lens[:, 1].astype(np.int64)
     lo, hi = lag_arrays(batch, lag_ranges)
-    torch = _native.require_gpu()
-    if batch.dtype == _native.FFS_DTYPE_U8:
-        batch = batch.to_bits()
-    k = int(block_samples)
-    n_blocks = (sub_len + k - 1) // k
-    max_b = int(n_blocks.max())
-    plan = _get_plan(n, max_b, int((hi - lo + 1).max()), int(max(sub_len.max(), ref_len.max())), int(max_step),
-                     pairs_in_flight)
-    dev = batch.data.device
-    offs, scores, totals = split_outputs(n, max_b, dev)
-    jumps = torch.empty(n * max_b, dtype=torch.uint8, device=dev)
-    plan.align(*batch.pair_arrays(), k, lo, hi, float(split_penalty), int(max_step), float(step_cost), offs, scores,
-               jumps, totals)
-    return drift_results(offs, scores, jumps, totals, n_blocks, k, sub_len)
+    call = BlockCall(batch, block_samples)
+    plan = _get_plan(call.n, call.max_b, *call.lag_dims(lo, hi), int(max_step), pairs_in_flight)
+    outs = drift_outputs(call)
+    plan.align(*call.pair_arrays(), call.k, lo, hi, float(split_penalty), int(max_step), float(step_cost), *outs)
+    return drift_results(*outs, call.n_blocks, call.k, call.sub_len)
 
 
 def cut_drift_sync(problems, lag_range=None, block_samples: int = DEFAULT_BLOCK_SAMPLES,

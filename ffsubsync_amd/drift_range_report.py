@@ -24,10 +24,13 @@ from . import _native, cut_report, quality, split_refine
 from .constants import SAMPLE_RATE, candidate_ratios
 from .cut_align import DEFAULT_CUT_PENALTY, full_range, lag_arrays, solve_ratios_windowless, validate_range
 from .cut_align import validate_args as validate_cut_args
-from .drift_align import DEFAULT_MAX_STEP, DriftResult, Segment, drift_results, map_cues_drift, validate_drift_args
-from .drift_range import DEFAULT_RANGE_STEP_COST, code_planes
+from .cut_report import _records
+from .drift_align import (DEFAULT_MAX_STEP, DriftResult, Segment, drift_outputs, drift_results, map_cues_drift,
+                          validate_drift_args)
+from .drift_range import DEFAULT_RANGE_STEP_COST, workspace_per_pair
 from .drift_report import DriftReport, SegmentQuality, assess_drift, from_record, jump_support
-from .split_align import DEFAULT_BLOCK_SAMPLES, _check_batch, split_outputs
+from .side_call import BlockCall, pairs_for_budget, record_lists
+from .split_align import DEFAULT_BLOCK_SAMPLES, _check_batch
 
 DEFAULT_TOP_K = quality.DEFAULT_TOP_K
 DEFAULT_EXCLUSION_SAMPLES = quality.DEFAULT_EXCLUSION_SAMPLES
@@ -76,31 +79,14 @@ def _get_plan(n_pairs: int, max_blocks: int, max_lags: int, max_samples: int, ma
     """The report's own plan (drift_range's never grows), sized for the rows its first report call adds: 8 rows of 12
     bytes per lag and pair."""
     if pairs_in_flight is None:  # drift_range's workspace plus the rows (~138 MB per 2 h full-range pair) in ~12 GiB
-        per_pair = (max_blocks * (code_planes(max_step) * max_lags / 8.0 + 8) + max_lags * 16.0 + max_samples / 4.0 + 4096
+        per_pair = (workspace_per_pair(max_blocks, max_lags, max_samples, max_step)
                     + ROUND_SEGMENTS * (max_lags + 65) * 12.0 + (max_samples / 8192.0 + 2 * max_blocks + 2) * 32.0)
-        pairs_in_flight = int(max(1, min(n_pairs, 256, (12 << 30) // per_pair)))
+        pairs_in_flight = pairs_for_budget(n_pairs, per_pair)
     return _plans.get(pairs_in_flight, max_blocks, max_lags, max_samples, max_step)
 
 
 def clear_plan_cache() -> None:
     _plans.clear()
-
-
-def _shape(batch, block_samples):
-    ref_len, sub_len = batch.lens[:, 0].astype(np.int64), batch.lens[:, 1].astype(np.int64)
-    n_blocks = (sub_len + int(block_samples) - 1) // int(block_samples)
-    return ref_len, sub_len, n_blocks, int(n_blocks.max())
-
-
-def _records(batch, lo, hi, offsets, jumps, block_samples, top_k, exclusion_samples, plan, max_b):
-    """The device report of a path (int32 / uint8 CUDA tensors [n_pairs * max_b]): (records [n_pairs, max_b], counts)."""
-    torch = _native.require_gpu()
-    n, dev = batch.n_pairs, batch.data.device
-    rep = torch.empty(n * max_b * _native.SEGMENT_REPORT_BYTES // 8, dtype=torch.int64, device=dev)
-    counts = torch.empty(n, dtype=torch.int32, device=dev)
-    plan.report(*batch.pair_arrays(), int(block_samples), lo, hi, offsets, jumps, int(top_k), int(exclusion_samples), rep,
-                counts)
-    return rep.cpu().numpy().view(_native.SEGMENT_REPORT_DTYPE).reshape(n, max_b), counts.cpu().numpy()
 
 
 def drift_range_path_report_batch(batch, results_or_offsets_and_jumps, lag_ranges=None,
@@ -114,35 +100,24 @@ def drift_range_path_report_batch(batch, results_or_offsets_and_jumps, lag_range
     validate_args(block_samples, 0.0, 0, 0.0, top_k, exclusion_samples)
     _check_batch(batch)
     lo, hi = lag_arrays(batch, lag_ranges)
-    torch = _native.require_gpu()
-    if batch.dtype == _native.FFS_DTYPE_U8:
-        batch = batch.to_bits()
-    k = int(block_samples)
-    ref_len, sub_len, n_blocks, max_b = _shape(batch, k)
-    n = batch.n_pairs
+    call = BlockCall(batch, block_samples)
     given = results_or_offsets_and_jumps
     if isinstance(given, tuple) and len(given) == 2 and not isinstance(given[0], DriftResult):
         all_offs, all_jumps = given
     else:
         all_offs, all_jumps = [r.block_offsets for r in given], [r.block_jump for r in given]
-    if len(all_offs) != n or len(all_jumps) != n:
+    if len(all_offs) != call.n or len(all_jumps) != call.n:
         raise ValueError("one path per pair")
-    offs = np.zeros((n, max_b), np.int32)
-    jumps = np.zeros((n, max_b), np.uint8)
-    for p in range(n):
-        row = np.asarray(all_offs[p], dtype=np.int64)[:int(n_blocks[p])]
-        flags = np.asarray(all_jumps[p])[:int(n_blocks[p])] != 0
-        if row.size != n_blocks[p] or flags.size != n_blocks[p]:
-            raise ValueError("pair %d: %d block offsets and %d jump flags for %d blocks" % (p, row.size, flags.size,
-                                                                                            n_blocks[p]))
-        offs[p, :row.size], jumps[p, :flags.size] = row, flags
-    plan = _get_plan(n, max_b, int((hi - lo + 1).max()), int(max(sub_len.max(), ref_len.max())), 0, pairs_in_flight)
-    dev = batch.data.device
-    recs, counts = _records(batch, lo, hi, torch.from_numpy(offs.ravel()).to(dev), torch.from_numpy(jumps.ravel()).to(dev),
-                            k, top_k, exclusion_samples, plan, max_b)
+    all_offs = [np.asarray(o, dtype=np.int64) for o in all_offs]
+    all_jumps = [np.asarray(j) != 0 for j in all_jumps]
+    what = lambda p, _size, blocks: ("pair %d: %d block offsets and %d jump flags for %d blocks"
+                                     % (p, min(all_offs[p].size, blocks), min(all_jumps[p].size, blocks), blocks))
+    path = call.place(what, (all_offs, np.int32), (all_jumps, np.uint8), clip=True)
+    plan = _get_plan(call.n, call.max_b, *call.lag_dims(lo, hi), 0, pairs_in_flight)
+    recs, counts = _records(call, plan, _native.SEGMENT_REPORT_DTYPE, lo, hi, path, top_k, exclusion_samples)
     if raw:
         return recs, counts
-    return [[from_record(x) for x in recs[p, :int(counts[p])]] for p in range(n)]
+    return record_lists(recs, counts, from_record)
 
 
 def drift_range_report_batch(batch, lag_ranges=None, block_samples: int = DEFAULT_BLOCK_SAMPLES,
@@ -156,24 +131,16 @@ def drift_range_report_batch(batch, lag_ranges=None, block_samples: int = DEFAUL
     validate_args(block_samples, split_penalty, max_step, step_cost, top_k, exclusion_samples)
     _check_batch(batch)
     lo, hi = lag_arrays(batch, lag_ranges)
-    torch = _native.require_gpu()
-    if batch.dtype == _native.FFS_DTYPE_U8:
-        batch = batch.to_bits()
-    k = int(block_samples)
-    ref_len, sub_len, n_blocks, max_b = _shape(batch, k)
-    n = batch.n_pairs
-    plan = _get_plan(n, max_b, int((hi - lo + 1).max()), int(max(sub_len.max(), ref_len.max())), int(max_step),
-                     pairs_in_flight)
-    dev = batch.data.device
-    offs, scores, totals = split_outputs(n, max_b, dev)
-    jumps = torch.empty(n * max_b, dtype=torch.uint8, device=dev)
-    plan.align(*batch.pair_arrays(), k, lo, hi, float(split_penalty), int(max_step), float(step_cost), offs, scores,
+    call = BlockCall(batch, block_samples)
+    plan = _get_plan(call.n, call.max_b, *call.lag_dims(lo, hi), int(max_step), pairs_in_flight)
+    offs, scores, jumps, totals = drift_outputs(call)
+    plan.align(*call.pair_arrays(), call.k, lo, hi, float(split_penalty), int(max_step), float(step_cost), offs, scores,
                jumps, totals)
-    recs, counts = _records(batch, lo, hi, offs, jumps, k, top_k, exclusion_samples, plan, max_b)
-    res = drift_results(offs, scores, jumps, totals, n_blocks, k, sub_len)
+    recs, counts = _records(call, plan, _native.SEGMENT_REPORT_DTYPE, lo, hi, (offs, jumps), top_k, exclusion_samples)
+    res = drift_results(offs, scores, jumps, totals, call.n_blocks, call.k, call.sub_len)
     if raw:
         return res, recs, counts
-    return [DriftReport(r, [from_record(x) for x in recs[p, :int(counts[p])]]) for p, r in enumerate(res)]
+    return [DriftReport(r, q) for r, q in zip(res, record_lists(recs, counts, from_record))]
 
 
 def checked_cut_drift_sync(problems, lag_range=None, block_samples: int = DEFAULT_BLOCK_SAMPLES,

@@ -22,11 +22,11 @@ from . import _native
 from .constants import SAMPLE_RATE, candidate_ratios
 from .cut_align import (DEFAULT_CUT_PENALTY, full_range, lag_arrays, solve_ratios_windowless, validate_args,
                         validate_range)
-from .drift_align import DEFAULT_MAX_STEP, drift_results, validate_drift_args
-from .drift_range import DEFAULT_RANGE_STEP_COST, CutDriftSyncResult, code_planes
-from .drift_smooth import (SmoothResult, SmoothSegment, map_cues_smooth, smooth_segments_from_blocks,
-                           validate_smooth_args)
-from .split_align import DEFAULT_BLOCK_SAMPLES, _check_batch, split_outputs
+from .drift_align import DEFAULT_MAX_STEP, validate_drift_args
+from .drift_range import DEFAULT_RANGE_STEP_COST, CutDriftSyncResult, workspace_per_pair
+from .drift_smooth import SmoothSegment, _smooth, map_cues_smooth, validate_smooth_args
+from .side_call import BlockCall, pairs_for_budget
+from .split_align import DEFAULT_BLOCK_SAMPLES, _check_batch
 
 # UNCALIBRATED: these are drift_smooth's defaults.  profiles/drift_range_smooth_calibration.py applied drift_smooth's
 # rule on the CPU model over workloads/cut_drift.py (profiles/drift_range_smooth_calibration.json) and it
@@ -53,10 +53,10 @@ def _get_plan(n_pairs: int, max_blocks: int, max_lags: int, max_samples: int, ma
               pairs_in_flight: Optional[int]):
     """The cached smooth plan of this device (its own: drift_range's plan never grows)."""
     if pairs_in_flight is None:  # drift_range's bound, plus the fit's tables and band rows per block
-        per_pair = (max_blocks * (code_planes(max_step) * max_lags / 8.0 + 8) + max_lags * 16.0 + max_samples / 4.0 + 4096
+        per_pair = (workspace_per_pair(max_blocks, max_lags, max_samples, max_step)
                     + (max_blocks + 15) * (_native.SMOOTH_BLOCK_BYTES + 2 * _native.range_band_row(
                         max_step, _native.SMOOTH_MAX_KNOT_BLOCKS, _native.SMOOTH_MAX_RADIUS)))
-        pairs_in_flight = int(max(1, min(n_pairs, 256, (12 << 30) // per_pair)))
+        pairs_in_flight = pairs_for_budget(n_pairs, per_pair)
     return _plans.get(pairs_in_flight, max_blocks, max_lags, max_samples, max_step)
 
 
@@ -77,41 +77,11 @@ def smooth_align_range_batch(batch, lag_ranges=None, block_samples: int = DEFAUL
     validate_drift_args(max_step, step_cost)
     validate_smooth_args(knot_blocks, radius, bend_cost)
     _check_batch(batch)
-    n = batch.n_pairs
-    ref_len, sub_len = batch.lens[:, 0].astype(np.int64), batch.lens[:, 1].astype(np.int64)
     lo, hi = lag_arrays(batch, lag_ranges)
-    torch = _native.require_gpu()
-    if batch.dtype == _native.FFS_DTYPE_U8:
-        batch = batch.to_bits()
-    k = int(block_samples)
-    n_blocks = (sub_len + k - 1) // k
-    max_b = int(n_blocks.max())
-    plan = _get_plan(n, max_b, int((hi - lo + 1).max()), int(max(sub_len.max(), ref_len.max())), int(max_step),
-                     pairs_in_flight)
-    dev = batch.data.device
-    offs, scores, totals = split_outputs(n, max_b, dev)
-    jumps = torch.empty(n * max_b, dtype=torch.uint8, device=dev)
-    smooth = torch.empty(n * max_b, dtype=torch.int32, device=dev)
-    knot = torch.empty(n * max_b, dtype=torch.uint8, device=dev)
-    rec = torch.empty(n * max_b * _native.SMOOTH_SEGMENT_BYTES // 8, dtype=torch.int64, device=dev)
-    counts = torch.empty(n, dtype=torch.int32, device=dev)
-    plan.smooth(*batch.pair_arrays(), k, lo, hi, float(split_penalty), int(max_step), float(step_cost), int(knot_blocks),
-                int(radius), float(bend_cost), offs, scores, jumps, totals, smooth, knot, rec, counts)
-    res = drift_results(offs, scores, jumps, totals, n_blocks, k, sub_len)
-    smooth_h = smooth.cpu().numpy().reshape(n, max_b)
-    knot_h = knot.cpu().numpy().reshape(n, max_b)
-    recs = rec.cpu().numpy().view(_native.SMOOTH_SEGMENT_DTYPE).reshape(n, max_b)
-    counts_h = counts.cpu().numpy()
-    if raw:
-        return res, smooth_h, knot_h, recs, counts_h
-    out = []
-    for p, r in enumerate(res):
-        nb = int(n_blocks[p])
-        if int(counts_h[p]) != len(r.segments):
-            raise RuntimeError("pair %d: %d segments on the device, %d on the host" % (p, int(counts_h[p]), len(r.segments)))
-        so, kn = smooth_h[p, :nb].copy(), knot_h[p, :nb].copy()
-        out.append(SmoothResult(r, so, kn, smooth_segments_from_blocks(r, so, kn, recs[p, :len(r.segments)], k)))
-    return out
+    call = BlockCall(batch, block_samples)
+    plan = _get_plan(call.n, call.max_b, *call.lag_dims(lo, hi), int(max_step), pairs_in_flight)
+    return _smooth(call, plan, (lo, hi), (float(split_penalty), int(max_step), float(step_cost), int(knot_blocks),
+                                          int(radius), float(bend_cost)), raw)
 
 
 def smooth_cut_sync(problems, lag_range=None, block_samples: int = DEFAULT_BLOCK_SAMPLES,

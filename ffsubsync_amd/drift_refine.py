@@ -34,6 +34,7 @@ from .drift_range_smooth import (DEFAULT_RANGE_BEND_COST, DEFAULT_RANGE_KNOT_BLO
                                  SmoothCutSyncResult, smooth_align_range_batch)
 from .drift_smooth import (DEFAULT_BEND_COST, DEFAULT_KNOT_BLOCKS, DEFAULT_RADIUS, SmoothResult, SmoothSyncResult,
                            map_cues_smooth, polyline_shift, smooth_align_batch, validate_smooth_args)
+from .side_call import BlockCall, block_shape, no_workspace_split_plan, pad_rows, record_lists
 from .split_align import (DEFAULT_BLOCK_SAMPLES, DEFAULT_SPLIT_PENALTY, _check_batch, _scaled_us, _td_us, solve_ratios,
                           validate_args)
 from .split_refine import (DEFAULT_RADIUS_SAMPLES, DEFAULT_UNMATCHED_MARGIN, UNMATCHED_PIECE, RefinedBreak, from_record,
@@ -48,7 +49,7 @@ _plans = _native.SidePlanCache(_native.SplitPlan)
 
 def _get_plan(n_pairs: int):
     """A split plan of this device that holds no split workspace, as ``split_refine``'s."""
-    return _plans.get(int(max(1, min(n_pairs, 256))), 1, 2, 1)
+    return no_workspace_split_plan(_plans, n_pairs)
 
 
 def clear_plan_cache() -> None:
@@ -73,38 +74,22 @@ def refine_jumps_batch(batch, results: Sequence, block_samples: int = DEFAULT_BL
     validate_refine_args(block_samples, radius_samples, unmatched_margin)
     _check_batch(batch)
     k = int(block_samples)
-    n = batch.n_pairs
-    if len(results) != n:
-        raise ValueError("%d drift results for %d pairs" % (len(results), n))
-    sub_len = batch.lens[:, 1].astype(np.int64)
-    n_blocks = (sub_len + k - 1) // k
+    if len(results) != batch.n_pairs:
+        raise ValueError("%d drift results for %d pairs" % (len(results), batch.n_pairs))
     paths = [_path(r) for r in results]
-    for p, (d, o) in enumerate(paths):
-        if np.asarray(o).size != n_blocks[p] or np.asarray(d.block_jump).size != n_blocks[p]:
-            raise ValueError("pair %d: %d block offsets and %d jump flags, %d blocks of %d samples"
-                             % (p, np.asarray(o).size, np.asarray(d.block_jump).size, int(n_blocks[p]), k))
-    torch = _native.require_gpu()
-    if batch.dtype == _native.FFS_DTYPE_U8:
-        batch = batch.to_bits()
-    max_b = int(n_blocks.max())
-    offs = np.zeros((n, max_b), np.int32)
-    jumps = np.zeros((n, max_b), np.uint8)
-    for p, (d, o) in enumerate(paths):
-        offs[p, :n_blocks[p]] = np.asarray(o)
-        jumps[p, :n_blocks[p]] = np.asarray(d.block_jump) != 0
-    dev = batch.data.device
-    offs_dev = torch.from_numpy(offs.reshape(-1)).to(dev)
-    jumps_dev = torch.from_numpy(jumps.reshape(-1)).to(dev)
-    rec_out = torch.empty(n * max_b * _native.BREAK_REFINE_BYTES, dtype=torch.uint8, device=dev)
-    n_out = torch.empty(n, dtype=torch.int32, device=dev)
-    plan = _get_plan(n)
-    plan.drift_refine(*batch.pair_arrays(), k, offs_dev, jumps_dev, int(radius_samples),
+    all_offs, all_jumps = [np.asarray(o) for _, o in paths], [np.asarray(d.block_jump) != 0 for d, _ in paths]
+    what = lambda p, _size, blocks: ("pair %d: %d block offsets and %d jump flags, %d blocks of %d samples"
+                                     % (p, all_offs[p].size, all_jumps[p].size, blocks, k))
+    path = pad_rows(block_shape(batch, k)[2], what, (all_offs, np.int32), (all_jumps, np.uint8))
+    call = BlockCall(batch, k)
+    rec_out, n_out = call.records(_native.BREAK_REFINE_DTYPE), call.per_pair(np.int32)
+    plan = _get_plan(call.n)
+    plan.drift_refine(*call.pair_arrays(), k, *call.upload(path), int(radius_samples),
                       math.nan if unmatched_margin is None else float(unmatched_margin), rec_out, n_out)
-    recs = rec_out.cpu().numpy().view(_native.BREAK_REFINE_DTYPE).reshape(n, max_b)
-    counts = n_out.cpu().numpy()
+    recs, counts = call.read_records(rec_out, _native.BREAK_REFINE_DTYPE), n_out.cpu().numpy()
     if raw:
         return recs, counts
-    return [[from_record(x) for x in recs[p, :int(counts[p])]] for p in range(n)]
+    return record_lists(recs, counts, from_record)
 
 
 def _refined_cues(start_us, end_us, ratio, segments, breaks, sample_rate, shift_us):

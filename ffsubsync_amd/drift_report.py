@@ -25,7 +25,6 @@ problem to ``split_report.checked_split_sync``.  Parity is against the in-repo n
 ``tests/drift_report_model.py``, bit for bit.  ``drift_sync``, ``drift_align_batch`` and every existing entry point
 are unchanged.
 """
-import math
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence, Tuple
 
@@ -33,9 +32,10 @@ import numpy as np
 
 from . import _native, quality, split_report
 from .constants import SAMPLE_RATE, candidate_ratios
-from .drift_align import (DEFAULT_MAX_STEP, DEFAULT_STEP_COST, DriftResult, Segment, drift_results, map_cues_drift,
-                          validate_drift_args)
-from .split_align import DEFAULT_BLOCK_SAMPLES, DEFAULT_SPLIT_PENALTY, _check_batch, solve_ratios, split_outputs
+from .drift_align import (DEFAULT_MAX_STEP, DEFAULT_STEP_COST, DriftResult, Segment, drift_outputs, drift_results,
+                          map_cues_drift, validate_drift_args)
+from .side_call import BlockCall, pairs_for_budget, record_lists
+from .split_align import DEFAULT_BLOCK_SAMPLES, DEFAULT_SPLIT_PENALTY, _check_batch, solve_ratios
 
 DEFAULT_TOP_K = quality.DEFAULT_TOP_K
 DEFAULT_EXCLUSION_SAMPLES = quality.DEFAULT_EXCLUSION_SAMPLES
@@ -117,23 +117,12 @@ def validate_args(block_samples, max_offset_samples, split_penalty, max_step, st
 def from_record(rec) -> SegmentQuality:
     """SegmentQuality of one ``_native.SEGMENT_REPORT_DTYPE`` record, with psr, margin and the gains derived on the
     host."""
-    n = int(rec["n_peaks"])
-    peaks = [(float(rec["peak_score"][i]), int(rec["peak_shift"][i])) for i in range(n)]
+    peaks = [(float(rec["peak_score"][i]), int(rec["peak_shift"][i])) for i in range(int(rec["n_peaks"]))]
     mean, std = float(rec["mean"]), float(rec["std"])
     own, prev, nxt = float(rec["own_score"]), float(rec["prev_score"]), float(rec["next_score"])
     flat_score = float(rec["flat_score"])
-    flags = int(rec["flags"])
-    if std == 0 or n == 0:
-        psr = margin = drift_gain = 0.0
-        gain_prev = math.nan if math.isnan(prev) else 0.0
-        gain_next = math.nan if math.isnan(nxt) else 0.0
-        flags |= _native.QUALITY_FLAT
-    else:
-        psr = (peaks[0][0] - mean) / std
-        margin = (peaks[0][0] - peaks[1][0]) / std if n > 1 else math.inf
-        gain_prev = (own - prev) / std
-        gain_next = (own - nxt) / std
-        drift_gain = (own - flat_score) / std
+    psr, margin, flags, (gain_prev, gain_next) = quality.derive(peaks, mean, std, int(rec["flags"]), own, (prev, nxt))
+    drift_gain = 0.0 if std == 0 or not peaks else (own - flat_score) / std
     return SegmentQuality(int(rec["first_block"]), int(rec["end_block"]), int(rec["start_sample"]),
                           int(rec["end_sample"]), int(rec["first_offset"]), int(rec["last_offset"]),
                           int(rec["min_offset"]), int(rec["max_offset"]), own, prev, nxt, flat_score,
@@ -173,7 +162,7 @@ def _get_plan(n_pairs: int, max_blocks: int, max_lags: int, max_samples: int, pa
     """The cached report plan of this device (its own: drift_align's plan never grows)."""
     if pairs_in_flight is None:  # drift_align's ~2.7 bytes per (block, lag), plus 8 fp64 rows of lags
         per_pair = max_blocks * (max_lags + 64) * 2.7 + (max_lags + 64) * 64 + 1
-        pairs_in_flight = int(max(1, min(n_pairs, 256, (12 << 30) // per_pair)))
+        pairs_in_flight = pairs_for_budget(n_pairs, per_pair)
     return _plans.get(pairs_in_flight, max_blocks, max_lags, max_samples)
 
 
@@ -191,28 +180,18 @@ def drift_report_batch(batch, max_offset_samples: int, block_samples: int = DEFA
     ``_native.SEGMENT_REPORT_DTYPE`` records [n_pairs, max_b], segment counts)."""
     validate_args(block_samples, max_offset_samples, split_penalty, max_step, step_cost, top_k, exclusion_samples)
     _check_batch(batch)
-    torch = _native.require_gpu()
-    if batch.dtype == _native.FFS_DTYPE_U8:
-        batch = batch.to_bits()
-    k, w = int(block_samples), int(max_offset_samples)
-    n = batch.n_pairs
-    sub_len = batch.lens[:, 1].astype(np.int64)
-    n_blocks = (sub_len + k - 1) // k
-    max_b = int(n_blocks.max())
-    plan = _get_plan(n, max_b, 2 * w, int(sub_len.max()), pairs_in_flight)
-    dev = batch.data.device
-    offs, scores, totals = split_outputs(n, max_b, dev)
-    jumps = torch.empty(n * max_b, dtype=torch.uint8, device=dev)
-    rep = torch.empty(n * max_b * _native.SEGMENT_REPORT_BYTES // 8, dtype=torch.int64, device=dev)
-    counts = torch.empty(n, dtype=torch.int32, device=dev)
-    plan.report(*batch.pair_arrays(), k, w, float(split_penalty), int(max_step), float(step_cost), int(top_k),
-                int(exclusion_samples), offs, scores, jumps, totals, rep, counts)
-    res = drift_results(offs, scores, jumps, totals, n_blocks, k, sub_len)
-    recs = rep.cpu().numpy().view(_native.SEGMENT_REPORT_DTYPE).reshape(n, max_b)
-    counts_h = counts.cpu().numpy()
+    call = BlockCall(batch, block_samples)
+    w = int(max_offset_samples)
+    plan = _get_plan(call.n, call.max_b, 2 * w, int(call.sub_len.max()), pairs_in_flight)
+    outs = drift_outputs(call)
+    rep, counts = call.records(_native.SEGMENT_REPORT_DTYPE), call.per_pair(np.int32)
+    plan.report(*call.pair_arrays(), call.k, w, float(split_penalty), int(max_step), float(step_cost), int(top_k),
+                int(exclusion_samples), *outs, rep, counts)
+    res = drift_results(*outs, call.n_blocks, call.k, call.sub_len)
+    recs, counts_h = call.read_records(rep, _native.SEGMENT_REPORT_DTYPE), counts.cpu().numpy()
     if raw:
         return res, recs, counts_h
-    return [DriftReport(r, [from_record(x) for x in recs[p, :int(counts_h[p])]]) for p, r in enumerate(res)]
+    return [DriftReport(r, q) for r, q in zip(res, record_lists(recs, counts_h, from_record))]
 
 
 def checked_drift_sync(problems, max_offset_seconds: float = 600, block_samples: int = DEFAULT_BLOCK_SAMPLES,

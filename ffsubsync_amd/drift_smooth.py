@@ -23,10 +23,11 @@ import numpy as np
 
 from . import _native
 from .constants import SAMPLE_RATE, candidate_ratios
-from .drift_align import (DEFAULT_MAX_STEP, DEFAULT_STEP_COST, DriftResult, DriftSyncResult, drift_results,
-                          validate_drift_args)
+from .drift_align import (DEFAULT_MAX_STEP, DEFAULT_STEP_COST, DriftResult, DriftSyncResult, drift_outputs,
+                          drift_results, validate_drift_args)
+from .side_call import BlockCall, pairs_for_budget
 from .split_align import (DEFAULT_BLOCK_SAMPLES, DEFAULT_SPLIT_PENALTY, _check_batch, _scaled_us, solve_ratios,
-                          split_outputs, validate_args)
+                          validate_args)
 
 # Chosen on the CPU model by profiles/drift_smooth_calibration.py over workloads/drift.py
 # (profiles/drift_smooth_calibration.json): the smallest power-of-two bend cost at which every one of the 40
@@ -104,7 +105,7 @@ def _get_plan(n_pairs: int, max_blocks: int, max_lags: int, max_samples: int, pa
     """The cached smooth plan of this device (its own: drift_align's plan never grows)."""
     if pairs_in_flight is None:  # drift_align's ~2.7 bytes per (block, lag), plus the fit's tables per block
         per_pair = max_blocks * (max_lags + 64) * 2.7 + max_blocks * _native.SMOOTH_BLOCK_BYTES + 1
-        pairs_in_flight = int(max(1, min(n_pairs, 256, (12 << 30) // per_pair)))
+        pairs_in_flight = pairs_for_budget(n_pairs, per_pair)
     return _plans.get(pairs_in_flight, max_blocks, max_lags, max_samples)
 
 
@@ -125,38 +126,33 @@ def smooth_align_batch(batch, max_offset_samples: int, block_samples: int = DEFA
     validate_drift_args(max_step, step_cost)
     validate_smooth_args(knot_blocks, radius, bend_cost)
     _check_batch(batch)
-    torch = _native.require_gpu()
-    if batch.dtype == _native.FFS_DTYPE_U8:
-        batch = batch.to_bits()
-    k, w = int(block_samples), int(max_offset_samples)
-    n = batch.n_pairs
-    sub_len = batch.lens[:, 1].astype(np.int64)
-    n_blocks = (sub_len + k - 1) // k
-    max_b = int(n_blocks.max())
-    plan = _get_plan(n, max_b, 2 * w, int(sub_len.max()), pairs_in_flight)
-    dev = batch.data.device
-    offs, scores, totals = split_outputs(n, max_b, dev)
-    jumps = torch.empty(n * max_b, dtype=torch.uint8, device=dev)
-    smooth = torch.empty(n * max_b, dtype=torch.int32, device=dev)
-    knot = torch.empty(n * max_b, dtype=torch.uint8, device=dev)
-    rec = torch.empty(n * max_b * _native.SMOOTH_SEGMENT_BYTES // 8, dtype=torch.int64, device=dev)
-    counts = torch.empty(n, dtype=torch.int32, device=dev)
-    plan.smooth(*batch.pair_arrays(), k, w, float(split_penalty), int(max_step), float(step_cost), int(knot_blocks),
-                int(radius), float(bend_cost), offs, scores, jumps, totals, smooth, knot, rec, counts)
-    res = drift_results(offs, scores, jumps, totals, n_blocks, k, sub_len)
-    smooth_h = smooth.cpu().numpy().reshape(n, max_b)
-    knot_h = knot.cpu().numpy().reshape(n, max_b)
-    recs = rec.cpu().numpy().view(_native.SMOOTH_SEGMENT_DTYPE).reshape(n, max_b)
-    counts_h = counts.cpu().numpy()
+    call = BlockCall(batch, block_samples)
+    w = int(max_offset_samples)
+    plan = _get_plan(call.n, call.max_b, 2 * w, int(call.sub_len.max()), pairs_in_flight)
+    return _smooth(call, plan, (w,), (float(split_penalty), int(max_step), float(step_cost), int(knot_blocks), int(radius),
+                                      float(bend_cost)), raw)
+
+
+def _smooth(call: BlockCall, plan, window_args, fit_args, raw: bool):
+    """The device call and read-back of both smooth entry points, this one and ``drift_range_smooth``'s:
+    ``plan.smooth`` with the lag set as the plan takes it (``window_args``: (W,) or (lag_lo, lag_hi)), then the cost
+    and fit parameters ``fit_args``."""
+    outs = drift_outputs(call)
+    smooth, knot = call.per_block(np.int32), call.per_block(np.uint8)
+    rec, counts = call.records(_native.SMOOTH_SEGMENT_DTYPE), call.per_pair(np.int32)
+    plan.smooth(*call.pair_arrays(), call.k, *window_args, *fit_args, *outs, smooth, knot, rec, counts)
+    res = drift_results(*outs, call.n_blocks, call.k, call.sub_len)
+    smooth_h, knot_h = call.read_blocks(smooth), call.read_blocks(knot)
+    recs, counts_h = call.read_records(rec, _native.SMOOTH_SEGMENT_DTYPE), counts.cpu().numpy()
     if raw:
         return res, smooth_h, knot_h, recs, counts_h
     out = []
     for p, r in enumerate(res):
-        nb = int(n_blocks[p])
+        nb = int(call.n_blocks[p])
         if int(counts_h[p]) != len(r.segments):
             raise RuntimeError("pair %d: %d segments on the device, %d on the host" % (p, int(counts_h[p]), len(r.segments)))
         so, kn = smooth_h[p, :nb].copy(), knot_h[p, :nb].copy()
-        out.append(SmoothResult(r, so, kn, smooth_segments_from_blocks(r, so, kn, recs[p, :len(r.segments)], k)))
+        out.append(SmoothResult(r, so, kn, smooth_segments_from_blocks(r, so, kn, recs[p, :len(r.segments)], call.k)))
     return out
 
 

@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _native, quality
 from .constants import SAMPLE_RATE, candidate_ratios
-from .split_align import empty_error
+from .side_call import empty_error, pairs_for_budget
 
 ALGORITHMS = tuple(sorted(_native.MATCH_ALGORITHMS))
 DEFAULT_BLOCK_PAIRS = 16384  # pairs solved and reported at a time (whole reference rows)
@@ -150,7 +150,7 @@ def clear_plan_cache() -> None:
 
 def _get_plan(n_pairs: int, max_lags: int, max_samples: int, n_vectors: int, pairs_in_flight: Optional[int]):
     if pairs_in_flight is None:  # bound the per-pair workspace (12 B per lag) to ~2 GiB
-        pairs_in_flight = int(max(1, min(n_pairs, 1024, (2 << 30) // (12 * max_lags + 1))))
+        pairs_in_flight = pairs_for_budget(n_pairs, 12 * max_lags + 1, cap=1024, budget=2 << 30)
     return _plans.get(pairs_in_flight, max_lags, max_samples, max(n_vectors, 2))
 
 

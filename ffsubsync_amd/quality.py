@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _native
 from .constants import SAMPLE_RATE, candidate_ratios
-from .split_align import empty_error
+from .side_call import bits_batch, check_two_level_batch, pairs_for_budget
 
 DEFAULT_TOP_K = 3
 DEFAULT_EXCLUSION_SAMPLES = 300  # 3 s at 100 Hz: a runner-up closer than that is the same peak's shoulder
@@ -73,18 +73,23 @@ def validate_args(max_offset_samples, top_k, exclusion_samples) -> None:
         raise ValueError("exclusion_samples=%r: need an integer >= 1" % (exclusion_samples,))
 
 
+def derive(peaks, mean: float, std: float, flags: int, own: float = math.nan, others: Sequence[float] = ()):
+    """The host derivation of every curve report (whole file, piece, segment): (psr, margin, flags, gains) of a curve
+    with these ``peaks`` ((score, lag), the maximum first) and moments.  gains: (own - x) / std for each x of
+    ``others`` (the curve at a neighbour's lag).  A curve with std 0 or no peak is flat: ``QUALITY_FLAT`` is set, psr and
+    margin are 0, and a gain is 0 unless its x is NaN (there is no such neighbour), which stays NaN."""
+    if std == 0 or not peaks:
+        return 0.0, 0.0, flags | _native.QUALITY_FLAT, [math.nan if math.isnan(x) else 0.0 for x in others]
+    psr = (peaks[0][0] - mean) / std
+    margin = (peaks[0][0] - peaks[1][0]) / std if len(peaks) > 1 else math.inf
+    return psr, margin, flags, [(own - x) / std for x in others]
+
+
 def from_record(rec) -> AlignmentQuality:
     """AlignmentQuality of one ``_native.QUALITY_RESULT_DTYPE`` record, with psr and margin derived on the host."""
-    n = int(rec["n_peaks"])
-    peaks = [(float(rec["peak_score"][i]), int(rec["peak_offset"][i])) for i in range(n)]
+    peaks = [(float(rec["peak_score"][i]), int(rec["peak_offset"][i])) for i in range(int(rec["n_peaks"]))]
     mean, std = float(rec["mean"]), float(rec["std"])
-    flags = int(rec["flags"])
-    if std == 0 or n == 0:
-        psr = margin = 0.0
-        flags |= _native.QUALITY_FLAT
-    else:
-        psr = (peaks[0][0] - mean) / std
-        margin = (peaks[0][0] - peaks[1][0]) / std if n > 1 else math.inf
+    psr, margin, flags, _ = derive(peaks, mean, std, int(rec["flags"]))
     return AlignmentQuality(peaks, mean, std, int(rec["n_lags"]), psr, margin, flags)
 
 
@@ -104,23 +109,7 @@ def assess(q: AlignmentQuality, min_psr: float = DEFAULT_MIN_PSR, min_margin: fl
 
 
 def _check_batch(batch) -> None:
-    if batch.n_cand != 1:
-        raise ValueError("quality_batch needs one candidate per pair (DeviceBatch.select_candidates)")
-    two_level = (_native.FFS_DTYPE_U1, _native.FFS_DTYPE_U8, _native.FFS_DTYPE_RUNS)
-    ref_dt = batch.dtype if batch.ref_dtype is None else batch.ref_dtype
-    if ref_dt in (_native.FFS_DTYPE_F32, _native.FFS_DTYPE_F64):
-        raise ValueError("quality_batch needs a two-level reference: a multi-level float reference (FFS_DTYPE_%s) is not "
-                         "supported" % ("F64" if ref_dt == _native.FFS_DTYPE_F64 else "F32"))
-    if ref_dt != batch.dtype or batch.dtype not in two_level:
-        raise ValueError("quality_batch needs two-level vectors of one type: bit-packed (FFS_DTYPE_U1), 0/1 bytes "
-                         "(FFS_DTYPE_U8) or boundary lists (FFS_DTYPE_RUNS)")
-    lens = np.asarray(batch.lens)
-    for p in range(lens.shape[0]):
-        if lens[p, 0] <= 0 or lens[p, 1] <= 0:
-            raise empty_error(max(int(lens[p, 0]), 0), max(int(lens[p, 1]), 0))
-    levels = np.concatenate([np.ravel(batch.lo), np.ravel(batch.hi)])
-    if not np.all(np.isfinite(levels)):
-        raise ValueError("two-level vectors need finite levels")
+    check_two_level_batch(batch, "quality_batch", float_ref_message=True, lists=True)
 
 
 def n_lags(ref_len: int, sub_len: int, max_offset_samples: Optional[int]) -> int:
@@ -143,7 +132,7 @@ _plans = _native.SidePlanCache(_native.QualityPlan)
 
 def _get_plan(n_pairs: int, max_lags: int, max_samples: int, pairs_in_flight: Optional[int]):
     if pairs_in_flight is None:  # bound the workspace (12 B per lag: 144 KB per pair at +-60 s) to ~2 GiB
-        pairs_in_flight = int(max(1, min(n_pairs, 1024, (2 << 30) // (12 * max_lags + 1))))
+        pairs_in_flight = pairs_for_budget(n_pairs, 12 * max_lags + 1, cap=1024, budget=2 << 30)
     return _plans.get(pairs_in_flight, max_lags, max_samples)
 
 
@@ -166,8 +155,7 @@ def quality_batch(batch, max_offset_samples: Optional[int], top_k: int = DEFAULT
     n = batch.n_pairs
     max_lags = max(n_lags(int(r), int(s), max_offset_samples) for r, s in zip(ref_len, sub_len))
     plan = _get_plan(n, max(max_lags, 1), int(max(ref_len.max(), sub_len.max())), pairs_in_flight)
-    if batch.dtype == _native.FFS_DTYPE_U8:
-        batch = batch.to_bits()
+    batch = bits_batch(batch)
     args = list(batch.pair_arrays())
     if batch.dtype == _native.FFS_DTYPE_RUNS:
         words = (batch.lens.astype(np.int64) + 31) // 32

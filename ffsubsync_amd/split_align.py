@@ -19,6 +19,7 @@ import numpy as np
 
 from . import _native
 from .constants import SAMPLE_RATE, candidate_ratios
+from .side_call import BlockCall, check_two_level_batch, empty_error, pairs_for_budget
 
 DEFAULT_BLOCK_SAMPLES = 1024  # 10.24 s at 100 Hz
 DEFAULT_SPLIT_PENALTY = 8192.0  # no spurious pieces above 4 000 in the CPU model; kept after the GPU tests
@@ -75,12 +76,6 @@ def validate_args(block_samples, max_offset_samples, split_penalty) -> None:
         raise ValueError("split_penalty=%r: need a number >= 0 (inf = never split)" % (split_penalty,))
 
 
-def empty_error(ref_len: int, sub_len: int) -> ValueError:
-    """aligners.py:58-66's wording for empty speech data."""
-    return ValueError("cannot align empty speech data (reference length=%d, subtitle length=%d); the reference or subtitles "
-                      "may contain no detectable speech" % (ref_len, sub_len))
-
-
 def pieces_from_blocks(block_offsets, block_scores, block_samples: int, sub_len: int) -> List[Piece]:
     """Maximal runs of equal block offsets, with their sample ranges and scores (summed in block order from 0.0)."""
     offs = np.asarray(block_offsets)
@@ -97,17 +92,8 @@ def pieces_from_blocks(block_offsets, block_scores, block_samples: int, sub_len:
 
 
 def _check_batch(batch) -> None:
-    if batch.n_cand != 1:
-        raise ValueError("split_align_batch needs one candidate per pair (DeviceBatch.select_candidates)")
-    if batch.ref_dtype not in (None, batch.dtype) or batch.dtype not in (_native.FFS_DTYPE_U1, _native.FFS_DTYPE_U8):
-        raise ValueError("split_align_batch needs two-level vectors: bit-packed (FFS_DTYPE_U1) or 0/1 bytes (FFS_DTYPE_U8)")
-    lens = np.asarray(batch.lens)
-    for p in range(lens.shape[0]):
-        if lens[p, 0] <= 0 or lens[p, 1] <= 0:
-            raise empty_error(int(lens[p, 0]), int(lens[p, 1]))
-    levels = np.concatenate([np.ravel(batch.lo), np.ravel(batch.hi)])
-    if not np.all(np.isfinite(levels)):
-        raise ValueError("two-level vectors need finite levels")
+    """The batch check of every block-wise entry point, in ``split_align_batch``'s words."""
+    check_two_level_batch(batch, "split_align_batch")
 
 
 _plans = _native.SidePlanCache(_native.SplitPlan)
@@ -119,7 +105,7 @@ def _get_plan(n_pairs: int, max_blocks: int, max_lags: int, max_samples: int, pa
     the first report call adds (4 more bytes per block and lag)."""
     if pairs_in_flight is None:  # bound the workspace (~170 MB of counts per pair at 2 h, +-10 min, K = 1024) to ~12 GiB
         per_pair = max_blocks * (max_lags + 64) * (6.2 if report else 2.2) + 1
-        pairs_in_flight = int(max(1, min(n_pairs, 256, (12 << 30) // per_pair)))
+        pairs_in_flight = pairs_for_budget(n_pairs, per_pair)
     return _plans.get(pairs_in_flight, max_blocks, max_lags, max_samples, role="report" if report else None)
 
 
@@ -142,28 +128,19 @@ def _solve(batch, max_offset_samples, block_samples, split_penalty, pairs_in_fli
     """The device call behind ``split_align_batch`` (arguments checked); with ``report`` = (top_k, exclusion_samples)
     ``ffs_align_split_report_batch``.  Returns (SplitResults, piece report records [n, max_b] or None, piece counts or
     None)."""
-    torch = _native.require_gpu()
-    if batch.dtype == _native.FFS_DTYPE_U8:
-        batch = batch.to_bits()
-    k, w = int(block_samples), int(max_offset_samples)
-    n = batch.n_pairs
-    sub_len = batch.lens[:, 1].astype(np.int64)
-    n_blocks = (sub_len + k - 1) // k
-    max_b = int(n_blocks.max())
-    plan = _get_plan(n, max_b, 2 * w, int(sub_len.max()), pairs_in_flight, report is not None)
-    dev = batch.data.device
-    outs = split_outputs(n, max_b, dev)
-    args = batch.pair_arrays() + (k, w, float(split_penalty))
+    call = BlockCall(batch, block_samples)
+    w = int(max_offset_samples)
+    plan = _get_plan(call.n, call.max_b, 2 * w, int(call.sub_len.max()), pairs_in_flight, report is not None)
+    outs = split_outputs(call.n, call.max_b, call.dev)
+    args = call.pair_arrays() + (call.k, w, float(split_penalty))
     recs = counts = None
     if report is None:
         plan.align(*args, *outs)
     else:
-        rep_out = torch.empty(n * max_b * _native.PIECE_REPORT_BYTES, dtype=torch.uint8, device=dev)
-        n_out = torch.empty(n, dtype=torch.int32, device=dev)
+        rep_out, n_out = call.records(_native.PIECE_REPORT_DTYPE), call.per_pair(np.int32)
         plan.align_report(*args, int(report[0]), int(report[1]), *outs, rep_out, n_out)
-        recs = rep_out.cpu().numpy().view(_native.PIECE_REPORT_DTYPE).reshape(n, max_b)
-        counts = n_out.cpu().numpy()
-    return split_results(outs, n_blocks, k, sub_len), recs, counts
+        recs, counts = call.read_records(rep_out, _native.PIECE_REPORT_DTYPE), n_out.cpu().numpy()
+    return split_results(outs, call.n_blocks, call.k, call.sub_len), recs, counts
 
 
 def split_outputs(n_pairs: int, max_b: int, device):

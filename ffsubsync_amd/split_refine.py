@@ -22,6 +22,7 @@ import numpy as np
 
 from . import _native, quality, split_report
 from .constants import SAMPLE_RATE
+from .side_call import BlockCall, block_shape, no_workspace_split_plan, pad_rows, record_lists
 from .split_align import (DEFAULT_BLOCK_SAMPLES, DEFAULT_SPLIT_PENALTY, Piece, SplitResult, _check_batch, _scaled_us,
                           _td_us, validate_block_samples)
 
@@ -79,7 +80,7 @@ _plans = _native.SidePlanCache(_native.SplitPlan)
 
 def _get_plan(n_pairs: int):
     """A split plan of this device that holds no split workspace: refine calls use its sub-batching and descriptors."""
-    return _plans.get(int(max(1, min(n_pairs, 256))), 1, 2, 1)
+    return no_workspace_split_plan(_plans, n_pairs)
 
 
 def clear_plan_cache() -> None:
@@ -95,34 +96,19 @@ def refine_breaks_batch(batch, split_results: Sequence[SplitResult], block_sampl
     validate_args(block_samples, radius_samples, unmatched_margin)
     _check_batch(batch)
     k = int(block_samples)
-    n = batch.n_pairs
-    if len(split_results) != n:
-        raise ValueError("%d split results for %d pairs" % (len(split_results), n))
-    sub_len = batch.lens[:, 1].astype(np.int64)
-    n_blocks = (sub_len + k - 1) // k
-    for p, res in enumerate(split_results):
-        if np.asarray(res.block_offsets).size != n_blocks[p]:
-            raise ValueError("pair %d: %d block offsets, %d blocks of %d samples" % (p, np.asarray(res.block_offsets).size,
-                                                                                     int(n_blocks[p]), k))
-    torch = _native.require_gpu()
-    if batch.dtype == _native.FFS_DTYPE_U8:
-        batch = batch.to_bits()
-    max_b = int(n_blocks.max())
-    offs = np.zeros((n, max_b), np.int32)
-    for p, res in enumerate(split_results):
-        offs[p, :n_blocks[p]] = np.asarray(res.block_offsets)
-    dev = batch.data.device
-    offs_dev = torch.from_numpy(offs.reshape(-1)).to(dev)
-    rec_out = torch.empty(n * max_b * _native.BREAK_REFINE_BYTES, dtype=torch.uint8, device=dev)
-    n_out = torch.empty(n, dtype=torch.int32, device=dev)
-    plan = _get_plan(n)
-    plan.refine(*batch.pair_arrays(), k, offs_dev, int(radius_samples),
+    if len(split_results) != batch.n_pairs:
+        raise ValueError("%d split results for %d pairs" % (len(split_results), batch.n_pairs))
+    what = lambda p, size, blocks: "pair %d: %d block offsets, %d blocks of %d samples" % (p, size, blocks, k)
+    path = pad_rows(block_shape(batch, k)[2], what, ([r.block_offsets for r in split_results], np.int32))
+    call = BlockCall(batch, k)
+    rec_out, n_out = call.records(_native.BREAK_REFINE_DTYPE), call.per_pair(np.int32)
+    plan = _get_plan(call.n)
+    plan.refine(*call.pair_arrays(), k, *call.upload(path), int(radius_samples),
                 math.nan if unmatched_margin is None else float(unmatched_margin), rec_out, n_out)
-    recs = rec_out.cpu().numpy().view(_native.BREAK_REFINE_DTYPE).reshape(n, max_b)
-    counts = n_out.cpu().numpy()
+    recs, counts = call.read_records(rec_out, _native.BREAK_REFINE_DTYPE), n_out.cpu().numpy()
     if raw:
         return recs, counts
-    return [[from_record(x) for x in recs[p, :int(counts[p])]] for p in range(n)]
+    return record_lists(recs, counts, from_record)
 
 
 def map_cues_refined(start_us, end_us, ratio: float, pieces: Sequence[Piece], breaks: Sequence[RefinedBreak],

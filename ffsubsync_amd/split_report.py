@@ -19,7 +19,6 @@ leaves the cues alone -- what upstream's ``--skip-sync-on-low-quality`` does.
 Parity is against the in-repo numpy model ``tests/split_report_model.py``, bit for bit.  ``split_sync``,
 ``split_align_batch``, the ``quality`` functions and every existing entry point are unchanged.
 """
-import math
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence, Tuple
 
@@ -27,6 +26,7 @@ import numpy as np
 
 from . import _native, quality
 from .constants import SAMPLE_RATE, candidate_ratios
+from .side_call import record_lists
 from .split_align import (DEFAULT_BLOCK_SAMPLES, DEFAULT_SPLIT_PENALTY, Piece, SplitResult, _check_batch, _solve,
                           map_cues, solve_ratios, validate_args as validate_split_args)
 
@@ -98,21 +98,10 @@ def validate_args(block_samples, max_offset_samples, split_penalty, top_k, exclu
 
 def from_record(rec) -> PieceQuality:
     """PieceQuality of one ``_native.PIECE_REPORT_DTYPE`` record, with psr, margin and the gains derived on the host."""
-    n = int(rec["n_peaks"])
-    peaks = [(float(rec["peak_score"][i]), int(rec["peak_offset"][i])) for i in range(n)]
+    peaks = [(float(rec["peak_score"][i]), int(rec["peak_offset"][i])) for i in range(int(rec["n_peaks"]))]
     mean, std = float(rec["mean"]), float(rec["std"])
     own, prev, nxt = float(rec["own_score"]), float(rec["prev_score"]), float(rec["next_score"])
-    flags = int(rec["flags"])
-    if std == 0 or n == 0:
-        psr = margin = 0.0
-        gain_prev = math.nan if math.isnan(prev) else 0.0
-        gain_next = math.nan if math.isnan(nxt) else 0.0
-        flags |= _native.QUALITY_FLAT
-    else:
-        psr = (peaks[0][0] - mean) / std
-        margin = (peaks[0][0] - peaks[1][0]) / std if n > 1 else math.inf
-        gain_prev = (own - prev) / std
-        gain_next = (own - nxt) / std
+    psr, margin, flags, (gain_prev, gain_next) = quality.derive(peaks, mean, std, int(rec["flags"]), own, (prev, nxt))
     return PieceQuality(int(rec["first_block"]), int(rec["end_block"]), int(rec["start_sample"]), int(rec["end_sample"]),
                         int(rec["offset"]), own, prev, nxt, peaks, mean, std, int(rec["n_lags"]), psr, margin, gain_prev,
                         gain_next, flags)
@@ -152,7 +141,7 @@ def split_report_batch(batch, max_offset_samples: int, block_samples: int = DEFA
                                report=(int(top_k), int(exclusion_samples)))
     if raw:
         return res, recs, counts
-    return [SplitReport(r, [from_record(x) for x in recs[p, :int(counts[p])]]) for p, r in enumerate(res)]
+    return [SplitReport(r, q) for r, q in zip(res, record_lists(recs, counts, from_record))]
 
 
 def checked_split_sync(problems, max_offset_seconds: float = 600, block_samples: int = DEFAULT_BLOCK_SAMPLES,
