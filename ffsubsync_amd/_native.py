@@ -137,6 +137,18 @@ RETIME_SUMMARY_DTYPE = np.dtype(
 )
 RETIME_SUMMARY_BYTES = 40
 assert RETIME_SUMMARY_DTYPE.itemsize == RETIME_SUMMARY_BYTES
+# ffs_sweep_profile (include/ffsubsync_amd.h; static size 232 bytes)
+SWEEP_MAX_PEAKS = 8
+SWEEP_FLAT = 1  # FFS_SWEEP_FLAT: every point not skipped scores the same, or none is left (std = 0)
+SWEEP_EMPTY = 2  # FFS_SWEEP_EMPTY: no point left after skipping
+SWEEP_AMBIGUOUS = 4  # FFS_SWEEP_AMBIGUOUS: some point carried FFS_FLAG_AMBIGUOUS
+SWEEP_PROFILE_DTYPE = np.dtype(
+    [("peak_score", "<f8", (SWEEP_MAX_PEAKS,)), ("peak_offset", "<i8", (SWEEP_MAX_PEAKS,)),
+     ("peak_index", "<i8", (SWEEP_MAX_PEAKS,)), ("mean", "<f8"), ("std", "<f8"), ("n_points", "<i8"), ("n_skipped", "<i8"),
+     ("n_peaks", "<i4"), ("flags", "<i4")], align=True
+)
+SWEEP_PROFILE_BYTES = 232
+assert SWEEP_PROFILE_DTYPE.itemsize == SWEEP_PROFILE_BYTES
 
 # every symbol include/ffsubsync_amd.h declares (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = (
@@ -210,6 +222,7 @@ EXPORTED_SYMBOLS = (
     "ffs_match_plan_destroy",
     "ffs_match_plan_workspace_bytes",
     "ffs_match_quality_batch",
+    "ffs_sweep_peaks",
     "ffs_last_error",
     "ffs_version",
 )
@@ -495,6 +508,8 @@ def load():
                                                 c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int,
                                                 c.c_void_p, c.c_void_p, c.c_int64, c.c_int, c.c_int64, c.c_int,
                                                 c.c_void_p, c.c_void_p]
+        lib.ffs_sweep_peaks.restype = c.c_int
+        lib.ffs_sweep_peaks.argtypes = [c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_int64, c.c_void_p, c.c_void_p]
         lib.ffs_last_error.restype = c.c_char_p
         lib.ffs_last_error.argtypes = []
         lib.ffs_version.restype = c.c_int
@@ -791,6 +806,23 @@ def speech_bounds(frames):
                                    current_stream_ptr(torch)))
     lo, hi = (int(v) for v in out.cpu())
     return (None, None) if hi < 0 else (lo, hi)
+
+
+def sweep_peaks(records, first, n_files: int, top_k: int, exclusion_steps: int, out=None):
+    """``ffs_sweep_peaks`` on the current stream: ``records`` a CUDA tensor of ffs_cand_result records (24 bytes each),
+    ``first`` an int64 CUDA tensor of n_files + 1 ascending point indices; returns the uint8 CUDA tensor of n_files
+    ``SWEEP_PROFILE_DTYPE`` records (``out``, if given, is written in place)."""
+    torch = require_gpu()
+    n_files = int(n_files)
+    if first.dtype != torch.int64 or first.numel() < n_files + 1 or not first.is_contiguous():
+        raise ValueError("first must be a contiguous int64 tensor of n_files + 1 entries")
+    if out is None:
+        out = torch.empty(max(n_files, 1) * SWEEP_PROFILE_BYTES, dtype=torch.uint8, device=first.device)
+    elif _nbytes(out) < n_files * SWEEP_PROFILE_BYTES:
+        raise ValueError("output buffer too small")
+    check(load().ffs_sweep_peaks(records.data_ptr(), first.data_ptr(), n_files, int(top_k), int(exclusion_steps),
+                                 out.data_ptr(), current_stream_ptr(torch)))
+    return out
 
 
 def _us_arrays(start_us, end_us, is_metadata):

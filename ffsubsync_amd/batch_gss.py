@@ -80,87 +80,25 @@ def fit_gss_batch(refs: Sequence, subtitle_records: Sequence[Tuple[np.ndarray, n
     path (``_fit_gss_batch_per_file``).  ``stats``, if given, receives {"steps", "files", "plan_length", "lists"}."""
     from . import _native
     from .aligners import _Vec
-    from .batch import TrackSet
 
     n = len(refs)
     ref_vecs = [_Vec(r) for r in refs]
     if n == 0 or not all(v.two_level and len(v) > 0 for v in ref_vecs) or any(len(t[0]) == 0 for t in subtitle_records):
         return _fit_gss_batch_per_file(refs, subtitle_records, max_offset_samples, sample_rate, start_seconds)
-    torch = _native.require_gpu()
-    # references: bit-packed, one buffer, uploaded once
-    words = [None if v.raster is not None else (v.packed if v.packed is not None else np.packbits(v.bits, bitorder="little"))
-             for v in ref_vecs]
-    offs = np.zeros(n, dtype=np.int64)
-    total = 0
-    for i, wv in enumerate(words):
-        if wv is not None:
-            offs[i] = total
-            total += (wv.size + 63) // 64 * 64
-    host = np.zeros(max(total, 64), dtype=np.uint8)
-    for wv, o in zip(words, offs):
-        if wv is not None:
-            host[o:o + wv.size] = wv
-    ref_dev = torch.from_numpy(host).cuda()
-    keep = [v.raster.packed_words() if v.raster is not None else None for v in ref_vecs]  # HBM-resident references, in place
-    ref_ptr = np.array([k.data_ptr() if k is not None else ref_dev.data_ptr() + int(o) for k, o in zip(keep, offs)], dtype=np.uint64)
-    ref_len = np.array([len(v) for v in ref_vecs], dtype=np.int64)
-    tracks = TrackSet(list(subtitle_records))
-    # one plan for the whole search: long enough for the longest candidate (ratio 1.1)
-    longest = _native.raster_lengths(tracks.end_max, np.full(n, MAX_FRAMERATE_RATIO), sample_rate)
-    n_fft = max(_native.plan_length(int(r), int(s), max_offset_samples) for r, s in zip(ref_len, longest))
-    if n_fft > _native.MAX_FFT_LENGTH:
-        raise ValueError("inputs too long for the device transform (N=%d > 2^24)" % n_fft)
-    plan = _native.get_plan(n_fft, pairs_in_flight=min(max(n, 1), 512), max_cand=8)
-    cand_out = torch.empty(n * 24, dtype=torch.uint8, device="cuda")
-    pair_out = torch.empty(n * 24, dtype=torch.uint8, device="cuda")
-    lo = np.zeros(2 * n, dtype=np.float64)
-    hi = np.ones(2 * n, dtype=np.float64)
-    lo[0::2] = [v.lo for v in ref_vecs]
-    hi[0::2] = [v.hi for v in ref_vecs]
-    ptrs = np.zeros(2 * n, dtype=np.uint64)
-    lens = np.zeros(2 * n, dtype=np.int64)
-    ptrs[0::2], lens[0::2] = ref_ptr, ref_len
+    solver = PreparedRatioSolve(ref_vecs, subtitle_records, max_offset_samples, sample_rate, start_seconds,
+                                MAX_FRAMERATE_RATIO, max_vectors=n)
+    cand_out = solver.torch.empty(n * 24, dtype=solver.torch.uint8, device="cuda")
     recorded = [None] * n
     which = np.arange(n)
     steps = [0]
-    # boundary lists on both sides when the rasteriser may write them (start_seconds <= 0) and every reference fits one
-    use_lists = start_seconds <= 0
-    ref_lists = None
-    bounds = np.zeros(2 * n, dtype=np.int32)
-    if use_lists:
-        cap = 32768
-        block = (_native.runs_list_bytes(cap) + 63) // 64 * 64
-        ref_lists = torch.empty(n * block, dtype=torch.uint8, device="cuda")
-        list_ptr = ref_lists.data_ptr() + (np.arange(n, dtype=np.uint64) * np.uint64(block))
-        _native.runs_from_bits_batch(ref_ptr, ref_len, list_ptr, np.full(n, cap, dtype=np.int64))
-        n_ref = ref_lists.view(torch.int32).reshape(n, block // 4)[:, 0].cpu().numpy()  # (one small read-back per search)
-        if (n_ref >= cap).any():
-            use_lists, ref_lists = False, None
-        else:
-            tracks.to_device()
-            ptrs[0::2] = list_ptr
-            bounds[0::2] = np.maximum(n_ref, 2)
-    dtypes = (_native.FFS_DTYPE_RUNS, _native.FFS_DTYPE_RUNS) if use_lists else _native.FFS_DTYPE_U1
-
     timers = stats.setdefault("timers_us", {"rasterize": 0.0, "solve": 0.0, "read_back": 0.0}) if stats is not None and stats.get("time_steps") else None
     import time as _time
 
     def evaluate(ratios, is_last):
-        t0 = _time.perf_counter()
-        if use_lists:
-            data, c_offs, c_lens, c_bounds = tracks.rasterize_runs(which, ratios, sample_rate, start_seconds)
-            bounds[1::2] = c_bounds
-        else:
-            data, c_offs, c_lens = tracks.rasterize(which, ratios, sample_rate, start_seconds)
-        ptrs[1::2] = data.data_ptr() + c_offs.astype(np.uint64)
-        lens[1::2] = c_lens
-        hi[1::2] = np.minimum(1.0 / np.asarray(ratios, dtype=np.float64), 1.0)  # speech_transformers.py:977
-        t1 = _time.perf_counter()
-        plan.align_batch(n, 1, dtypes, ptrs, lens, lo, hi, max_offset_samples, None, cand_out, pair_out,
-                         vec_max_boundaries=bounds if use_lists else None)
-        t2 = _time.perf_counter()
+        solver.evaluate(which, ratios, cand_out)
         cres = cand_out.cpu().numpy().view(_native.CAND_RESULT_DTYPE)[:n]
         if timers is not None:
+            t0, t1, t2 = solver.last_times
             t3 = _time.perf_counter()
             timers["rasterize"] += 1e6 * (t1 - t0)
             timers["solve"] += 1e6 * (t2 - t1)
@@ -178,9 +116,119 @@ def fit_gss_batch(refs: Sequence, subtitle_records: Sequence[Tuple[np.ndarray, n
     except _Ambiguous:
         return _fit_gss_batch_per_file(refs, subtitle_records, max_offset_samples, sample_rate, start_seconds)
     if stats is not None:
-        stats.update({"steps": steps[0], "files": n, "plan_length": int(n_fft), "lists": bool(use_lists)})
-    del ref_dev, keep, ref_lists
+        stats.update({"steps": steps[0], "files": n, "plan_length": int(solver.n_fft), "lists": bool(solver.use_lists)})
+    del solver
     return recorded
+
+
+class PreparedRatioSolve:
+    """The state that many single-ratio solves of the same files share, prepared once: the references bit-packed in one
+    buffer (or in place, when they are HBM-resident), converted to boundary lists once when the rasteriser may write
+    lists (``start_seconds <= 0``) and every reference fits one, the subtitle tables uploaded once
+    (``TrackSet.to_device``), and one plan long enough for every track at ``longest_ratio``.  ``evaluate`` then solves
+    any selection of vectors v = (file ``which[v]``, ``ratios[v]``) with ONE rasteriser call and ONE
+    ``align_batch(n_vec, 1, ...)``.  ``fit_gss_batch`` asks for one ratio per file and step, ``ratio_sweep`` for a grid
+    of ratios per file.  ``ref_vecs``: ``aligners._Vec`` of two-level, non-empty references."""
+
+    LIST_CAP = 32768  # entries of a reference's boundary list; a denser reference sends every solve through the bit rasters
+
+    def __init__(self, ref_vecs, subtitle_records, max_offset_samples, sample_rate: int, start_seconds: float,
+                 longest_ratio: float, max_vectors: int, max_cand: int = 8) -> None:
+        from . import _native
+        from .batch import TrackSet
+
+        self.torch = torch = _native.require_gpu()
+        n = self.n = len(ref_vecs)
+        self.max_offset_samples, self.sample_rate, self.start_seconds = max_offset_samples, sample_rate, start_seconds
+        # references: bit-packed, one buffer, uploaded once
+        words = [None if v.raster is not None else (v.packed if v.packed is not None else np.packbits(v.bits, bitorder="little"))
+                 for v in ref_vecs]
+        offs = np.zeros(n, dtype=np.int64)
+        total = 0
+        for i, wv in enumerate(words):
+            if wv is not None:
+                offs[i] = total
+                total += (wv.size + 63) // 64 * 64
+        host = np.zeros(max(total, 64), dtype=np.uint8)
+        for wv, o in zip(words, offs):
+            if wv is not None:
+                host[o:o + wv.size] = wv
+        self._ref_dev = torch.from_numpy(host).cuda()
+        self._keep = [v.raster.packed_words() if v.raster is not None else None for v in ref_vecs]  # HBM-resident references, in place
+        self.ref_ptr = np.array([k.data_ptr() if k is not None else self._ref_dev.data_ptr() + int(o)
+                                 for k, o in zip(self._keep, offs)], dtype=np.uint64)
+        self.ref_len = np.array([len(v) for v in ref_vecs], dtype=np.int64)
+        self.ref_lo = np.array([v.lo for v in ref_vecs], dtype=np.float64)
+        self.ref_hi = np.array([v.hi for v in ref_vecs], dtype=np.float64)
+        self.tracks = TrackSet(list(subtitle_records))
+        # one plan for every solve: long enough for the longest candidate
+        longest = _native.raster_lengths(self.tracks.end_max, np.full(n, float(longest_ratio)), sample_rate)
+        self.n_fft = max(_native.plan_length(int(r), int(s), max_offset_samples) for r, s in zip(self.ref_len, longest))
+        if self.n_fft > _native.MAX_FFT_LENGTH:
+            raise ValueError("inputs too long for the device transform (N=%d > 2^24)" % self.n_fft)
+        self.plan = _native.get_plan(self.n_fft, pairs_in_flight=min(max(int(max_vectors), 1), 512), max_cand=max_cand)
+        # boundary lists on both sides when the rasteriser may write them (start_seconds <= 0) and every reference fits one
+        self.use_lists = start_seconds <= 0
+        self._ref_lists = None
+        self.ref_bound = np.zeros(n, dtype=np.int32)
+        if self.use_lists:
+            cap = self.LIST_CAP
+            block = (_native.runs_list_bytes(cap) + 63) // 64 * 64
+            self._ref_lists = torch.empty(n * block, dtype=torch.uint8, device="cuda")
+            list_ptr = self._ref_lists.data_ptr() + (np.arange(n, dtype=np.uint64) * np.uint64(block))
+            _native.runs_from_bits_batch(self.ref_ptr, self.ref_len, list_ptr, np.full(n, cap, dtype=np.int64))
+            n_ref = self._ref_lists.view(torch.int32).reshape(n, block // 4)[:, 0].cpu().numpy()  # (one small read-back)
+            if (n_ref >= cap).any():
+                self.use_lists, self._ref_lists = False, None
+            else:
+                self.tracks.to_device()
+                self.ref_ptr = list_ptr
+                self.ref_bound = np.maximum(n_ref, 2).astype(np.int32)
+        self.dtypes = (_native.FFS_DTYPE_RUNS, _native.FFS_DTYPE_RUNS) if self.use_lists else _native.FFS_DTYPE_U1
+        self._pair_out = None
+        self.last_times = (0.0, 0.0, 0.0)
+
+    def vector_bytes(self, longest_ratio: float) -> int:
+        """Upper bound of the bytes one rasterised vector of the largest track takes in ``evaluate``'s buffer."""
+        if self.use_lists:
+            return int(16 + 8 * (2 * int(self.tracks.counts.max()) + 2) + 63)
+        from . import _native
+
+        longest = _native.raster_lengths(self.tracks.end_max, np.full(self.n, float(longest_ratio)), self.sample_rate)
+        return int((int(longest.max()) + 31) // 32 * 4 + 63)
+
+    def evaluate(self, which, ratios, cand_out):
+        """Queue the solves of the vectors v = (file ``which[v]``, ``ratios[v]``) on the current stream: their
+        ``ffs_cand_result`` records land in ``cand_out`` (a uint8 CUDA tensor of at least 24 bytes a vector), in order.
+        Nothing is read back.  ``last_times``: perf_counter before the rasteriser call, after it, after the solve call."""
+        import time as _time
+
+        which = np.asarray(which, dtype=np.int64).ravel()
+        ratios = np.ascontiguousarray(ratios, dtype=np.float64).ravel()
+        m = which.size
+        t0 = _time.perf_counter()
+        ptrs = np.zeros(2 * m, dtype=np.uint64)
+        lens = np.zeros(2 * m, dtype=np.int64)
+        lo = np.zeros(2 * m, dtype=np.float64)
+        hi = np.ones(2 * m, dtype=np.float64)
+        bounds = np.zeros(2 * m, dtype=np.int32)
+        ptrs[0::2], lens[0::2] = self.ref_ptr[which], self.ref_len[which]
+        lo[0::2], hi[0::2], bounds[0::2] = self.ref_lo[which], self.ref_hi[which], self.ref_bound[which]
+        if self.use_lists:
+            data, c_offs, c_lens, c_bounds = self.tracks.rasterize_runs(which, ratios, self.sample_rate, self.start_seconds)
+            bounds[1::2] = c_bounds
+        else:
+            data, c_offs, c_lens = self.tracks.rasterize(which, ratios, self.sample_rate, self.start_seconds)
+        ptrs[1::2] = data.data_ptr() + c_offs.astype(np.uint64)
+        lens[1::2] = c_lens
+        hi[1::2] = np.minimum(1.0 / ratios, 1.0)  # speech_transformers.py:977
+        if self._pair_out is None or self._pair_out.numel() < m * 24:
+            self._pair_out = self.torch.empty(max(m, 1) * 24, dtype=self.torch.uint8, device="cuda")
+        t1 = _time.perf_counter()
+        self.plan.align_batch(m, 1, self.dtypes, ptrs, lens, lo, hi, self.max_offset_samples, None, cand_out, self._pair_out,
+                              vec_max_boundaries=bounds if self.use_lists else None)
+        self.last_times = (t0, t1, _time.perf_counter())
+        return cand_out
 
 
 class _Ambiguous(Exception):

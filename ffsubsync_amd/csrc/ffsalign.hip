@@ -41,6 +41,7 @@
 #include "ffs_drift_range.h"
 #include "ffs_drift_range_smooth.h"
 #include "ffs_drift_range_report.h"
+#include "ffs_sweep.h"
 
 using namespace ffsa;
 
@@ -3093,6 +3094,28 @@ int ffs_speech_bounds(const float* frames_dev, int64_t n_frames, int64_t* bounds
                            (long long*)bounds_dev);
     }
     hipLaunchKernelGGL(k_bounds_fix, dim3(1), dim3(1), 0, st, (long long*)bounds_dev);
+    HIP_TRY(hipGetLastError());
+    return FFS_OK;
+}
+
+int ffs_sweep_peaks(const ffs_cand_result* rec_dev, const int64_t* first_dev, int n_files, int top_k,
+                    int64_t exclusion_steps, ffs_sweep_profile* out_dev, void* hip_stream) {
+    static_assert(sizeof(ffs_sweep_profile) == sizeof(SweepProfile) && sizeof(ffs_cand_result) == sizeof(CandResult),
+                  "device records must match the header's");
+    if (n_files < 0) return fail(FFS_E_INVALID, "ffs_sweep_peaks: n_files=%d is negative", n_files);
+    if (top_k < 1 || top_k > SWEEP_MAX_PEAKS)
+        return fail(FFS_E_INVALID, "ffs_sweep_peaks: top_k=%d outside [1, %d]", top_k, SWEEP_MAX_PEAKS);
+    if (exclusion_steps < 1)
+        return fail(FFS_E_INVALID, "ffs_sweep_peaks: exclusion_steps=%lld, need >= 1", (long long)exclusion_steps);
+    if (!rec_dev || !first_dev || !out_dev) return fail(FFS_E_INVALID, "ffs_sweep_peaks: null record, first or output pointer");
+    if (((uintptr_t)rec_dev | (uintptr_t)first_dev | (uintptr_t)out_dev) & 7)
+        return fail(FFS_E_INVALID, "ffs_sweep_peaks: misaligned record, first or output pointer (8 bytes)");
+    if (n_files == 0) return FFS_OK;
+    DeviceGuard guard;
+    int rc_dev;
+    if ((rc_dev = guard.enter(out_dev))) return rc_dev;
+    hipLaunchKernelGGL(k_sweep_peaks, dim3((unsigned)n_files), dim3(SWEEP_THREADS), 0, (hipStream_t)hip_stream,
+                       (const CandResult*)rec_dev, first_dev, top_k, exclusion_steps, (SweepProfile*)out_dev);
     HIP_TRY(hipGetLastError());
     return FFS_OK;
 }

@@ -1190,6 +1190,42 @@ int ffs_drift_range_report_batch(ffs_drift_range_plan* plan, int n_pairs, const 
                                  int top_k, int64_t exclusion_samples, ffs_segment_report* report_out_dev,
                                  int32_t* n_segments_out_dev, void* hip_stream);
 
+/* ---- ratio sweep: peaks and moments of ratio profiles (csrc/ffs_sweep.h) ---------------------------------------
+ * Replaces: nothing in the reference.  A ratio sweep (ffsubsync_amd/ratio_sweep.py) solves every file at a grid of speed
+ * factors with the batch solve above and keeps the ffs_cand_result records in HBM; this call reduces each file's
+ * profile to one record.  Stateless: no plan, everything is queued on hip_stream.  Pinned against tests/sweep_model.py.
+ *
+ * File f owns the points rec_dev[first_dev[f] .. first_dev[f+1]) (first_dev: n_files + 1 ascending int64 on the device;
+ * point index j = position in that range).  A point is SKIPPED when its score is not finite or its flags carry
+ * FFS_FLAG_EMPTY_WINDOW.  Peak 1 = the largest score among the points not skipped, the smaller index on ties; peak k+1 =
+ * the same over the indices j with |j - j_i| >= exclusion_steps for every earlier peak i; fewer than top_k (1..8) peaks
+ * when no point is eligible.  Moments: mean and population std (ddof = 0) over the points not skipped, two passes, in a
+ * fixed summation order; when all of them are equal, mean = that score and std = 0 exactly (FFS_SWEEP_FLAT).  No point
+ * left: mean = std = 0, no peak, FFS_SWEEP_FLAT | FFS_SWEEP_EMPTY.  FFS_SWEEP_AMBIGUOUS: some point of the file (skipped
+ * or not) carried FFS_FLAG_AMBIGUOUS.  Records are read, never written; exactly n_files output records are written.
+ * FFS_E_INVALID for top_k outside [1, 8], exclusion_steps < 1, n_files < 0, or a null or misaligned (8 bytes)
+ * pointer: refused before any launch, the outputs untouched. */
+#define FFS_SWEEP_FLAT 1      /* every point not skipped scores the same (or none is left): std = 0 */
+#define FFS_SWEEP_EMPTY 2     /* no point left after skipping */
+#define FFS_SWEEP_AMBIGUOUS 4 /* some point carried FFS_FLAG_AMBIGUOUS */
+
+typedef struct ffs_sweep_profile {
+    double peak_score[8];       /* peaks 0 .. n_peaks-1 (entries beyond: 0) */
+    int64_t peak_offset[8];     /* the peak record's offset (samples) */
+    int64_t peak_index[8];      /* the peak's point index inside the file */
+    double mean, std;           /* of the scores of the points not skipped */
+    int64_t n_points, n_skipped;
+    int32_t n_peaks, flags;     /* flags: FFS_SWEEP_* */
+} ffs_sweep_profile;
+#ifdef __cplusplus
+static_assert(sizeof(ffs_sweep_profile) == 232, "ffs_sweep_profile is 232 bytes");
+#else
+_Static_assert(sizeof(ffs_sweep_profile) == 232, "ffs_sweep_profile is 232 bytes");
+#endif
+
+int ffs_sweep_peaks(const ffs_cand_result* rec_dev, const int64_t* first_dev, int n_files, int top_k,
+                    int64_t exclusion_steps, ffs_sweep_profile* out_dev, void* hip_stream);
+
 /* Thread-local description of the last error returned on this thread ("" if none). */
 const char* ffs_last_error(void);
 
