@@ -149,6 +149,16 @@ SWEEP_PROFILE_DTYPE = np.dtype(
 )
 SWEEP_PROFILE_BYTES = 232
 assert SWEEP_PROFILE_DTYPE.itemsize == SWEEP_PROFILE_BYTES
+# ffs_prog_state (include/ffsubsync_amd.h; static size 64 bytes)
+PROG_STATE_DTYPE = np.dtype(
+    [("ref_len", "<i8"), ("offset", "<i8"), ("score", "<f8"), ("mean", "<f8"), ("std", "<f8"), ("runner_up", "<f8"),
+     ("other_best", "<f8"), ("best_cand", "<i4"), ("flags", "<i4")], align=True
+)
+PROG_STATE_BYTES = 64
+assert PROG_STATE_DTYPE.itemsize == PROG_STATE_BYTES
+PROG_MAX_CAND = 8  # PROG_MAX_CAND (csrc/ffs_progressive.h)
+PROG_MAX_LAGS = 262144  # 2W of a slot's lag window, at most
+PROG_PIECE_SAMPLES = 512 * 32  # PROG_PIECE words: the reference samples k_prog_counts stages at a time
 
 # every symbol include/ffsubsync_amd.h declares (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = (
@@ -223,6 +233,13 @@ EXPORTED_SYMBOLS = (
     "ffs_match_plan_workspace_bytes",
     "ffs_match_quality_batch",
     "ffs_sweep_peaks",
+    "ffs_prog_plan_create",
+    "ffs_prog_plan_destroy",
+    "ffs_prog_plan_workspace_bytes",
+    "ffs_prog_open",
+    "ffs_prog_append",
+    "ffs_prog_reference",
+    "ffs_prog_close",
     "ffs_last_error",
     "ffs_version",
 )
@@ -510,6 +527,21 @@ def load():
                                                 c.c_void_p, c.c_void_p]
         lib.ffs_sweep_peaks.restype = c.c_int
         lib.ffs_sweep_peaks.argtypes = [c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_int64, c.c_void_p, c.c_void_p]
+        lib.ffs_prog_plan_create.restype = c.c_int
+        lib.ffs_prog_plan_create.argtypes = [c.c_int, c.c_int, c.c_int, c.c_int64, c.c_int64, c.c_int64, c.POINTER(c.c_void_p)]
+        lib.ffs_prog_plan_destroy.restype = c.c_int
+        lib.ffs_prog_plan_destroy.argtypes = [c.c_void_p]
+        lib.ffs_prog_plan_workspace_bytes.restype = c.c_int64
+        lib.ffs_prog_plan_workspace_bytes.argtypes = [c.c_void_p]
+        lib.ffs_prog_open.restype = c.c_int
+        lib.ffs_prog_open.argtypes = [c.c_void_p, c.c_int] + [c.c_void_p] * 10
+        lib.ffs_prog_append.restype = c.c_int
+        lib.ffs_prog_append.argtypes = [c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int,
+                                        c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p]
+        lib.ffs_prog_reference.restype = c.c_int
+        lib.ffs_prog_reference.argtypes = [c.c_void_p, c.c_int, c.POINTER(c.c_void_p), c.POINTER(c.c_int64)]
+        lib.ffs_prog_close.restype = c.c_int
+        lib.ffs_prog_close.argtypes = [c.c_void_p, c.c_int, c.c_void_p]
         lib.ffs_last_error.restype = c.c_char_p
         lib.ffs_last_error.argtypes = []
         lib.ffs_version.restype = c.c_int
@@ -1457,6 +1489,55 @@ class MatchPlan(_SidePlan):
                                                *[b.ctypes.data for b in stb], pr.size, pr.ctypes.data, ps.ctypes.data, mo,
                                                int(top_k), int(exclusion_samples), match_algorithm_code(algorithm),
                                                out.data_ptr(), self._stream(stream)))
+
+
+class ProgPlan(_SidePlan):
+    """Owns one ``ffs_prog_plan``: ``max_slots`` files of a progressive solve (``progressive.py``), each a growing
+    reference prefix of up to ``max_ref_samples`` against up to ``max_cand`` candidates of up to ``max_sub_samples``
+    over up to ``max_lags`` lags.  Every call is queued on the stream; the host arrays are copied before it returns."""
+
+    _create, _destroy, _workspace = "ffs_prog_plan_create", "ffs_prog_plan_destroy", "ffs_prog_plan_workspace_bytes"
+
+    _limits = ("max_slots", "max_cand", "max_lags", "max_ref_samples", "max_sub_samples")
+
+    def __init__(self, max_slots: int, max_cand: int, max_lags: int, max_ref_samples: int, max_sub_samples: int,
+                 device: Optional[int] = None) -> None:
+        super().__init__((max_slots, max_cand, max_lags, max_ref_samples, max_sub_samples), device)
+
+    def open(self, slot, n_cand, sub_ptr, sub_len, sub_lo, sub_hi, ref_lo, ref_hi, max_offset_samples,
+             stream: Optional[int] = None) -> None:
+        """``ffs_prog_open``: one entry per slot, and [n, max_cand] candidate tables (rows padded with anything)."""
+        kinds = (np.int32, np.int32, np.uint64, np.int64, np.float64, np.float64, np.float64, np.float64, np.int64)
+        bufs = [np.ascontiguousarray(a, dtype=t) for a, t in zip(
+            (slot, n_cand, sub_ptr, sub_len, sub_lo, sub_hi, ref_lo, ref_hi, max_offset_samples), kinds)]
+        n = bufs[0].size
+        if not all(b.size == (n * self.max_cand if 2 <= i <= 5 else n) for i, b in enumerate(bufs)):
+            raise ValueError("one entry per slot, max_cand candidate entries per slot")
+        check(self.lib.ffs_prog_open(self.handle, n, *[b.ctypes.data for b in bufs], self._stream(stream)))
+
+    def append(self, slot, chunk_ptr, first_bit, n_new, top_k: int, exclusion_samples: int, cand_out, state_out,
+               stream: Optional[int] = None) -> None:
+        """``ffs_prog_append`` into uint8 CUDA tensors of n * max_cand * 160 and n * 64 bytes (asynchronous)."""
+        kinds = (np.int32, np.uint64, np.int32, np.int64)
+        bufs = [np.ascontiguousarray(a, dtype=t) for a, t in zip((slot, chunk_ptr, first_bit, n_new), kinds)]
+        n = bufs[0].size
+        if not all(b.size == n for b in bufs):
+            raise ValueError("one entry per slot")
+        if _nbytes(cand_out) < n * self.max_cand * QUALITY_RESULT_BYTES or _nbytes(state_out) < n * PROG_STATE_BYTES:
+            raise ValueError("output buffer too small")
+        check(self.lib.ffs_prog_append(self.handle, n, *[b.ctypes.data for b in bufs], int(top_k), int(exclusion_samples),
+                                       cand_out.data_ptr(), state_out.data_ptr(), self._stream(stream)))
+
+    def reference(self, slot: int) -> Tuple[int, int]:
+        """``ffs_prog_reference``: (device address of the plan's bits of the consumed prefix, its length)."""
+        ptr, length = ctypes.c_void_p(), ctypes.c_int64()
+        check(self.lib.ffs_prog_reference(self.handle, int(slot), ctypes.byref(ptr), ctypes.byref(length)))
+        return int(ptr.value), int(length.value)
+
+    def close_slots(self, slot) -> None:
+        """``ffs_prog_close``."""
+        buf = np.ascontiguousarray(slot, dtype=np.int32)
+        check(self.lib.ffs_prog_close(self.handle, buf.size, buf.ctypes.data))
 
 
 class SidePlanCache:

@@ -42,6 +42,7 @@
 #include "ffs_drift_range_smooth.h"
 #include "ffs_drift_range_report.h"
 #include "ffs_sweep.h"
+#include "ffs_progressive.h"
 
 using namespace ffsa;
 
@@ -5098,6 +5099,277 @@ int ffs_match_quality_batch(ffs_match_plan* plan, int n_ref, const void* const* 
         HIP_TRY(hipGetLastError());
     }
     return plan->end(st);
+}
+
+/* ---- progressive alignment: the report of a growing reference prefix (csrc/ffs_progressive.h) -------------------- */
+
+namespace {
+struct ProgSlot {  // what the host knows of a slot: every refusal is decided from this, before any launch
+    bool open = false;
+    int n_cand = 0;
+    int64_t W = 0, L = 0;
+    int64_t S[ffsa::PROG_MAX_CAND];
+    double s0[ffsa::PROG_MAX_CAND], s1[ffsa::PROG_MAX_CAND], r0, r1;  // mapped levels
+};
+}  // namespace
+
+struct ffs_prog_plan : PlanCore {
+    int max_slots, max_cand;
+    int64_t max_lags, max_ref, max_sub;
+    int64_t lpad, rw, sw;       // padded curve row, words (and prefix entries) per reference and per candidate
+    uint32_t* ref;              // [slot][rw]
+    int32_t* pre_r;             // [slot][rw]
+    uint32_t* sub;              // [slot][cand][sw]
+    int32_t* pre_s;             // [slot][cand][sw]
+    uint32_t* curve;            // [slot][cand][lpad]
+    double* sc;                 // [slot][cand][lpad]
+    std::vector<ProgSlot> slots;
+    std::vector<char> named;    // per slot: named by the call being checked
+                                // desc: ProgOpenDesc[max_slots * max_cand] at open; at append ProgSlotDesc[max_slots],
+                                // then QualDesc[max_slots * max_cand]
+
+    void carve(Carver& c) {
+        const int64_t n = max_slots, nc = (int64_t)max_slots * max_cand;
+        sc = c.take<double>(nc * lpad);
+        curve = c.take<uint32_t>(nc * lpad);
+        ref = c.take<uint32_t>(n * rw);
+        pre_r = c.take<int32_t>(n * rw);
+        sub = c.take<uint32_t>(nc * sw);
+        pre_s = c.take<int32_t>(nc * sw);
+    }
+
+    // the slot list of a call: every slot in range and named once; `want_open`: and open
+    int check_slots(const char* call, int n, const int32_t* slot, bool want_open) {
+        std::fill(named.begin(), named.end(), 0);
+        for (int i = 0; i < n; ++i) {
+            const int s = slot[i];
+            if (s < 0 || s >= max_slots) return fail(FFS_E_INVALID, "%s: slot %d outside [0, %d)", call, s, max_slots);
+            if (named[s]) return fail(FFS_E_INVALID, "%s: slot %d named twice", call, s);
+            named[s] = 1;
+            if (want_open && !slots[s].open) return fail(FFS_E_INVALID, "%s: slot %d is not open", call, s);
+        }
+        return FFS_OK;
+    }
+};
+
+int ffs_prog_plan_create(int device, int max_slots, int max_cand, int64_t max_lags, int64_t max_ref_samples,
+                         int64_t max_sub_samples, ffs_prog_plan** out) {
+    if (!out) return fail(FFS_E_INVALID, "null output handle");
+    *out = nullptr;
+    if (max_slots < 1 || max_slots > 65536 || max_cand < 1 || max_cand > ffsa::PROG_MAX_CAND || max_lags < 2 ||
+        max_lags > 262144 || max_ref_samples < 1 || max_ref_samples >= (int64_t(1) << 30) || max_sub_samples < 1 ||
+        max_sub_samples >= (int64_t(1) << 30))
+        return fail(FFS_E_INVALID, "progressive plan: need 1 <= max_slots <= 65536, 1 <= max_cand <= 8, 2 <= max_lags <= "
+                                   "262144, 1 <= max_ref_samples, max_sub_samples < 2^30");
+    HIP_TRY(hipSetDevice(device));
+    ffs_prog_plan* p = new (std::nothrow) ffs_prog_plan();
+    if (!p) return fail(FFS_E_NOMEM, "progressive plan");
+    p->max_slots = max_slots;
+    p->max_cand = max_cand;
+    p->max_lags = max_lags;
+    p->max_ref = max_ref_samples;
+    p->max_sub = max_sub_samples;
+    p->lpad = split_align_up(max_lags, 64);
+    p->rw = split_align_up(max_ref_samples / 32 + 2, 16);
+    p->sw = split_align_up(max_sub_samples / 32 + 2, 16);
+    p->slots.resize(max_slots);
+    p->named.resize(max_slots);
+    Carver size{nullptr};
+    p->carve(size);
+    if (int rc = p->open(device, max_slots, size.used, "progressive plan")) {
+        ffs_prog_plan_destroy(p);
+        return rc;
+    }
+    Carver place{(char*)p->work};
+    p->carve(place);
+    const size_t nc = (size_t)max_slots * max_cand;
+    const size_t desc_bytes = std::max(sizeof(ffsa::ProgOpenDesc) * nc,
+                                       sizeof(ffsa::ProgSlotDesc) * (size_t)max_slots + sizeof(ffsa::QualDesc) * nc);
+    if (p->desc.create(desc_bytes) != FFS_OK) {
+        ffs_prog_plan_destroy(p);
+        return fail(FFS_E_HIP, "progressive plan: descriptor buffers / events");
+    }
+    *out = p;
+    return FFS_OK;
+}
+
+int ffs_prog_plan_destroy(ffs_prog_plan* plan) {
+    if (!plan) return FFS_OK;
+    plan->close();
+    delete plan;
+    return FFS_OK;
+}
+
+int64_t ffs_prog_plan_workspace_bytes(const ffs_prog_plan* plan) { return plan ? plan->workspace_bytes() : 0; }
+
+int ffs_prog_open(ffs_prog_plan* plan, int n, const int32_t* slot, const int32_t* n_cand, const void* const* sub_ptr,
+                  const int64_t* sub_len, const double* sub_lo, const double* sub_hi, const double* ref_lo,
+                  const double* ref_hi, const int64_t* max_offset_samples, void* hip_stream) {
+    if (int rc = check_call(plan, "progressive", n,
+                            !slot || !n_cand || !sub_ptr || !sub_len || !sub_lo || !sub_hi || !ref_lo || !ref_hi ||
+                                !max_offset_samples);
+        rc != CALL_GO_ON)
+        return rc;
+    if (n > plan->max_slots) return fail(FFS_E_INVALID, "ffs_prog_open: %d slots exceed the plan's max_slots %d", n, plan->max_slots);
+    if (int rc = plan->check_slots("ffs_prog_open", n, slot, false)) return rc;
+    const int mc = plan->max_cand;
+    for (int i = 0; i < n; ++i) {
+        if (n_cand[i] < 1 || n_cand[i] > mc)
+            return fail(FFS_E_INVALID, "ffs_prog_open: slot %d: n_cand=%d outside [1, %d]", slot[i], n_cand[i], mc);
+        if (int rc = check_window(max_offset_samples[i], plan->max_lags)) return rc;
+        if (!(std::isfinite(ref_lo[i]) && std::isfinite(ref_hi[i])))
+            return fail(FFS_E_INVALID, "ffs_prog_open: slot %d: levels must be finite", slot[i]);
+        for (int c = 0; c < n_cand[i]; ++c) {
+            const int64_t k = (int64_t)i * mc + c;
+            if (!sub_ptr[k] || ((uintptr_t)sub_ptr[k] & 3))
+                return fail(FFS_E_INVALID, "ffs_prog_open: slot %d candidate %d: null or misaligned vector", slot[i], c);
+            if (sub_len[k] < 1 || sub_len[k] > plan->max_sub)
+                return fail(FFS_E_INVALID, "ffs_prog_open: slot %d candidate %d: length %lld outside [1, max_sub_samples %lld]",
+                            slot[i], c, (long long)sub_len[k], (long long)plan->max_sub);
+            if (!(std::isfinite(sub_lo[k]) && std::isfinite(sub_hi[k])))
+                return fail(FFS_E_INVALID, "ffs_prog_open: slot %d candidate %d: levels must be finite", slot[i], c);
+        }
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (int rc = plan->begin(st)) return rc;
+    if (int rc = plan->desc.wait_free()) return rc;
+    ffsa::ProgOpenDesc* hd = (ffsa::ProgOpenDesc*)plan->desc.host;
+    int nd = 0;
+    for (int i = 0; i < n; ++i) {
+        ProgSlot& ps = plan->slots[slot[i]];
+        ps.open = true;
+        ps.n_cand = n_cand[i];
+        ps.W = max_offset_samples[i];
+        ps.L = 0;
+        ps.r0 = mapped(ref_lo[i]);
+        ps.r1 = mapped(ref_hi[i]);
+        for (int c = 0; c < n_cand[i]; ++c) {
+            const int64_t k = (int64_t)i * mc + c, at = (int64_t)slot[i] * mc + c;
+            ps.S[c] = sub_len[k];
+            ps.s0[c] = mapped(sub_lo[k]);
+            ps.s1[c] = mapped(sub_hi[k]);
+            ffsa::ProgOpenDesc& d = hd[nd++];
+            d.src = (const uint32_t*)sub_ptr[k];
+            d.s = plan->sub + at * plan->sw;
+            d.pre_s = plan->pre_s + at * plan->sw;
+            d.curve = plan->curve + at * plan->lpad;
+            d.r = c == 0 ? plan->ref + (int64_t)slot[i] * plan->rw : nullptr;
+            d.pre_r = c == 0 ? plan->pre_r + (int64_t)slot[i] * plan->rw : nullptr;
+            d.S = sub_len[k];
+            d.lpad = plan->lpad;
+            d.r_words = plan->rw;
+        }
+    }
+    if (int rc = plan->desc.upload(sizeof(ffsa::ProgOpenDesc) * nd, st)) return rc;
+    hipLaunchKernelGGL(ffsa::k_prog_open, dim3((unsigned)nd), dim3(ffsa::PROG_THREADS), 0, st,
+                       (const ffsa::ProgOpenDesc*)plan->desc.dev);
+    HIP_TRY(hipGetLastError());
+    return plan->end(st);
+}
+
+int ffs_prog_append(ffs_prog_plan* plan, int n, const int32_t* slot, const void* const* chunk_dev, const int32_t* first_bit,
+                    const int64_t* n_new, int top_k, int64_t exclusion_samples, ffs_quality_result* cand_out_dev,
+                    ffs_prog_state* state_out_dev, void* hip_stream) {
+    static_assert(sizeof(ffs_prog_state) == sizeof(ffsa::ProgState), "device records must match the header's");
+    if (int rc = check_call(plan, "progressive", n, !slot || !chunk_dev || !first_bit || !n_new || !cand_out_dev || !state_out_dev);
+        rc != CALL_GO_ON)
+        return rc;
+    if (int rc = check_peaks(top_k, exclusion_samples)) return rc;
+    if (((uintptr_t)cand_out_dev | (uintptr_t)state_out_dev) & 7) return fail(FFS_E_INVALID, "misaligned output records");
+    if (n > plan->max_slots) return fail(FFS_E_INVALID, "ffs_prog_append: %d slots exceed the plan's max_slots %d", n, plan->max_slots);
+    if (int rc = plan->check_slots("ffs_prog_append", n, slot, true)) return rc;
+    for (int i = 0; i < n; ++i) {
+        const ProgSlot& ps = plan->slots[slot[i]];
+        if (!chunk_dev[i] || ((uintptr_t)chunk_dev[i] & 3))
+            return fail(FFS_E_INVALID, "ffs_prog_append: slot %d: null or misaligned chunk", slot[i]);
+        if (first_bit[i] < 0 || first_bit[i] > 31)
+            return fail(FFS_E_INVALID, "ffs_prog_append: slot %d: first_bit=%d outside [0, 32)", slot[i], first_bit[i]);
+        if (n_new[i] < 0) return fail(FFS_E_INVALID, "ffs_prog_append: slot %d: n_new=%lld is negative", slot[i], (long long)n_new[i]);
+        if (n_new[i] > plan->max_ref - ps.L)
+            return fail(FFS_E_INVALID, "ffs_prog_append: slot %d: %lld + %lld samples exceed the plan's max_ref_samples %lld",
+                        slot[i], (long long)ps.L, (long long)n_new[i], (long long)plan->max_ref);
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (int rc = plan->begin(st)) return rc;
+    if (int rc = plan->desc.wait_free()) return rc;
+    const int mc = plan->max_cand;
+    ffsa::ProgSlotDesc* hs = (ffsa::ProgSlotDesc*)plan->desc.host;
+    ffsa::QualDesc* hq = (ffsa::QualDesc*)(hs + plan->max_slots);
+    const ffsa::ProgSlotDesc* ds = (const ffsa::ProgSlotDesc*)plan->desc.dev;
+    const ffsa::QualDesc* dq = (const ffsa::QualDesc*)(ds + plan->max_slots);
+    int nq = 0;
+    int64_t max_w = 0;
+    for (int i = 0; i < n; ++i) {
+        ProgSlot& ps = plan->slots[slot[i]];
+        ffsa::ProgSlotDesc& s = hs[i];
+        memset(&s, 0, sizeof s);
+        s.chunk = (const uint32_t*)chunk_dev[i];
+        s.r = plan->ref + (int64_t)slot[i] * plan->rw;
+        s.pre_r = plan->pre_r + (int64_t)slot[i] * plan->rw;
+        s.L = ps.L;
+        s.n_new = n_new[i];
+        s.W = ps.W;
+        s.first_bit = first_bit[i];
+        s.n_cand = ps.n_cand;
+        s.desc0 = nq;
+        ps.L += n_new[i];
+        max_w = std::max(max_w, ps.W);
+        for (int c = 0; c < ps.n_cand; ++c) {
+            const int64_t at = (int64_t)slot[i] * mc + c;
+            ffsa::QualDesc& q = hq[nq++];
+            memset(&q, 0, sizeof q);
+            q.r = s.r;
+            q.s = plan->sub + at * plan->sw;
+            q.R = ps.L;
+            q.S = ps.S[c];
+            q.d_lo = -ps.W + 1;
+            q.n_lags = 2 * ps.W;
+            const int64_t clo = std::max(q.d_lo, 1 - q.S), chi = std::min(ps.W, q.R - 1);
+            q.c_lo = clo;
+            q.n_count = chi >= clo ? chi - clo + 1 : 0;
+            q.cd.R = (int32_t)q.R;
+            q.cd.S = (int32_t)q.S;
+            q.cd.s0 = ps.s0[c];
+            q.cd.s1 = ps.s1[c];
+            q.cd.r0 = ps.r0;
+            q.cd.r1 = ps.r1;
+            q.pre_r = s.pre_r;
+            q.pre_s = plan->pre_s + at * plan->sw;
+            q.curve = plan->curve + at * plan->lpad;
+            q.sc = plan->sc + at * plan->lpad;
+            q.out_row = (int64_t)i * mc + c;
+        }
+    }
+    // one upload of both arrays (the QualDesc half is at a fixed offset: copy the whole used span)
+    if (int rc = plan->desc.upload(sizeof(ffsa::ProgSlotDesc) * plan->max_slots + sizeof(ffsa::QualDesc) * nq, st)) return rc;
+    const int n_tiles = (int)((2 * max_w + ffsa::PROG_TILE - 1) / ffsa::PROG_TILE);
+    hipLaunchKernelGGL(ffsa::k_prog_ingest, dim3((unsigned)n), dim3(ffsa::PROG_THREADS), 0, st, ds);
+    hipLaunchKernelGGL(ffsa::k_prog_counts, dim3((unsigned)((int64_t)n * mc * n_tiles)), dim3(ffsa::PROG_CNT_THREADS), 0, st, ds,
+                       dq, n_tiles, mc);
+    hipLaunchKernelGGL(ffsa::k_quality_peaks, dim3((unsigned)nq), dim3(ffsa::QUAL_PEAK_THREADS), 0, st, dq, top_k,
+                       exclusion_samples, (ffsa::QualResult*)cand_out_dev);
+    hipLaunchKernelGGL(ffsa::k_prog_pick, dim3((unsigned)n), dim3(ffsa::PROG_PICK_THREADS), 0, st, ds, mc,
+                       (ffsa::QualResult*)cand_out_dev, (ffsa::ProgState*)state_out_dev);
+    HIP_TRY(hipGetLastError());
+    return plan->end(st);
+}
+
+int ffs_prog_reference(ffs_prog_plan* plan, int slot, const uint32_t** bits_dev, int64_t* len) {
+    if (!plan) return fail(FFS_E_INVALID, "null progressive plan");
+    if (!bits_dev || !len) return fail(FFS_E_INVALID, "null argument");
+    if (slot < 0 || slot >= plan->max_slots) return fail(FFS_E_INVALID, "ffs_prog_reference: slot %d outside [0, %d)", slot, plan->max_slots);
+    if (!plan->slots[slot].open) return fail(FFS_E_INVALID, "ffs_prog_reference: slot %d is not open", slot);
+    *bits_dev = plan->ref + (int64_t)slot * plan->rw;
+    *len = plan->slots[slot].L;
+    return FFS_OK;
+}
+
+int ffs_prog_close(ffs_prog_plan* plan, int n, const int32_t* slot) {
+    if (int rc = check_call(plan, "progressive", n, !slot); rc != CALL_GO_ON) return rc;
+    if (n > plan->max_slots) return fail(FFS_E_INVALID, "ffs_prog_close: %d slots exceed the plan's max_slots %d", n, plan->max_slots);
+    if (int rc = plan->check_slots("ffs_prog_close", n, slot, true)) return rc;
+    for (int i = 0; i < n; ++i) plan->slots[slot[i]].open = false;
+    return FFS_OK;
 }
 
 }  // extern "C"

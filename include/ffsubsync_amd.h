@@ -1226,6 +1226,72 @@ _Static_assert(sizeof(ffs_sweep_profile) == 232, "ffs_sweep_profile is 232 bytes
 int ffs_sweep_peaks(const ffs_cand_result* rec_dev, const int64_t* first_dev, int n_files, int top_k,
                     int64_t exclusion_steps, ffs_sweep_profile* out_dev, void* hip_stream);
 
+/* ---- progressive alignment: the quality report of a growing reference prefix (csrc/ffs_progressive.h) -----------
+ * Replaces: nothing in the reference (its --multi-segment-sync, speech_transformers.py:760-903, samples eight minutes
+ * and hopes they suffice).  Score counts are additive over the reference, so after every appended chunk of reference
+ * samples the exact report of the prefix read so far costs one pass over the NEW samples.  Pinned against the numpy
+ * model tests/progressive_model.py.
+ *
+ * A plan holds max_slots slots; a slot holds one file: a two-level reference prefix r[0, L) that grows by appends,
+ * n_cand <= max_cand (<= 8) two-level candidate vectors s_c fixed at open, and the lag window d in [-W+1, W]
+ * (W = max_offset_samples, n_lags = 2W <= max_lags <= 262144) fixed at open.  Subtitle sample i meets reference sample
+ * i + d.  Score of candidate c at lag d at prefix length L: two_level_score of (n11, n1x, nx1) over the overlap
+ * i in [max(0, -d), min(S_c, L - d)), exactly 0.0 where it is empty -- the scores of ffs_align_quality_batch on
+ * (r[0, L), s_c), over this window whatever L is.
+ *
+ * ffs_prog_open (slot i of the call: slot[i]; its candidate c: entry i * max_cand + c of sub_ptr / sub_len / sub_lo /
+ * sub_hi, the entries of c >= n_cand[i] are not read): the candidates (FFS_DTYPE_U1, device) are copied into the plan
+ * on the stream, their prefix sums computed, curves and reference zeroed, L = 0.  Reopening an open slot is allowed and
+ * leaves nothing of the old problem.
+ * ffs_prog_append: bits [first_bit[i], first_bit[i] + n_new[i]) of the 32-bit words at chunk_dev[i] (device, 4-byte
+ * aligned, first_bit in [0, 32): what ffs_vad_energy_bits wrote at a byte offset can be handed over in place) become
+ * reference samples [L, L + n_new); n_new = 0 is allowed.  Only the words that hold those bits are loaded, no other
+ * bit of them is interpreted.  Then, per slot of the call, cand_out_dev[i * max_cand + c] = the ffs_quality_result of
+ * candidate c on the prefix (greedy top_k peaks at least exclusion_samples apart, largest lag on ties, two-pass moments,
+ * FFS_QUALITY_FLAT, n_lags = 2W; zeros for c >= n_cand) and state_out_dev[i] = the slot's ffs_prog_state.
+ * ffs_prog_reference: the plan's bits of the consumed prefix (device; valid until the slot is reopened or the plan
+ * destroyed; bits at positions >= len are 0) and its length.  ffs_prog_close marks slots as not open.
+ *
+ * Everything is queued on hip_stream; host arrays may be freed on return.  The plan keeps L per slot on the host, so
+ * every refusal (FFS_E_INVALID) happens before any launch, with state and outputs untouched: a null or misaligned
+ * pointer, first_bit outside [0, 32), n_new < 0, L + n_new > max_ref_samples, a slot out of range, not open (append,
+ * reference, close) or named twice in one call, n_cand outside [1, max_cand], a candidate length < 1 or >
+ * max_sub_samples, W < 1 or 2W > max_lags, non-finite levels, top_k outside [1, 8], exclusion_samples < 1.
+ * ffs_prog_plan_destroy waits for pending work.
+ *
+ * Workspace (ffs_prog_plan_workspace_bytes), with lpad = max_lags rounded up to 64 and words(x) = x / 32 + 2 rounded up
+ * to 16:  max_slots * (8 * words(max_ref_samples) + max_cand * (8 * words(max_sub_samples) + 12 * lpad)) bytes, plus
+ * the descriptors of one call (less than 256 bytes per slot and candidate, not counted). */
+typedef struct ffs_prog_state {
+    int64_t ref_len;    /* L after the append */
+    int64_t offset;     /* peak 1 of the best candidate (samples) */
+    double score;       /* its score */
+    double mean, std;   /* of the best candidate's curve */
+    double runner_up;   /* the best candidate's peak-2 score; NaN when it has none */
+    double other_best;  /* the largest peak-1 score among the other candidates; NaN with one candidate */
+    int32_t best_cand;  /* the largest peak-1 score, the smallest candidate index on ties */
+    int32_t flags;      /* the best candidate's FFS_QUALITY_* flags */
+} ffs_prog_state;
+#ifdef __cplusplus
+static_assert(sizeof(ffs_prog_state) == 64, "ffs_prog_state is 64 bytes");
+#else
+_Static_assert(sizeof(ffs_prog_state) == 64, "ffs_prog_state is 64 bytes");
+#endif
+
+typedef struct ffs_prog_plan ffs_prog_plan;
+int ffs_prog_plan_create(int device, int max_slots, int max_cand, int64_t max_lags, int64_t max_ref_samples,
+                         int64_t max_sub_samples, ffs_prog_plan** out);
+int ffs_prog_plan_destroy(ffs_prog_plan* plan);
+int64_t ffs_prog_plan_workspace_bytes(const ffs_prog_plan* plan);
+int ffs_prog_open(ffs_prog_plan* plan, int n, const int32_t* slot, const int32_t* n_cand, const void* const* sub_ptr,
+                  const int64_t* sub_len, const double* sub_lo, const double* sub_hi, const double* ref_lo,
+                  const double* ref_hi, const int64_t* max_offset_samples, void* hip_stream);
+int ffs_prog_append(ffs_prog_plan* plan, int n, const int32_t* slot, const void* const* chunk_dev, const int32_t* first_bit,
+                    const int64_t* n_new, int top_k, int64_t exclusion_samples, ffs_quality_result* cand_out_dev,
+                    ffs_prog_state* state_out_dev, void* hip_stream);
+int ffs_prog_reference(ffs_prog_plan* plan, int slot, const uint32_t** bits_dev, int64_t* len);
+int ffs_prog_close(ffs_prog_plan* plan, int n, const int32_t* slot);
+
 /* Thread-local description of the last error returned on this thread ("" if none). */
 const char* ffs_last_error(void);
 
