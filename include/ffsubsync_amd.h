@@ -1250,7 +1250,9 @@ int ffs_sweep_peaks(const ffs_cand_result* rec_dev, const int64_t* first_dev, in
  * candidate c on the prefix (greedy top_k peaks at least exclusion_samples apart, largest lag on ties, two-pass moments,
  * FFS_QUALITY_FLAT, n_lags = 2W; zeros for c >= n_cand) and state_out_dev[i] = the slot's ffs_prog_state.
  * ffs_prog_reference: the plan's bits of the consumed prefix (device; valid until the slot is reopened or the plan
- * destroyed; bits at positions >= len are 0) and its length.  ffs_prog_close marks slots as not open.
+ * destroyed; bits at positions >= len are 0) and its length.  The call itself queues nothing and waits for nothing: a read
+ * of the returned pointer must be ordered behind the stream of the slot's last ffs_prog_append (queue it on that stream,
+ * or behind an event recorded there).  ffs_prog_close marks slots as not open.
  *
  * Everything is queued on hip_stream; host arrays may be freed on return.  The plan keeps L per slot on the host, so
  * every refusal (FFS_E_INVALID) happens before any launch, with state and outputs untouched: a null or misaligned

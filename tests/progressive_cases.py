@@ -42,14 +42,17 @@ def speech(rng, n, scale=40.0, density=0.45):
     return np.concatenate([v, np.zeros(n - v.size, bool)])
 
 
-def make_case(seed, total, S_list, W, ref_levels=(0.0, 1.0), top_k=3, exclusion=None):
+def make_case(seed, total, S_list, W, ref_levels=(0.0, 1.0), top_k=3, exclusion=None, shifts=None):
     """dict(ref, cands=[(bits, (lo, hi))], ref_levels, W, top_k, e): candidates are noisy shifted copies of the reference
-    where they can be, with amplitudes hi = 1 and min(1 / ratio, 1) in turn."""
+    where they can be, with amplitudes hi = 1 and min(1 / ratio, 1) in turn.  ``shifts``: the lag each candidate's copy
+    is planted at, instead of a random lag of the window."""
     rng = np.random.RandomState(7000 + seed)
     ref = speech(rng, total)
     cands = []
     for c, S in enumerate(S_list):
         shift = int(rng.randint(-W + 1, W + 1))
+        if shifts is not None:
+            shift = int(shifts[c])
         idx = np.arange(S) + shift
         ok = (idx >= 0) & (idx < total)
         s = speech(rng, S)
@@ -145,3 +148,87 @@ def window_cases():
             case = make_case(100 + 5 * i + j, total, [S], W, (0.0, 1.0) if j % 2 else (0.1, 1.0))
             out.append(("W%d-S%d-L%d" % (W, S, total), case, "random", FIRST_BITS[(i + j) % 4]))
     return out
+
+
+# ---- the windows at which k_prog_counts changes shape ------------------------------------------------------------------
+TILE = 4096  # PROG_TILE: the lags e = W - d of one workgroup of k_prog_counts; tile k holds e in [4096 k, 4096 k + 4096)
+MAX_LAGS = 262144  # _native.PROG_MAX_LAGS: 64 tiles, lpad = max_lags
+TILE_WINDOWS = (2048, 2049, 4096)  # 2W = one full tile, one full tile and two lags, two full tiles
+TILE_SUB_LENGTHS = (33, 5000)
+TILE_TOTALS = (1000, 4130)
+LIMIT_W, LIMIT_CUTS, LIMIT_SUB_LENGTHS = MAX_LAGS // 2, (1000, 1, 1999), (5000, 200000)
+
+
+def tile_of(W, lag):
+    """The tile of k_prog_counts that owns lag d of a window W."""
+    return (int(W) - int(lag)) // TILE
+
+
+def tile_shift(W, S, total):
+    """The lag a tile case plants its candidate at.  A subtitle longer than the window: the most negative lag, the last
+    of the last tile, written to curve[0] (at 2W = 4098 the lag before it: the first of the two lags of tile 1).  A
+    short one: the largest lag the reference reaches, W itself (the first lag of tile 0, the top of the curve) where it
+    can."""
+    if S > W:
+        return -W + 2 if (2 * W) % TILE == 2 else -W + 1
+    return min(W, total - S)
+
+
+def tile_cases():
+    """(name, case, append lengths, first_bit): 2W = 4096, 4098 and 8192 against a subtitle shorter and one longer than
+    the window, at a total below and one above a tile, in one append and in a random cut; then the limit window
+    2W = MAX_LAGS, whose long subtitle meets the reference in tiles 33 and beyond."""
+    out, i = [], 0
+    for W in TILE_WINDOWS:
+        for S in TILE_SUB_LENGTHS:
+            for total in TILE_TOTALS:
+                for kind in ("once", "random"):
+                    case = make_case(200 + i, total, [S], W, (0.0, 1.0) if i % 2 else (0.1, 1.0), top_k=8,
+                                     shifts=[tile_shift(W, S, total)])
+                    out.append(("W%d-S%d-L%d-%s" % (W, S, total, kind), case, cut(total, kind, seed=i), FIRST_BITS[i % 4]))
+                    i += 1
+    limit = make_case(260, sum(LIMIT_CUTS), LIMIT_SUB_LENGTHS, LIMIT_W, (0.1, 1.0), top_k=8, exclusion=LIMIT_W // 8,
+                      shifts=[-4500, -100000])  # (tiles 33 and 56)
+    out.append(("W%d-limit" % LIMIT_W, limit, list(LIMIT_CUTS), FIRST_BITS[i % 4]))
+    return out
+
+
+def tile_slot_cases():
+    """(cases, append lengths per round): W = 2048, 4096 and 16 in three slots of one plan, appended in one call: n_tiles
+    comes from the largest window, so the workgroups of the surplus tiles of the small slots must return."""
+    cases = [make_case(270, 1000, [5000, 33], 2048, top_k=8, shifts=[-2047, 967]),
+             make_case(271, 700, [5000], 4096, (0.1, 1.0), top_k=8, shifts=[-4095]),
+             make_case(272, 333, [33, 700], 16, top_k=8)]
+    return cases, [(200, 65, 33), (0, 1, 300), (800, 634, 0)]
+
+
+def tile_e2_case():
+    """(case, append lengths): W = 2048 with L = S = 2100 at the end, where the reference's own mask is the window."""
+    return make_case(280, 2100, [2100], 2048, top_k=8), [1000, 1060, 39, 1]
+
+
+# ---- queued and shared-stream sequences (tests/test_gpu_progressive_streams.py) ----------------------------------------
+QUEUE_LENGTHS = (0, 1, 31, 32, 33, 65, 200)
+# the appends of the plugged queue: (slots, n_new per slot, first_bit of the call), every slot's total within its case
+QUEUE_CALLS = (([2, 0, 1], [200, 33, 65], 1), ([1], [0], 31), ([0, 2], [1, 31], 8), ([1, 2, 0], [32, 65, 200], 0),
+               ([2], [33], 5), ([0, 1], [0, 200], 17), ([1, 0, 2], [1, 31, 32], 30), ([2, 1], [200, 33], 13))
+
+
+def queue_cases():
+    """The three slots of the plugged queue (the sizes of tests/test_gpu_progressive.py's slot cases)."""
+    return [make_case(940, 700, [700, 33], 600), make_case(941, 333, [5000], 33, (0.1, 1.0)),
+            make_case(942, 1000, [31, 700, 33], 16)]
+
+
+TWO_STREAM_LENGTHS = (33, 65, 1, 200, 31, 32, 64, 100, 7, 150)  # no empty append: every call must change the answer
+
+
+def two_stream_case():
+    """One slot fed from two streams in turn (appends 0, 2, 4, ... on A; 1, 3, 5, ... on B)."""
+    return make_case(950, 700, [700, 33], 600, (0.1, 1.0))
+
+
+def reopen_cases():
+    """(the long problem of slot 1, the short one it is reopened on, the neighbour in slot 0)."""
+    return (make_case(960, 700, [5000], 600), make_case(961, 200, [33], 16, (0.1, 1.0)),
+            make_case(962, 333, [700, 33], 33))

@@ -171,6 +171,78 @@ def test_windows_against_subtitle_lengths(name, case, kind, first_bit):
     _run_single(case, pc.cut(case["ref"].size, kind, seed=len(name)), first_bit, poison=False)
 
 
+TILE_CASES = pc.tile_cases()
+
+
+@pytest.mark.parametrize("name,case,cuts,first_bit", TILE_CASES, ids=[c[0] for c in TILE_CASES])
+def test_windows_of_whole_tiles_and_the_limit_window(name, case, cuts, first_bit):
+    """2W = 4096, 4098 and 8192 lags (one full tile of k_prog_counts, a tile and two lags, two full tiles) and the ABI
+    limit 2W = 262 144 on a plan of exactly that many lags: 64 tiles, lpad = max_lags."""
+    from ffsubsync_amd import _native
+
+    assert 2 * case["W"] <= _native.PROG_MAX_LAGS == pc.MAX_LAGS
+    _run_single(case, cuts, first_bit)
+
+
+def test_three_windows_in_one_call_leave_the_surplus_tiles_alone():
+    """W = 2048, 4096 and 16 in three slots appended in one call: the grid has the two tiles of the largest window for
+    every slot, and the workgroups of a tile beyond a slot's own window must return."""
+    from ffsubsync_amd import _native
+
+    cases, rounds = pc.tile_slot_cases()
+    plan = _native.ProgPlan(3, 2, 8192, 1000, 5000)
+    cands = Cands(cases)
+    models = [pm.Slot(k["cands"], k["ref_levels"], k["W"]) for k in cases]
+    pos = [0, 0, 0]
+    try:
+        _open(plan, [0, 1, 2], cases, cands)
+        for rnd, ns in enumerate(rounds):
+            chunks = [k["ref"][p:p + n] for k, p, n in zip(cases, pos, ns)]
+            pos = [p + n for p, n in zip(pos, ns)]
+            keep = [_dev(_words(ch, 8 + i)) for i, ch in enumerate(chunks)]
+            out = Outputs(3, 2)
+            plan.append([0, 1, 2], [w.data_ptr() for w in keep], [8, 9, 10], list(ns), 8, 40, *out.views())
+            recs, states = out.read()
+            for i, k in enumerate(cases):
+                reps, mstate = models[i].append(chunks[i], 8, 40)
+                _check(recs[i], states[i], reps, mstate, len(k["cands"]), 8, ("round", rnd, "slot", i))
+    finally:
+        plan.close()
+
+
+def test_records_equal_quality_batch_at_a_full_tile():
+    """E2 at W = 2048, L = S = 2100: wherever the reference's own mask is the window (checked on the host; L = 2100 is
+    such a place) the records are byte-identical to quality_batch(raw=True)."""
+    from ffsubsync_amd import _native, batch, quality
+    from ffsubsync_amd.subtitle_raster import DeviceRaster
+
+    case, cuts = pc.tile_e2_case()
+    W, (s, lv) = case["W"], case["cands"][0]
+    plan = _native.ProgPlan(1, 1, 2 * W, 2100, 2100)
+    cands = Cands([case])
+    checked = []
+    try:
+        _open(plan, [0], [case], cands)
+        o = 0
+        for n in cuts:
+            chunk = case["ref"][o:o + n]
+            o += n
+            out = Outputs(1, 1)
+            words = _dev(_words(chunk, 31))
+            plan.append([0], [words.data_ptr()], [31], [n], case["top_k"], case["e"], *out.views())
+            recs, _ = out.read()
+            if not pm.window_is_reference_mask(o, len(s), W):
+                continue
+            ref = DeviceRaster(_dev(_words(case["ref"][:o], fill=False)), 0.0, 1.0, o)
+            sub = DeviceRaster(_dev(_words(s, fill=False)), lv[0], lv[1], len(s))
+            want = quality.quality_batch(batch.pack_pairs([(ref, [sub])]), W, case["top_k"], case["e"], raw=True)
+            assert want.tobytes() == recs[0, :1].tobytes(), o
+            checked.append(o)
+    finally:
+        plan.close()
+    assert 2100 in checked and len(checked) >= 2
+
+
 def test_an_append_longer_than_the_staged_piece():
     from ffsubsync_amd import _native
 

@@ -114,3 +114,105 @@ def test_the_case_list_covers_what_it_claims():
     assert 1.0 in his and any(h < 1.0 for h in his)
     assert any(c[1]["W"] > len(c[1]["cands"][0][0]) for c in both) and any(c[1]["W"] > c[1]["ref"].size for c in both)
     assert 2 * max(pc.WINDOWS) > 4096  # crosses a lag tile of k_prog_counts
+
+
+def _peak_tiles(case, cuts):
+    """The tiles of k_prog_counts that hold a model peak of any candidate after the last append."""
+    slot = pm.Slot(case["cands"], case["ref_levels"], case["W"])
+    o = 0
+    for n in cuts:
+        reps, _ = slot.append(case["ref"][o:o + n], case["top_k"], case["e"])
+        o += n
+    return {pc.tile_of(case["W"], lag) for rep in reps for _, lag in rep["peaks"]}
+
+
+def test_the_tile_cases_cover_what_they_claim():
+    cases = pc.tile_cases()
+    by_w = {}
+    for name, case, cuts, fb in cases:
+        assert sum(cuts) == case["ref"].size and min(cuts) >= 0 and case["top_k"] == 8 and fb in pc.FIRST_BITS
+        by_w.setdefault(case["W"], []).append((name, case, cuts))
+    full = [W for W in by_w if (2 * W) % pc.TILE == 0 and 2 * W < pc.MAX_LAGS]
+    plus_two = [W for W in by_w if (2 * W) % pc.TILE == 2]
+    assert sorted(by_w) == [2048, 2049, 4096, pc.LIMIT_W] and 2 * pc.LIMIT_W == pc.MAX_LAGS == 64 * pc.TILE
+    assert sorted(full) == [2048, 4096] and plus_two == [2049]  # one full tile, two full tiles; a tile and two lags
+    for W in pc.TILE_WINDOWS:
+        got = {(len(c["cands"][0][0]), c["ref"].size, len(cuts) == 1) for _, c, cuts in by_w[W]}
+        assert got == {(S, total, once) for S in pc.TILE_SUB_LENGTHS for total in pc.TILE_TOTALS for once in (True, False)}
+    assert {fb for _, _, _, fb in cases} == set(pc.FIRST_BITS)
+    name, limit, cuts = by_w[pc.LIMIT_W][0]
+    assert cuts == [1000, 1, 1999] and [len(s) for s, _ in limit["cands"]] == [5000, 200000]
+    assert limit["ref_levels"] == (0.1, 1.0) and limit["e"] == pc.LIMIT_W // 8
+    # for a window of two full tiles, for the one of a tile and two lags and for the limit: a case whose model peaks lie
+    # in at least two tiles (2W = 4096 is one tile).  The planted lag is peak 1 and lies where tile_shift says.
+    for W, S in ((4096, 5000), (2049, 5000)):
+        name, case, cuts = next(x for x in by_w[W] if len(x[1]["cands"][0][0]) == S and len(x[2]) == 1)
+        tiles = _peak_tiles(case, cuts)
+        assert len(tiles) >= 2 and pc.tile_of(W, pc.tile_shift(W, S, case["ref"].size)) in tiles, (name, tiles)
+    assert pc.tile_of(2049, pc.tile_shift(2049, 5000, 1000)) == 1 and pc.tile_of(2049, -2048) == 1 and pc.tile_of(2049, -2046) == 0
+    assert pc.tile_of(2048, -2047) == 0 and pc.tile_of(4096, 0) == 1 and pc.tile_of(4096, 1) == 0
+    tiles = _peak_tiles(limit, cuts)
+    assert len(tiles) >= 2 and max(tiles) >= 33, tiles
+    slot_cases, rounds = pc.tile_slot_cases()
+    assert [c["W"] for c in slot_cases] == [2048, 4096, 16]
+    assert all(sum(r[i] for r in rounds) <= c["ref"].size for i, c in enumerate(slot_cases))
+    e2, cuts = pc.tile_e2_case()
+    assert e2["W"] == 2048 and sum(cuts) == 2100 == len(e2["cands"][0][0]) and pm.window_is_reference_mask(2100, 2100, 2048)
+
+
+def test_incremental_counts_equal_brute_force_at_a_full_tile():
+    """W = 2048 (2W = one tile of k_prog_counts) at tiny S and L, in three appends."""
+    rng = np.random.RandomState(2048)
+    s, r = rng.rand(70) < 0.5, rng.rand(90) < 0.5
+    slot = pm.Slot([(s, (0.0, 1.0))], (0.0, 1.0), 2048)
+    for lo, hi in ((0, 33), (33, 34), (34, 90)):
+        slot.append(r[lo:hi], 1, 1)
+    assert slot.n11[0].size == 4096 and (slot.n11[0] == pm.n11_brute(r, s, 2048)).all() and slot.n11[0].any()
+
+
+def _queue_fits():
+    cases = pc.queue_cases()
+    fed = [0] * len(cases)
+    for slots, ns, fb in pc.QUEUE_CALLS:
+        assert len(set(slots)) == len(slots) == len(ns) and 0 <= fb < 32
+        for s, n in zip(slots, ns):
+            fed[s] += n
+    return cases, fed
+
+
+def test_the_queued_sequences_cover_what_they_claim():
+    cases, fed = _queue_fits()
+    assert len(pc.QUEUE_CALLS) == 8 and len(cases) == 3 and all(f <= c["ref"].size for f, c in zip(fed, cases))
+    assert {n for _, ns, _ in pc.QUEUE_CALLS for n in ns} == set(pc.QUEUE_LENGTHS)
+    assert len({fb for _, _, fb in pc.QUEUE_CALLS}) == 8  # a different first_bit per call
+    orders = {tuple(slots) for slots, _, _ in pc.QUEUE_CALLS}
+    assert any(list(o) != sorted(o) for o in orders) and {len(o) for o in orders} == {1, 2, 3}
+    assert all(c["W"] <= 600 and c["ref"].size <= 1000 for c in cases + list(pc.reopen_cases()) + [pc.two_stream_case()])
+    long, short, _ = pc.reopen_cases()
+    assert (len(long["cands"][0][0]), long["W"]) == (5000, 600) and (len(short["cands"][0][0]), short["W"]) == (33, 16)
+
+
+def test_every_append_of_the_two_stream_sequence_changes_the_answer():
+    """Appends k and k + 1 of tests/test_gpu_progressive_streams.py's two-stream test come from different streams with
+    nothing but the plan to order them.  If they ran swapped, record k would be the model's of the prefix plus chunk
+    k + 1: that differs from the model's record k only if consecutive chunks and consecutive answers differ."""
+    case = pc.two_stream_case()
+    assert len(pc.TWO_STREAM_LENGTHS) == 10 and sum(pc.TWO_STREAM_LENGTHS) <= case["ref"].size
+    slot = pm.Slot(case["cands"], case["ref_levels"], case["W"])
+
+    def answer(reps, st):
+        return ([(rep["peaks"], rep["mean"], rep["std"]) for rep in reps],
+                {k: repr(v) for k, v in st.items() if k != "ref_len"})
+
+    o, chunks, seen = 0, [], []
+    for n in pc.TWO_STREAM_LENGTHS:
+        chunks.append(case["ref"][o:o + n])
+        seen.append(answer(*slot.append(chunks[-1], case["top_k"], case["e"])))
+        o += n
+    for k in range(9):
+        assert seen[k] != seen[k + 1] and seen[k][0] != seen[k + 1][0], k
+        assert chunks[k].tobytes() != chunks[k + 1].tobytes(), k
+        # what a swapped pair would leave in record k: the prefix and chunk k + 1
+        swapped = pm.Slot(case["cands"], case["ref_levels"], case["W"])
+        swapped.append(case["ref"][:sum(pc.TWO_STREAM_LENGTHS[:k])], case["top_k"], case["e"])
+        assert answer(*swapped.append(chunks[k + 1], case["top_k"], case["e"])) != seen[k], k
