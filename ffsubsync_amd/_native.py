@@ -158,6 +158,7 @@ PROG_STATE_BYTES = 64
 assert PROG_STATE_DTYPE.itemsize == PROG_STATE_BYTES
 PROG_MAX_CAND = 8  # PROG_MAX_CAND (csrc/ffs_progressive.h)
 PROG_MAX_LAGS = 262144  # 2W of a slot's lag window, at most
+PROG_MAX_INTERVALS = 256  # FFS_PROG_MAX_INTERVALS: merged known intervals of a sampled slot
 PROG_PIECE_SAMPLES = 512 * 32  # PROG_PIECE words: the reference samples k_prog_counts stages at a time
 
 # every symbol include/ffsubsync_amd.h declares (checked by tests/test_abi.py)
@@ -240,6 +241,10 @@ EXPORTED_SYMBOLS = (
     "ffs_prog_append",
     "ffs_prog_reference",
     "ffs_prog_close",
+    "ffs_prog_open_sampled",
+    "ffs_prog_append_at",
+    "ffs_prog_known",
+    "ffs_prog_plan_sampled_bytes",
     "ffs_last_error",
     "ffs_version",
 )
@@ -542,6 +547,15 @@ def load():
         lib.ffs_prog_reference.argtypes = [c.c_void_p, c.c_int, c.POINTER(c.c_void_p), c.POINTER(c.c_int64)]
         lib.ffs_prog_close.restype = c.c_int
         lib.ffs_prog_close.argtypes = [c.c_void_p, c.c_int, c.c_void_p]
+        lib.ffs_prog_open_sampled.restype = c.c_int
+        lib.ffs_prog_open_sampled.argtypes = [c.c_void_p, c.c_int] + [c.c_void_p] * 11
+        lib.ffs_prog_append_at.restype = c.c_int
+        lib.ffs_prog_append_at.argtypes = [c.c_void_p, c.c_int] + [c.c_void_p] * 5 + [c.c_int, c.c_int64, c.c_void_p,
+                                                                                     c.c_void_p, c.c_void_p]
+        lib.ffs_prog_known.restype = c.c_int
+        lib.ffs_prog_known.argtypes = [c.c_void_p, c.c_int, c.c_void_p, c.c_int, c.POINTER(c.c_int)]
+        lib.ffs_prog_plan_sampled_bytes.restype = c.c_int64
+        lib.ffs_prog_plan_sampled_bytes.argtypes = [c.c_void_p]
         lib.ffs_last_error.restype = c.c_char_p
         lib.ffs_last_error.argtypes = []
         lib.ffs_version.restype = c.c_int
@@ -1538,6 +1552,40 @@ class ProgPlan(_SidePlan):
         """``ffs_prog_close``."""
         buf = np.ascontiguousarray(slot, dtype=np.int32)
         check(self.lib.ffs_prog_close(self.handle, buf.size, buf.ctypes.data))
+
+    def open_sampled(self, slot, n_cand, sub_ptr, sub_len, sub_lo, sub_hi, ref_lo, ref_hi, max_offset_samples, ref_total,
+                     stream: Optional[int] = None) -> None:
+        """``ffs_prog_open_sampled``: ``open`` plus the declared reference length of every slot."""
+        kinds = (np.int32, np.int32, np.uint64, np.int64, np.float64, np.float64, np.float64, np.float64, np.int64, np.int64)
+        bufs = [np.ascontiguousarray(a, dtype=t) for a, t in zip(
+            (slot, n_cand, sub_ptr, sub_len, sub_lo, sub_hi, ref_lo, ref_hi, max_offset_samples, ref_total), kinds)]
+        n = bufs[0].size
+        if not all(b.size == (n * self.max_cand if 2 <= i <= 5 else n) for i, b in enumerate(bufs)):
+            raise ValueError("one entry per slot, max_cand candidate entries per slot")
+        check(self.lib.ffs_prog_open_sampled(self.handle, n, *[b.ctypes.data for b in bufs], self._stream(stream)))
+
+    def append_at(self, slot, chunk_ptr, first_bit, position, n_new, top_k: int, exclusion_samples: int, cand_out, state_out,
+                  stream: Optional[int] = None) -> None:
+        """``ffs_prog_append_at`` into uint8 CUDA tensors of n * max_cand * 160 and n * 64 bytes (asynchronous)."""
+        kinds = (np.int32, np.uint64, np.int32, np.int64, np.int64)
+        bufs = [np.ascontiguousarray(a, dtype=t) for a, t in zip((slot, chunk_ptr, first_bit, position, n_new), kinds)]
+        n = bufs[0].size
+        if not all(b.size == n for b in bufs):
+            raise ValueError("one entry per slot")
+        if _nbytes(cand_out) < n * self.max_cand * QUALITY_RESULT_BYTES or _nbytes(state_out) < n * PROG_STATE_BYTES:
+            raise ValueError("output buffer too small")
+        check(self.lib.ffs_prog_append_at(self.handle, n, *[b.ctypes.data for b in bufs], int(top_k), int(exclusion_samples),
+                                          cand_out.data_ptr(), state_out.data_ptr(), self._stream(stream)))
+
+    def known(self, slot: int):
+        """``ffs_prog_known``: the merged known intervals of a sampled slot as an int64 array [n, 2], ascending."""
+        buf, n = np.zeros((PROG_MAX_INTERVALS, 2), np.int64), ctypes.c_int()
+        check(self.lib.ffs_prog_known(self.handle, int(slot), buf.ctypes.data, PROG_MAX_INTERVALS, ctypes.byref(n)))
+        return buf[:n.value].copy()
+
+    def sampled_bytes(self) -> int:
+        """``ffs_prog_plan_sampled_bytes``."""
+        return int(self.lib.ffs_prog_plan_sampled_bytes(self.handle))
 
 
 class SidePlanCache:

@@ -127,6 +127,39 @@ __global__ void __launch_bounds__(PROG_THREADS) k_prog_ingest(const ProgSlotDesc
     prog_extend_prefix(d.r, d.pre_r, g0, g1, base, s_part);
 }
 
+// The count loop of one (slot, candidate, 4096-lag tile) workgroup over the reference words [g0, g1): acc[sh] += n11 of
+// tile lag 32 t + sh (e = e0 + 32 t + sh = W - d).  The words are staged in LDS in pieces of PROG_PIECE with the subtitle
+// words they can meet; word(g) hands over reference word g with every bit that is not to be counted masked off.  Every
+// thread of the PROG_CNT_THREADS workgroup calls it; k_prog_counts and k_samp_counts (ffs_sampled.h) differ in the mask.
+template <class WordF>
+FFS_DEV void prog_count_words(const uint32_t* s, int64_t S, int64_t g0, int64_t g1, int64_t W, int64_t e0, WordF word,
+                              uint32_t* s_ref, uint32_t* s_sub, uint32_t (&acc)[32]) {
+    const int t = threadIdx.x;
+    for (int64_t gp = g0; gp < g1; gp += PROG_PIECE) {
+        const int nw = (int)(g1 - gp < PROG_PIECE ? g1 - gp : PROG_PIECE);
+        // subtitle bits [base + 32 k, +32) for k <= nw + PROG_CNT_THREADS meet reference word gp + w at tile lag 32 q + sh
+        const int64_t base = 32 * gp - W + e0;
+        if (base + 32 * (int64_t)(nw + PROG_CNT_THREADS + 1) <= 0 || base >= S) continue;  // (uniform) no subtitle sample
+        const int64_t gbase = base >= 0 ? (base >> 5) : -((31 - base) >> 5);  // floor(base / 32)
+        const int bsh = (int)(base - gbase * 32);
+        __syncthreads();  // the previous piece has been read
+        for (int k = t; k <= nw + PROG_CNT_THREADS; k += PROG_CNT_THREADS) {
+            const uint32_t lo = split_word(s, S, gbase + k), hi = split_word(s, S, gbase + k + 1);
+            s_sub[k] = __builtin_amdgcn_alignbit(hi, lo, bsh);
+        }
+        for (int w = t; w < nw; w += PROG_CNT_THREADS) s_ref[w] = word(gp + w);
+        __syncthreads();
+        uint32_t lo = s_sub[t];
+        for (int w = 0; w < nw; ++w) {
+            const uint32_t rw = s_ref[w];  // (one address per wave: broadcast)
+            const uint32_t hi = s_sub[t + w + 1];
+#pragma unroll
+            for (int sh = 0; sh < 32; ++sh) acc[sh] += __popc(__builtin_amdgcn_alignbit(hi, lo, sh) & rw);
+            lo = hi;
+        }
+    }
+}
+
 // n11 of one 4096-lag tile of one candidate over the new reference samples; grid.x = slots * max_cand * n_tiles
 __global__ void __launch_bounds__(PROG_CNT_THREADS) k_prog_counts(const ProgSlotDesc* __restrict__ slots,
                                                                    const QualDesc* __restrict__ qd, int n_tiles, int max_cand) {
@@ -145,33 +178,14 @@ __global__ void __launch_bounds__(PROG_CNT_THREADS) k_prog_counts(const ProgSlot
     uint32_t acc[32];
 #pragma unroll
     for (int sh = 0; sh < 32; ++sh) acc[sh] = 0;
-    for (int64_t gp = g0; gp < g1; gp += PROG_PIECE) {
-        const int nw = (int)(g1 - gp < PROG_PIECE ? g1 - gp : PROG_PIECE);
-        // subtitle bits [base + 32 k, +32) for k <= nw + PROG_CNT_THREADS meet reference word gp + w at tile lag 32 q + sh
-        const int64_t base = 32 * gp - sd.W + e0;
-        if (base + 32 * (int64_t)(nw + PROG_CNT_THREADS + 1) <= 0 || base >= d.S) continue;  // (uniform) no subtitle sample
-        const int64_t gbase = base >= 0 ? (base >> 5) : -((31 - base) >> 5);  // floor(base / 32)
-        const int bsh = (int)(base - gbase * 32);
-        __syncthreads();  // the previous piece has been read
-        for (int k = t; k <= nw + PROG_CNT_THREADS; k += PROG_CNT_THREADS) {
-            const uint32_t lo = split_word(d.s, d.S, gbase + k), hi = split_word(d.s, d.S, gbase + k + 1);
-            s_sub[k] = __builtin_amdgcn_alignbit(hi, lo, bsh);
-        }
-        for (int w = t; w < nw; w += PROG_CNT_THREADS) {
-            uint32_t rw = d.r[gp + w];  // (bits at and beyond L1 are zero)
-            if (32 * (gp + w) < L) rw &= 0xFFFFFFFFu << (int)(L - 32 * (gp + w));  // counted by earlier appends
-            s_ref[w] = rw;
-        }
-        __syncthreads();
-        uint32_t lo = s_sub[t];
-        for (int w = 0; w < nw; ++w) {
-            const uint32_t rw = s_ref[w];  // (one address per wave: broadcast)
-            const uint32_t hi = s_sub[t + w + 1];
-#pragma unroll
-            for (int sh = 0; sh < 32; ++sh) acc[sh] += __popc(__builtin_amdgcn_alignbit(hi, lo, sh) & rw);
-            lo = hi;
-        }
-    }
+    prog_count_words(
+        d.s, d.S, g0, g1, sd.W, e0,
+        [&](int64_t g) {
+            uint32_t rw = d.r[g];  // (bits at and beyond L1 are zero)
+            if (32 * g < L) rw &= 0xFFFFFFFFu << (int)(L - 32 * g);  // counted by earlier appends
+            return rw;
+        },
+        s_ref, s_sub, acc);
 #pragma unroll
     for (int sh = 0; sh < 32; ++sh) s_acc[t * 33 + sh] = acc[sh];
     __syncthreads();

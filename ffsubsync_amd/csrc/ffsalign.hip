@@ -43,6 +43,7 @@
 #include "ffs_drift_range_report.h"
 #include "ffs_sweep.h"
 #include "ffs_progressive.h"
+#include "ffs_sampled.h"
 
 using namespace ffsa;
 
@@ -5108,6 +5109,9 @@ struct ProgSlot {  // what the host knows of a slot: every refusal is decided fr
     bool open = false;
     int n_cand = 0;
     int64_t W = 0, L = 0;
+    bool sampled = false;  // a sampled slot (csrc/ffs_sampled.h): L = |K|, the merged intervals in the plan's tables
+    int64_t T = 0;
+    int n_iv = 0;
     int64_t S[ffsa::PROG_MAX_CAND];
     double s0[ffsa::PROG_MAX_CAND], s1[ffsa::PROG_MAX_CAND], r0, r1;  // mapped levels
 };
@@ -5127,6 +5131,12 @@ struct ffs_prog_plan : PlanCore {
     std::vector<char> named;    // per slot: named by the call being checked
                                 // desc: ProgOpenDesc[max_slots * max_cand] at open; at append ProgSlotDesc[max_slots],
                                 // then QualDesc[max_slots * max_cand]
+    // sampled slots, made by the first ffs_prog_open_sampled
+    uint32_t* side = nullptr;   // [slot][cand][3][lpad]: ov, n1x, nx1
+    DescStaging samp_desc;      // SampOpenDesc[max_slots * max_cand] at open; at append ProgSlotDesc[max_slots],
+                                // SampSlotDesc[max_slots], then SampDesc[max_slots * max_cand]
+    std::vector<int64_t> iv;    // [slot][FFS_PROG_MAX_INTERVALS][2]: the merged known intervals, ascending
+    int64_t sampled_bytes = 0;  // what the three above hold, each counted when it is made
 
     void carve(Carver& c) {
         const int64_t n = max_slots, nc = (int64_t)max_slots * max_cand;
@@ -5200,44 +5210,76 @@ int ffs_prog_plan_destroy(ffs_prog_plan* plan) {
     return FFS_OK;
 }
 
-int64_t ffs_prog_plan_workspace_bytes(const ffs_prog_plan* plan) { return plan ? plan->workspace_bytes() : 0; }
+// (what sampled slots add on first use is reported by ffs_prog_plan_sampled_bytes, not here: the formula stays)
+int64_t ffs_prog_plan_workspace_bytes(const ffs_prog_plan* plan) { return plan ? plan->work_bytes : 0; }
 
-int ffs_prog_open(ffs_prog_plan* plan, int n, const int32_t* slot, const int32_t* n_cand, const void* const* sub_ptr,
-                  const int64_t* sub_len, const double* sub_lo, const double* sub_hi, const double* ref_lo,
-                  const double* ref_hi, const int64_t* max_offset_samples, void* hip_stream) {
+namespace {
+// ffs_prog_open, and with `ref_total` ffs_prog_open_sampled: the same checks and the same k_prog_open
+int prog_open(const char* call, ffs_prog_plan* plan, int n, const int32_t* slot, const int32_t* n_cand,
+              const void* const* sub_ptr, const int64_t* sub_len, const double* sub_lo, const double* sub_hi,
+              const double* ref_lo, const double* ref_hi, const int64_t* max_offset_samples, const int64_t* ref_total,
+              bool sampled, void* hip_stream) {
     if (int rc = check_call(plan, "progressive", n,
                             !slot || !n_cand || !sub_ptr || !sub_len || !sub_lo || !sub_hi || !ref_lo || !ref_hi ||
-                                !max_offset_samples);
+                                !max_offset_samples || (sampled && !ref_total));
         rc != CALL_GO_ON)
         return rc;
-    if (n > plan->max_slots) return fail(FFS_E_INVALID, "ffs_prog_open: %d slots exceed the plan's max_slots %d", n, plan->max_slots);
-    if (int rc = plan->check_slots("ffs_prog_open", n, slot, false)) return rc;
+    if (n > plan->max_slots) return fail(FFS_E_INVALID, "%s: %d slots exceed the plan's max_slots %d", call, n, plan->max_slots);
+    if (int rc = plan->check_slots(call, n, slot, false)) return rc;
     const int mc = plan->max_cand;
     for (int i = 0; i < n; ++i) {
         if (n_cand[i] < 1 || n_cand[i] > mc)
-            return fail(FFS_E_INVALID, "ffs_prog_open: slot %d: n_cand=%d outside [1, %d]", slot[i], n_cand[i], mc);
+            return fail(FFS_E_INVALID, "%s: slot %d: n_cand=%d outside [1, %d]", call, slot[i], n_cand[i], mc);
         if (int rc = check_window(max_offset_samples[i], plan->max_lags)) return rc;
         if (!(std::isfinite(ref_lo[i]) && std::isfinite(ref_hi[i])))
-            return fail(FFS_E_INVALID, "ffs_prog_open: slot %d: levels must be finite", slot[i]);
+            return fail(FFS_E_INVALID, "%s: slot %d: levels must be finite", call, slot[i]);
         for (int c = 0; c < n_cand[i]; ++c) {
             const int64_t k = (int64_t)i * mc + c;
             if (!sub_ptr[k] || ((uintptr_t)sub_ptr[k] & 3))
-                return fail(FFS_E_INVALID, "ffs_prog_open: slot %d candidate %d: null or misaligned vector", slot[i], c);
+                return fail(FFS_E_INVALID, "%s: slot %d candidate %d: null or misaligned vector", call, slot[i], c);
             if (sub_len[k] < 1 || sub_len[k] > plan->max_sub)
-                return fail(FFS_E_INVALID, "ffs_prog_open: slot %d candidate %d: length %lld outside [1, max_sub_samples %lld]",
+                return fail(FFS_E_INVALID, "%s: slot %d candidate %d: length %lld outside [1, max_sub_samples %lld]", call,
                             slot[i], c, (long long)sub_len[k], (long long)plan->max_sub);
             if (!(std::isfinite(sub_lo[k]) && std::isfinite(sub_hi[k])))
-                return fail(FFS_E_INVALID, "ffs_prog_open: slot %d candidate %d: levels must be finite", slot[i], c);
+                return fail(FFS_E_INVALID, "%s: slot %d candidate %d: levels must be finite", call, slot[i], c);
         }
+        if (sampled && (ref_total[i] < 1 || ref_total[i] > plan->max_ref))
+            return fail(FFS_E_INVALID, "%s: slot %d: ref_total=%lld outside [1, max_ref_samples %lld]", call, slot[i],
+                        (long long)ref_total[i], (long long)plan->max_ref);
     }
     hipStream_t st = (hipStream_t)hip_stream;
     if (int rc = plan->begin(st)) return rc;
+    if (sampled) {  // the first sampled slot of this plan: side curves, descriptors, interval tables
+        const size_t ms = (size_t)plan->max_slots, nc = ms * plan->max_cand;
+        if (!plan->side) {
+            const int64_t side_bytes = (int64_t)nc * 3 * plan->lpad * (int64_t)sizeof(uint32_t);
+            void* mem = nullptr;
+            if (int rc = plan->add_block(&mem, side_bytes, "progressive plan", "sampled side curve")) return rc;
+            plan->side = (uint32_t*)mem;
+            plan->sampled_bytes += side_bytes;
+        }
+        if (!plan->samp_desc.dev) {
+            const size_t desc_bytes =
+                std::max(sizeof(ffsa::SampOpenDesc) * nc,
+                         (sizeof(ffsa::ProgSlotDesc) + sizeof(ffsa::SampSlotDesc)) * ms + sizeof(ffsa::SampDesc) * nc);
+            if (int rc = plan->add_staging(&plan->samp_desc, desc_bytes, 0, "progressive plan: sampled descriptor buffers / events"))
+                return rc;
+            plan->iv.assign(ms * FFS_PROG_MAX_INTERVALS * 2, 0);
+            plan->sampled_bytes += (int64_t)desc_bytes + (int64_t)(plan->iv.size() * sizeof(int64_t));
+        }
+    }
     if (int rc = plan->desc.wait_free()) return rc;
+    if (sampled)
+        if (int rc = plan->samp_desc.wait_free()) return rc;
     ffsa::ProgOpenDesc* hd = (ffsa::ProgOpenDesc*)plan->desc.host;
+    ffsa::SampOpenDesc* hz = sampled ? (ffsa::SampOpenDesc*)plan->samp_desc.host : nullptr;
     int nd = 0;
     for (int i = 0; i < n; ++i) {
         ProgSlot& ps = plan->slots[slot[i]];
         ps.open = true;
+        ps.sampled = sampled;
+        ps.T = sampled ? ref_total[i] : 0;
+        ps.n_iv = 0;
         ps.n_cand = n_cand[i];
         ps.W = max_offset_samples[i];
         ps.L = 0;
@@ -5248,6 +5290,13 @@ int ffs_prog_open(ffs_prog_plan* plan, int n, const int32_t* slot, const int32_t
             ps.S[c] = sub_len[k];
             ps.s0[c] = mapped(sub_lo[k]);
             ps.s1[c] = mapped(sub_hi[k]);
+            if (sampled) {
+                ffsa::SampOpenDesc& z = hz[nd];
+                z.side = plan->side + at * 3 * plan->lpad;
+                z.pre_r = c == 0 ? plan->pre_r + (int64_t)slot[i] * plan->rw : nullptr;
+                z.lpad = plan->lpad;
+                z.r_words = plan->rw;
+            }
             ffsa::ProgOpenDesc& d = hd[nd++];
             d.src = (const uint32_t*)sub_ptr[k];
             d.s = plan->sub + at * plan->sw;
@@ -5263,9 +5312,32 @@ int ffs_prog_open(ffs_prog_plan* plan, int n, const int32_t* slot, const int32_t
     if (int rc = plan->desc.upload(sizeof(ffsa::ProgOpenDesc) * nd, st)) return rc;
     hipLaunchKernelGGL(ffsa::k_prog_open, dim3((unsigned)nd), dim3(ffsa::PROG_THREADS), 0, st,
                        (const ffsa::ProgOpenDesc*)plan->desc.dev);
+    if (sampled) {
+        if (int rc = plan->samp_desc.upload(sizeof(ffsa::SampOpenDesc) * nd, st)) return rc;
+        hipLaunchKernelGGL(ffsa::k_samp_zero, dim3((unsigned)nd), dim3(ffsa::PROG_THREADS), 0, st,
+                           (const ffsa::SampOpenDesc*)plan->samp_desc.dev);
+    }
     HIP_TRY(hipGetLastError());
     return plan->end(st);
 }
+}  // namespace
+
+int ffs_prog_open(ffs_prog_plan* plan, int n, const int32_t* slot, const int32_t* n_cand, const void* const* sub_ptr,
+                  const int64_t* sub_len, const double* sub_lo, const double* sub_hi, const double* ref_lo,
+                  const double* ref_hi, const int64_t* max_offset_samples, void* hip_stream) {
+    return prog_open("ffs_prog_open", plan, n, slot, n_cand, sub_ptr, sub_len, sub_lo, sub_hi, ref_lo, ref_hi,
+                     max_offset_samples, nullptr, false, hip_stream);
+}
+
+int ffs_prog_open_sampled(ffs_prog_plan* plan, int n, const int32_t* slot, const int32_t* n_cand, const void* const* sub_ptr,
+                          const int64_t* sub_len, const double* sub_lo, const double* sub_hi, const double* ref_lo,
+                          const double* ref_hi, const int64_t* max_offset_samples, const int64_t* ref_total,
+                          void* hip_stream) {
+    return prog_open("ffs_prog_open_sampled", plan, n, slot, n_cand, sub_ptr, sub_len, sub_lo, sub_hi, ref_lo, ref_hi,
+                     max_offset_samples, ref_total, true, hip_stream);
+}
+
+int64_t ffs_prog_plan_sampled_bytes(const ffs_prog_plan* plan) { return plan ? plan->sampled_bytes : 0; }
 
 int ffs_prog_append(ffs_prog_plan* plan, int n, const int32_t* slot, const void* const* chunk_dev, const int32_t* first_bit,
                     const int64_t* n_new, int top_k, int64_t exclusion_samples, ffs_quality_result* cand_out_dev,
@@ -5280,6 +5352,7 @@ int ffs_prog_append(ffs_prog_plan* plan, int n, const int32_t* slot, const void*
     if (int rc = plan->check_slots("ffs_prog_append", n, slot, true)) return rc;
     for (int i = 0; i < n; ++i) {
         const ProgSlot& ps = plan->slots[slot[i]];
+        if (ps.sampled) return fail(FFS_E_INVALID, "ffs_prog_append: slot %d is a sampled slot: use ffs_prog_append_at", slot[i]);
         if (!chunk_dev[i] || ((uintptr_t)chunk_dev[i] & 3))
             return fail(FFS_E_INVALID, "ffs_prog_append: slot %d: null or misaligned chunk", slot[i]);
         if (first_bit[i] < 0 || first_bit[i] > 31)
@@ -5360,7 +5433,157 @@ int ffs_prog_reference(ffs_prog_plan* plan, int slot, const uint32_t** bits_dev,
     if (slot < 0 || slot >= plan->max_slots) return fail(FFS_E_INVALID, "ffs_prog_reference: slot %d outside [0, %d)", slot, plan->max_slots);
     if (!plan->slots[slot].open) return fail(FFS_E_INVALID, "ffs_prog_reference: slot %d is not open", slot);
     *bits_dev = plan->ref + (int64_t)slot * plan->rw;
-    *len = plan->slots[slot].L;
+    *len = plan->slots[slot].sampled ? plan->slots[slot].T : plan->slots[slot].L;
+    return FFS_OK;
+}
+
+namespace {
+// index of the first of the n ascending, disjoint intervals iv[2k], iv[2k + 1] that ends at or behind a (n: none)
+int prog_first_ending_at(const int64_t* iv, int n, int64_t a) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) / 2;
+        if (iv[2 * mid + 1] < a)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+}  // namespace
+
+int ffs_prog_append_at(ffs_prog_plan* plan, int n, const int32_t* slot, const void* const* chunk_dev, const int32_t* first_bit,
+                       const int64_t* position, const int64_t* n_new, int top_k, int64_t exclusion_samples,
+                       ffs_quality_result* cand_out_dev, ffs_prog_state* state_out_dev, void* hip_stream) {
+    if (int rc = check_call(plan, "progressive", n,
+                            !slot || !chunk_dev || !first_bit || !position || !n_new || !cand_out_dev || !state_out_dev);
+        rc != CALL_GO_ON)
+        return rc;
+    if (int rc = check_peaks(top_k, exclusion_samples)) return rc;
+    if (((uintptr_t)cand_out_dev | (uintptr_t)state_out_dev) & 7) return fail(FFS_E_INVALID, "misaligned output records");
+    if (n > plan->max_slots) return fail(FFS_E_INVALID, "ffs_prog_append_at: %d slots exceed the plan's max_slots %d", n, plan->max_slots);
+    if (int rc = plan->check_slots("ffs_prog_append_at", n, slot, true)) return rc;
+    for (int i = 0; i < n; ++i) {
+        const ProgSlot& ps = plan->slots[slot[i]];
+        if (!ps.sampled) return fail(FFS_E_INVALID, "ffs_prog_append_at: slot %d is a prefix slot: use ffs_prog_append", slot[i]);
+        if (!chunk_dev[i] || ((uintptr_t)chunk_dev[i] & 3))
+            return fail(FFS_E_INVALID, "ffs_prog_append_at: slot %d: null or misaligned chunk", slot[i]);
+        if (first_bit[i] < 0 || first_bit[i] > 31)
+            return fail(FFS_E_INVALID, "ffs_prog_append_at: slot %d: first_bit=%d outside [0, 32)", slot[i], first_bit[i]);
+        if (n_new[i] < 0) return fail(FFS_E_INVALID, "ffs_prog_append_at: slot %d: n_new=%lld is negative", slot[i], (long long)n_new[i]);
+        const int64_t a = position[i];
+        if (a < 0 || a > ps.T || n_new[i] > ps.T - a)
+            return fail(FFS_E_INVALID, "ffs_prog_append_at: slot %d: [%lld, %lld + %lld) outside the reference [0, %lld)", slot[i],
+                        (long long)a, (long long)a, (long long)n_new[i], (long long)ps.T);
+        if (n_new[i] == 0) continue;
+        const int64_t b = a + n_new[i];
+        const int64_t* iv = plan->iv.data() + (size_t)slot[i] * FFS_PROG_MAX_INTERVALS * 2;
+        // the table is ascending and disjoint: only the first interval that ends at or behind a, and the one after an
+        // abutting one, can meet [a, b) -- a search, so that the host's share of a call does not grow with what is known
+        int joins = 0, k = prog_first_ending_at(iv, ps.n_iv, a);
+        if (k < ps.n_iv && iv[2 * k + 1] == a) ++joins, ++k;
+        if (k < ps.n_iv && iv[2 * k] < b)
+            return fail(FFS_E_INVALID, "ffs_prog_append_at: slot %d: [%lld, %lld) overlaps the known interval [%lld, %lld)",
+                        slot[i], (long long)a, (long long)b, (long long)iv[2 * k], (long long)iv[2 * k + 1]);
+        if (k < ps.n_iv && iv[2 * k] == b) ++joins;
+        if (ps.n_iv + 1 - joins > FFS_PROG_MAX_INTERVALS)
+            return fail(FFS_E_INVALID, "ffs_prog_append_at: slot %d: more than %d known intervals", slot[i], FFS_PROG_MAX_INTERVALS);
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (int rc = plan->begin(st)) return rc;
+    if (int rc = plan->samp_desc.wait_free()) return rc;
+    const int mc = plan->max_cand;
+    ffsa::ProgSlotDesc* hp = (ffsa::ProgSlotDesc*)plan->samp_desc.host;
+    ffsa::SampSlotDesc* hs = (ffsa::SampSlotDesc*)(hp + plan->max_slots);
+    ffsa::SampDesc* hq = (ffsa::SampDesc*)(hs + plan->max_slots);
+    const ffsa::ProgSlotDesc* dp = (const ffsa::ProgSlotDesc*)plan->samp_desc.dev;
+    const ffsa::SampSlotDesc* ds = (const ffsa::SampSlotDesc*)(dp + plan->max_slots);
+    const ffsa::SampDesc* dq = (const ffsa::SampDesc*)(ds + plan->max_slots);
+    int nq = 0;
+    int64_t max_w = 0;
+    for (int i = 0; i < n; ++i) {
+        ProgSlot& ps = plan->slots[slot[i]];
+        ffsa::ProgSlotDesc& p = hp[i];  // what k_prog_pick reads: ref_len = |K| after the append, n_cand
+        memset(&p, 0, sizeof p);
+        p.L = ps.L;
+        p.n_new = n_new[i];
+        p.n_cand = ps.n_cand;
+        ffsa::SampSlotDesc& s = hs[i];
+        memset(&s, 0, sizeof s);
+        s.chunk = (const uint32_t*)chunk_dev[i];
+        s.r = plan->ref + (int64_t)slot[i] * plan->rw;
+        s.pre_r = plan->pre_r + (int64_t)slot[i] * plan->rw;
+        s.a = position[i];
+        s.n_new = n_new[i];
+        s.T = ps.T;
+        s.W = ps.W;
+        s.first_bit = first_bit[i];
+        s.n_cand = ps.n_cand;
+        s.desc0 = nq;
+        if (n_new[i] > 0) {  // merge [a, b) into the slot's table: it stays ascending
+            int64_t a = position[i], b = a + n_new[i];
+            int64_t* iv = plan->iv.data() + (size_t)slot[i] * FFS_PROG_MAX_INTERVALS * 2;
+            const int at = prog_first_ending_at(iv, ps.n_iv, a);
+            int last = at;                                    // [at, last): the intervals that abut [a, b)
+            if (last < ps.n_iv && iv[2 * last + 1] == a) a = iv[2 * last++];
+            if (last < ps.n_iv && iv[2 * last] == b) b = iv[2 * last++ + 1];
+            const int removed = last - at;
+            if (removed == 0)
+                memmove(iv + 2 * (at + 1), iv + 2 * at, sizeof(int64_t) * 2 * (size_t)(ps.n_iv - at));
+            else if (removed == 2)
+                memmove(iv + 2 * (at + 1), iv + 2 * (at + 2), sizeof(int64_t) * 2 * (size_t)(ps.n_iv - at - 2));
+            iv[2 * at] = a;
+            iv[2 * at + 1] = b;
+            ps.n_iv += 1 - removed;
+            ps.L += n_new[i];
+        }
+        max_w = std::max(max_w, ps.W);
+        for (int c = 0; c < ps.n_cand; ++c) {
+            const int64_t at = (int64_t)slot[i] * mc + c;
+            ffsa::SampDesc& q = hq[nq++];
+            memset(&q, 0, sizeof q);
+            q.s = plan->sub + at * plan->sw;
+            q.pre_s = plan->pre_s + at * plan->sw;
+            q.n11 = plan->curve + at * plan->lpad;
+            q.side = plan->side + at * 3 * plan->lpad;
+            q.sc = plan->sc + at * plan->lpad;
+            q.S = ps.S[c];
+            q.lpad = plan->lpad;
+            q.n_lags = 2 * ps.W;
+            q.d_lo = -ps.W + 1;
+            q.out_row = (int64_t)i * mc + c;
+            q.s0 = ps.s0[c];
+            q.s1 = ps.s1[c];
+            q.r0 = ps.r0;
+            q.r1 = ps.r1;
+        }
+    }
+    // one upload of the three arrays (the later two are at fixed offsets: copy the whole used span)
+    if (int rc = plan->samp_desc.upload((sizeof(ffsa::ProgSlotDesc) + sizeof(ffsa::SampSlotDesc)) * plan->max_slots +
+                                            sizeof(ffsa::SampDesc) * nq, st))
+        return rc;
+    const int n_tiles = (int)((2 * max_w + ffsa::PROG_TILE - 1) / ffsa::PROG_TILE);
+    hipLaunchKernelGGL(ffsa::k_samp_ingest, dim3((unsigned)n), dim3(ffsa::PROG_THREADS), 0, st, ds);
+    hipLaunchKernelGGL(ffsa::k_samp_counts, dim3((unsigned)((int64_t)n * mc * n_tiles)), dim3(ffsa::PROG_CNT_THREADS), 0, st, ds,
+                       dq, n_tiles, mc);
+    hipLaunchKernelGGL(ffsa::k_samp_peaks, dim3((unsigned)nq), dim3(ffsa::QUAL_PEAK_THREADS), 0, st, dq, top_k,
+                       exclusion_samples, (ffsa::QualResult*)cand_out_dev);
+    hipLaunchKernelGGL(ffsa::k_prog_pick, dim3((unsigned)n), dim3(ffsa::PROG_PICK_THREADS), 0, st, dp, mc,
+                       (ffsa::QualResult*)cand_out_dev, (ffsa::ProgState*)state_out_dev);
+    HIP_TRY(hipGetLastError());
+    return plan->end(st);
+}
+
+int ffs_prog_known(ffs_prog_plan* plan, int slot, int64_t* bounds_out, int cap, int* n_out) {
+    if (!plan) return fail(FFS_E_INVALID, "null progressive plan");
+    if (!n_out || cap < 0 || (cap > 0 && !bounds_out)) return fail(FFS_E_INVALID, "null argument");
+    if (slot < 0 || slot >= plan->max_slots) return fail(FFS_E_INVALID, "ffs_prog_known: slot %d outside [0, %d)", slot, plan->max_slots);
+    const ProgSlot& ps = plan->slots[slot];
+    if (!ps.open || !ps.sampled) return fail(FFS_E_INVALID, "ffs_prog_known: slot %d is not an open sampled slot", slot);
+    if (ps.n_iv > cap) return fail(FFS_E_INVALID, "ffs_prog_known: %d intervals exceed cap=%d", ps.n_iv, cap);
+    if (ps.n_iv > 0)
+        memcpy(bounds_out, plan->iv.data() + (size_t)slot * FFS_PROG_MAX_INTERVALS * 2, sizeof(int64_t) * 2 * (size_t)ps.n_iv);
+    *n_out = ps.n_iv;
     return FFS_OK;
 }
 

@@ -131,10 +131,10 @@ def _check_tracks(tracks) -> None:
             raise empty_error(1, 0)
 
 
-def _float_reference_error(dtype) -> ValueError:
+def _float_reference_error(dtype, name="ProgressiveSolve.append") -> ValueError:
     """side_call.check_two_level_batch's words for a multi-level float reference."""
-    return ValueError("ProgressiveSolve.append needs a two-level reference: a multi-level float reference (FFS_DTYPE_%s) "
-                      "is not supported" % ("F32" if np.dtype(dtype) == np.float32 else "F64"))
+    return ValueError("%s needs a two-level reference: a multi-level float reference (FFS_DTYPE_%s) "
+                      "is not supported" % (name, "F32" if np.dtype(dtype) == np.float32 else "F64"))
 
 
 class _DeviceWords:
@@ -148,6 +148,8 @@ class _DeviceWords:
 class ProgressiveSolve:
     """The progressive solve of many files: every track rasterised once on the device at every ratio, one slot of an
     ``ffs_prog_plan`` per file.  ``append`` feeds reference labels and returns each file's state on what it has read."""
+
+    _append_name = "ProgressiveSolve.append"
 
     def __init__(self, tracks, max_offset_seconds: float = 60, ratios: Optional[Sequence[float]] = None,
                  sample_rate: int = SAMPLE_RATE, max_reference_seconds: float = DEFAULT_MAX_REFERENCE_SECONDS,
@@ -188,15 +190,26 @@ class ProgressiveSolve:
         self.device = torch.device("cuda", self.plan.device)
         self.consumed = [0] * self.n_files
         shape = (self.n_files, self.n_cand)
-        self.plan.open(np.arange(self.n_files), np.full(self.n_files, self.n_cand),
-                       np.array([[c.packed_words().data_ptr() for c in cands] for cands in self.rasters], np.uint64),
-                       np.array([[c.n for c in cands] for cands in self.rasters], np.int64),
-                       np.array([[c.lo for c in cands] for cands in self.rasters]).reshape(shape),
-                       np.array([[c.hi for c in cands] for cands in self.rasters]).reshape(shape),
-                       np.full(self.n_files, lo), np.full(self.n_files, hi), np.full(self.n_files, self.w))
+        self._open(np.arange(self.n_files), np.full(self.n_files, self.n_cand),
+                   np.array([[c.packed_words().data_ptr() for c in cands] for cands in self.rasters], np.uint64),
+                   np.array([[c.n for c in cands] for cands in self.rasters], np.int64),
+                   np.array([[c.lo for c in cands] for cands in self.rasters]).reshape(shape),
+                   np.array([[c.hi for c in cands] for cands in self.rasters]).reshape(shape),
+                   np.full(self.n_files, lo), np.full(self.n_files, hi), np.full(self.n_files, self.w))
+
+    def _open(self, *tables) -> None:
+        self.plan.open(*tables)
 
     def _chunk(self, f, chunk):
-        """(tensor kept alive, device address, first_bit, n) of one file's chunk."""
+        """(words or None, first_bit, n) of one file's chunk."""
+        words, first_bit, n = self._chunk_form(chunk)
+        if self.consumed[f] + n > self.max_ref:
+            raise ValueError("file %d: %d + %d samples exceed max_reference_seconds (%d samples)"
+                             % (f, self.consumed[f], n, self.max_ref))
+        return words, first_bit, n
+
+    def _chunk_form(self, chunk):
+        """(words or None, first_bit, n) of a chunk in any of its forms."""
         torch = self.torch
         if isinstance(chunk, tuple):
             if len(chunk) != 3:
@@ -220,15 +233,27 @@ class ProgressiveSolve:
             host = np.asarray(chunk)
             if host.dtype != np.bool_:
                 if host.dtype.kind == "f" and not np.all((host == 0) | (host == 1)):
-                    raise _float_reference_error(host.dtype if host.dtype == np.float32 else np.float64)
+                    raise _float_reference_error(host.dtype if host.dtype == np.float32 else np.float64, self._append_name)
                 if not np.all((host == 0) | (host == 1)):
                     raise ValueError("a host chunk must hold 0/1 or bool samples")
             n, first_bit = int(host.size), 0
             words = None
-        if self.consumed[f] + n > self.max_ref:
-            raise ValueError("file %d: %d + %d samples exceed max_reference_seconds (%d samples)"
-                             % (f, self.consumed[f], n, self.max_ref))
         return words, first_bit, n
+
+    def _device_words(self, chunk, words, n):
+        """The int32 CUDA words of a checked chunk (packed here unless it came packed)."""
+        torch = self.torch
+        if words is None:
+            if hasattr(chunk, "is_cuda"):
+                words = _native.pack_bits(chunk.contiguous().reshape(-1)) if n else None
+            elif n:
+                packed = np.packbits(np.asarray(chunk).ravel() != 0, bitorder="little")
+                host = np.zeros((n + 31) // 32 * 4, np.uint8)
+                host[:packed.size] = packed
+                words = torch.from_numpy(host.view(np.int32)).to(self.device)
+            if words is None or words.numel() == 0:
+                words = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return words
 
     def append(self, chunks: Dict[int, object]) -> Dict[int, ProgressState]:
         """Feed one chunk per named file (index into the tracks): a host 0/1 or bool array, a CUDA label tensor
@@ -245,17 +270,7 @@ class ProgressiveSolve:
         checked = [self._chunk(f, chunks[f]) for f in files]  # every ValueError before any native call
         keep, ptrs = [], []
         for f, (words, first_bit, n) in zip(files, checked):
-            if words is None:
-                chunk = chunks[f]
-                if hasattr(chunk, "is_cuda"):
-                    words = _native.pack_bits(chunk.contiguous().reshape(-1)) if n else None
-                elif n:
-                    packed = np.packbits(np.asarray(chunk).ravel() != 0, bitorder="little")
-                    host = np.zeros((n + 31) // 32 * 4, np.uint8)
-                    host[:packed.size] = packed
-                    words = torch.from_numpy(host.view(np.int32)).to(self.device)
-                if words is None or words.numel() == 0:
-                    words = torch.zeros(1, dtype=torch.int32, device=self.device)
+            words = self._device_words(chunks[f], words, n)
             keep.append(words)
             ptrs.append(words.data_ptr())
         n = len(files)

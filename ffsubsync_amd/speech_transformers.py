@@ -18,6 +18,7 @@ multi-segment path are control plane and stay with the reference's own classes:
 :func:`install_detectors` puts the GPU detector behind them through the reference's factory seam.
 webrtcvad / silero arithmetic lives in absent third-party wheels (seams only).
 """
+import math
 from typing import Callable, List, Optional, Sequence, Union
 
 import numpy as np
@@ -352,13 +353,19 @@ def install_detectors(ref_speech_transformers=None) -> None:
     ref_speech_transformers._make_auditok_detector = _make_auditok_detector
 
 
-def assemble_sparse_reference(segment_labels, starts_seconds, total_duration: float, sample_rate: int):
+def assemble_sparse_reference(segment_labels, starts_seconds, total_duration: float, sample_rate: int, unknown=None):
     """Device-side scatter of ``MultiSegmentVideoSpeechTransformer.fit`` (speech_transformers.py:871-890):
     ``sparse = zeros(int(total_duration*sample_rate) + 2)`` and, for every sampled window,
     ``sparse[begin:end] = labels[:end-begin]`` with ``begin = int(start*sample_rate)`` clipped at the end.
     ``segment_labels`` are float32 CUDA label vectors (e.g. from :func:`detect_device`); windows are
     applied in the order given (later ones win where windows overlap, as in the reference's loop).
-    Returns the float32 CUDA vector; raises the reference's error when no frame is speech."""
+    Returns the float32 CUDA vector; raises the reference's error when no frame is speech.
+    ``unknown``: the value of the frames no window covers (default: the reference's zeros, which every aligner charges
+    as silence).  With ``unknown=0.5`` an unread frame maps to 2 * 0.5 - 1 = 0 and contributes nothing, so the one-shot
+    ``MaxScoreAligner`` path scores what the sampled plan (``sampled.py``) scores; the "no speech" check then looks at
+    the windows only."""
+    if unknown is not None and not (isinstance(unknown, (int, float)) and math.isfinite(unknown)):
+        raise ValueError("unknown=%r: need a finite fill value" % (unknown,))
     torch = _native.require_gpu()
     out_len = int(total_duration * sample_rate) + 2
     lens = np.array([int(t.numel()) for t in segment_labels], dtype=np.int64)
@@ -391,9 +398,17 @@ def assemble_sparse_reference(segment_labels, starts_seconds, total_duration: fl
         order = rest
     if sparse is None:
         sparse = torch.zeros(out_len, dtype=torch.float32, device="cuda")
-    if not bool((sparse > 0).any()):
+    covered = None
+    if unknown is not None:
+        covered = torch.zeros(out_len, dtype=torch.bool, device=sparse.device)
+        for a, n in zip(dst, lens):
+            if min(int(a + n), out_len) > max(int(a), 0):
+                covered[max(int(a), 0):min(int(a + n), out_len)] = True
+    if not bool((sparse > 0).any() if covered is None else (sparse[covered] > 0).any()):
         raise ValueError("Unable to detect speech in any sampled segment. "
                          "Perhaps try specifying a different stream / track, or a different vad.")
+    if covered is not None:
+        sparse = torch.where(covered, sparse, torch.full_like(sparse, float(unknown)))
     return sparse
 
 

@@ -1294,6 +1294,48 @@ int ffs_prog_append(ffs_prog_plan* plan, int n, const int32_t* slot, const void*
 int ffs_prog_reference(ffs_prog_plan* plan, int slot, const uint32_t** bits_dev, int64_t* len);
 int ffs_prog_close(ffs_prog_plan* plan, int n, const int32_t* slot);
 
+/* ---- sampled alignment: masked scores for a reference read in segments (csrc/ffs_sampled.h) ----------------------
+ * Replaces: the score behind the reference's --multi-segment-sync (MultiSegmentVideoSpeechTransformer,
+ * speech_transformers.py:760-903), which places a few decoded windows in a vector that is zero everywhere else, so that
+ * every cue on unread audio is charged as a mismatch.  Here unread frames contribute nothing.  Pinned against the numpy
+ * model tests/sampled_model.py.
+ *
+ * A sampled slot of an ffs_prog_plan holds a reference of declared length T = ref_total (1 <= T <= max_ref_samples) of
+ * which disjoint intervals [a, b) arrive in any order; K is their union (abutting intervals merge; at most
+ * FFS_PROG_MAX_INTERVALS merged intervals).  Candidates, levels and the lag window d in [-W+1, W] are ffs_prog_open's.
+ * Counts of candidate c at lag d over I(d) = { i : 0 <= i < S_c, i + d in K }: ov = |I|, n11 = sum_I s[i] r[i+d],
+ * n1x = sum_I s[i], nx1 = sum_I r[i+d].  Score: exactly 0.0 where ov = 0, else two_level_score's expression on
+ * (n11, n1x, nx1) with this ov in place of the overlap length -- what the reference aligner computes on a reference
+ * vector that holds 0.5 in every unread frame (2 * 0.5 - 1 = 0).  The records for a given K do not depend on the order
+ * or the cutting of the appends (all sums are integers), and for K = [0, L) they are ffs_prog_append's byte for byte.
+ *
+ * ffs_prog_open_sampled: ffs_prog_open plus ref_total[i]; K is empty.  A slot may be reopened as either kind.
+ * ffs_prog_append_at: bits [first_bit[i], first_bit[i] + n_new[i]) of the words at chunk_dev[i] become reference samples
+ * [position[i], position[i] + n_new[i]); then the candidates' ffs_quality_result records and the slot's ffs_prog_state
+ * (ref_len = |K|), as ffs_prog_append writes them.  n_new = 0 re-reports.  The cost of an append does not depend on
+ * what is already known, except that the slot's prefix popcounts are recomputed from position to T.
+ * ffs_prog_known (host only; queues nothing): the merged intervals, ascending, as bounds_out[2k], bounds_out[2k + 1];
+ * *n_out of them; FFS_E_INVALID when cap is too small.
+ * ffs_prog_reference on a sampled slot: the bits (zero outside K) and len = T.
+ * ffs_prog_plan_sampled_bytes: what sampled slots add to the plan, made by the first ffs_prog_open_sampled (0 before):
+ * 12 * lpad bytes per slot and candidate for the ov, n1x, nx1 curves, the descriptors of one call, and the host's
+ * interval tables (16 * FFS_PROG_MAX_INTERVALS bytes per slot).  ffs_prog_plan_workspace_bytes does not include it.
+ *
+ * Every refusal is FFS_E_INVALID before any launch, state and outputs untouched: everything ffs_prog_open /
+ * ffs_prog_append refuse, T outside [1, max_ref_samples], position < 0 or position + n_new > T, an interval that
+ * overlaps K, more than FFS_PROG_MAX_INTERVALS intervals after merging, ffs_prog_append on a sampled slot,
+ * ffs_prog_append_at on a prefix slot. */
+#define FFS_PROG_MAX_INTERVALS 256
+int ffs_prog_open_sampled(ffs_prog_plan* plan, int n, const int32_t* slot, const int32_t* n_cand, const void* const* sub_ptr,
+                          const int64_t* sub_len, const double* sub_lo, const double* sub_hi, const double* ref_lo,
+                          const double* ref_hi, const int64_t* max_offset_samples, const int64_t* ref_total,
+                          void* hip_stream);
+int ffs_prog_append_at(ffs_prog_plan* plan, int n, const int32_t* slot, const void* const* chunk_dev, const int32_t* first_bit,
+                       const int64_t* position, const int64_t* n_new, int top_k, int64_t exclusion_samples,
+                       ffs_quality_result* cand_out_dev, ffs_prog_state* state_out_dev, void* hip_stream);
+int ffs_prog_known(ffs_prog_plan* plan, int slot, int64_t* bounds_out, int cap, int* n_out);
+int64_t ffs_prog_plan_sampled_bytes(const ffs_prog_plan* plan);
+
 /* Thread-local description of the last error returned on this thread ("" if none). */
 const char* ffs_last_error(void);
 

@@ -48,16 +48,9 @@ def timed(prepare, fn, repeats):
     return best
 
 
-def end_to_end(n_files, minutes):
-    """Reading 3: bench.py's end-to-end shape (per file 48 kHz s16le PCM in pinned host memory whose loud frames follow
-    the subtitles stretched by one of the seven ratios and shifted by a known offset).  Wall clock around whole calls,
-    one warm run first: full ingest (``detect_pinned_stream``) + ``quality_sync`` against ``progressive_sync`` on
-    ``pcm_label_chunks`` of the same tensors with the default StopRule."""
-    import time
-
-    from ffsubsync_amd import progressive
+def make_files(n_files, minutes):
+    """([(pinned int16 PCM tensor, track)], [(true ratio index, true offset)]) of the end-to-end shape."""
     from ffsubsync_amd.constants import candidate_ratios
-    from ffsubsync_amd.speech_transformers import detect_pinned_stream
 
     ratios = candidate_ratios()
     frame, n_frames = 480, int(minutes * 60 * 100)
@@ -79,6 +72,21 @@ def end_to_end(n_files, minutes):
         del pcm, sigma
         files.append((host, track))
         truth.append((idx, shift))
+    return files, truth
+
+
+def end_to_end(n_files, minutes):
+    """Reading 3: bench.py's end-to-end shape (per file 48 kHz s16le PCM in pinned host memory whose loud frames follow
+    the subtitles stretched by one of the seven ratios and shifted by a known offset).  Wall clock around whole calls,
+    one warm run first: full ingest (``detect_pinned_stream``) + ``quality_sync`` against ``progressive_sync`` on
+    ``pcm_label_chunks`` of the same tensors with the default StopRule."""
+    import time
+
+    from ffsubsync_amd import progressive
+    from ffsubsync_amd.speech_transformers import detect_pinned_stream
+
+    files, truth = make_files(n_files, minutes)
+    n_frames = int(minutes * 60 * 100)
 
     def full():
         refs = [detect_pinned_stream(host, 100, 48000, 0.0, packed=True) for host, _ in files]
