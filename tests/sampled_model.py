@@ -63,6 +63,28 @@ def counts_brute(ref01, known, sub01, W):
     return out
 
 
+def counts_direct(ref01, known, sub01, W):
+    """(n11, n1x, nx1, ov) of every lag of the window from scratch over the whole known set, in int64, with nothing
+    incremental: no append order, no interval as it was fed, no word.  With k the known mask and kr = k & r,
+        ov(d) = sum_p k[p] [0 <= p - d < S]    n1x(d) = sum_p k[p] s[p - d]
+        nx1(d) = sum_p kr[p] [0 <= p - d < S]  n11(d) = sum_p kr[p] s[p - d]
+    and each sum over p runs over the maximal runs [a, b) of its mask, where it is a difference of two entries of a prefix
+    sum (of ones, or of s) at b - d and a - d cut to [0, S]."""
+    r, s, k = np.asarray(ref01) != 0, np.asarray(sub01) != 0, np.asarray(known) != 0
+    lags = pm.window_lags(W)
+    ones = np.arange(s.size + 1, dtype=np.int64)
+    cs = np.concatenate([[0], np.cumsum(s.astype(np.int64))])
+
+    def over(mask, prefix):
+        edges = np.flatnonzero(np.diff(np.concatenate([[0], mask.astype(np.int8), [0]])))
+        total = np.zeros(lags.size, np.int64)
+        for a, b in zip(edges[::2], edges[1::2]):
+            total += prefix[np.clip(b - lags, 0, s.size)] - prefix[np.clip(a - lags, 0, s.size)]
+        return total
+
+    return np.stack([over(k & r, cs), over(k, cs), over(k & r, ones), over(k, ones)])
+
+
 def scores_from_counts(n11, n1x, nx1, ov, ref_levels, sub_levels, W):
     """progressive_model.scores_from_counts with the overlap given: (lags, numpy scores, exact_at, slack)."""
     lags = pm.window_lags(W)

@@ -4,6 +4,7 @@ Shapes from tests/sampled_cases.py; the record helpers are tests/test_gpu_progre
 import numpy as np
 import pytest
 
+import progressive_cases as pc
 import progressive_model as pm
 import quality_model as qm
 import sampled_cases as sc
@@ -27,11 +28,12 @@ def _open_sampled(plan, slots, cases, cands, rows=None):
                       [k["ref_levels"][1] for k in sel], [k["W"] for k in sel], [k["T"] for k in sel])
 
 
-def _plan_for(cases, n_slots=None):
+def _plan_for(cases, n_slots=None, max_lags=None):
     from ffsubsync_amd import _native
 
-    return _native.ProgPlan(n_slots or len(cases), max(len(k["cands"]) for k in cases), 2 * max(k["W"] for k in cases),
-                            max(k["T"] for k in cases), max(len(s) for k in cases for s, _ in k["cands"]))
+    return _native.ProgPlan(n_slots or len(cases), max(len(k["cands"]) for k in cases),
+                            max_lags or 2 * max(k["W"] for k in cases), max(k["T"] for k in cases),
+                            max(len(s) for k in cases for s, _ in k["cands"]))
 
 
 def _reference_bits(plan, slot, T):
@@ -47,11 +49,11 @@ def _reference_bits(plan, slot, T):
     return np.unpackbits(words.view(np.uint8), bitorder="little")[:T].astype(bool), words
 
 
-def _run_script(case, script, poison=True):
+def _run_script(case, script, poison=True, max_lags=None):
     """One sampled slot through its appends, checked against the model after each; returns (raw bytes after the last,
-    the model slot)."""
+    the model slot).  ``max_lags``: the plan's, where it is not the case's own 2W."""
     n_cand = len(case["cands"])
-    plan = _plan_for([case])
+    plan = _plan_for([case], max_lags=max_lags)
     cands = Cands([case])
     slot = sm.Slot(case["cands"], case["ref_levels"], case["W"], case["T"])
     last = None
@@ -89,6 +91,82 @@ SHAPES = sc.shape_cases()
 def test_every_named_shape_equals_the_model_after_every_append(name, case, script):
     """S1 on 2W = 64, 4096 and 4098 with first_bit 0, 5 and 31: what each script holds is in tests/sampled_cases.py."""
     _run_script(case, script)
+
+
+TILES = sc.tile_cases()
+
+
+@pytest.mark.parametrize("name,case,script", TILES, ids=[c[0] for c in TILES])
+def test_windows_of_whole_tiles_the_tie_run_and_the_limit_window(name, case, script):
+    """2W = 4096, 4098 and 8192 with the candidates planted on the tile edges, the peaks picked from a run of exact 0.0
+    scores that crosses a tile edge, and the ABI limit 2W = 262 144 on a plan of exactly that many lags (64 tiles,
+    lpad = max_lags): what each script holds is in tests/sampled_cases.py and asserted in
+    tests/test_sampled_model_host.py."""
+    from ffsubsync_amd import _native
+
+    assert 2 * case["W"] <= _native.PROG_MAX_LAGS == pc.MAX_LAGS
+    limit = 2 * case["W"] == _native.PROG_MAX_LAGS
+    _run_script(case, script, max_lags=_native.PROG_MAX_LAGS if limit else None)
+
+
+def test_three_windows_in_one_call_leave_the_surplus_tiles_alone():
+    """W = 2048, 4096 and 16 in three sampled slots appended in one call: the grid has the two tiles of the widest window
+    for every slot, and the workgroups of a tile beyond a slot's own window must return."""
+    cases, rounds = sc.tile_slot_cases()
+    plan = _plan_for(cases)
+    cands = Cands(cases)
+    models = [sm.Slot(k["cands"], k["ref_levels"], k["W"], k["T"]) for k in cases]
+    mc = plan.max_cand
+    try:
+        _open_sampled(plan, [0, 1, 2], cases, cands)
+        for rnd, spec in enumerate(rounds):
+            chunks = [k["ref"][a:a + n] for k, (a, n) in zip(cases, spec)]
+            keep = [_dev(_words(ch, 8 + i)) for i, ch in enumerate(chunks)]
+            out = Outputs(3, mc)
+            plan.append_at([0, 1, 2], [w.data_ptr() for w in keep], [8, 9, 10], [a for a, _ in spec], [n for _, n in spec], 8,
+                           40, *out.views())
+            recs, states = out.read()
+            for i, k in enumerate(cases):
+                reps, mstate = models[i].append_at(spec[i][0], chunks[i], 8, 40)
+                _check(recs[i], states[i], reps, mstate, len(k["cands"]), 8, ("round", rnd, "slot", i))
+                assert [tuple(x) for x in plan.known(i)] == models[i].intervals
+    finally:
+        plan.close()
+
+
+ROW_ENDS = sc.row_end_cases()
+
+
+@pytest.mark.parametrize("T,cases,steps", ROW_ENDS, ids=["T%d" % c[0] for c in ROW_ENDS])
+def test_a_segment_ending_at_the_plans_max_ref_samples_stays_inside_the_slots_row(T, cases, steps):
+    """Two sampled slots on a plan with ``max_ref_samples`` = T = the slots' declared length, T % 32 = 0, 1 and 31 and no
+    padding word behind a row: slot 0 takes a segment ending at T, slot 1 -- the next row of ``ref`` and ``pre_r`` -- is
+    fed before and after, its later segments over the words a stray write would land in.  A reference word written past
+    slot 0's row shows in slot 1's reference bits, and in its records once a segment is fed over it; a stray ``pre_r``
+    entry would not show (every record reads differences of ``pre_r`` from the appended interval's first word on, and the
+    append recomputes the row from there: DESIGN 3.23)."""
+    plan = _plan_for(cases)
+    assert plan.max_cand == 2
+    cands = Cands(cases)
+    models = [sm.Slot(k["cands"], k["ref_levels"], k["W"], T) for k in cases]
+    try:
+        _open_sampled(plan, [0, 1], cases, cands)
+        for s, a, n, fb in steps:
+            chunk = cases[s]["ref"][a:a + n]
+            words = _dev(_words(chunk, fb))
+            out = Outputs(1, 2)
+            plan.append_at([s], [words.data_ptr()], [fb], [a], [n], 3, 8, *out.views())
+            recs, states = out.read()
+            reps, mstate = models[s].append_at(a, chunk, 3, 8)
+            _check(recs[0], states[0], reps, mstate, 2, 3, ("slot", s, "a", a, "n", n))
+        for s in (0, 1):
+            bits, words = _reference_bits(plan, s, T)
+            assert (bits == (models[s].ref & models[s].known)).all(), ("slot", s)
+            if T % 32:
+                assert int(words[-1]) >> (T % 32) == 0, "bits beyond T"
+            assert [tuple(x) for x in plan.known(s)] == models[s].intervals
+    finally:
+        plan.close()
 
 
 def test_a_segment_beyond_every_subtitles_reach_alone_is_flat_zero():
