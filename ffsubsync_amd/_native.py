@@ -149,6 +149,19 @@ SWEEP_PROFILE_DTYPE = np.dtype(
 )
 SWEEP_PROFILE_BYTES = 232
 assert SWEEP_PROFILE_DTYPE.itemsize == SWEEP_PROFILE_BYTES
+# ffs_null_result and the limits of ffs_surrogate_lists (include/ffsubsync_amd.h; static size 56 bytes)
+SURR_MAX_UNITS = 8192  # FFS_SURR_MAX_UNITS: units (runs but the last) of a list
+SURR_MAX_K = 4096  # FFS_SURR_MAX_K: surrogates per vector
+SURR_BAD_ODD, SURR_BAD_TRUNCATED, SURR_BAD_BOUND, SURR_BAD_UNITS = 1, 2, 4, 8  # FFS_SURR_BAD_*: bits of a vector's status
+NULL_FLAT = 1  # FFS_NULL_FLAT: every usable null scores the same, or none is left (std = 0)
+NULL_EMPTY = 2  # FFS_NULL_EMPTY: no usable null record, or the real record is not usable
+NULL_AMBIGUOUS = 4  # FFS_NULL_AMBIGUOUS: some record carried FFS_FLAG_AMBIGUOUS
+NULL_RESULT_DTYPE = np.dtype(
+    [("real_score", "<f8"), ("null_mean", "<f8"), ("null_std", "<f8"), ("null_min", "<f8"), ("null_max", "<f8"),
+     ("n_null", "<i4"), ("n_ge", "<i4"), ("n_gt", "<i4"), ("flags", "<i4")], align=True
+)
+NULL_RESULT_BYTES = 56
+assert NULL_RESULT_DTYPE.itemsize == NULL_RESULT_BYTES
 # ffs_prog_state (include/ffsubsync_amd.h; static size 64 bytes)
 PROG_STATE_DTYPE = np.dtype(
     [("ref_len", "<i8"), ("offset", "<i8"), ("score", "<f8"), ("mean", "<f8"), ("std", "<f8"), ("runner_up", "<f8"),
@@ -234,6 +247,8 @@ EXPORTED_SYMBOLS = (
     "ffs_match_plan_workspace_bytes",
     "ffs_match_quality_batch",
     "ffs_sweep_peaks",
+    "ffs_surrogate_lists",
+    "ffs_null_stats",
     "ffs_prog_plan_create",
     "ffs_prog_plan_destroy",
     "ffs_prog_plan_workspace_bytes",
@@ -532,6 +547,11 @@ def load():
                                                 c.c_void_p, c.c_void_p]
         lib.ffs_sweep_peaks.restype = c.c_int
         lib.ffs_sweep_peaks.argtypes = [c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_int64, c.c_void_p, c.c_void_p]
+        lib.ffs_surrogate_lists.restype = c.c_int
+        lib.ffs_surrogate_lists.argtypes = [c.c_void_p] * 5 + [c.c_int64, c.c_int, c.c_int, c.c_void_p, c.c_int64,
+                                                                c.c_void_p, c.c_void_p]
+        lib.ffs_null_stats.restype = c.c_int
+        lib.ffs_null_stats.argtypes = [c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_void_p]
         lib.ffs_prog_plan_create.restype = c.c_int
         lib.ffs_prog_plan_create.argtypes = [c.c_int, c.c_int, c.c_int, c.c_int64, c.c_int64, c.c_int64, c.POINTER(c.c_void_p)]
         lib.ffs_prog_plan_destroy.restype = c.c_int
@@ -868,6 +888,42 @@ def sweep_peaks(records, first, n_files: int, top_k: int, exclusion_steps: int, 
         raise ValueError("output buffer too small")
     check(load().ffs_sweep_peaks(records.data_ptr(), first.data_ptr(), n_files, int(top_k), int(exclusion_steps),
                                  out.data_ptr(), current_stream_ptr(torch)))
+    return out
+
+
+def surrogate_lists(list_ptr, n_bound, seeds, out_off, out_cap, n_surrogates: int, block_units: int, out, status) -> None:
+    """``ffs_surrogate_lists`` on the current stream: per vector the device pointer of its ``ffs_runs_list``, a host-known
+    bound of its length, its uint32 seed, the byte offset in ``out`` (uint8 / int32 CUDA tensor) of the first of its
+    ``n_surrogates`` back-to-back blocks and their capacity in entries; ``status``: int32 CUDA tensor, one per vector."""
+    torch = require_gpu()
+    list_ptr = np.ascontiguousarray(list_ptr, dtype=np.uint64)
+    n_bound = np.ascontiguousarray(n_bound, dtype=np.int32)
+    seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
+    out_off = np.ascontiguousarray(out_off, dtype=np.int64)
+    out_cap = np.ascontiguousarray(out_cap, dtype=np.int64)
+    n_vec = list_ptr.size
+    if not (n_bound.size == seeds.size == out_off.size == out_cap.size == n_vec):
+        raise ValueError("the vector tables must have the same length")
+    if status.dtype != torch.int32 or status.numel() < n_vec or not status.is_contiguous():
+        raise ValueError("status must be a contiguous int32 tensor with one entry per vector")
+    check(load().ffs_surrogate_lists(list_ptr.ctypes.data, n_bound.ctypes.data, seeds.ctypes.data, out_off.ctypes.data,
+                                     out_cap.ctypes.data, n_vec, int(n_surrogates), int(block_units), out.data_ptr(),
+                                     _nbytes(out), status.data_ptr(), current_stream_ptr(torch)))
+
+
+def null_stats(records, n_files: int, n_surrogates: int, out=None):
+    """``ffs_null_stats`` on the current stream: ``records`` a CUDA tensor of n_files * (n_surrogates + 1)
+    ffs_cand_result records (24 bytes each; per file the real list's solve, then the surrogates'); returns the uint8 CUDA
+    tensor of n_files ``NULL_RESULT_DTYPE`` records (``out``, if given, is written in place)."""
+    torch = require_gpu()
+    n_files, k = int(n_files), int(n_surrogates)
+    if n_files < 0 or k < 0 or _nbytes(records) < n_files * (k + 1) * 24:
+        raise ValueError("the table holds fewer than n_files * (n_surrogates + 1) records")
+    if out is None:
+        out = torch.empty(max(n_files, 1) * NULL_RESULT_BYTES, dtype=torch.uint8, device=records.device)
+    elif _nbytes(out) < n_files * NULL_RESULT_BYTES:
+        raise ValueError("output buffer too small")
+    check(load().ffs_null_stats(records.data_ptr(), n_files, k, out.data_ptr(), current_stream_ptr(torch)))
     return out
 
 

@@ -1226,6 +1226,73 @@ _Static_assert(sizeof(ffs_sweep_profile) == 232, "ffs_sweep_profile is 232 bytes
 int ffs_sweep_peaks(const ffs_cand_result* rec_dev, const int64_t* first_dev, int n_files, int top_k,
                     int64_t exclusion_steps, ffs_sweep_profile* out_dev, void* hip_stream);
 
+/* ---- shuffled-cue significance: surrogate lists and the empirical null of their scores (csrc/ffs_surrogate.h) ---
+ * Replaces: nothing in the reference.  "Is this subtitle related to this audio at all?" answered without a tuned
+ * threshold (ffsubsync_amd/surrogate.py): the window-maximum score of the real subtitle is compared with the scores of K
+ * surrogate subtitles that keep every cue, every silence, the length, the number of speech samples and the reference,
+ * and differ only in which cue sits where.  Both calls are stateless: no plan, everything is queued on hip_stream,
+ * nothing is waited for or read back.  Pinned against tests/surrogate_model.py.
+ *
+ * ffs_surrogate_lists.  Vector v: a valid ffs_runs_list at list_dev[v] (device, 8-byte aligned) with n boundaries,
+ * m = n / 2 runs; n_bound[v] = a host-known upper bound of n (the convention of vec_max_boundaries); seed[v].  Unit j,
+ * j < m - 1, is run j together with the silence behind it: pos[2j+2] - pos[2j] samples of which pos[2j+1] - pos[2j]
+ * are ones.  The silence in front of run 0, the last run and the tail behind it stay where they are.  The U = m - 1
+ * units are cut into nb = ceil(U / block_units) blocks of block_units consecutive units (the last may be short).
+ * Surrogate s (0 <= s < n_surrogates) places the blocks in ascending order of (key(seed, s, b), b),
+ *   key = fmix32(fmix32(seed + 0x9E3779B9 * (s + 1)) ^ b),
+ *   fmix32(h): h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16   (all uint32),
+ * units keeping their order inside a block (fmix32 is a bijection of uint32, so two blocks of one surrogate never share
+ * a key: the index completes the order's statement and never decides it).  Its list -- the same n, ones and len, cap = out_cap[v], pos strictly
+ * ascending, ones_before exact, e[n] = (INT32_MAX, ones) -- is written to out_dev + out_off[v] + s *
+ * ffs_runs_list_bytes(out_cap[v]): the K blocks of a vector lie back to back.  With m <= 2 it equals the input.  Only
+ * the header and the n + 1 entries are written.  status_dev[v] (int32, always written) = 0, or FFS_SURR_BAD_* bits for
+ * a list whose header is odd, truncated (n >= cap, or negative), above its bound or above the unit limit: all K
+ * surrogates of such a list are empty lists (n = 0, ones = 0, the same len, the sentinel only); other vectors of the
+ * call are not affected.  Host arrays may be freed after return.
+ * FFS_E_INVALID, before any launch, outputs and status untouched: n_surrogates outside [1, FFS_SURR_MAX_K], block_units
+ * outside [1, FFS_SURR_MAX_UNITS], a negative n_vec, out_bytes or n_bound, a null or misaligned pointer (lists and
+ * output 8 bytes, status 4), out_off not a multiple of 8, out_cap < n_bound + 1 or out_cap >= 2^28, K blocks that do
+ * not fit [out_off, out_bytes), or n_vec * n_surrogates >= 2^31 (one workgroup per surrogate: more than a grid holds).
+ *
+ * ffs_null_stats.  File f owns the n_surrogates + 1 records rec_dev[f * (n_surrogates + 1) ..]: record 0 the real
+ * list's solve, the others the surrogates'.  A record is USABLE when its score is finite and its flags do not carry
+ * FFS_FLAG_EMPTY_WINDOW.  real_score = record 0's score; n_null = usable null records; null_mean / null_std
+ * (population, two passes in a fixed order; std exactly 0 and mean = that score when min == max) and null_min /
+ * null_max over them (all 0 with none); n_ge / n_gt = usable nulls with score >= / > real_score (0 when record 0 is not
+ * usable).  flags: FFS_NULL_FLAT (no usable null, or all equal), FFS_NULL_EMPTY (no usable null, or record 0 not
+ * usable), FFS_NULL_AMBIGUOUS (some record of the file carried FFS_FLAG_AMBIGUOUS).  The host derives
+ * z = (real_score - null_mean) / null_std (0 when FLAT) and p = (1 + n_ge) / (1 + n_null).  Records are read, never
+ * written; exactly n_files output records are written.  FFS_E_INVALID for n_surrogates outside [1, FFS_SURR_MAX_K],
+ * n_files < 0, or a null or misaligned (8 bytes) pointer: refused before any launch, the outputs untouched. */
+#define FFS_SURR_MAX_UNITS 8192 /* units of a list: lists of up to 16 386 boundaries */
+#define FFS_SURR_MAX_K 4096     /* surrogates per vector */
+#define FFS_SURR_BAD_ODD 1       /* status: n is odd */
+#define FFS_SURR_BAD_TRUNCATED 2 /* status: n >= cap (or negative) */
+#define FFS_SURR_BAD_BOUND 4     /* status: n > n_bound */
+#define FFS_SURR_BAD_UNITS 8     /* status: more than FFS_SURR_MAX_UNITS units */
+#define FFS_NULL_FLAT 1      /* every usable null scores the same (or none is left): std = 0 */
+#define FFS_NULL_EMPTY 2     /* no usable null record, or the real record is not usable */
+#define FFS_NULL_AMBIGUOUS 4 /* some record carried FFS_FLAG_AMBIGUOUS */
+
+typedef struct ffs_null_result {
+    double real_score;           /* record 0's score */
+    double null_mean, null_std;  /* of the usable null scores */
+    double null_min, null_max;
+    int32_t n_null, n_ge, n_gt;
+    int32_t flags;               /* FFS_NULL_* */
+} ffs_null_result;
+#ifdef __cplusplus
+static_assert(sizeof(ffs_null_result) == 56, "ffs_null_result is 56 bytes");
+#else
+_Static_assert(sizeof(ffs_null_result) == 56, "ffs_null_result is 56 bytes");
+#endif
+
+int ffs_surrogate_lists(const void* const* list_dev, const int32_t* n_bound, const uint32_t* seed, const int64_t* out_off,
+                        const int64_t* out_cap, int64_t n_vec, int n_surrogates, int block_units, void* out_dev,
+                        int64_t out_bytes, int32_t* status_dev, void* hip_stream);
+int ffs_null_stats(const ffs_cand_result* rec_dev, int n_files, int n_surrogates, ffs_null_result* out_dev,
+                   void* hip_stream);
+
 /* ---- progressive alignment: the quality report of a growing reference prefix (csrc/ffs_progressive.h) -----------
  * Replaces: nothing in the reference (its --multi-segment-sync, speech_transformers.py:760-903, samples eight minutes
  * and hopes they suffice).  Score counts are additive over the reference, so after every appended chunk of reference
