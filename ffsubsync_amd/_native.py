@@ -162,6 +162,21 @@ NULL_RESULT_DTYPE = np.dtype(
 )
 NULL_RESULT_BYTES = 56
 assert NULL_RESULT_DTYPE.itemsize == NULL_RESULT_BYTES
+# ffs_stability_result and the limits of ffs_subsample_lists (include/ffsubsync_amd.h; static size 112 bytes)
+STAB_MAX_K = 4096  # FFS_STAB_MAX_K: subsamples per vector
+STAB_MAX_BLOCK_RUNS = 1 << 24  # FFS_STAB_MAX_BLOCK_RUNS
+SUB_BAD_ODD, SUB_BAD_TRUNCATED, SUB_BAD_BOUND = 1, 2, 4  # FFS_SUB_BAD_*: bits of a vector's status
+STAB_EMPTY = 1  # FFS_STAB_EMPTY: the real record is not usable, or no subsample record is
+STAB_AMBIGUOUS = 2  # FFS_STAB_AMBIGUOUS: some record carried FFS_FLAG_AMBIGUOUS
+STAB_NO_PAIRS = 4  # FFS_STAB_NO_PAIRS: no pair (2j, 2j + 1) with both members usable
+STABILITY_RESULT_DTYPE = np.dtype(
+    [("real_score", "<f8"), ("real_offset", "<i8"), ("off_min", "<i8"), ("off_max", "<i8"), ("off_median", "<i8"),
+     ("off_lo", "<i8"), ("off_hi", "<i8"), ("max_dev", "<i8"), ("max_pair_gap", "<i8"), ("pair_score_min", "<f8"),
+     ("n_sub", "<i4"), ("n_within", "<i4"), ("n_pairs", "<i4"), ("n_pairs_within", "<i4"), ("tol", "<i8"), ("flags", "<i4"),
+     ("reserved", "<i4")], align=True
+)
+STABILITY_RESULT_BYTES = 112
+assert STABILITY_RESULT_DTYPE.itemsize == STABILITY_RESULT_BYTES
 # ffs_prog_state (include/ffsubsync_amd.h; static size 64 bytes)
 PROG_STATE_DTYPE = np.dtype(
     [("ref_len", "<i8"), ("offset", "<i8"), ("score", "<f8"), ("mean", "<f8"), ("std", "<f8"), ("runner_up", "<f8"),
@@ -249,6 +264,8 @@ EXPORTED_SYMBOLS = (
     "ffs_sweep_peaks",
     "ffs_surrogate_lists",
     "ffs_null_stats",
+    "ffs_subsample_lists",
+    "ffs_offset_stats",
     "ffs_prog_plan_create",
     "ffs_prog_plan_destroy",
     "ffs_prog_plan_workspace_bytes",
@@ -552,6 +569,10 @@ def load():
                                                                 c.c_void_p, c.c_void_p]
         lib.ffs_null_stats.restype = c.c_int
         lib.ffs_null_stats.argtypes = [c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_void_p]
+        lib.ffs_subsample_lists.restype = c.c_int
+        lib.ffs_subsample_lists.argtypes = lib.ffs_surrogate_lists.argtypes
+        lib.ffs_offset_stats.restype = c.c_int
+        lib.ffs_offset_stats.argtypes = [c.c_void_p, c.c_int, c.c_int, c.c_int64, c.c_void_p, c.c_void_p]
         lib.ffs_prog_plan_create.restype = c.c_int
         lib.ffs_prog_plan_create.argtypes = [c.c_int, c.c_int, c.c_int, c.c_int64, c.c_int64, c.c_int64, c.POINTER(c.c_void_p)]
         lib.ffs_prog_plan_destroy.restype = c.c_int
@@ -924,6 +945,41 @@ def null_stats(records, n_files: int, n_surrogates: int, out=None):
     elif _nbytes(out) < n_files * NULL_RESULT_BYTES:
         raise ValueError("output buffer too small")
     check(load().ffs_null_stats(records.data_ptr(), n_files, k, out.data_ptr(), current_stream_ptr(torch)))
+    return out
+
+
+def subsample_lists(list_ptr, n_bound, seeds, out_off, out_cap, n_subsamples: int, block_runs: int, out, status) -> None:
+    """``ffs_subsample_lists`` on the current stream: the arguments of ``surrogate_lists``, with ``n_subsamples`` thinned
+    lists per vector and blocks of ``block_runs`` runs."""
+    torch = require_gpu()
+    list_ptr = np.ascontiguousarray(list_ptr, dtype=np.uint64)
+    n_bound = np.ascontiguousarray(n_bound, dtype=np.int32)
+    seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
+    out_off = np.ascontiguousarray(out_off, dtype=np.int64)
+    out_cap = np.ascontiguousarray(out_cap, dtype=np.int64)
+    n_vec = list_ptr.size
+    if not (n_bound.size == seeds.size == out_off.size == out_cap.size == n_vec):
+        raise ValueError("the vector tables must have the same length")
+    if status.dtype != torch.int32 or status.numel() < n_vec or not status.is_contiguous():
+        raise ValueError("status must be a contiguous int32 tensor with one entry per vector")
+    check(load().ffs_subsample_lists(list_ptr.ctypes.data, n_bound.ctypes.data, seeds.ctypes.data, out_off.ctypes.data,
+                                     out_cap.ctypes.data, n_vec, int(n_subsamples), int(block_runs), out.data_ptr(),
+                                     _nbytes(out), status.data_ptr(), current_stream_ptr(torch)))
+
+
+def offset_stats(records, n_files: int, n_subsamples: int, tol: int, out=None):
+    """``ffs_offset_stats`` on the current stream: ``records`` a CUDA tensor of n_files * (n_subsamples + 1)
+    ffs_cand_result records (24 bytes each; per file the real list's solve, then the subsamples'); returns the uint8 CUDA
+    tensor of n_files ``STABILITY_RESULT_DTYPE`` records (``out``, if given, is written in place)."""
+    torch = require_gpu()
+    n_files, k = int(n_files), int(n_subsamples)
+    if n_files < 0 or k < 0 or _nbytes(records) < n_files * (k + 1) * 24:
+        raise ValueError("the table holds fewer than n_files * (n_subsamples + 1) records")
+    if out is None:
+        out = torch.empty(max(n_files, 1) * STABILITY_RESULT_BYTES, dtype=torch.uint8, device=records.device)
+    elif _nbytes(out) < n_files * STABILITY_RESULT_BYTES:
+        raise ValueError("output buffer too small")
+    check(load().ffs_offset_stats(records.data_ptr(), n_files, k, int(tol), out.data_ptr(), current_stream_ptr(torch)))
     return out
 
 

@@ -43,6 +43,7 @@
 #include "ffs_drift_range_report.h"
 #include "ffs_sweep.h"
 #include "ffs_surrogate.h"
+#include "ffs_stability.h"
 #include "ffs_progressive.h"
 #include "ffs_sampled.h"
 
@@ -3197,6 +3198,78 @@ int ffs_null_stats(const ffs_cand_result* rec_dev, int n_files, int n_surrogates
     if ((rc_dev = guard.enter(out_dev))) return rc_dev;
     hipLaunchKernelGGL(k_null_stats, dim3((unsigned)n_files), dim3(SWEEP_THREADS), 0, (hipStream_t)hip_stream,
                        (const CandResult*)rec_dev, n_surrogates, (NullResult*)out_dev);
+    HIP_TRY(hipGetLastError());
+    return FFS_OK;
+}
+
+int ffs_subsample_lists(const void* const* list_dev, const int32_t* n_bound, const uint32_t* seed, const int64_t* out_off,
+                        const int64_t* out_cap, int64_t n_vec, int n_subsamples, int block_runs, void* out_dev,
+                        int64_t out_bytes, int32_t* status_dev, void* hip_stream) {
+    if (n_vec < 0 || out_bytes < 0)
+        return fail(FFS_E_INVALID, "ffs_subsample_lists: n_vec=%lld or out_bytes=%lld is negative", (long long)n_vec, (long long)out_bytes);
+    if (n_subsamples < 1 || n_subsamples > STAB_MAX_K)
+        return fail(FFS_E_INVALID, "ffs_subsample_lists: n_subsamples=%d outside [1, %d]", n_subsamples, STAB_MAX_K);
+    if (block_runs < 1 || block_runs > STAB_MAX_BLOCK_RUNS)
+        return fail(FFS_E_INVALID, "ffs_subsample_lists: block_runs=%d outside [1, %d]", block_runs, STAB_MAX_BLOCK_RUNS);
+    if (n_vec == 0) return FFS_OK;
+    if (!list_dev || !n_bound || !seed || !out_off || !out_cap) return fail(FFS_E_INVALID, "ffs_subsample_lists: null vector table");
+    if (!out_dev || !status_dev) return fail(FFS_E_INVALID, "ffs_subsample_lists: null output or status pointer");
+    if (((uintptr_t)out_dev & 7) || ((uintptr_t)status_dev & 3))
+        return fail(FFS_E_INVALID, "ffs_subsample_lists: misaligned output (8 bytes) or status (4 bytes) pointer");
+    if (n_vec * n_subsamples >= (int64_t(1) << 31))
+        return fail(FFS_E_INVALID, "ffs_subsample_lists: n_vec * n_subsamples = %lld, need < 2^31", (long long)(n_vec * n_subsamples));
+    for (int64_t v = 0; v < n_vec; ++v) {
+        if (!list_dev[v] || ((uintptr_t)list_dev[v] & 7))
+            return fail(FFS_E_INVALID, "ffs_subsample_lists: vector %lld: null or misaligned list pointer", (long long)v);
+        if (n_bound[v] < 0) return fail(FFS_E_INVALID, "ffs_subsample_lists: vector %lld: n_bound=%d is negative", (long long)v, n_bound[v]);
+        if (out_cap[v] < (int64_t)n_bound[v] + 1 || out_cap[v] >= (int64_t(1) << 28))
+            return fail(FFS_E_INVALID, "ffs_subsample_lists: vector %lld: capacity %lld below n_bound + 1 = %lld (or 2^28 and more)",
+                        (long long)v, (long long)out_cap[v], (long long)n_bound[v] + 1);
+        if (out_off[v] < 0 || (out_off[v] & 7) || out_off[v] > out_bytes ||
+            ffs_runs_list_bytes(out_cap[v]) * n_subsamples > out_bytes - out_off[v])
+            return fail(FFS_E_INVALID, "ffs_subsample_lists: vector %lld: its %d blocks lie outside the buffer or are misaligned",
+                        (long long)v, n_subsamples);
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    DeviceGuard guard;
+    int rc_dev;
+    if ((rc_dev = guard.enter(out_dev))) return rc_dev;
+    PinnedStage* stage = nullptr;
+    int rc = stage_acquire((size_t)n_vec * sizeof(SurrVec), &stage);
+    if (rc) return rc;
+    SurrVec* hv = (SurrVec*)stage->host;
+    for (int64_t v = 0; v < n_vec; ++v)
+        hv[v] = SurrVec{(const char*)list_dev[v], (long long)out_off[v], seed[v], n_bound[v], (int32_t)out_cap[v], 0};
+    SurrVec* d = nullptr;
+    HIP_TRY(hipMallocAsync((void**)&d, (size_t)n_vec * sizeof(SurrVec), st));
+    if (hipMemcpyAsync(d, hv, (size_t)n_vec * sizeof(SurrVec), hipMemcpyHostToDevice, st) != hipSuccess)
+        rc = fail(FFS_E_HIP, "ffs_subsample_lists: copying the vector table failed");
+    if (rc == FFS_OK && hipEventRecord(stage->done, st) == hipSuccess) stage->pending = true;
+    if (rc == FFS_OK) {
+        hipLaunchKernelGGL(k_subsample_lists, dim3((unsigned)(n_vec * n_subsamples)), dim3(STAB_THREADS), 0, st, (const SurrVec*)d,
+                           n_subsamples, block_runs, (char*)out_dev, status_dev);
+        if (hipGetLastError() != hipSuccess) rc = fail(FFS_E_HIP, "k_subsample_lists launch failed");
+    }
+    (void)hipFreeAsync(d, st);
+    return rc;
+}
+
+int ffs_offset_stats(const ffs_cand_result* rec_dev, int n_files, int n_subsamples, int64_t tol, ffs_stability_result* out_dev,
+                     void* hip_stream) {
+    static_assert(sizeof(ffs_stability_result) == sizeof(StabilityResult), "device records must match the header's");
+    if (n_files < 0) return fail(FFS_E_INVALID, "ffs_offset_stats: n_files=%d is negative", n_files);
+    if (n_subsamples < 1 || n_subsamples > STAB_MAX_K)
+        return fail(FFS_E_INVALID, "ffs_offset_stats: n_subsamples=%d outside [1, %d]", n_subsamples, STAB_MAX_K);
+    if (tol < 0) return fail(FFS_E_INVALID, "ffs_offset_stats: tol=%lld is negative", (long long)tol);
+    if (!rec_dev || !out_dev) return fail(FFS_E_INVALID, "ffs_offset_stats: null record or output pointer");
+    if (((uintptr_t)rec_dev | (uintptr_t)out_dev) & 7)
+        return fail(FFS_E_INVALID, "ffs_offset_stats: misaligned record or output pointer (8 bytes)");
+    if (n_files == 0) return FFS_OK;
+    DeviceGuard guard;
+    int rc_dev;
+    if ((rc_dev = guard.enter(out_dev))) return rc_dev;
+    hipLaunchKernelGGL(k_offset_stats, dim3((unsigned)n_files), dim3(STAB_THREADS), 0, (hipStream_t)hip_stream,
+                       (const CandResult*)rec_dev, n_subsamples, (long long)tol, (StabilityResult*)out_dev);
     HIP_TRY(hipGetLastError());
     return FFS_OK;
 }

@@ -376,6 +376,45 @@ def _check_sync(problems, max_offset_seconds, ratios, sample_rate, start_seconds
     return w, ratios
 
 
+def _winning_lists(who, problems, ratios, w, sample_rate):
+    """The first half of ``null_sync`` (and of ``stability.stable_sync``): the seven-ratio solve of every problem and the
+    winners rasterised to boundary lists.  Returns (solver, records [n, ratios], winning index per file, winning ratio
+    per file, (buffer, byte offsets, lengths, bounds) of the lists, their boundary counts read back from the headers).
+    Refuses by name (``who``) a multi-level or too dense reference before any device work."""
+    from .aligners import _Vec
+    from .batch_gss import PreparedRatioSolve
+    from .ratio_sweep import _careful as careful_ratios
+
+    ref_vecs = [_Vec(ref) for ref, _ in problems]
+    for v in ref_vecs:
+        if not v.two_level:
+            raise ValueError("%s needs a two-level reference: a multi-level float reference (FFS_DTYPE_F64) is not "
+                             "supported" % who)
+        if v.raster is None and _host_boundaries(v) >= PreparedRatioSolve.LIST_CAP:
+            raise ValueError("%s: a reference has %d or more run boundaries: too dense for a boundary list"
+                             % (who, PreparedRatioSolve.LIST_CAP))
+    torch = _native.require_gpu()
+    n, g = len(problems), len(ratios)
+    tracks = [(np.asarray(s), np.asarray(e), None if m is None else np.asarray(m)) for _, (s, e, m) in problems]
+    solver = PreparedRatioSolve(ref_vecs, tracks, w, sample_rate, 0, max(ratios), n * g, max_cand=1)
+    if not solver.use_lists:  # (a reference that was already on the device: counted there)
+        raise ValueError("%s: a reference has %d or more run boundaries: too dense for a boundary list"
+                         % (who, PreparedRatioSolve.LIST_CAP))
+    # the seven-ratio solve: one rasteriser call, one align_batch
+    which, rs = np.repeat(np.arange(n), g), np.tile(np.array(ratios, dtype=np.float64), n)
+    seven = torch.empty(n * g * 24, dtype=torch.uint8, device="cuda")
+    solver.evaluate(which, rs, seven)
+    recs = seven.cpu().numpy().view(_native.CAND_RESULT_DTYPE)[:n * g].reshape(n, g).copy()
+    for f in np.flatnonzero(((recs["flags"] & _native.FLAG_AMBIGUOUS) != 0).any(axis=1)):
+        recs[f] = careful_ratios(ref_vecs[f], problems[f][1], ratios, w, sample_rate)
+    best = np.array([int(np.argmax(r["score"])) for r in recs])  # (the first maximal candidate, aligners.py:154-167)
+    best_ratio = np.array([ratios[j] for j in best], dtype=np.float64)
+    # the winners as lists and their headers (one small read-back: how many boundaries there are to work on)
+    data, offs, lens, bounds = solver.tracks.rasterize_runs(np.arange(n), best_ratio, sample_rate, 0)
+    n_sub = data.view(torch.int32)[torch.from_numpy(offs // 4).to(data.device)].cpu().numpy()
+    return solver, recs, best, best_ratio, (data, offs, lens, bounds), n_sub
+
+
 def null_sync(problems, max_offset_seconds: float = 60, ratios: Optional[Sequence[float]] = None,
               n_surrogates: int = DEFAULT_SURROGATES, block_units: int = 1, seed: int = 0, min_z: float = DEFAULT_MIN_Z,
               sample_rate: int = SAMPLE_RATE, start_seconds: float = 0) -> List[NullSyncResult]:
@@ -390,42 +429,13 @@ def null_sync(problems, max_offset_seconds: float = 60, ratios: Optional[Sequenc
     that are not metadata than a surrogate list has runs (the host's bound: cues that would merge on the sample grid
     still count one each), a host reference too dense for a boundary list (counted on the host; a reference that is
     already on the device is refused once its list has been counted there)."""
-    from .aligners import _Vec
-    from .batch_gss import PreparedRatioSolve
-    from .ratio_sweep import _careful as careful_ratios
-
     _check_shuffle(n_surrogates, block_units)
     _check_seed(seed)
     w, ratios = _check_sync(problems, max_offset_seconds, ratios, sample_rate, start_seconds, min_z)
     if not problems:
         return []
-    ref_vecs = [_Vec(ref) for ref, _ in problems]
-    for v in ref_vecs:
-        if not v.two_level:
-            raise ValueError("null_sync needs a two-level reference: a multi-level float reference (FFS_DTYPE_F64) is not "
-                             "supported")
-        if v.raster is None and _host_boundaries(v) >= PreparedRatioSolve.LIST_CAP:
-            raise ValueError("null_sync: a reference has %d or more run boundaries: too dense for a boundary list"
-                             % PreparedRatioSolve.LIST_CAP)
-    torch = _native.require_gpu()
-    n, g = len(problems), len(ratios)
-    tracks = [(np.asarray(s), np.asarray(e), None if m is None else np.asarray(m)) for _, (s, e, m) in problems]
-    solver = PreparedRatioSolve(ref_vecs, tracks, w, sample_rate, 0, max(ratios), n * g, max_cand=1)
-    if not solver.use_lists:  # (a reference that was already on the device: counted there)
-        raise ValueError("null_sync: a reference has %d or more run boundaries: too dense for a boundary list"
-                         % PreparedRatioSolve.LIST_CAP)
-    # the seven-ratio solve: one rasteriser call, one align_batch
-    which, rs = np.repeat(np.arange(n), g), np.tile(np.array(ratios, dtype=np.float64), n)
-    seven = torch.empty(n * g * 24, dtype=torch.uint8, device="cuda")
-    solver.evaluate(which, rs, seven)
-    recs = seven.cpu().numpy().view(_native.CAND_RESULT_DTYPE)[:n * g].reshape(n, g).copy()
-    for f in np.flatnonzero(((recs["flags"] & _native.FLAG_AMBIGUOUS) != 0).any(axis=1)):
-        recs[f] = careful_ratios(ref_vecs[f], problems[f][1], ratios, w, sample_rate)
-    best = np.array([int(np.argmax(r["score"])) for r in recs])  # (the first maximal candidate, aligners.py:154-167)
-    best_ratio = np.array([ratios[j] for j in best], dtype=np.float64)
-    # the winners as lists, their headers (one small read-back: how many boundaries were there to shuffle), the null
-    data, offs, lens, bounds = solver.tracks.rasterize_runs(np.arange(n), best_ratio, sample_rate, 0)
-    n_sub = data.view(torch.int32)[torch.from_numpy(offs // 4).to(data.device)].cpu().numpy()
+    n = len(problems)
+    solver, recs, best, best_ratio, (data, offs, lens, bounds), n_sub = _winning_lists("null_sync", problems, ratios, w, sample_rate)
     test = null_test_lists(solver.ref_ptr, solver.ref_len, solver.ref_bound, np.uint64(data.data_ptr()) + offs.astype(np.uint64),
                            lens, bounds, w, n_surrogates, block_units, seed, solver.ref_lo, solver.ref_hi, None,
                            np.minimum(1.0 / best_ratio, 1.0))

@@ -1293,6 +1293,76 @@ int ffs_surrogate_lists(const void* const* list_dev, const int32_t* n_bound, con
 int ffs_null_stats(const ffs_cand_result* rec_dev, int n_files, int n_surrogates, ffs_null_result* out_dev,
                    void* hip_stream);
 
+/* ---- half-sample stability: thinned lists and the order statistics of their solved offsets (csrc/ffs_stability.h) ---
+ * Replaces: nothing in the reference.  "How precisely is this offset known, and would the peak that won still win on
+ * another half of the cues?" answered without a tuned score threshold (ffsubsync_amd/stability.py): K subtitles that
+ * each keep a hashed half of the cue blocks, positions untouched, are solved beside the real one; a real sync peaks at
+ * the same lag on every half, a chance maximum all over the window.  Both calls are stateless: no plan, everything is
+ * queued on hip_stream, nothing is waited for or read back.  Pinned against tests/stability_model.py.
+ *
+ * ffs_subsample_lists.  The argument shapes and conventions of ffs_surrogate_lists.  Vector v: a valid ffs_runs_list
+ * at list_dev[v] (device, 8-byte aligned) with n boundaries, m = n / 2 runs; n_bound[v] = a host-known upper bound of
+ * n; seed[v].  The m runs -- all of them, the first and the last included -- are cut into nb = ceil(m / block_runs)
+ * blocks of block_runs consecutive runs (the last may be short).  Subsample s (0 <= s < n_subsamples) keeps block b iff
+ *   ((key(seed, s >> 1, b) >> 31) ^ (s & 1)) == 1,   key = the hash of ffs_surrogate_lists with p = s >> 1 for its s,
+ * so subsamples 2j and 2j + 1 are complementary: every run of the input is in exactly one of them (with an odd
+ * n_subsamples the last has no partner).  Its list -- the kept runs in input order: n' = 2 kept, pos copied unchanged,
+ * ones_before the prefix sum of the kept runs' lengths, ones' their total, the same len, cap = out_cap[v],
+ * e[n'] = (INT32_MAX, ones') -- is written to out_dev + out_off[v] + s * ffs_runs_list_bytes(out_cap[v]): the K blocks
+ * of a vector lie back to back.  A subsample may keep nothing (n' = 0, the sentinel only) or everything.  Only the
+ * header and the n' + 1 entries are written.  status_dev[v] (int32, always written) = 0, or FFS_SUB_BAD_* bits for a
+ * list whose header is odd, truncated (n >= cap, or negative) or above its bound: all K subsamples of such a list are
+ * empty lists of the same len; other vectors of the call are not affected.  There is no unit limit.  Host arrays may
+ * be freed after return.
+ * FFS_E_INVALID, before any launch, outputs and status untouched: n_subsamples outside [1, FFS_STAB_MAX_K], block_runs
+ * outside [1, FFS_STAB_MAX_BLOCK_RUNS], a negative n_vec, out_bytes or n_bound, a null or misaligned pointer (lists and
+ * output 8 bytes, status 4), out_off not a multiple of 8, out_cap < n_bound + 1 or out_cap >= 2^28, K blocks that do
+ * not fit [out_off, out_bytes), or n_vec * n_subsamples >= 2^31.  n_vec == 0 returns 0.
+ *
+ * ffs_offset_stats.  File f owns the n_subsamples + 1 records rec_dev[f * (n_subsamples + 1) ..]: record 0 the real
+ * list's solve, record 1 + s subsample s.  A record is USABLE by the rule of ffs_null_stats.  With the c usable
+ * subsample offsets sorted ascending: off_min, off_max, off_median = sorted[(c - 1) / 2], off_lo = sorted[(c - 1) / 20],
+ * off_hi = sorted[c - 1 - (c - 1) / 20] (integer division: the central 90 %); max_dev = max |off - real_offset| and
+ * n_within = those with |off - real_offset| <= tol.  Over the pairs (2j, 2j + 1) with both members usable: n_pairs,
+ * max_pair_gap = max |off(2j) - off(2j + 1)|, n_pairs_within = pairs whose gap <= tol, pair_score_min = min of
+ * score(2j) + score(2j + 1) (one addition of two doubles; -0.0 orders below +0.0); all 0 without such a pair.
+ * flags: FFS_STAB_EMPTY (record 0 not usable, or c = 0: the five order statistics, max_dev and n_within are then 0),
+ * FFS_STAB_AMBIGUOUS (some record of the file carried FFS_FLAG_AMBIGUOUS), FFS_STAB_NO_PAIRS (n_pairs = 0).  Offsets
+ * are 64-bit all the way.  Records are read, never written; exactly n_files output records are written, every byte of
+ * them.  FFS_E_INVALID for n_subsamples outside [1, FFS_STAB_MAX_K], n_files < 0, tol < 0, or a null or misaligned
+ * (8 bytes) pointer: refused before any launch, the outputs untouched. */
+#define FFS_STAB_MAX_K 4096              /* subsamples per vector */
+#define FFS_STAB_MAX_BLOCK_RUNS 16777216 /* 2^24 */
+#define FFS_SUB_BAD_ODD 1       /* status: n is odd (= FFS_SURR_BAD_ODD) */
+#define FFS_SUB_BAD_TRUNCATED 2 /* status: n >= cap (or negative) */
+#define FFS_SUB_BAD_BOUND 4     /* status: n > n_bound */
+#define FFS_STAB_EMPTY 1     /* the real record is not usable, or no subsample record is */
+#define FFS_STAB_AMBIGUOUS 2 /* some record carried FFS_FLAG_AMBIGUOUS */
+#define FFS_STAB_NO_PAIRS 4  /* no pair (2j, 2j + 1) with both members usable */
+
+typedef struct ffs_stability_result {
+    double real_score;            /* record 0's score */
+    int64_t real_offset;          /* record 0's offset */
+    int64_t off_min, off_max, off_median, off_lo, off_hi; /* of the usable subsample offsets */
+    int64_t max_dev, max_pair_gap;
+    double pair_score_min;
+    int32_t n_sub, n_within, n_pairs, n_pairs_within;
+    int64_t tol;
+    int32_t flags;                /* FFS_STAB_* */
+    int32_t reserved;             /* 0 */
+} ffs_stability_result;
+#ifdef __cplusplus
+static_assert(sizeof(ffs_stability_result) == 112, "ffs_stability_result is 112 bytes");
+#else
+_Static_assert(sizeof(ffs_stability_result) == 112, "ffs_stability_result is 112 bytes");
+#endif
+
+int ffs_subsample_lists(const void* const* list_dev, const int32_t* n_bound, const uint32_t* seed, const int64_t* out_off,
+                        const int64_t* out_cap, int64_t n_vec, int n_subsamples, int block_runs, void* out_dev,
+                        int64_t out_bytes, int32_t* status_dev, void* hip_stream);
+int ffs_offset_stats(const ffs_cand_result* rec_dev, int n_files, int n_subsamples, int64_t tol,
+                     ffs_stability_result* out_dev, void* hip_stream);
+
 /* ---- progressive alignment: the quality report of a growing reference prefix (csrc/ffs_progressive.h) -----------
  * Replaces: nothing in the reference (its --multi-segment-sync, speech_transformers.py:760-903, samples eight minutes
  * and hopes they suffice).  Score counts are additive over the reference, so after every appended chunk of reference
