@@ -177,6 +177,24 @@ STABILITY_RESULT_DTYPE = np.dtype(
 )
 STABILITY_RESULT_BYTES = 112
 assert STABILITY_RESULT_DTYPE.itemsize == STABILITY_RESULT_BYTES
+# ffs_vad_threshold and the limits of the adaptive energy VAD (include/ffsubsync_amd.h; static size 48 bytes)
+VAD_MAX_EDGES = 255  # FFS_VAD_MAX_EDGES
+VAD_MAX_BINS = 256  # FFS_VAD_MAX_BINS
+VAD_MAX_FRAMES = 1 << 23  # FFS_VAD_MAX_FRAMES: frames of one histogram the pick takes before it falls back
+VAD_RULE_OTSU, VAD_RULE_FLOOR = 0, 1  # FFS_VAD_RULE_*
+VAD_RULES = {"otsu": VAD_RULE_OTSU, "floor": VAD_RULE_FLOOR}
+VAD_THR_FALLBACK = 1  # FFS_VAD_THR_FALLBACK: threshold_bin is fallback_bin
+VAD_THR_TOO_LONG = 2  # FFS_VAD_THR_TOO_LONG
+VAD_THR_EMPTY = 4  # FFS_VAD_THR_EMPTY: no frame at or above lo_bin
+VAD_THR_FLAT = 8  # FFS_VAD_THR_FLAT: all counted frames share one bin
+VAD_THR_CLAMPED_LO = 16  # FFS_VAD_THR_CLAMPED_LO
+VAD_THR_CLAMPED_HI = 32  # FFS_VAD_THR_CLAMPED_HI
+VAD_THRESHOLD_DTYPE = np.dtype(
+    [("threshold_bin", "<i4"), ("flags", "<i4"), ("floor_bin", "<i4"), ("top_bin", "<i4"), ("n_frames", "<i8"),
+     ("n_counted", "<i8"), ("n_speech", "<i8"), ("eta", "<f8")], align=True
+)
+VAD_THRESHOLD_BYTES = 48
+assert VAD_THRESHOLD_DTYPE.itemsize == VAD_THRESHOLD_BYTES
 # ffs_prog_state (include/ffsubsync_amd.h; static size 64 bytes)
 PROG_STATE_DTYPE = np.dtype(
     [("ref_len", "<i8"), ("offset", "<i8"), ("score", "<f8"), ("mean", "<f8"), ("std", "<f8"), ("runner_up", "<f8"),
@@ -266,6 +284,10 @@ EXPORTED_SYMBOLS = (
     "ffs_null_stats",
     "ffs_subsample_lists",
     "ffs_offset_stats",
+    "ffs_vad_levels",
+    "ffs_vad_level_hist",
+    "ffs_vad_pick_threshold",
+    "ffs_vad_level_labels",
     "ffs_prog_plan_create",
     "ffs_prog_plan_destroy",
     "ffs_prog_plan_workspace_bytes",
@@ -405,6 +427,16 @@ def load():
         lib.ffs_vad_tokenize.restype = c.c_int
         lib.ffs_vad_tokenize.argtypes = [c.c_void_p, c.c_int64, c.c_int64, c.c_int, c.c_int, c.c_int, c.c_float,
                                          c.c_void_p, c.c_void_p]
+        lib.ffs_vad_levels.restype = c.c_int
+        lib.ffs_vad_levels.argtypes = [c.c_void_p, c.c_int64, c.c_int, c.c_void_p, c.c_int, c.c_void_p, c.c_void_p]
+        lib.ffs_vad_level_hist.restype = c.c_int
+        lib.ffs_vad_level_hist.argtypes = [c.c_void_p, c.c_int64, c.c_int, c.c_void_p, c.c_void_p]
+        lib.ffs_vad_pick_threshold.restype = c.c_int
+        lib.ffs_vad_pick_threshold.argtypes = [c.c_void_p, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int,
+                                               c.c_int, c.c_void_p, c.c_void_p]
+        lib.ffs_vad_level_labels.restype = c.c_int
+        lib.ffs_vad_level_labels.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int, c.c_float, c.c_void_p, c.c_void_p,
+                                             c.c_void_p]
         lib.ffs_speech_bounds.restype = c.c_int
         lib.ffs_speech_bounds.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p]
         lib.ffs_raster_length.restype = c.c_int64

@@ -46,6 +46,7 @@
 #include "ffs_stability.h"
 #include "ffs_progressive.h"
 #include "ffs_sampled.h"
+#include "ffs_adaptive_vad.h"
 
 using namespace ffsa;
 
@@ -3080,6 +3081,99 @@ int ffs_vad_tokenize(const float* valid_dev, int64_t n_frames, int64_t chunk_fra
                            valid_dev, (long long)n_frames, (long long)chunk_frames, min_length, max_length,
                            max_continuous_silence, non_speech_label, labels_dev);
     }
+    HIP_TRY(hipGetLastError());
+    return FFS_OK;
+}
+
+// ---- adaptive energy VAD (ffs_adaptive_vad.h) -------------------------------------------------------------
+
+int ffs_vad_levels(const int16_t* pcm_dev, int64_t n_samples, int frame_len, const double* edges_dev, int n_edges,
+                   uint8_t* levels_dev, void* hip_stream) {
+    if (n_samples < 0 || frame_len < 1)
+        return fail(FFS_E_INVALID, "ffs_vad_levels: bad n_samples=%lld / frame_len=%d", (long long)n_samples, frame_len);
+    if (n_edges < 1 || n_edges > VAD_MAX_EDGES)
+        return fail(FFS_E_INVALID, "ffs_vad_levels: n_edges=%d outside [1, %d]", n_edges, VAD_MAX_EDGES);
+    if (n_samples == 0) return FFS_OK;
+    if (!pcm_dev || !edges_dev || !levels_dev) return fail(FFS_E_INVALID, "ffs_vad_levels: null device pointer");
+    if ((reinterpret_cast<uintptr_t>(pcm_dev) & 1) || (reinterpret_cast<uintptr_t>(edges_dev) & 7))
+        return fail(FFS_E_INVALID, "ffs_vad_levels: misaligned PCM (2 bytes) or edge table (8 bytes)");
+    DeviceGuard guard;
+    int rc_dev;
+    if ((rc_dev = guard.enter(levels_dev))) return rc_dev;
+    const long long n_frames = (n_samples + frame_len - 1) / frame_len;
+    long long blocks = ((n_frames + VAD_FPT - 1) / VAD_FPT + 3) / 4;  // k_vad_energy's grid: a wave per VAD_FPT frames
+    if (blocks > 256 * 64) blocks = 256 * 64;
+    hipLaunchKernelGGL(k_vad_levels, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)hip_stream, pcm_dev,
+                       (long long)n_samples, frame_len, n_frames, edges_dev, n_edges, levels_dev);
+    HIP_TRY(hipGetLastError());
+    return FFS_OK;
+}
+
+int ffs_vad_level_hist(const uint8_t* levels_dev, int64_t n_frames, int n_bins, uint32_t* hist_dev, void* hip_stream) {
+    if (n_frames < 0) return fail(FFS_E_INVALID, "ffs_vad_level_hist: n_frames=%lld is negative", (long long)n_frames);
+    if (n_bins < 2 || n_bins > VAD_MAX_BINS)
+        return fail(FFS_E_INVALID, "ffs_vad_level_hist: n_bins=%d outside [2, %d]", n_bins, VAD_MAX_BINS);
+    if (!hist_dev || (n_frames > 0 && !levels_dev)) return fail(FFS_E_INVALID, "ffs_vad_level_hist: null device pointer");
+    if (reinterpret_cast<uintptr_t>(hist_dev) & 3) return fail(FFS_E_INVALID, "ffs_vad_level_hist: misaligned histogram (4 bytes)");
+    DeviceGuard guard;
+    int rc_dev;
+    if ((rc_dev = guard.enter(hist_dev))) return rc_dev;
+    hipStream_t st = (hipStream_t)hip_stream;
+    HIP_TRY(hipMemsetAsync(hist_dev, 0, sizeof(uint32_t) * (size_t)n_bins, st));
+    if (n_frames == 0) return FFS_OK;  // the histogram of no frames
+    long long blocks = (n_frames + HIST_BYTES_PER_TRIP - 1) / HIST_BYTES_PER_TRIP;
+    if (blocks > HIST_MAX_BLOCKS) blocks = HIST_MAX_BLOCKS;
+    hipLaunchKernelGGL(k_vad_level_hist, dim3((unsigned)blocks), dim3(HIST_THREADS), 0, st, levels_dev, (long long)n_frames,
+                       n_bins, hist_dev);
+    HIP_TRY(hipGetLastError());
+    return FFS_OK;
+}
+
+int ffs_vad_pick_threshold(const uint32_t* hist_dev, int n_hist, int n_bins, int rule, int lo_bin, int t_min, int t_max,
+                           int fallback_bin, int floor_ppm, int margin_bins, ffs_vad_threshold* records_dev, void* hip_stream) {
+    static_assert(sizeof(ffs_vad_threshold) == sizeof(VadThreshold), "device records must match the header's");
+    if (n_hist < 0) return fail(FFS_E_INVALID, "ffs_vad_pick_threshold: n_hist=%d is negative", n_hist);
+    if (n_bins < 2 || n_bins > VAD_MAX_BINS)
+        return fail(FFS_E_INVALID, "ffs_vad_pick_threshold: n_bins=%d outside [2, %d]", n_bins, VAD_MAX_BINS);
+    if (rule != VAD_RULE_OTSU && rule != VAD_RULE_FLOOR) return fail(FFS_E_INVALID, "ffs_vad_pick_threshold: unknown rule %d", rule);
+    if (!(0 <= lo_bin && lo_bin < t_min && t_min <= t_max && t_max <= n_bins - 1))
+        return fail(FFS_E_INVALID, "ffs_vad_pick_threshold: need 0 <= lo_bin=%d < t_min=%d <= t_max=%d <= n_bins - 1 = %d", lo_bin,
+                    t_min, t_max, n_bins - 1);
+    if (fallback_bin < 0 || fallback_bin > n_bins)
+        return fail(FFS_E_INVALID, "ffs_vad_pick_threshold: fallback_bin=%d outside [0, %d]", fallback_bin, n_bins);
+    if (floor_ppm < 0 || floor_ppm > 1000000)
+        return fail(FFS_E_INVALID, "ffs_vad_pick_threshold: floor_ppm=%d outside [0, 1000000]", floor_ppm);
+    if (margin_bins < 0 || margin_bins > VAD_MAX_EDGES)
+        return fail(FFS_E_INVALID, "ffs_vad_pick_threshold: margin_bins=%d outside [0, %d]", margin_bins, VAD_MAX_EDGES);
+    if (n_hist == 0) return FFS_OK;
+    if (!hist_dev || !records_dev) return fail(FFS_E_INVALID, "ffs_vad_pick_threshold: null histogram or record pointer");
+    if ((reinterpret_cast<uintptr_t>(hist_dev) & 3) || (reinterpret_cast<uintptr_t>(records_dev) & 7))
+        return fail(FFS_E_INVALID, "ffs_vad_pick_threshold: misaligned histogram (4 bytes) or record (8 bytes) pointer");
+    DeviceGuard guard;
+    int rc_dev;
+    if ((rc_dev = guard.enter(records_dev))) return rc_dev;
+    hipLaunchKernelGGL(k_vad_pick_threshold, dim3((unsigned)n_hist), dim3(64), 0, (hipStream_t)hip_stream, hist_dev, n_bins, rule,
+                       lo_bin, t_min, t_max, fallback_bin, floor_ppm, margin_bins, (VadThreshold*)records_dev);
+    HIP_TRY(hipGetLastError());
+    return FFS_OK;
+}
+
+int ffs_vad_level_labels(const uint8_t* levels_dev, int64_t n_frames, const int32_t* threshold_dev, int threshold_host,
+                         float non_speech_label, float* labels_dev, uint8_t* bits_dev, void* hip_stream) {
+    if (n_frames < 0) return fail(FFS_E_INVALID, "ffs_vad_level_labels: n_frames=%lld is negative", (long long)n_frames);
+    if (!threshold_dev && (threshold_host < 0 || threshold_host > VAD_MAX_BINS))
+        return fail(FFS_E_INVALID, "ffs_vad_level_labels: threshold_host=%d outside [0, %d]", threshold_host, VAD_MAX_BINS);
+    if (n_frames == 0) return FFS_OK;
+    if (!levels_dev || (!labels_dev && !bits_dev)) return fail(FFS_E_INVALID, "ffs_vad_level_labels: null device pointer");
+    if ((reinterpret_cast<uintptr_t>(threshold_dev) & 3) || (reinterpret_cast<uintptr_t>(labels_dev) & 3))
+        return fail(FFS_E_INVALID, "ffs_vad_level_labels: misaligned threshold or label pointer (4 bytes)");
+    DeviceGuard guard;
+    int rc_dev;
+    if ((rc_dev = guard.enter(levels_dev))) return rc_dev;
+    long long blocks = (n_frames + LABEL_THREADS - 1) / LABEL_THREADS;
+    if (blocks > LABEL_MAX_BLOCKS) blocks = LABEL_MAX_BLOCKS;
+    hipLaunchKernelGGL(k_vad_level_labels, dim3((unsigned)blocks), dim3(LABEL_THREADS), 0, (hipStream_t)hip_stream, levels_dev,
+                       (long long)n_frames, (const int*)threshold_dev, threshold_host, non_speech_label, labels_dev, bits_dev);
     HIP_TRY(hipGetLastError());
     return FFS_OK;
 }

@@ -164,44 +164,59 @@ def detect_pinned_stream(pcm_host, sample_rate: int, frame_rate: int, non_speech
         out = torch.zeros((n_frames + 31) // 32, dtype=torch.int32, device="cuda")
     else:
         out = torch.empty(n_frames, dtype=torch.float32, device="cuda")
-    main = torch.cuda.current_stream()
-    if n:
-        own = staging is None
-        if own:
-            staging = ([torch.empty(chunk, dtype=torch.int16, device="cuda") for _ in range(2)], torch.cuda.Stream())
-        bufs, copy_stream = staging
-        # the staging blocks may still carry work of the caller's stream (fresh from the caching allocator, or the
-        # previous file's last sweep): the first copies wait for it
-        copy_stream.wait_stream(main)
-        if own:
-            for b in bufs:
-                b.record_stream(copy_stream)
-        filled = [torch.cuda.Event() for _ in range(2)]
-        drained = [None, None]
-        lib = _native.load()
-        for i, o in enumerate(range(0, n, chunk)):
-            k = i % 2
-            m = min(chunk, n - o)
-            with torch.cuda.stream(copy_stream):
-                if drained[k] is not None:
-                    copy_stream.wait_event(drained[k])  # the sweep that last read this staging buffer is done
-                bufs[k][:m].copy_(pcm_host[o:o + m], non_blocking=True)
-                filled[k].record(copy_stream)
-            main.wait_event(filled[k])
-            f0 = o // frame_len
-            if packed:
-                _native.check(lib.ffs_vad_energy_bits(bufs[k].data_ptr(), m, frame_len, float(energy_threshold_db),
-                                                      out.data_ptr() + f0 // 8, main.cuda_stream))
-            else:
-                _native.check(lib.ffs_vad_energy(bufs[k].data_ptr(), m, frame_len, float(energy_threshold_db),
-                                                 float(non_speech_label), out[f0:].data_ptr(), main.cuda_stream))
-            drained[k] = torch.cuda.Event()
-            drained[k].record(main)
+    lib = _native.load()
+
+    def sweep(buf, m, o, main):
+        f0 = o // frame_len
+        if packed:
+            _native.check(lib.ffs_vad_energy_bits(buf.data_ptr(), m, frame_len, float(energy_threshold_db),
+                                                  out.data_ptr() + f0 // 8, main.cuda_stream))
+        else:
+            _native.check(lib.ffs_vad_energy(buf.data_ptr(), m, frame_len, float(energy_threshold_db),
+                                             float(non_speech_label), out[f0:].data_ptr(), main.cuda_stream))
+
+    stream_pinned_buffers(pcm_host, chunk, staging, sweep)
     if packed:
         from .subtitle_raster import DeviceRaster
 
         return DeviceRaster(out, float(non_speech_label), 1.0, n_frames)
     return out
+
+
+def stream_pinned_buffers(pcm_host, chunk: int, staging, sweep) -> None:
+    """The double-buffered copy loop of :func:`detect_pinned_stream`: every ``chunk`` samples of the pinned int16 tensor
+    go to one of two HBM staging buffers on a copy stream, and ``sweep(buffer, n_samples, first_sample, main_stream)``
+    queues the work on that buffer on the caller's stream while the next copy runs.  ``staging`` = (buffers,
+    copy_stream) or None for buffers of its own."""
+    torch = _native.require_gpu()
+    n = int(pcm_host.numel())
+    if not n:
+        return
+    main = torch.cuda.current_stream()
+    own = staging is None
+    if own:
+        staging = ([torch.empty(chunk, dtype=torch.int16, device="cuda") for _ in range(2)], torch.cuda.Stream())
+    bufs, copy_stream = staging
+    # the staging blocks may still carry work of the caller's stream (fresh from the caching allocator, or the
+    # previous file's last sweep): the first copies wait for it
+    copy_stream.wait_stream(main)
+    if own:
+        for b in bufs:
+            b.record_stream(copy_stream)
+    filled = [torch.cuda.Event() for _ in range(2)]
+    drained = [None, None]
+    for i, o in enumerate(range(0, n, chunk)):
+        k = i % 2
+        m = min(chunk, n - o)
+        with torch.cuda.stream(copy_stream):
+            if drained[k] is not None:
+                copy_stream.wait_event(drained[k])  # the sweep that last read this staging buffer is done
+            bufs[k][:m].copy_(pcm_host[o:o + m], non_blocking=True)
+            filled[k].record(copy_stream)
+        main.wait_event(filled[k])
+        sweep(bufs[k], m, o, main)
+        drained[k] = torch.cuda.Event()
+        drained[k].record(main)
 
 
 class ComputeSpeechFrameBoundariesMixin:
@@ -251,6 +266,7 @@ class PCMSpeechTransformer(TransformerMixin):
         self._non_speech_label = non_speech_label
         self.progress_handler = progress_handler
         self.video_speech_results_: Optional[np.ndarray] = None
+        self.vad_threshold_ = None  # vad="adaptive": the file's adaptive_vad.ThresholdRecord
 
     def _make_detector(self):
         if "fused" in self.vad:  # e.g. "fused" or "fused:intersection" (speech_transformers.py:655-665)
@@ -291,6 +307,32 @@ class PCMSpeechTransformer(TransformerMixin):
         pipe, and the labels come back in one transfer at the end."""
         torch = _native.require_gpu()
         frame_len = frames_per_window(self.sample_rate, self.frame_rate)
+        labels = self._sweep_pipelined(source, chunk_bytes,
+                                       lambda pcm: _native.vad_energy(pcm, frame_len, DEFAULT_ENERGY_THRESHOLD_DB, 0.0))
+        if not labels:
+            return []
+        return [_labels_float64(torch.cat(labels), self._non_speech_label)]
+
+    def _fit_adaptive_pipelined(self, source, chunk_bytes) -> List[np.ndarray]:
+        """``vad="adaptive"``: the same pipelined chunk loop with the level sweep of ``adaptive_vad`` as pass 1; the
+        histogram, the pick and the labels run once over the whole stream, so one threshold serves the file.  The
+        record is kept as ``vad_threshold_``."""
+        from . import adaptive_vad
+
+        torch = _native.require_gpu()
+        frame_len = frames_per_window(self.sample_rate, self.frame_rate)
+        levels = self._sweep_pipelined(source, chunk_bytes, lambda pcm: adaptive_vad.frame_levels(pcm, frame_len))
+        if not levels:
+            return []
+        levels = torch.cat(levels)
+        self.vad_threshold_ = adaptive_vad.pick_threshold(adaptive_vad.level_hist(levels))
+        speech = adaptive_vad.level_labels(levels, self.vad_threshold_.threshold_bin, 0.0)
+        return [_labels_float64(speech, self._non_speech_label)]
+
+    def _sweep_pipelined(self, source, chunk_bytes, sweep) -> list:
+        """``sweep(int16 CUDA chunk)`` of every chunk of the stream through the two staging buffers; the device
+        tensors it returned, in order."""
+        torch = _native.require_gpu()
         pinned = [torch.empty(chunk_bytes, dtype=torch.uint8).pin_memory() for _ in range(2)]
         device = [torch.empty(chunk_bytes, dtype=torch.uint8, device="cuda") for _ in range(2)]
         copied = [None, None]
@@ -302,7 +344,7 @@ class PCMSpeechTransformer(TransformerMixin):
             processed += len(in_bytes) / float(BYTES_PER_SAMPLE) / self.frame_rate
             self._progress(processed)
             if n == 0:
-                labels.append(torch.empty(0, dtype=torch.float32, device="cuda"))
+                labels.append(sweep(device[k][:0].view(torch.int16)))
                 continue
             if copied[k] is not None:
                 copied[k].synchronize()  # the copy that last used this staging buffer is done
@@ -311,15 +353,15 @@ class PCMSpeechTransformer(TransformerMixin):
             copied[k] = torch.cuda.Event()
             copied[k].record()
             pcm = device[k][:n].view(torch.int16)
-            labels.append(_native.vad_energy(pcm, frame_len, DEFAULT_ENERGY_THRESHOLD_DB, 0.0))
-        if not labels:
-            return []
-        return [_labels_float64(torch.cat(labels), self._non_speech_label)]
+            labels.append(sweep(pcm))
+        return labels
 
     def fit(self, source, *_) -> "PCMSpeechTransformer":
         bytes_per_window = BYTES_PER_SAMPLE * self.frame_rate // self.sample_rate  # :683-684
         chunk_bytes = bytes_per_window * WINDOWS_PER_BUFFER
-        if "energy" in self.vad and "fused" not in self.vad and "auditok" not in self.vad:
+        if "adaptive" in self.vad:  # tested first: the name holds none of the reference's substrings
+            media_bstring = self._fit_adaptive_pipelined(source, chunk_bytes)
+        elif "energy" in self.vad and "fused" not in self.vad and "auditok" not in self.vad:
             media_bstring = self._fit_energy_pipelined(source, chunk_bytes)
         else:
             detector = self._make_detector()

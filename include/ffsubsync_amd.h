@@ -1363,6 +1363,88 @@ int ffs_subsample_lists(const void* const* list_dev, const int32_t* n_bound, con
 int ffs_offset_stats(const ffs_cand_result* rec_dev, int n_files, int n_subsamples, int64_t tol,
                      ffs_stability_result* out_dev, void* hip_stream);
 
+/* ---- adaptive energy VAD: a per-file threshold from frame-level counts (csrc/ffs_adaptive_vad.h) -----------------
+ * Replaces: nothing in the reference.  This is the project's own rule with no upstream counterpart (the reference's
+ * adaptive detector is WebRTC's, a third-party wheel): parity is against the in-repo numpy model
+ * tests/adaptive_vad_model.py only, bit for bit.  ffs_vad_energy and its fixed threshold are unchanged.
+ *
+ * Edges.  edges[0 .. n_edges) are doubles, ascending, positive and finite, 1 <= n_edges <= FFS_VAD_MAX_EDGES, supplied
+ * by the caller in device memory (adaptive_vad.default_edges(): 10^(k / 20), k = 1 .. 191, i.e. half-dB steps; edges[99]
+ * is 10^5 = 50 dB).  B = n_edges + 1 level bins.
+ * Level of frame f.  E_f the exact 64-bit sum of squares and n_f the sample count of the frame (the last one may be
+ * short), as in ffs_vad_energy:  level[f] = #{k : (double)E_f >= edges[k] * (double)n_f}  -- one fp64 multiply and one
+ * compare per edge, the evaluation ffs_vad_energy uses for its one threshold.  A count of satisfied edges: defined for
+ * any table; for an ascending one  level >= t  <=>  the fixed rule with threshold edges[t - 1].  uint8, in [0, n_edges].
+ * Histogram.  hist[b] = number of frames with level b, uint32[n_bins]; a level byte >= n_bins is counted nowhere.
+ * Pick.  0 <= lo_bin < t_min <= t_max <= B - 1, 0 <= fallback_bin <= B, 0 <= floor_ppm <= 10^6, 0 <= margin_bins <= 255.
+ *   h'[b] = hist[b] for b >= lo_bin, else 0 (frames below lo_bin are silence and never counted, so stretches of
+ *   digital silence cannot become one of the two classes);  N' = sum h', S = sum b h', Q = sum b^2 h'.  In order:
+ *   1. sum hist > FFS_VAD_MAX_FRAMES (2^23): TOO_LONG | FALLBACK.
+ *   2. N' == 0: EMPTY | FALLBACK.
+ *   3. FFS_VAD_RULE_OTSU: for t in lo_bin + 1 .. B - 1 with n0 = sum_{b<t} h', s0 = sum_{b<t} b h' and 0 < n0 < N':
+ *      d = S n0 - N' s0 and m = n0 (N' - n0) in exact int64, v(t) = ((double)d * (double)d) / (double)m (conversions
+ *      round to nearest; one multiply, one correctly rounded divide, no add).  The smallest t of the largest v wins;
+ *      eta = v_max / (double)(N' Q - S S), the share of the counted levels' variance the split explains, in [0, 1].
+ *      No such t (all counted frames in one bin): FLAT | FALLBACK, eta = 0.
+ *   4. FFS_VAD_RULE_FLOOR: need = max(1, (N' floor_ppm + 999999) / 1000000) in integers, floor_bin the smallest b with
+ *      sum_{lo_bin <= b' <= b} h' >= need, t = floor_bin + margin_bins; FLAT is flagged when it holds, the result
+ *      stands; eta = 0.
+ *   5. A rule's result outside [t_min, t_max] is clamped and flagged CLAMPED_LO / CLAMPED_HI.
+ *   6. A fallback sets threshold_bin = fallback_bin, unclamped (100 with the default table: the fixed 50 dB rule).
+ *   floor_bin is reported under either rule with the given floor_ppm (-1 when N' == 0), top_bin is the highest occupied
+ *   counted bin (-1 when N' == 0), n_speech = sum_{b >= threshold_bin} hist[b].
+ * Labels.  Frame f is speech iff level[f] >= threshold_bin.
+ *
+ * ffs_vad_levels streams the PCM once and writes ceil(n_samples / frame_len) level bytes, nothing behind them; it can
+ * be called chunk by chunk (a caller sweeping 100 s buffers points each call at levels_dev + first_frame; any byte
+ * address).  ffs_vad_level_hist zeroes hist_dev on the stream and counts (n_frames == 0 leaves the zeros: the
+ * histogram of no frames); a few thousand integer atomics per call whatever the length, so the result does not depend
+ * on arrival order.  ffs_vad_pick_threshold reduces n_hist >= 0 histograms, n_bins apart, to one 48-byte record each.
+ * ffs_vad_level_labels reads the threshold ON THE DEVICE from threshold_dev when that is not NULL -- a record's
+ * address works, threshold_bin is its first field, and nothing waits for a read-back -- else it is threshold_host in
+ * [0, 256].  Its outputs are ffs_vad_energy's two forms, either may be NULL: labels_dev[f] = 1.0f / non_speech_label,
+ * and bits_dev as ffs_vad_energy_bits writes it (ceil(n_frames / 8) bytes, the unused high bits of the last byte 0,
+ * nothing beyond them).
+ * FFS_E_INVALID with a message, before any launch: negative counts, frame_len < 1, n_edges outside [1, 255], n_bins
+ * outside [2, 256], an unknown rule, a parameter outside the ranges above, a null or misaligned pointer.  A count of 0
+ * is FFS_OK with nothing written (but for ffs_vad_level_hist's zeros).  The calls are stateless. */
+#define FFS_VAD_MAX_EDGES 255
+#define FFS_VAD_MAX_BINS 256
+#define FFS_VAD_MAX_FRAMES 8388608 /* 2^23: frames of one histogram the Otsu arithmetic is exact for */
+#define FFS_VAD_RULE_OTSU 0
+#define FFS_VAD_RULE_FLOOR 1
+#define FFS_VAD_THR_FALLBACK 1    /* threshold_bin is fallback_bin */
+#define FFS_VAD_THR_TOO_LONG 2    /* more than FFS_VAD_MAX_FRAMES frames */
+#define FFS_VAD_THR_EMPTY 4       /* no frame at or above lo_bin */
+#define FFS_VAD_THR_FLAT 8        /* all counted frames share one bin */
+#define FFS_VAD_THR_CLAMPED_LO 16 /* the rule's result was below t_min */
+#define FFS_VAD_THR_CLAMPED_HI 32 /* the rule's result was above t_max */
+
+typedef struct ffs_vad_threshold {
+    int32_t threshold_bin;        /* speech <=> level >= threshold_bin (first field: ffs_vad_level_labels reads it in place) */
+    int32_t flags;                /* FFS_VAD_THR_* */
+    int32_t floor_bin;            /* the floor_ppm quantile of the counted bins, or -1 */
+    int32_t top_bin;              /* the highest occupied counted bin, or -1 */
+    int64_t n_frames;             /* sum hist */
+    int64_t n_counted;            /* N' */
+    int64_t n_speech;             /* frames at or above threshold_bin */
+    double eta;                   /* Otsu's separability, 0 otherwise */
+} ffs_vad_threshold;
+#ifdef __cplusplus
+static_assert(sizeof(ffs_vad_threshold) == 48, "ffs_vad_threshold is 48 bytes");
+#else
+_Static_assert(sizeof(ffs_vad_threshold) == 48, "ffs_vad_threshold is 48 bytes");
+#endif
+
+int ffs_vad_levels(const int16_t* pcm_dev, int64_t n_samples, int frame_len, const double* edges_dev, int n_edges,
+                   uint8_t* levels_dev, void* hip_stream);
+int ffs_vad_level_hist(const uint8_t* levels_dev, int64_t n_frames, int n_bins, uint32_t* hist_dev, void* hip_stream);
+int ffs_vad_pick_threshold(const uint32_t* hist_dev, int n_hist, int n_bins, int rule, int lo_bin, int t_min, int t_max,
+                           int fallback_bin, int floor_ppm, int margin_bins, ffs_vad_threshold* records_dev,
+                           void* hip_stream);
+int ffs_vad_level_labels(const uint8_t* levels_dev, int64_t n_frames, const int32_t* threshold_dev, int threshold_host,
+                         float non_speech_label, float* labels_dev, uint8_t* bits_dev, void* hip_stream);
+
 /* ---- progressive alignment: the quality report of a growing reference prefix (csrc/ffs_progressive.h) -----------
  * Replaces: nothing in the reference (its --multi-segment-sync, speech_transformers.py:760-903, samples eight minutes
  * and hopes they suffice).  Score counts are additive over the reference, so after every appended chunk of reference
