@@ -212,22 +212,23 @@ def reasons(rec, blocks, min_z):
 
 
 def null_sync(reference, track, max_offset_samples=6000, ratios=None, n_surrogates=64, block_units=1, seed=0, index=0,
-              min_z=None, sample_rate=100):
+              min_z=None, sample_rate=100, levels=(0.0, 1.0)):
     """One problem through the model: the seven-ratio solve (the first maximal candidate), then the null at the winning
-    ratio.  dict(ratio, offset, score, record, z, p, blocks, scores, reasons (None without ``min_z``))."""
+    ratio.  dict(ratio, offset, score, record, z, p, blocks, scores, reasons (None without ``min_z``)).  ``levels``: the
+    two values the reference's samples take, (lo, hi)."""
     import exact_reference as er
     from oracle import raster_oracle as ro
 
     ratios = list(SEVEN if ratios is None else ratios)
-    spec = er.RefSpectrum(np.asarray(reference) != 0)
+    spec = er.RefSpectrum(np.asarray(reference) != levels[0])
     best = None
     for r in ratios:
         v = ro.rasterize(track[0], track[1], track[2], float(r), sample_rate, 0) > 0
-        rec = er.candidate(spec, v, (0.0, 1.0), (0.0, min(1.0 / r, 1.0)), max_offset_samples)
+        rec = er.candidate(spec, v, levels, (0.0, min(1.0 / r, 1.0)), max_offset_samples)
         if best is None or rec["score"] > best[1]["score"]:
             best = (r, rec, v)
     r, rec, v = best
-    sc, fl = null_scores(spec, v, (0.0, 1.0), (0.0, min(1.0 / r, 1.0)), max_offset_samples, file_seed(seed, index),
+    sc, fl = null_scores(spec, v, levels, (0.0, min(1.0 / r, 1.0)), max_offset_samples, file_seed(seed, index),
                          n_surrogates, block_units)
     record = stats(sc, fl)
     z, p = z_p(record)
