@@ -927,6 +927,15 @@ def speech_bounds(frames):
     return (None, None) if hi < 0 else (lo, hi)
 
 
+def _record_out(out, torch, n_files: int, record_bytes: int, device):
+    """The output buffer of a per-file reduction: ``out`` if it holds n_files records, else a fresh uint8 tensor."""
+    if out is None:
+        return torch.empty(max(n_files, 1) * record_bytes, dtype=torch.uint8, device=device)
+    if _nbytes(out) < n_files * record_bytes:
+        raise ValueError("output buffer too small")
+    return out
+
+
 def sweep_peaks(records, first, n_files: int, top_k: int, exclusion_steps: int, out=None):
     """``ffs_sweep_peaks`` on the current stream: ``records`` a CUDA tensor of ffs_cand_result records (24 bytes each),
     ``first`` an int64 CUDA tensor of n_files + 1 ascending point indices; returns the uint8 CUDA tensor of n_files
@@ -935,12 +944,40 @@ def sweep_peaks(records, first, n_files: int, top_k: int, exclusion_steps: int, 
     n_files = int(n_files)
     if first.dtype != torch.int64 or first.numel() < n_files + 1 or not first.is_contiguous():
         raise ValueError("first must be a contiguous int64 tensor of n_files + 1 entries")
-    if out is None:
-        out = torch.empty(max(n_files, 1) * SWEEP_PROFILE_BYTES, dtype=torch.uint8, device=first.device)
-    elif _nbytes(out) < n_files * SWEEP_PROFILE_BYTES:
-        raise ValueError("output buffer too small")
+    out = _record_out(out, torch, n_files, SWEEP_PROFILE_BYTES, first.device)
     check(load().ffs_sweep_peaks(records.data_ptr(), first.data_ptr(), n_files, int(top_k), int(exclusion_steps),
                                  out.data_ptr(), current_stream_ptr(torch)))
+    return out
+
+
+def _resampled_lists(fn, list_ptr, n_bound, seeds, out_off, out_cap, k: int, block: int, out, status) -> None:
+    """The list export named ``fn`` (``ffs_surrogate_lists`` / ``ffs_subsample_lists``: the same argument shapes) on the
+    current stream."""
+    torch = require_gpu()
+    list_ptr = np.ascontiguousarray(list_ptr, dtype=np.uint64)
+    n_bound = np.ascontiguousarray(n_bound, dtype=np.int32)
+    seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
+    out_off = np.ascontiguousarray(out_off, dtype=np.int64)
+    out_cap = np.ascontiguousarray(out_cap, dtype=np.int64)
+    n_vec = list_ptr.size
+    if not (n_bound.size == seeds.size == out_off.size == out_cap.size == n_vec):
+        raise ValueError("the vector tables must have the same length")
+    if status.dtype != torch.int32 or status.numel() < n_vec or not status.is_contiguous():
+        raise ValueError("status must be a contiguous int32 tensor with one entry per vector")
+    check(getattr(load(), fn)(list_ptr.ctypes.data, n_bound.ctypes.data, seeds.ctypes.data, out_off.ctypes.data,
+                              out_cap.ctypes.data, n_vec, int(k), int(block), out.data_ptr(), _nbytes(out), status.data_ptr(),
+                              current_stream_ptr(torch)))
+
+
+def _record_stats(fn, records, n_files: int, k: int, record_bytes: int, what: str, *extra, out=None):
+    """The reduction named ``fn`` (``ffs_null_stats`` / ``ffs_offset_stats``) of n_files * (k + 1) solve records on the
+    current stream; ``extra``: its arguments between k and the output, ``what``: the name of k in the message."""
+    torch = require_gpu()
+    n_files, k = int(n_files), int(k)
+    if n_files < 0 or k < 0 or _nbytes(records) < n_files * (k + 1) * 24:
+        raise ValueError("the table holds fewer than n_files * (%s + 1) records" % what)
+    out = _record_out(out, torch, n_files, record_bytes, records.device)
+    check(getattr(load(), fn)(records.data_ptr(), n_files, k, *extra, out.data_ptr(), current_stream_ptr(torch)))
     return out
 
 
@@ -948,71 +985,28 @@ def surrogate_lists(list_ptr, n_bound, seeds, out_off, out_cap, n_surrogates: in
     """``ffs_surrogate_lists`` on the current stream: per vector the device pointer of its ``ffs_runs_list``, a host-known
     bound of its length, its uint32 seed, the byte offset in ``out`` (uint8 / int32 CUDA tensor) of the first of its
     ``n_surrogates`` back-to-back blocks and their capacity in entries; ``status``: int32 CUDA tensor, one per vector."""
-    torch = require_gpu()
-    list_ptr = np.ascontiguousarray(list_ptr, dtype=np.uint64)
-    n_bound = np.ascontiguousarray(n_bound, dtype=np.int32)
-    seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
-    out_off = np.ascontiguousarray(out_off, dtype=np.int64)
-    out_cap = np.ascontiguousarray(out_cap, dtype=np.int64)
-    n_vec = list_ptr.size
-    if not (n_bound.size == seeds.size == out_off.size == out_cap.size == n_vec):
-        raise ValueError("the vector tables must have the same length")
-    if status.dtype != torch.int32 or status.numel() < n_vec or not status.is_contiguous():
-        raise ValueError("status must be a contiguous int32 tensor with one entry per vector")
-    check(load().ffs_surrogate_lists(list_ptr.ctypes.data, n_bound.ctypes.data, seeds.ctypes.data, out_off.ctypes.data,
-                                     out_cap.ctypes.data, n_vec, int(n_surrogates), int(block_units), out.data_ptr(),
-                                     _nbytes(out), status.data_ptr(), current_stream_ptr(torch)))
+    _resampled_lists("ffs_surrogate_lists", list_ptr, n_bound, seeds, out_off, out_cap, n_surrogates, block_units, out, status)
 
 
 def null_stats(records, n_files: int, n_surrogates: int, out=None):
     """``ffs_null_stats`` on the current stream: ``records`` a CUDA tensor of n_files * (n_surrogates + 1)
     ffs_cand_result records (24 bytes each; per file the real list's solve, then the surrogates'); returns the uint8 CUDA
     tensor of n_files ``NULL_RESULT_DTYPE`` records (``out``, if given, is written in place)."""
-    torch = require_gpu()
-    n_files, k = int(n_files), int(n_surrogates)
-    if n_files < 0 or k < 0 or _nbytes(records) < n_files * (k + 1) * 24:
-        raise ValueError("the table holds fewer than n_files * (n_surrogates + 1) records")
-    if out is None:
-        out = torch.empty(max(n_files, 1) * NULL_RESULT_BYTES, dtype=torch.uint8, device=records.device)
-    elif _nbytes(out) < n_files * NULL_RESULT_BYTES:
-        raise ValueError("output buffer too small")
-    check(load().ffs_null_stats(records.data_ptr(), n_files, k, out.data_ptr(), current_stream_ptr(torch)))
-    return out
+    return _record_stats("ffs_null_stats", records, n_files, n_surrogates, NULL_RESULT_BYTES, "n_surrogates", out=out)
 
 
 def subsample_lists(list_ptr, n_bound, seeds, out_off, out_cap, n_subsamples: int, block_runs: int, out, status) -> None:
     """``ffs_subsample_lists`` on the current stream: the arguments of ``surrogate_lists``, with ``n_subsamples`` thinned
     lists per vector and blocks of ``block_runs`` runs."""
-    torch = require_gpu()
-    list_ptr = np.ascontiguousarray(list_ptr, dtype=np.uint64)
-    n_bound = np.ascontiguousarray(n_bound, dtype=np.int32)
-    seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
-    out_off = np.ascontiguousarray(out_off, dtype=np.int64)
-    out_cap = np.ascontiguousarray(out_cap, dtype=np.int64)
-    n_vec = list_ptr.size
-    if not (n_bound.size == seeds.size == out_off.size == out_cap.size == n_vec):
-        raise ValueError("the vector tables must have the same length")
-    if status.dtype != torch.int32 or status.numel() < n_vec or not status.is_contiguous():
-        raise ValueError("status must be a contiguous int32 tensor with one entry per vector")
-    check(load().ffs_subsample_lists(list_ptr.ctypes.data, n_bound.ctypes.data, seeds.ctypes.data, out_off.ctypes.data,
-                                     out_cap.ctypes.data, n_vec, int(n_subsamples), int(block_runs), out.data_ptr(),
-                                     _nbytes(out), status.data_ptr(), current_stream_ptr(torch)))
+    _resampled_lists("ffs_subsample_lists", list_ptr, n_bound, seeds, out_off, out_cap, n_subsamples, block_runs, out, status)
 
 
 def offset_stats(records, n_files: int, n_subsamples: int, tol: int, out=None):
     """``ffs_offset_stats`` on the current stream: ``records`` a CUDA tensor of n_files * (n_subsamples + 1)
     ffs_cand_result records (24 bytes each; per file the real list's solve, then the subsamples'); returns the uint8 CUDA
     tensor of n_files ``STABILITY_RESULT_DTYPE`` records (``out``, if given, is written in place)."""
-    torch = require_gpu()
-    n_files, k = int(n_files), int(n_subsamples)
-    if n_files < 0 or k < 0 or _nbytes(records) < n_files * (k + 1) * 24:
-        raise ValueError("the table holds fewer than n_files * (n_subsamples + 1) records")
-    if out is None:
-        out = torch.empty(max(n_files, 1) * STABILITY_RESULT_BYTES, dtype=torch.uint8, device=records.device)
-    elif _nbytes(out) < n_files * STABILITY_RESULT_BYTES:
-        raise ValueError("output buffer too small")
-    check(load().ffs_offset_stats(records.data_ptr(), n_files, k, int(tol), out.data_ptr(), current_stream_ptr(torch)))
-    return out
+    return _record_stats("ffs_offset_stats", records, n_files, n_subsamples, STABILITY_RESULT_BYTES, "n_subsamples", int(tol),
+                         out=out)
 
 
 def _us_arrays(start_us, end_us, is_metadata):

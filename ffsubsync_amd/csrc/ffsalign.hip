@@ -3196,6 +3196,132 @@ int ffs_speech_bounds(const float* frames_dev, int64_t n_frames, int64_t* bounds
     return FFS_OK;
 }
 
+/* ---- host code shared by the per-file reductions and by the two resampled-list exports ------------------------ */
+
+namespace {
+extern "C++" {  // (function templates, inside this file's extern "C" block)
+// The launch of a reduction with one workgroup per file, behind its export's own checks: nothing for no files, else
+// `launch()` under the guard of the output's device.
+template <class Launch>
+int launch_per_file(int n_files, const void* out_dev, Launch launch) {
+    if (n_files == 0) return FFS_OK;
+    DeviceGuard guard;
+    int rc_dev;
+    if ((rc_dev = guard.enter(out_dev))) return rc_dev;
+    launch();
+    HIP_TRY(hipGetLastError());
+    return FFS_OK;
+}
+
+// A reduction of n_files * (k + 1) solve records to one record per file (ffs_null_stats, ffs_offset_stats): the checks
+// in the exports' order -- the counts, `own_checks()` for an export's further arguments, the pointers -- then the launch.
+template <class Checks, class Launch>
+int record_stats(const char* fn, const char* k_name, int k_max, const void* rec_dev, int n_files, int k, const void* out_dev,
+                 Checks own_checks, Launch launch) {
+    if (n_files < 0) return fail(FFS_E_INVALID, "%s: n_files=%d is negative", fn, n_files);
+    if (k < 1 || k > k_max) return fail(FFS_E_INVALID, "%s: %s=%d outside [1, %d]", fn, k_name, k, k_max);
+    if (int rc = own_checks()) return rc;
+    if (!rec_dev || !out_dev) return fail(FFS_E_INVALID, "%s: null record or output pointer", fn);
+    if (((uintptr_t)rec_dev | (uintptr_t)out_dev) & 7)
+        return fail(FFS_E_INVALID, "%s: misaligned record or output pointer (8 bytes)", fn);
+    return launch_per_file(n_files, out_dev, launch);
+}
+}
+
+// What tells the two list exports apart: their names, their limits and the launch of their kernel, which receives the
+// staged vector table (on the host and on the device) and returns an FFS_* code.
+struct ListExport {
+    const char* fn;
+    const char* k_name;
+    const char* block_name;
+    int k_max, block_max;
+    int (*launch)(const SurrVec* vecs_host, const SurrVec* vecs_dev, int64_t n_vec, int k, int block, char* out_dev,
+                  int32_t* status_dev, hipStream_t st);
+};
+
+// K resampled lists per vector (ffs_surrogate_lists, ffs_subsample_lists): every argument check before the device is
+// touched, the vector table staged in pinned memory and uploaded behind the caller's stream, then the export's launch.
+int resampled_lists(const ListExport& x, const void* const* list_dev, const int32_t* n_bound, const uint32_t* seed,
+                    const int64_t* out_off, const int64_t* out_cap, int64_t n_vec, int k, int block, void* out_dev,
+                    int64_t out_bytes, int32_t* status_dev, void* hip_stream) {
+    if (n_vec < 0 || out_bytes < 0)
+        return fail(FFS_E_INVALID, "%s: n_vec=%lld or out_bytes=%lld is negative", x.fn, (long long)n_vec, (long long)out_bytes);
+    if (k < 1 || k > x.k_max) return fail(FFS_E_INVALID, "%s: %s=%d outside [1, %d]", x.fn, x.k_name, k, x.k_max);
+    if (block < 1 || block > x.block_max)
+        return fail(FFS_E_INVALID, "%s: %s=%d outside [1, %d]", x.fn, x.block_name, block, x.block_max);
+    if (n_vec == 0) return FFS_OK;
+    if (!list_dev || !n_bound || !seed || !out_off || !out_cap) return fail(FFS_E_INVALID, "%s: null vector table", x.fn);
+    if (!out_dev || !status_dev) return fail(FFS_E_INVALID, "%s: null output or status pointer", x.fn);
+    if (((uintptr_t)out_dev & 7) || ((uintptr_t)status_dev & 3))
+        return fail(FFS_E_INVALID, "%s: misaligned output (8 bytes) or status (4 bytes) pointer", x.fn);
+    if (n_vec * k >= (int64_t(1) << 31))
+        return fail(FFS_E_INVALID, "%s: n_vec * %s = %lld, need < 2^31", x.fn, x.k_name, (long long)(n_vec * k));
+    for (int64_t v = 0; v < n_vec; ++v) {
+        if (!list_dev[v] || ((uintptr_t)list_dev[v] & 7))
+            return fail(FFS_E_INVALID, "%s: vector %lld: null or misaligned list pointer", x.fn, (long long)v);
+        if (n_bound[v] < 0) return fail(FFS_E_INVALID, "%s: vector %lld: n_bound=%d is negative", x.fn, (long long)v, n_bound[v]);
+        if (out_cap[v] < (int64_t)n_bound[v] + 1 || out_cap[v] >= (int64_t(1) << 28))
+            return fail(FFS_E_INVALID, "%s: vector %lld: capacity %lld below n_bound + 1 = %lld (or 2^28 and more)", x.fn,
+                        (long long)v, (long long)out_cap[v], (long long)n_bound[v] + 1);
+        if (out_off[v] < 0 || (out_off[v] & 7) || out_off[v] > out_bytes ||
+            ffs_runs_list_bytes(out_cap[v]) * k > out_bytes - out_off[v])
+            return fail(FFS_E_INVALID, "%s: vector %lld: its %d blocks lie outside the buffer or are misaligned", x.fn,
+                        (long long)v, k);
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    DeviceGuard guard;
+    int rc_dev;
+    if ((rc_dev = guard.enter(out_dev))) return rc_dev;
+    PinnedStage* stage = nullptr;
+    int rc = stage_acquire((size_t)n_vec * sizeof(SurrVec), &stage);
+    if (rc) return rc;
+    SurrVec* hv = (SurrVec*)stage->host;
+    for (int64_t v = 0; v < n_vec; ++v)
+        hv[v] = SurrVec{(const char*)list_dev[v], (long long)out_off[v], seed[v], n_bound[v], (int32_t)out_cap[v], 0};
+    SurrVec* d = nullptr;
+    HIP_TRY(hipMallocAsync((void**)&d, (size_t)n_vec * sizeof(SurrVec), st));
+    if (hipMemcpyAsync(d, hv, (size_t)n_vec * sizeof(SurrVec), hipMemcpyHostToDevice, st) != hipSuccess)
+        rc = fail(FFS_E_HIP, "%s: copying the vector table failed", x.fn);
+    if (rc == FFS_OK && hipEventRecord(stage->done, st) == hipSuccess) stage->pending = true;
+    if (rc == FFS_OK) rc = x.launch(hv, d, n_vec, k, block, (char*)out_dev, status_dev, st);
+    (void)hipFreeAsync(d, st);
+    return rc;
+}
+
+// The surrogate kernel sorts a list's blocks in dynamic LDS: sized for the largest block count of the call.
+int launch_surrogate_lists(const SurrVec* vecs_host, const SurrVec* vecs_dev, int64_t n_vec, int n_surrogates, int block_units,
+                           char* out_dev, int32_t* status_dev, hipStream_t st) {
+    int most_blocks = 1;
+    for (int64_t v = 0; v < n_vec; ++v) {
+        // (a list above the unit limit is answered by empty surrogates: its blocks never reach the sort)
+        const int n_bound = vecs_host[v].n_bound;
+        const int units = n_bound / 2 - 1 < SURR_MAX_UNITS ? n_bound / 2 - 1 : SURR_MAX_UNITS;
+        const int blocks = units > 0 ? (units + block_units - 1) / block_units : 0;
+        if (blocks > most_blocks) most_blocks = blocks;
+    }
+    const size_t lds = surr_lds_bytes(most_blocks);
+    if (lds > (64u << 10))
+        HIP_TRY(hipFuncSetAttribute((const void*)k_surrogate_lists, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_surrogate_lists, dim3((unsigned)(n_vec * n_surrogates)), dim3(SURR_THREADS), lds, st, vecs_dev,
+                       n_surrogates, block_units, out_dev, status_dev);
+    if (hipGetLastError() != hipSuccess) return fail(FFS_E_HIP, "k_surrogate_lists launch failed");
+    return FFS_OK;
+}
+
+int launch_subsample_lists(const SurrVec*, const SurrVec* vecs_dev, int64_t n_vec, int n_subsamples, int block_runs,
+                           char* out_dev, int32_t* status_dev, hipStream_t st) {
+    hipLaunchKernelGGL(k_subsample_lists, dim3((unsigned)(n_vec * n_subsamples)), dim3(STAB_THREADS), 0, st, vecs_dev,
+                       n_subsamples, block_runs, out_dev, status_dev);
+    if (hipGetLastError() != hipSuccess) return fail(FFS_E_HIP, "k_subsample_lists launch failed");
+    return FFS_OK;
+}
+
+constexpr ListExport SURROGATE_LISTS = {"ffs_surrogate_lists", "n_surrogates", "block_units", SURR_MAX_K, SURR_MAX_UNITS,
+                                        launch_surrogate_lists};
+constexpr ListExport SUBSAMPLE_LISTS = {"ffs_subsample_lists", "n_subsamples", "block_runs", STAB_MAX_K, STAB_MAX_BLOCK_RUNS,
+                                        launch_subsample_lists};
+}  // namespace
+
 int ffs_sweep_peaks(const ffs_cand_result* rec_dev, const int64_t* first_dev, int n_files, int top_k,
                     int64_t exclusion_steps, ffs_sweep_profile* out_dev, void* hip_stream) {
     static_assert(sizeof(ffs_sweep_profile) == sizeof(SweepProfile) && sizeof(ffs_cand_result) == sizeof(CandResult),
@@ -3208,164 +3334,45 @@ int ffs_sweep_peaks(const ffs_cand_result* rec_dev, const int64_t* first_dev, in
     if (!rec_dev || !first_dev || !out_dev) return fail(FFS_E_INVALID, "ffs_sweep_peaks: null record, first or output pointer");
     if (((uintptr_t)rec_dev | (uintptr_t)first_dev | (uintptr_t)out_dev) & 7)
         return fail(FFS_E_INVALID, "ffs_sweep_peaks: misaligned record, first or output pointer (8 bytes)");
-    if (n_files == 0) return FFS_OK;
-    DeviceGuard guard;
-    int rc_dev;
-    if ((rc_dev = guard.enter(out_dev))) return rc_dev;
-    hipLaunchKernelGGL(k_sweep_peaks, dim3((unsigned)n_files), dim3(SWEEP_THREADS), 0, (hipStream_t)hip_stream,
-                       (const CandResult*)rec_dev, first_dev, top_k, exclusion_steps, (SweepProfile*)out_dev);
-    HIP_TRY(hipGetLastError());
-    return FFS_OK;
+    // (its pointer checks cover `first_dev` and word them so: only the launch is the reductions' shared one)
+    return launch_per_file(n_files, out_dev, [&] {
+        hipLaunchKernelGGL(k_sweep_peaks, dim3((unsigned)n_files), dim3(SWEEP_THREADS), 0, (hipStream_t)hip_stream,
+                           (const CandResult*)rec_dev, first_dev, top_k, exclusion_steps, (SweepProfile*)out_dev);
+    });
 }
 
 int ffs_surrogate_lists(const void* const* list_dev, const int32_t* n_bound, const uint32_t* seed, const int64_t* out_off,
                         const int64_t* out_cap, int64_t n_vec, int n_surrogates, int block_units, void* out_dev,
                         int64_t out_bytes, int32_t* status_dev, void* hip_stream) {
-    if (n_vec < 0 || out_bytes < 0)
-        return fail(FFS_E_INVALID, "ffs_surrogate_lists: n_vec=%lld or out_bytes=%lld is negative", (long long)n_vec, (long long)out_bytes);
-    if (n_surrogates < 1 || n_surrogates > SURR_MAX_K)
-        return fail(FFS_E_INVALID, "ffs_surrogate_lists: n_surrogates=%d outside [1, %d]", n_surrogates, SURR_MAX_K);
-    if (block_units < 1 || block_units > SURR_MAX_UNITS)
-        return fail(FFS_E_INVALID, "ffs_surrogate_lists: block_units=%d outside [1, %d]", block_units, SURR_MAX_UNITS);
-    if (n_vec == 0) return FFS_OK;
-    if (!list_dev || !n_bound || !seed || !out_off || !out_cap) return fail(FFS_E_INVALID, "ffs_surrogate_lists: null vector table");
-    if (!out_dev || !status_dev) return fail(FFS_E_INVALID, "ffs_surrogate_lists: null output or status pointer");
-    if (((uintptr_t)out_dev & 7) || ((uintptr_t)status_dev & 3))
-        return fail(FFS_E_INVALID, "ffs_surrogate_lists: misaligned output (8 bytes) or status (4 bytes) pointer");
-    if (n_vec * n_surrogates >= (int64_t(1) << 31)) return fail(FFS_E_INVALID, "ffs_surrogate_lists: n_vec * n_surrogates = %lld, need < 2^31", (long long)(n_vec * n_surrogates));
-    int most_blocks = 1;
-    for (int64_t v = 0; v < n_vec; ++v) {
-        if (!list_dev[v] || ((uintptr_t)list_dev[v] & 7))
-            return fail(FFS_E_INVALID, "ffs_surrogate_lists: vector %lld: null or misaligned list pointer", (long long)v);
-        if (n_bound[v] < 0) return fail(FFS_E_INVALID, "ffs_surrogate_lists: vector %lld: n_bound=%d is negative", (long long)v, n_bound[v]);
-        if (out_cap[v] < (int64_t)n_bound[v] + 1 || out_cap[v] >= (int64_t(1) << 28))
-            return fail(FFS_E_INVALID, "ffs_surrogate_lists: vector %lld: capacity %lld below n_bound + 1 = %lld (or 2^28 and more)",
-                        (long long)v, (long long)out_cap[v], (long long)n_bound[v] + 1);
-        if (out_off[v] < 0 || (out_off[v] & 7) || out_off[v] > out_bytes ||
-            ffs_runs_list_bytes(out_cap[v]) * n_surrogates > out_bytes - out_off[v])
-            return fail(FFS_E_INVALID, "ffs_surrogate_lists: vector %lld: its %d blocks lie outside the buffer or are misaligned",
-                        (long long)v, n_surrogates);
-        // (a list above the unit limit is answered by empty surrogates: its blocks never reach the sort)
-        const int units = n_bound[v] / 2 - 1 < SURR_MAX_UNITS ? n_bound[v] / 2 - 1 : SURR_MAX_UNITS;
-        const int blocks = units > 0 ? (units + block_units - 1) / block_units : 0;
-        if (blocks > most_blocks) most_blocks = blocks;
-    }
-    hipStream_t st = (hipStream_t)hip_stream;
-    DeviceGuard guard;
-    int rc_dev;
-    if ((rc_dev = guard.enter(out_dev))) return rc_dev;
-    const size_t lds = surr_lds_bytes(most_blocks);
-    if (lds > (64u << 10))
-        HIP_TRY(hipFuncSetAttribute((const void*)k_surrogate_lists, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const dim3 grid((unsigned)(n_vec * n_surrogates));
-    PinnedStage* stage = nullptr;
-    int rc = stage_acquire((size_t)n_vec * sizeof(SurrVec), &stage);
-    if (rc) return rc;
-    SurrVec* hv = (SurrVec*)stage->host;
-    for (int64_t v = 0; v < n_vec; ++v)
-        hv[v] = SurrVec{(const char*)list_dev[v], (long long)out_off[v], seed[v], n_bound[v], (int32_t)out_cap[v], 0};
-    SurrVec* d = nullptr;
-    HIP_TRY(hipMallocAsync((void**)&d, (size_t)n_vec * sizeof(SurrVec), st));
-    if (hipMemcpyAsync(d, hv, (size_t)n_vec * sizeof(SurrVec), hipMemcpyHostToDevice, st) != hipSuccess)
-        rc = fail(FFS_E_HIP, "ffs_surrogate_lists: copying the vector table failed");
-    if (rc == FFS_OK && hipEventRecord(stage->done, st) == hipSuccess) stage->pending = true;
-    if (rc == FFS_OK) {
-        hipLaunchKernelGGL(k_surrogate_lists, grid, dim3(SURR_THREADS), lds, st, (const SurrVec*)d, n_surrogates, block_units,
-                           (char*)out_dev, status_dev);
-        if (hipGetLastError() != hipSuccess) rc = fail(FFS_E_HIP, "k_surrogate_lists launch failed");
-    }
-    (void)hipFreeAsync(d, st);
-    return rc;
+    return resampled_lists(SURROGATE_LISTS, list_dev, n_bound, seed, out_off, out_cap, n_vec, n_surrogates, block_units, out_dev,
+                           out_bytes, status_dev, hip_stream);
 }
 
 int ffs_null_stats(const ffs_cand_result* rec_dev, int n_files, int n_surrogates, ffs_null_result* out_dev, void* hip_stream) {
     static_assert(sizeof(ffs_null_result) == sizeof(NullResult), "device records must match the header's");
-    if (n_files < 0) return fail(FFS_E_INVALID, "ffs_null_stats: n_files=%d is negative", n_files);
-    if (n_surrogates < 1 || n_surrogates > SURR_MAX_K)
-        return fail(FFS_E_INVALID, "ffs_null_stats: n_surrogates=%d outside [1, %d]", n_surrogates, SURR_MAX_K);
-    if (!rec_dev || !out_dev) return fail(FFS_E_INVALID, "ffs_null_stats: null record or output pointer");
-    if (((uintptr_t)rec_dev | (uintptr_t)out_dev) & 7)
-        return fail(FFS_E_INVALID, "ffs_null_stats: misaligned record or output pointer (8 bytes)");
-    if (n_files == 0) return FFS_OK;
-    DeviceGuard guard;
-    int rc_dev;
-    if ((rc_dev = guard.enter(out_dev))) return rc_dev;
-    hipLaunchKernelGGL(k_null_stats, dim3((unsigned)n_files), dim3(SWEEP_THREADS), 0, (hipStream_t)hip_stream,
-                       (const CandResult*)rec_dev, n_surrogates, (NullResult*)out_dev);
-    HIP_TRY(hipGetLastError());
-    return FFS_OK;
+    return record_stats("ffs_null_stats", "n_surrogates", SURR_MAX_K, rec_dev, n_files, n_surrogates, out_dev,
+                        [] { return FFS_OK; }, [&] {
+        hipLaunchKernelGGL(k_null_stats, dim3((unsigned)n_files), dim3(SWEEP_THREADS), 0, (hipStream_t)hip_stream,
+                           (const CandResult*)rec_dev, n_surrogates, (NullResult*)out_dev);
+    });
 }
 
 int ffs_subsample_lists(const void* const* list_dev, const int32_t* n_bound, const uint32_t* seed, const int64_t* out_off,
                         const int64_t* out_cap, int64_t n_vec, int n_subsamples, int block_runs, void* out_dev,
                         int64_t out_bytes, int32_t* status_dev, void* hip_stream) {
-    if (n_vec < 0 || out_bytes < 0)
-        return fail(FFS_E_INVALID, "ffs_subsample_lists: n_vec=%lld or out_bytes=%lld is negative", (long long)n_vec, (long long)out_bytes);
-    if (n_subsamples < 1 || n_subsamples > STAB_MAX_K)
-        return fail(FFS_E_INVALID, "ffs_subsample_lists: n_subsamples=%d outside [1, %d]", n_subsamples, STAB_MAX_K);
-    if (block_runs < 1 || block_runs > STAB_MAX_BLOCK_RUNS)
-        return fail(FFS_E_INVALID, "ffs_subsample_lists: block_runs=%d outside [1, %d]", block_runs, STAB_MAX_BLOCK_RUNS);
-    if (n_vec == 0) return FFS_OK;
-    if (!list_dev || !n_bound || !seed || !out_off || !out_cap) return fail(FFS_E_INVALID, "ffs_subsample_lists: null vector table");
-    if (!out_dev || !status_dev) return fail(FFS_E_INVALID, "ffs_subsample_lists: null output or status pointer");
-    if (((uintptr_t)out_dev & 7) || ((uintptr_t)status_dev & 3))
-        return fail(FFS_E_INVALID, "ffs_subsample_lists: misaligned output (8 bytes) or status (4 bytes) pointer");
-    if (n_vec * n_subsamples >= (int64_t(1) << 31))
-        return fail(FFS_E_INVALID, "ffs_subsample_lists: n_vec * n_subsamples = %lld, need < 2^31", (long long)(n_vec * n_subsamples));
-    for (int64_t v = 0; v < n_vec; ++v) {
-        if (!list_dev[v] || ((uintptr_t)list_dev[v] & 7))
-            return fail(FFS_E_INVALID, "ffs_subsample_lists: vector %lld: null or misaligned list pointer", (long long)v);
-        if (n_bound[v] < 0) return fail(FFS_E_INVALID, "ffs_subsample_lists: vector %lld: n_bound=%d is negative", (long long)v, n_bound[v]);
-        if (out_cap[v] < (int64_t)n_bound[v] + 1 || out_cap[v] >= (int64_t(1) << 28))
-            return fail(FFS_E_INVALID, "ffs_subsample_lists: vector %lld: capacity %lld below n_bound + 1 = %lld (or 2^28 and more)",
-                        (long long)v, (long long)out_cap[v], (long long)n_bound[v] + 1);
-        if (out_off[v] < 0 || (out_off[v] & 7) || out_off[v] > out_bytes ||
-            ffs_runs_list_bytes(out_cap[v]) * n_subsamples > out_bytes - out_off[v])
-            return fail(FFS_E_INVALID, "ffs_subsample_lists: vector %lld: its %d blocks lie outside the buffer or are misaligned",
-                        (long long)v, n_subsamples);
-    }
-    hipStream_t st = (hipStream_t)hip_stream;
-    DeviceGuard guard;
-    int rc_dev;
-    if ((rc_dev = guard.enter(out_dev))) return rc_dev;
-    PinnedStage* stage = nullptr;
-    int rc = stage_acquire((size_t)n_vec * sizeof(SurrVec), &stage);
-    if (rc) return rc;
-    SurrVec* hv = (SurrVec*)stage->host;
-    for (int64_t v = 0; v < n_vec; ++v)
-        hv[v] = SurrVec{(const char*)list_dev[v], (long long)out_off[v], seed[v], n_bound[v], (int32_t)out_cap[v], 0};
-    SurrVec* d = nullptr;
-    HIP_TRY(hipMallocAsync((void**)&d, (size_t)n_vec * sizeof(SurrVec), st));
-    if (hipMemcpyAsync(d, hv, (size_t)n_vec * sizeof(SurrVec), hipMemcpyHostToDevice, st) != hipSuccess)
-        rc = fail(FFS_E_HIP, "ffs_subsample_lists: copying the vector table failed");
-    if (rc == FFS_OK && hipEventRecord(stage->done, st) == hipSuccess) stage->pending = true;
-    if (rc == FFS_OK) {
-        hipLaunchKernelGGL(k_subsample_lists, dim3((unsigned)(n_vec * n_subsamples)), dim3(STAB_THREADS), 0, st, (const SurrVec*)d,
-                           n_subsamples, block_runs, (char*)out_dev, status_dev);
-        if (hipGetLastError() != hipSuccess) rc = fail(FFS_E_HIP, "k_subsample_lists launch failed");
-    }
-    (void)hipFreeAsync(d, st);
-    return rc;
+    return resampled_lists(SUBSAMPLE_LISTS, list_dev, n_bound, seed, out_off, out_cap, n_vec, n_subsamples, block_runs, out_dev,
+                           out_bytes, status_dev, hip_stream);
 }
 
 int ffs_offset_stats(const ffs_cand_result* rec_dev, int n_files, int n_subsamples, int64_t tol, ffs_stability_result* out_dev,
                      void* hip_stream) {
     static_assert(sizeof(ffs_stability_result) == sizeof(StabilityResult), "device records must match the header's");
-    if (n_files < 0) return fail(FFS_E_INVALID, "ffs_offset_stats: n_files=%d is negative", n_files);
-    if (n_subsamples < 1 || n_subsamples > STAB_MAX_K)
-        return fail(FFS_E_INVALID, "ffs_offset_stats: n_subsamples=%d outside [1, %d]", n_subsamples, STAB_MAX_K);
-    if (tol < 0) return fail(FFS_E_INVALID, "ffs_offset_stats: tol=%lld is negative", (long long)tol);
-    if (!rec_dev || !out_dev) return fail(FFS_E_INVALID, "ffs_offset_stats: null record or output pointer");
-    if (((uintptr_t)rec_dev | (uintptr_t)out_dev) & 7)
-        return fail(FFS_E_INVALID, "ffs_offset_stats: misaligned record or output pointer (8 bytes)");
-    if (n_files == 0) return FFS_OK;
-    DeviceGuard guard;
-    int rc_dev;
-    if ((rc_dev = guard.enter(out_dev))) return rc_dev;
-    hipLaunchKernelGGL(k_offset_stats, dim3((unsigned)n_files), dim3(STAB_THREADS), 0, (hipStream_t)hip_stream,
-                       (const CandResult*)rec_dev, n_subsamples, (long long)tol, (StabilityResult*)out_dev);
-    HIP_TRY(hipGetLastError());
-    return FFS_OK;
+    return record_stats("ffs_offset_stats", "n_subsamples", STAB_MAX_K, rec_dev, n_files, n_subsamples, out_dev,
+                        [&] { return tol < 0 ? fail(FFS_E_INVALID, "ffs_offset_stats: tol=%lld is negative", (long long)tol) : FFS_OK; },
+                        [&] {
+        hipLaunchKernelGGL(k_offset_stats, dim3((unsigned)n_files), dim3(STAB_THREADS), 0, (hipStream_t)hip_stream,
+                           (const CandResult*)rec_dev, n_subsamples, (long long)tol, (StabilityResult*)out_dev);
+    });
 }
 
 /* ---- host code shared by the split, split range and quality plans --------------------------------------------- */

@@ -17,6 +17,11 @@ A half-sample cuts ALL runs of the list into blocks of ``block_runs`` consecutiv
 the surrogate hash of (seed, s >> 1, b), flipped for odd s, is set: half-samples 2j and 2j + 1 are complementary.
 Seeds: file i of a call uses ``surrogate.file_seed(seed, i)`` unless the caller passes ``seeds``.
 
+Shared with ``surrogate.py`` and kept in ``resample_call.py``: the seeds, the list checks, the block layout around the
+native list call, the chunked solve with its careful redo, and the checks and first half of a sync.  This module's own:
+its limits and their checks, the half-sample list maker and the reduction with its ``tol``, the record, the interval,
+the verdict and its wording.
+
 What it says and what it does not.  The interval is the central 90 % of the half-sample offsets (``off_lo``, ``off_hi``);
 ``max_dev`` and ``n_within`` count against the full solve's offset.  The defaults come from SYNTHETIC data only
 (profiles/stability_calibration.json); nobody has measured real files.  By the rule of DESIGN 3.25 the calibration ships
@@ -27,16 +32,18 @@ the classes do not separate at it (``DEFAULT_MIN_SHARE`` is None: ``stable`` is 
 Parity is against the in-repo numpy model ``tests/stability_model.py``.  Nothing here changes an existing entry point;
 nothing is reachable from the reference CLI.
 """
+import functools
 import math
 from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import _native
-from .constants import SAMPLE_RATE, candidate_ratios
-from .side_call import pairs_for_budget
-from .surrogate import CHUNK_BUDGET, CHUNK_CAP, _check_lists, _check_seed, _list_vector, _winning_lists, file_seed, fmix32  # noqa: F401
+from . import _native, resample_call
+from .constants import SAMPLE_RATE
+# (the shared pieces keep their names here: tests reach them as ``stability.*``)
+from .resample_call import (CHUNK_BUDGET, CHUNK_CAP, ResampleKind, _check_lists, _check_seed, _list_vector, _winning_lists,
+                            file_seed, fmix32, list_blocks, test_lists)
 
 # By the rules of DESIGN 3.25 on the CPU model (profiles/stability_calibration.json; synthetic data, 10 min and 1 h, 32 + 32
 # files each, block_runs 1 and 8): twice the largest matched max_dev (8182: block_runs 8 at 10 min, a half-sample that kept
@@ -48,6 +55,7 @@ MAX_SUBSAMPLES = _native.STAB_MAX_K
 MAX_BLOCK_RUNS = _native.STAB_MAX_BLOCK_RUNS
 MAX_BOUND = (1 << 28) - 2  # boundaries of a list whose block of n + 1 entries the ABI takes
 MIN_BLOCKS = 8  # fewer blocks: a half-sample keeps none or one of them too often
+_LIMIT_TEXT = "what a list block holds (%d)" % MAX_BOUND
 
 
 @dataclass
@@ -126,26 +134,9 @@ def subsample_lists(list_ptr, n_bound, lens, seeds, n_subsamples: int = DEFAULT_
     ``n_bound + 1`` entries.  With ``raw`` the status is the int32 CUDA tensor and nothing is waited for or read back;
     otherwise it is read back to a host array."""
     _check_resample(n_subsamples, block_runs)
-    ptr, n_bound, lens = _check_lists("subsample_lists", list_ptr, n_bound, lens)
-    seeds = np.ascontiguousarray(seeds, dtype=np.int64).ravel()
-    if seeds.size != ptr.size or (seeds < 0).any() or (seeds > 0xFFFFFFFF).any():
-        raise ValueError("subsample_lists: need one seed in [0, 2^32) per vector")
-    if (n_bound > MAX_BOUND).any():
-        raise ValueError("subsample_lists: a list of up to %d boundaries is above what a list block holds (%d)"
-                         % (int(n_bound.max()), MAX_BOUND))
-    torch = _native.require_gpu()
-    k = int(n_subsamples)
-    caps = n_bound + 1
-    block = 16 + 8 * caps
-    first = np.zeros(ptr.size, dtype=np.int64)
-    if ptr.size:
-        np.cumsum((block * k)[:-1], out=first[1:])
-    total = int((block * k).sum())
-    out = torch.empty(max(total, 8), dtype=torch.uint8, device="cuda")
-    status = torch.empty(max(ptr.size, 1), dtype=torch.int32, device="cuda")
-    _native.subsample_lists(ptr, n_bound, seeds, first, caps, k, int(block_runs), out, status)
-    status = status[:ptr.size]
-    return out, first[:, None] + block[:, None] * np.arange(k, dtype=np.int64)[None, :], status if raw else status.cpu().numpy()
+    out, offs, status = list_blocks("subsample_lists", _native.subsample_lists, MAX_BOUND, _LIMIT_TEXT, list_ptr, n_bound, lens,
+                                    seeds, n_subsamples, block_runs)
+    return out, offs, status if raw else status.cpu().numpy()
 
 
 def offset_stats(table, n_files: int, n_subsamples: int, tol: int = DEFAULT_TOL, raw: bool = False):
@@ -163,26 +154,10 @@ def offset_stats(table, n_files: int, n_subsamples: int, tol: int = DEFAULT_TOL,
     return out.cpu().numpy().view(_native.STABILITY_RESULT_DTYPE)[:int(n_files)]
 
 
-def _levels(values, n, default):
-    if values is None:
-        return np.full(n, default, dtype=np.float64)
-    values = np.ascontiguousarray(values, dtype=np.float64).ravel()
-    if values.size != n or not np.all(np.isfinite(values)):
-        raise ValueError("stability_test_lists: need one finite level per file")
-    return values
-
-
-def _careful(ref, sub, seed, k, block_runs, w) -> np.ndarray:
-    """The K + 1 records of one file through the drop-in's ``solve_pairs`` (ambiguity handling), as ``surrogate._careful``
-    redoes a file: ``ref`` / ``sub`` = (list pointer, bound, length, lo, hi)."""
-    from .aligners import _Vec, solve_pairs
-
-    buf, offs, _ = subsample_lists([sub[0]], [sub[1]], [sub[2]], [seed], k, block_runs, raw=True)
-    ref_vec = _Vec(_list_vector(ref[0], ref[2], ref[3], ref[4]))
-    ptrs = [int(sub[0])] + [buf.data_ptr() + int(o) for o in offs[0]]
-    pairs = [(ref_vec, [_Vec(_list_vector(p, sub[2], sub[3], sub[4]))]) for p in ptrs]
-    cres, _ = solve_pairs(pairs, w)
-    return np.ascontiguousarray(cres[:, 0])
+_raw_lists = functools.partial(subsample_lists, raw=True)
+_careful = functools.partial(resample_call._careful, _raw_lists)  # (ref, sub, seed, k, block_runs, w)
+_KIND = ResampleKind("stability_test_lists", _raw_lists, _native.STABILITY_RESULT_DTYPE, _native.STAB_AMBIGUOUS, "n_subsamples",
+                     "block_runs", MAX_BOUND, _LIMIT_TEXT)
 
 
 def stability_test_lists(ref_ptr, ref_len, ref_bound, sub_ptr, sub_len, sub_bound, max_offset_samples: int,
@@ -205,75 +180,9 @@ def stability_test_lists(ref_ptr, ref_len, ref_bound, sub_ptr, sub_len, sub_boun
     _check_resample(n_subsamples, block_runs)
     seed = _check_seed(seed)
     tol = _check_tol(tol)
-    w = int(max_offset_samples)
-    if w != max_offset_samples or w < 1:
-        raise ValueError("max_offset_samples=%r: need a window of at least one sample" % (max_offset_samples,))
-    if int(budget_bytes) < 1:
-        raise ValueError("budget_bytes=%r: need a positive number of bytes" % (budget_bytes,))
-    ref_ptr, ref_bound, ref_len = _check_lists("stability_test_lists (references)", ref_ptr, ref_bound, ref_len)
-    sub_ptr, sub_bound, sub_len = _check_lists("stability_test_lists (subtitles)", sub_ptr, sub_bound, sub_len)
-    n = sub_ptr.size
-    if ref_ptr.size != n:
-        raise ValueError("stability_test_lists: %d references for %d subtitle lists" % (ref_ptr.size, n))
-    if (sub_bound > MAX_BOUND).any():
-        raise ValueError("stability_test_lists: a subtitle list of up to %d boundaries is above what a list block holds (%d)"
-                         % (int(sub_bound.max()), MAX_BOUND))
-    if (ref_bound >= 32768).any():
-        raise ValueError("stability_test_lists: a reference of %d or more run boundaries is too dense for a list" % 32768)
-    ref_lo, ref_hi = _levels(ref_lo, n, 0.0), _levels(ref_hi, n, 1.0)
-    sub_lo, sub_hi = _levels(sub_lo, n, 0.0), _levels(sub_hi, n, 1.0)
-    if seeds is None:
-        seeds = np.array([file_seed(seed, i) for i in range(n)], dtype=np.int64)
-    else:
-        seeds = np.ascontiguousarray(seeds, dtype=np.int64).ravel()
-        if seeds.size != n or (seeds < 0).any() or (seeds > 0xFFFFFFFF).any():
-            raise ValueError("stability_test_lists: need one seed in [0, 2^32) per file")
-    torch = _native.require_gpu()
-    k = int(n_subsamples)
-    stats = {"files": n, "n_subsamples": k, "block_runs": int(block_runs), "chunks": 0, "careful_files": 0}
-    table = torch.empty(max(n * (k + 1), 1) * 24, dtype=torch.uint8, device="cuda")
-    if n == 0:
-        return StabilityTest(np.zeros(0, _native.STABILITY_RESULT_DTYPE), table, np.zeros(0, np.int32), seeds.astype(np.uint32),
-                             stats)
-    per_file = k * (16 + 8 * (int(sub_bound.max()) + 1))
-    chunk = pairs_for_budget(n, per_file, cap=max(CHUNK_CAP // (k + 1), 1), budget=int(budget_bytes))
-    n_fft = max(_native.plan_length(int(r), int(s), w) for r, s in zip(ref_len, sub_len))
-    if n_fft > _native.MAX_FFT_LENGTH:
-        raise ValueError("inputs too long for the device transform (N=%d > 2^24)" % n_fft)
-    plan = _native.get_plan(n_fft, pairs_in_flight=min(chunk * (k + 1), 512), max_cand=1)
-    status = torch.empty(n, dtype=torch.int32, device="cuda")
-    pair_out = torch.empty(chunk * (k + 1) * 24, dtype=torch.uint8, device="cuda")
-    runs = (_native.FFS_DTYPE_RUNS, _native.FFS_DTYPE_RUNS)
-    for a in range(0, n, chunk):
-        b = min(a + chunk, n)
-        m = (b - a) * (k + 1)
-        buf, offs, st = subsample_lists(sub_ptr[a:b], sub_bound[a:b], sub_len[a:b], seeds[a:b], k, block_runs, raw=True)
-        status[a:b] = st
-        cand = np.empty((b - a, k + 1), dtype=np.uint64)
-        cand[:, 0] = sub_ptr[a:b]
-        cand[:, 1:] = np.uint64(buf.data_ptr()) + offs.astype(np.uint64)
-        rep = lambda x: np.repeat(x[a:b], k + 1)
-        ptrs, lens = np.empty(2 * m, np.uint64), np.empty(2 * m, np.int64)
-        lo, hi, bounds = np.empty(2 * m), np.empty(2 * m), np.empty(2 * m, np.int32)
-        ptrs[0::2], lens[0::2], lo[0::2], hi[0::2], bounds[0::2] = rep(ref_ptr), rep(ref_len), rep(ref_lo), rep(ref_hi), np.maximum(rep(ref_bound), 2)
-        ptrs[1::2], lens[1::2], lo[1::2], hi[1::2], bounds[1::2] = cand.ravel(), rep(sub_len), rep(sub_lo), rep(sub_hi), np.maximum(rep(sub_bound), 2)
-        plan.align_batch(m, 1, runs, ptrs, lens, lo, hi, w, None, table[a * (k + 1) * 24:], pair_out, vec_max_boundaries=bounds)
-        stats["chunks"] += 1
-        del buf  # (stream-ordered: the allocator hands the block out again only behind the solve)
-    out = _native.offset_stats(table, n, k, tol)
-    if raw:
-        return StabilityTest(out, table, status, seeds.astype(np.uint32), stats)
-    records = out.cpu().numpy().view(_native.STABILITY_RESULT_DTYPE)[:n].copy()
-    status_h = status.cpu().numpy()
-    amb = np.flatnonzero((records["flags"] & _native.STAB_AMBIGUOUS) != 0)
-    if amb.size:  # degenerate input (e.g. a silent reference): the careful path, file by file
-        for f in amb:
-            recs = _careful((ref_ptr[f], ref_bound[f], ref_len[f], ref_lo[f], ref_hi[f]),
-                            (sub_ptr[f], sub_bound[f], sub_len[f], sub_lo[f], sub_hi[f]), int(seeds[f]), k, block_runs, w)
-            table[f * (k + 1) * 24:(f + 1) * (k + 1) * 24] = torch.from_numpy(recs.view(np.uint8).copy()).cuda()
-            stats["careful_files"] += 1
-        records = _native.offset_stats(table, n, k, tol).cpu().numpy().view(_native.STABILITY_RESULT_DTYPE)[:n].copy()
-    return StabilityTest(records, table, status_h, seeds.astype(np.uint32), stats)
+    return StabilityTest(*test_lists(_KIND, functools.partial(_native.offset_stats, tol=tol), ref_ptr, ref_len, ref_bound,
+                                     sub_ptr, sub_len, sub_bound, max_offset_samples, n_subsamples, block_runs, seed, ref_lo,
+                                     ref_hi, sub_lo, sub_hi, seeds, budget_bytes, raw))
 
 
 def record_of(rec) -> StabilityRecord:
@@ -311,17 +220,10 @@ def assess(record: StabilityRecord, blocks: int, min_share: Optional[float] = DE
 
 def _check_sync(problems, max_offset_seconds, ratios, sample_rate, start_seconds, min_share):
     """Host checks of ``stable_sync`` (ValueError before any native call); returns (window in samples, ratios)."""
-    from .ratio_sweep import _check_problems
-
-    if start_seconds > 0:
-        raise ValueError("stable_sync needs start_seconds <= 0: boundary lists cannot hold the negative start samples of "
-                         "start_seconds > 0")
+    resample_call._check_start("stable_sync", start_seconds)
     if min_share is not None and not (math.isfinite(min_share) and 0 <= min_share <= 1):
         raise ValueError("min_share=%r: need a number in [0, 1] (or None: no verdict)" % (min_share,))
-    ratios = [float(r) for r in (candidate_ratios() if ratios is None else ratios)]
-    if not ratios or not all(math.isfinite(r) and r > 0 for r in ratios):
-        raise ValueError("ratios=%r: need at least one finite ratio > 0" % (ratios,))
-    return _check_problems(problems, max_offset_seconds, sample_rate, CHUNK_BUDGET), ratios
+    return resample_call._check_ratios_and_problems(problems, max_offset_seconds, ratios, sample_rate)
 
 
 def stable_sync(problems, max_offset_seconds: float = 60, ratios: Optional[Sequence[float]] = None,
@@ -353,8 +255,7 @@ def stable_sync(problems, max_offset_seconds: float = 60, ratios: Optional[Seque
     for f in range(len(problems)):
         record = record_of(test.records[f])
         blocks = n_blocks(int(n_sub[f]), block_runs)
-        out.append(StableSyncResult(float(best_ratio[f]), int(best[f]), int(recs[f][best[f]]["offset"]),
-                                    float(recs[f][best[f]]["score"]), record, (record.off_lo, record.off_hi),
+        out.append(StableSyncResult(*resample_call._sync_head(recs, best, best_ratio, f), record, (record.off_lo, record.off_hi),
                                     (record.off_lo / float(sample_rate), record.off_hi / float(sample_rate)),
                                     share_within(record), blocks, stable(record, min_share), assess(record, blocks, min_share)))
     return out

@@ -21,20 +21,27 @@ intact (the null then keeps scene-level clustering too, and is wider).
 Seeds: file i of a call is shuffled with ``fmix32(seed + i)`` (``file_seed``), so a file's null depends on its position
 in the call unless the caller passes ``seeds`` (one uint32 per file) to ``null_test_lists`` itself.
 
+Shared with ``stability.py`` and kept in ``resample_call.py``: the seeds, the list checks, the block layout around the
+native list call, the chunked solve with its careful redo, and the checks and first half of a sync.  This module's own:
+its limits and their checks, the surrogate list maker and the reduction, the record, z, p, the verdict and its wording.
+
 What the test says and what it does not: it tests "related at all", not "offset correct to the sample"; it covers the
 +-W lag window only; its z threshold (``DEFAULT_MIN_Z``) is calibrated on synthetic data, the ``n_ge == 0`` half of the
 verdict is not calibrated at all.  Parity is against the in-repo numpy model ``tests/surrogate_model.py``.  Nothing here
 changes an existing entry point; nothing is reachable from the reference CLI.
 """
+import functools
 import math
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
 import numpy as np
 
-from . import _native
-from .constants import SAMPLE_RATE, candidate_ratios
-from .side_call import pairs_for_budget
+from . import _native, resample_call
+from .constants import SAMPLE_RATE
+# (the shared pieces keep their names here: callers, profiles and tests reach them as ``surrogate.*``)
+from .resample_call import (CHUNK_BUDGET, CHUNK_CAP, ResampleKind, _check_lists, _check_seed, _host_boundaries, _list_vector,
+                            _winning_lists, file_seed, fmix32, list_blocks, test_lists)
 
 # Chosen on the CPU model by the rule of DESIGN 3.24 (profiles/null_calibration.json; synthetic data, 10 min and 1 h,
 # 32 + 32 files each, block_units 1 and 8): the midpoint between the smallest matched z and the largest wrong z
@@ -44,8 +51,7 @@ MAX_SURROGATES = _native.SURR_MAX_K
 MAX_UNITS = _native.SURR_MAX_UNITS
 MAX_BOUND = 2 * MAX_UNITS + 2  # boundaries of a list with MAX_UNITS units
 MIN_BLOCKS = 8  # fewer blocks: K surrogates repeat the few orders there are
-CHUNK_BUDGET = 2 << 30  # bytes of surrogate list blocks one chunk may hold
-CHUNK_CAP = 1 << 16  # solves per align_batch call at most
+_LIMIT_TEXT = "the unit limit (%d units, %d boundaries)" % (MAX_UNITS, MAX_BOUND)
 
 
 @dataclass
@@ -89,22 +95,6 @@ class NullSyncResult:
     reasons: List[str]  # what speaks against the result (the last kind, "too few cues", is a warning about the null)
 
 
-def fmix32(h: int) -> int:
-    """The 32-bit finaliser of the surrogate hash (include/ffsubsync_amd.h)."""
-    h &= 0xFFFFFFFF
-    h ^= h >> 16
-    h = (h * 0x85EBCA6B) & 0xFFFFFFFF
-    h ^= h >> 13
-    h = (h * 0xC2B2AE35) & 0xFFFFFFFF
-    h ^= h >> 16
-    return h
-
-
-def file_seed(seed: int, index: int) -> int:
-    """The seed of file ``index`` of a call made with ``seed``."""
-    return fmix32((int(seed) + int(index)) & 0xFFFFFFFF)
-
-
 def n_blocks(n_boundaries: int, block_units: int) -> int:
     """Blocks of a list with ``n_boundaries`` entries: ceil((n / 2 - 1) / block_units)."""
     return (max(int(n_boundaries) // 2 - 1, 0) + int(block_units) - 1) // int(block_units)
@@ -118,27 +108,6 @@ def _check_shuffle(n_surrogates, block_units) -> None:
         raise ValueError("block_units=%r: need an integer in [1, %d]" % (block_units, MAX_UNITS))
 
 
-def _check_seed(seed) -> int:
-    if int(seed) != seed or not 0 <= int(seed) <= 0xFFFFFFFF:
-        raise ValueError("seed=%r: need an integer in [0, 2^32)" % (seed,))
-    return int(seed)
-
-
-def _check_lists(what, ptr, n_bound, lens):
-    ptr = np.ascontiguousarray(ptr, dtype=np.uint64).ravel()
-    n_bound = np.ascontiguousarray(n_bound, dtype=np.int64).ravel()
-    lens = np.ascontiguousarray(lens, dtype=np.int64).ravel()
-    if not ptr.size == n_bound.size == lens.size:
-        raise ValueError("%s: pointers, bounds and lengths of different sizes" % what)
-    if (ptr == 0).any() or (ptr & np.uint64(7)).any():
-        raise ValueError("%s: a list pointer is null or not 8-byte aligned" % what)
-    if (lens < 1).any():
-        raise ValueError("%s: a vector of %d samples" % (what, int(lens.min())))
-    if (n_bound < 0).any():
-        raise ValueError("%s: a negative list bound" % what)
-    return ptr, n_bound, lens
-
-
 def surrogate_lists(list_ptr, n_bound, lens, seeds, n_surrogates: int = DEFAULT_SURROGATES, block_units: int = 1):
     """``ffs_surrogate_lists`` on the current stream.  Per vector: the device pointer of its ``ffs_runs_list``, a
     host-known bound of its length (``vec_max_boundaries``' convention), its length in samples and its uint32 seed.
@@ -146,25 +115,8 @@ def surrogate_lists(list_ptr, n_bound, lens, seeds, n_surrogates: int = DEFAULT_
     ``_native.SURR_BAD_*`` bits of a list whose header breaks the contract -- all its surrogates are empty lists then).
     Every block holds ``n_bound + 1`` entries.  Nothing is waited for or read back."""
     _check_shuffle(n_surrogates, block_units)
-    ptr, n_bound, lens = _check_lists("surrogate_lists", list_ptr, n_bound, lens)
-    seeds = np.ascontiguousarray(seeds, dtype=np.int64).ravel()
-    if seeds.size != ptr.size or (seeds < 0).any() or (seeds > 0xFFFFFFFF).any():
-        raise ValueError("surrogate_lists: need one seed in [0, 2^32) per vector")
-    if (n_bound > MAX_BOUND).any():
-        raise ValueError("surrogate_lists: a list of up to %d boundaries is above the unit limit (%d units, %d boundaries)"
-                         % (int(n_bound.max()), MAX_UNITS, MAX_BOUND))
-    torch = _native.require_gpu()
-    k = int(n_surrogates)
-    caps = n_bound + 1
-    block = 16 + 8 * caps
-    first = np.zeros(ptr.size, dtype=np.int64)
-    if ptr.size:
-        np.cumsum((block * k)[:-1], out=first[1:])
-    total = int((block * k).sum())
-    out = torch.empty(max(total, 8), dtype=torch.uint8, device="cuda")
-    status = torch.empty(max(ptr.size, 1), dtype=torch.int32, device="cuda")
-    _native.surrogate_lists(ptr, n_bound, seeds, first, caps, k, int(block_units), out, status)
-    return out, first[:, None] + block[:, None] * np.arange(k, dtype=np.int64)[None, :], status[:ptr.size]
+    return list_blocks("surrogate_lists", _native.surrogate_lists, MAX_BOUND, _LIMIT_TEXT, list_ptr, n_bound, lens, seeds,
+                       n_surrogates, block_units)
 
 
 def null_stats(table, n_files: int, n_surrogates: int, raw: bool = False):
@@ -182,35 +134,9 @@ def null_stats(table, n_files: int, n_surrogates: int, raw: bool = False):
     return out.cpu().numpy().view(_native.NULL_RESULT_DTYPE)[:int(n_files)]
 
 
-def _levels(values, n, default):
-    if values is None:
-        return np.full(n, default, dtype=np.float64)
-    values = np.ascontiguousarray(values, dtype=np.float64).ravel()
-    if values.size != n or not np.all(np.isfinite(values)):
-        raise ValueError("null_test_lists: need one finite level per file")
-    return values
-
-
-def _list_vector(ptr: int, length: int, lo: float, hi: float):
-    """The vector of a device-resident list on the host, as the careful path wants it."""
-    torch = _native.require_gpu()
-    words = torch.empty(_native.packed_words(length), dtype=torch.int32, device="cuda")
-    _native.check(_native.load().ffs_runs_to_bits(int(ptr), int(length), words.data_ptr(), _native.current_stream_ptr(torch)))
-    bits = _native.unpack_bits(words, length).cpu().numpy()
-    return lo + (hi - lo) * bits.astype(np.float64)
-
-
-def _careful(ref, sub, seed, k, block_units, w) -> np.ndarray:
-    """The K + 1 records of one file through the drop-in's ``solve_pairs`` (ambiguity handling), as ``ratio_sweep``
-    redoes a file: ``ref`` / ``sub`` = (list pointer, bound, length, lo, hi)."""
-    from .aligners import _Vec, solve_pairs
-
-    buf, offs, _ = surrogate_lists([sub[0]], [sub[1]], [sub[2]], [seed], k, block_units)
-    ref_vec = _Vec(_list_vector(ref[0], ref[2], ref[3], ref[4]))
-    ptrs = [int(sub[0])] + [buf.data_ptr() + int(o) for o in offs[0]]
-    pairs = [(ref_vec, [_Vec(_list_vector(p, sub[2], sub[3], sub[4]))]) for p in ptrs]
-    cres, _ = solve_pairs(pairs, w)
-    return np.ascontiguousarray(cres[:, 0])
+_careful = functools.partial(resample_call._careful, surrogate_lists)  # (ref, sub, seed, k, block_units, w)
+_KIND = ResampleKind("null_test_lists", surrogate_lists, _native.NULL_RESULT_DTYPE, _native.NULL_AMBIGUOUS, "n_surrogates",
+                     "block_units", MAX_BOUND, _LIMIT_TEXT)
 
 
 def null_test_lists(ref_ptr, ref_len, ref_bound, sub_ptr, sub_len, sub_bound, max_offset_samples: int,
@@ -231,74 +157,9 @@ def null_test_lists(ref_ptr, ref_len, ref_bound, sub_ptr, sub_len, sub_bound, ma
     ``NULL_AMBIGUOUS`` itself."""
     _check_shuffle(n_surrogates, block_units)
     seed = _check_seed(seed)
-    w = int(max_offset_samples)
-    if w != max_offset_samples or w < 1:
-        raise ValueError("max_offset_samples=%r: need a window of at least one sample" % (max_offset_samples,))
-    if int(budget_bytes) < 1:
-        raise ValueError("budget_bytes=%r: need a positive number of bytes" % (budget_bytes,))
-    ref_ptr, ref_bound, ref_len = _check_lists("null_test_lists (references)", ref_ptr, ref_bound, ref_len)
-    sub_ptr, sub_bound, sub_len = _check_lists("null_test_lists (subtitles)", sub_ptr, sub_bound, sub_len)
-    n = sub_ptr.size
-    if ref_ptr.size != n:
-        raise ValueError("null_test_lists: %d references for %d subtitle lists" % (ref_ptr.size, n))
-    if (sub_bound > MAX_BOUND).any():
-        raise ValueError("null_test_lists: a subtitle list of up to %d boundaries is above the unit limit (%d units, %d "
-                         "boundaries)" % (int(sub_bound.max()), MAX_UNITS, MAX_BOUND))
-    if (ref_bound >= 32768).any():
-        raise ValueError("null_test_lists: a reference of %d or more run boundaries is too dense for a list" % 32768)
-    ref_lo, ref_hi = _levels(ref_lo, n, 0.0), _levels(ref_hi, n, 1.0)
-    sub_lo, sub_hi = _levels(sub_lo, n, 0.0), _levels(sub_hi, n, 1.0)
-    if seeds is None:
-        seeds = np.array([file_seed(seed, i) for i in range(n)], dtype=np.int64)
-    else:
-        seeds = np.ascontiguousarray(seeds, dtype=np.int64).ravel()
-        if seeds.size != n or (seeds < 0).any() or (seeds > 0xFFFFFFFF).any():
-            raise ValueError("null_test_lists: need one seed in [0, 2^32) per file")
-    torch = _native.require_gpu()
-    k = int(n_surrogates)
-    stats = {"files": n, "n_surrogates": k, "block_units": int(block_units), "chunks": 0, "careful_files": 0}
-    table = torch.empty(max(n * (k + 1), 1) * 24, dtype=torch.uint8, device="cuda")
-    if n == 0:
-        return NullTest(np.zeros(0, _native.NULL_RESULT_DTYPE), table, np.zeros(0, np.int32), seeds.astype(np.uint32), stats)
-    per_file = k * (16 + 8 * (int(sub_bound.max()) + 1))
-    chunk = pairs_for_budget(n, per_file, cap=max(CHUNK_CAP // (k + 1), 1), budget=int(budget_bytes))
-    n_fft = max(_native.plan_length(int(r), int(s), w) for r, s in zip(ref_len, sub_len))
-    if n_fft > _native.MAX_FFT_LENGTH:
-        raise ValueError("inputs too long for the device transform (N=%d > 2^24)" % n_fft)
-    plan = _native.get_plan(n_fft, pairs_in_flight=min(chunk * (k + 1), 512), max_cand=1)
-    status = torch.empty(n, dtype=torch.int32, device="cuda")
-    pair_out = torch.empty(chunk * (k + 1) * 24, dtype=torch.uint8, device="cuda")
-    runs = (_native.FFS_DTYPE_RUNS, _native.FFS_DTYPE_RUNS)
-    for a in range(0, n, chunk):
-        b = min(a + chunk, n)
-        m = (b - a) * (k + 1)
-        buf, offs, st = surrogate_lists(sub_ptr[a:b], sub_bound[a:b], sub_len[a:b], seeds[a:b], k, block_units)
-        status[a:b] = st
-        cand = np.empty((b - a, k + 1), dtype=np.uint64)
-        cand[:, 0] = sub_ptr[a:b]
-        cand[:, 1:] = np.uint64(buf.data_ptr()) + offs.astype(np.uint64)
-        rep = lambda x: np.repeat(x[a:b], k + 1)
-        ptrs, lens = np.empty(2 * m, np.uint64), np.empty(2 * m, np.int64)
-        lo, hi, bounds = np.empty(2 * m), np.empty(2 * m), np.empty(2 * m, np.int32)
-        ptrs[0::2], lens[0::2], lo[0::2], hi[0::2], bounds[0::2] = rep(ref_ptr), rep(ref_len), rep(ref_lo), rep(ref_hi), np.maximum(rep(ref_bound), 2)
-        ptrs[1::2], lens[1::2], lo[1::2], hi[1::2], bounds[1::2] = cand.ravel(), rep(sub_len), rep(sub_lo), rep(sub_hi), np.maximum(rep(sub_bound), 2)
-        plan.align_batch(m, 1, runs, ptrs, lens, lo, hi, w, None, table[a * (k + 1) * 24:], pair_out, vec_max_boundaries=bounds)
-        stats["chunks"] += 1
-        del buf  # (stream-ordered: the allocator hands the block out again only behind the solve)
-    out = _native.null_stats(table, n, k)
-    if raw:
-        return NullTest(out, table, status, seeds.astype(np.uint32), stats)
-    records = out.cpu().numpy().view(_native.NULL_RESULT_DTYPE)[:n].copy()
-    status_h = status.cpu().numpy()
-    amb = np.flatnonzero((records["flags"] & _native.NULL_AMBIGUOUS) != 0)
-    if amb.size:  # degenerate input (e.g. a silent reference): the careful path, file by file
-        for f in amb:
-            recs = _careful((ref_ptr[f], ref_bound[f], ref_len[f], ref_lo[f], ref_hi[f]),
-                            (sub_ptr[f], sub_bound[f], sub_len[f], sub_lo[f], sub_hi[f]), int(seeds[f]), k, block_units, w)
-            table[f * (k + 1) * 24:(f + 1) * (k + 1) * 24] = torch.from_numpy(recs.view(np.uint8).copy()).cuda()
-            stats["careful_files"] += 1
-        records = _native.null_stats(table, n, k).cpu().numpy().view(_native.NULL_RESULT_DTYPE)[:n].copy()
-    return NullTest(records, table, status_h, seeds.astype(np.uint32), stats)
+    return NullTest(*test_lists(_KIND, _native.null_stats, ref_ptr, ref_len, ref_bound, sub_ptr, sub_len, sub_bound,
+                                max_offset_samples, n_surrogates, block_units, seed, ref_lo, ref_hi, sub_lo, sub_hi, seeds,
+                                budget_bytes, raw))
 
 
 def record_of(rec) -> NullRecord:
@@ -346,73 +207,18 @@ def _speech_cues(track) -> int:
     return len(track[0]) if meta is None else int(len(track[0]) - np.count_nonzero(np.asarray(meta)))
 
 
-def _host_boundaries(vec) -> int:
-    """Run boundaries of a two-level host vector (``aligners._Vec``), counted on the host."""
-    if vec.packed is not None:
-        bits = np.unpackbits(np.asarray(vec.packed, dtype=np.uint8), bitorder="little")[:len(vec)]
-    else:
-        bits = np.asarray(vec.bits, dtype=np.uint8)
-    return int(np.count_nonzero(np.diff(bits, prepend=0, append=0)))
-
-
 def _check_sync(problems, max_offset_seconds, ratios, sample_rate, start_seconds, min_z):
     """Host checks of ``null_sync`` (ValueError before any native call); returns (window in samples, ratios)."""
-    from .ratio_sweep import _check_problems
-
-    if start_seconds > 0:
-        raise ValueError("null_sync needs start_seconds <= 0: boundary lists cannot hold the negative start samples of "
-                         "start_seconds > 0")
+    resample_call._check_start("null_sync", start_seconds)
     if not math.isfinite(min_z):
         raise ValueError("min_z=%r: need a finite number" % (min_z,))
-    ratios = [float(r) for r in (candidate_ratios() if ratios is None else ratios)]
-    if not ratios or not all(math.isfinite(r) and r > 0 for r in ratios):
-        raise ValueError("ratios=%r: need at least one finite ratio > 0" % (ratios,))
-    w = _check_problems(problems, max_offset_seconds, sample_rate, CHUNK_BUDGET)
+    w, ratios = resample_call._check_ratios_and_problems(problems, max_offset_seconds, ratios, sample_rate)
     for i, (_, track) in enumerate(problems):
         cues = _speech_cues(track)
         if cues > MAX_UNITS + 1:
             raise ValueError("track %d has %d cues that are not metadata: above the unit limit of a surrogate list (%d units)"
                              % (i, cues, MAX_UNITS))
     return w, ratios
-
-
-def _winning_lists(who, problems, ratios, w, sample_rate):
-    """The first half of ``null_sync`` (and of ``stability.stable_sync``): the seven-ratio solve of every problem and the
-    winners rasterised to boundary lists.  Returns (solver, records [n, ratios], winning index per file, winning ratio
-    per file, (buffer, byte offsets, lengths, bounds) of the lists, their boundary counts read back from the headers).
-    Refuses by name (``who``) a multi-level or too dense reference before any device work."""
-    from .aligners import _Vec
-    from .batch_gss import PreparedRatioSolve
-    from .ratio_sweep import _careful as careful_ratios
-
-    ref_vecs = [_Vec(ref) for ref, _ in problems]
-    for v in ref_vecs:
-        if not v.two_level:
-            raise ValueError("%s needs a two-level reference: a multi-level float reference (FFS_DTYPE_F64) is not "
-                             "supported" % who)
-        if v.raster is None and _host_boundaries(v) >= PreparedRatioSolve.LIST_CAP:
-            raise ValueError("%s: a reference has %d or more run boundaries: too dense for a boundary list"
-                             % (who, PreparedRatioSolve.LIST_CAP))
-    torch = _native.require_gpu()
-    n, g = len(problems), len(ratios)
-    tracks = [(np.asarray(s), np.asarray(e), None if m is None else np.asarray(m)) for _, (s, e, m) in problems]
-    solver = PreparedRatioSolve(ref_vecs, tracks, w, sample_rate, 0, max(ratios), n * g, max_cand=1)
-    if not solver.use_lists:  # (a reference that was already on the device: counted there)
-        raise ValueError("%s: a reference has %d or more run boundaries: too dense for a boundary list"
-                         % (who, PreparedRatioSolve.LIST_CAP))
-    # the seven-ratio solve: one rasteriser call, one align_batch
-    which, rs = np.repeat(np.arange(n), g), np.tile(np.array(ratios, dtype=np.float64), n)
-    seven = torch.empty(n * g * 24, dtype=torch.uint8, device="cuda")
-    solver.evaluate(which, rs, seven)
-    recs = seven.cpu().numpy().view(_native.CAND_RESULT_DTYPE)[:n * g].reshape(n, g).copy()
-    for f in np.flatnonzero(((recs["flags"] & _native.FLAG_AMBIGUOUS) != 0).any(axis=1)):
-        recs[f] = careful_ratios(ref_vecs[f], problems[f][1], ratios, w, sample_rate)
-    best = np.array([int(np.argmax(r["score"])) for r in recs])  # (the first maximal candidate, aligners.py:154-167)
-    best_ratio = np.array([ratios[j] for j in best], dtype=np.float64)
-    # the winners as lists and their headers (one small read-back: how many boundaries there are to work on)
-    data, offs, lens, bounds = solver.tracks.rasterize_runs(np.arange(n), best_ratio, sample_rate, 0)
-    n_sub = data.view(torch.int32)[torch.from_numpy(offs // 4).to(data.device)].cpu().numpy()
-    return solver, recs, best, best_ratio, (data, offs, lens, bounds), n_sub
 
 
 def null_sync(problems, max_offset_seconds: float = 60, ratios: Optional[Sequence[float]] = None,
@@ -444,7 +250,6 @@ def null_sync(problems, max_offset_seconds: float = 60, ratios: Optional[Sequenc
         null = record_of(test.records[f])
         z, p = derive(null)
         blocks = n_blocks(int(n_sub[f]), block_units)
-        out.append(NullSyncResult(float(best_ratio[f]), int(best[f]), int(recs[f][best[f]]["offset"]),
-                                  float(recs[f][best[f]]["score"]), null, z, p, blocks, trusted(null, min_z),
+        out.append(NullSyncResult(*resample_call._sync_head(recs, best, best_ratio, f), null, z, p, blocks, trusted(null, min_z),
                                   assess(null, blocks, min_z)))
     return out

@@ -240,3 +240,99 @@ def test_the_defaults_follow_the_rule_from_the_committed_calibration():
     import stability_cases as sc
 
     assert sc.TOL == 2 * max(f["max_dev"] for f in matched if f["block_runs"] == 1)
+
+
+PARENT_SIGNATURES = {
+    "surrogate.surrogate_lists": "(list_ptr, n_bound, lens, seeds, n_surrogates: int = 64, block_units: int = 1)",
+    "surrogate.null_stats": "(table, n_files: int, n_surrogates: int, raw: bool = False)",
+    "surrogate.null_test_lists": "(ref_ptr, ref_len, ref_bound, sub_ptr, sub_len, sub_bound, max_offset_samples: int, "
+                                 "n_surrogates: int = 64, block_units: int = 1, seed: int = 0, ref_lo=None, ref_hi=None, "
+                                 "sub_lo=None, sub_hi=None, seeds=None, budget_bytes: int = 2147483648, raw: bool = False) "
+                                 "-> ffsubsync_amd.surrogate.NullTest",
+    "surrogate.null_sync": "(problems, max_offset_seconds: float = 60, ratios: Optional[Sequence[float]] = None, "
+                           "n_surrogates: int = 64, block_units: int = 1, seed: int = 0, min_z: float = 6.7, "
+                           "sample_rate: int = 100, start_seconds: float = 0) -> List[ffsubsync_amd.surrogate.NullSyncResult]",
+    "stability.subsample_lists": "(list_ptr, n_bound, lens, seeds, n_subsamples: int = 64, block_runs: int = 1, raw: bool = False)",
+    "stability.offset_stats": "(table, n_files: int, n_subsamples: int, tol: int = 16364, raw: bool = False)",
+    "stability.stability_test_lists": "(ref_ptr, ref_len, ref_bound, sub_ptr, sub_len, sub_bound, max_offset_samples: int, "
+                                      "n_subsamples: int = 64, block_runs: int = 1, seed: int = 0, tol: int = 16364, ref_lo=None, "
+                                      "ref_hi=None, sub_lo=None, sub_hi=None, seeds=None, budget_bytes: int = 2147483648, "
+                                      "raw: bool = False) -> ffsubsync_amd.stability.StabilityTest",
+    "stability.stable_sync": "(problems, max_offset_seconds: float = 60, ratios: Optional[Sequence[float]] = None, "
+                             "n_subsamples: int = 64, block_runs: int = 1, seed: int = 0, tol: int = 16364, "
+                             "min_share: Optional[float] = None, sample_rate: int = 100, start_seconds: float = 0) "
+                             "-> List[ffsubsync_amd.stability.StableSyncResult]",
+}
+
+
+def test_both_modules_go_through_the_one_resampling_core(monkeypatch):
+    """``surrogate`` and ``stability`` are callers of ``resample_call``: their ``*_lists``, ``*_test_lists`` and
+    ``_careful`` reach its one ``list_blocks``, ``test_lists`` and ``_careful`` with what is their own as arguments; the
+    names that callers, profiles and tests use still resolve; the eight entry points keep their signatures."""
+    import functools
+    import inspect
+
+    import ffsubsync_amd
+    from ffsubsync_amd import _native, resample_call, stability, surrogate
+
+    for mod in (surrogate, stability):
+        assert mod.list_blocks is resample_call.list_blocks and mod.test_lists is resample_call.test_lists
+        assert isinstance(mod._careful, functools.partial) and mod._careful.func is resample_call._careful
+        for name in ("fmix32", "file_seed", "_check_seed", "_check_lists", "_list_vector", "_winning_lists", "CHUNK_BUDGET",
+                     "CHUNK_CAP"):
+            assert getattr(mod, name) is getattr(resample_call, name), name
+        for name in ("MAX_BOUND", "MIN_BLOCKS", "n_blocks", "record_of", "assess", "_check_sync", "_KIND"):
+            assert hasattr(mod, name), name
+        assert not hasattr(mod, "_levels") and not hasattr(mod, "pairs_for_budget")  # (once, in the core)
+    for name in ("_speech_cues", "_host_boundaries", "_check_shuffle", "derive", "trusted", "MAX_SURROGATES", "MAX_UNITS",
+                 "DEFAULT_MIN_Z", "DEFAULT_SURROGATES"):
+        assert hasattr(surrogate, name), name
+    for name in ("_check_resample", "_check_tol", "share_within", "stable", "MAX_SUBSAMPLES", "MAX_BLOCK_RUNS", "DEFAULT_TOL",
+                 "DEFAULT_MIN_SHARE", "DEFAULT_SUBSAMPLES"):
+        assert hasattr(stability, name), name
+    # the list makers that the careful redo and the chunk loop call are the modules' own entry points
+    assert surrogate._careful.args == (surrogate.surrogate_lists,) and surrogate._KIND.make_lists is surrogate.surrogate_lists
+    raw_lists = stability._KIND.make_lists
+    assert stability._careful.args == (raw_lists,) and raw_lists.func is stability.subsample_lists and raw_lists.keywords == {"raw": True}
+    assert (surrogate._KIND.name, surrogate._KIND.k_name, surrogate._KIND.block_name) == ("null_test_lists", "n_surrogates", "block_units")
+    assert (stability._KIND.name, stability._KIND.k_name, stability._KIND.block_name) == ("stability_test_lists", "n_subsamples", "block_runs")
+    assert surrogate._KIND.record_dtype is _native.NULL_RESULT_DTYPE and surrogate._KIND.ambiguous == _native.NULL_AMBIGUOUS
+    assert stability._KIND.record_dtype is _native.STABILITY_RESULT_DTYPE and stability._KIND.ambiguous == _native.STAB_AMBIGUOUS
+    assert surrogate._KIND.max_bound == surrogate.MAX_BOUND and stability._KIND.max_bound == stability.MAX_BOUND
+
+    # the calls themselves: a module's own checks, then the core with the module's pieces
+    calls = []
+
+    def spy(result):
+        def call(*args):
+            calls.append(args)
+            return result
+        return call
+
+    lists = ([4096], [10], [100], [1])
+    monkeypatch.setattr(surrogate, "list_blocks", spy("blocks"))
+    assert surrogate.surrogate_lists(*lists, 4, 2) == "blocks"
+    assert calls.pop() == ("surrogate_lists", _native.surrogate_lists, surrogate.MAX_BOUND, surrogate._LIMIT_TEXT, *lists, 4, 2)
+    monkeypatch.setattr(stability, "list_blocks", spy(("buffer", "offsets", "status")))
+    assert stability.subsample_lists(*lists, 4, 2, raw=True) == ("buffer", "offsets", "status")
+    assert calls.pop() == ("subsample_lists", _native.subsample_lists, stability.MAX_BOUND, stability._LIMIT_TEXT, *lists, 4, 2)
+    files = ([4096], [100], [10], [8192], [90], [10], 50)
+    monkeypatch.setattr(surrogate, "test_lists", spy(("records", "table", "status", "seeds", {"n_surrogates": 4})))
+    assert surrogate.null_test_lists(*files, 4, 2, 7) == surrogate.NullTest("records", "table", "status", "seeds", {"n_surrogates": 4})
+    assert calls.pop() == (surrogate._KIND, _native.null_stats, *files, 4, 2, 7, None, None, None, None, None,
+                           resample_call.CHUNK_BUDGET, False)
+    monkeypatch.setattr(stability, "test_lists", spy(("records", "table", "status", "seeds", {"n_subsamples": 4})))
+    got = stability.stability_test_lists(*files, 4, 2, 7, 33, raw=True)
+    assert got == stability.StabilityTest("records", "table", "status", "seeds", {"n_subsamples": 4})
+    kind, stats_call, *rest = calls.pop()
+    assert kind is stability._KIND and stats_call.func is _native.offset_stats and stats_call.keywords == {"tol": 33}
+    assert tuple(rest) == (*files, 4, 2, 7, None, None, None, None, None, resample_call.CHUNK_BUDGET, True) and not calls
+    with pytest.raises(ValueError, match="n_surrogates=0"):  # (the module's own check comes first)
+        surrogate.null_test_lists(*files, 0)
+    with pytest.raises(ValueError, match="tol=-1"):
+        stability.stability_test_lists(*files, tol=-1)
+    assert not calls
+
+    for name, want in PARENT_SIGNATURES.items():
+        mod, fn = name.split(".")
+        assert str(inspect.signature(getattr(getattr(ffsubsync_amd, mod), fn))).replace("typing.", "") == want, name
