@@ -1656,29 +1656,38 @@ class ProgPlan(_SidePlan):
                  device: Optional[int] = None) -> None:
         super().__init__((max_slots, max_cand, max_lags, max_ref_samples, max_sub_samples), device)
 
-    def open(self, slot, n_cand, sub_ptr, sub_len, sub_lo, sub_hi, ref_lo, ref_hi, max_offset_samples,
-             stream: Optional[int] = None) -> None:
-        """``ffs_prog_open``: one entry per slot, and [n, max_cand] candidate tables (rows padded with anything)."""
-        kinds = (np.int32, np.int32, np.uint64, np.int64, np.float64, np.float64, np.float64, np.float64, np.int64)
-        bufs = [np.ascontiguousarray(a, dtype=t) for a, t in zip(
-            (slot, n_cand, sub_ptr, sub_len, sub_lo, sub_hi, ref_lo, ref_hi, max_offset_samples), kinds)]
+    _OPEN_KINDS = (np.int32, np.int32, np.uint64, np.int64, np.float64, np.float64, np.float64, np.float64, np.int64)
+
+    def _open(self, native, columns, kinds, stream) -> None:
+        """Either open: the host columns in their dtypes (columns 2 to 5 are the candidate tables), one native call."""
+        bufs = [np.ascontiguousarray(a, dtype=t) for a, t in zip(columns, kinds)]
         n = bufs[0].size
         if not all(b.size == (n * self.max_cand if 2 <= i <= 5 else n) for i, b in enumerate(bufs)):
             raise ValueError("one entry per slot, max_cand candidate entries per slot")
-        check(self.lib.ffs_prog_open(self.handle, n, *[b.ctypes.data for b in bufs], self._stream(stream)))
+        check(native(self.handle, n, *[b.ctypes.data for b in bufs], self._stream(stream)))
 
-    def append(self, slot, chunk_ptr, first_bit, n_new, top_k: int, exclusion_samples: int, cand_out, state_out,
-               stream: Optional[int] = None) -> None:
-        """``ffs_prog_append`` into uint8 CUDA tensors of n * max_cand * 160 and n * 64 bytes (asynchronous)."""
-        kinds = (np.int32, np.uint64, np.int32, np.int64)
-        bufs = [np.ascontiguousarray(a, dtype=t) for a, t in zip((slot, chunk_ptr, first_bit, n_new), kinds)]
+    def _append(self, native, columns, kinds, top_k, exclusion_samples, cand_out, state_out, stream) -> None:
+        """Either append: one entry per slot in every host column, room in both outputs, one native call."""
+        bufs = [np.ascontiguousarray(a, dtype=t) for a, t in zip(columns, kinds)]
         n = bufs[0].size
         if not all(b.size == n for b in bufs):
             raise ValueError("one entry per slot")
         if _nbytes(cand_out) < n * self.max_cand * QUALITY_RESULT_BYTES or _nbytes(state_out) < n * PROG_STATE_BYTES:
             raise ValueError("output buffer too small")
-        check(self.lib.ffs_prog_append(self.handle, n, *[b.ctypes.data for b in bufs], int(top_k), int(exclusion_samples),
-                                       cand_out.data_ptr(), state_out.data_ptr(), self._stream(stream)))
+        check(native(self.handle, n, *[b.ctypes.data for b in bufs], int(top_k), int(exclusion_samples),
+                     cand_out.data_ptr(), state_out.data_ptr(), self._stream(stream)))
+
+    def open(self, slot, n_cand, sub_ptr, sub_len, sub_lo, sub_hi, ref_lo, ref_hi, max_offset_samples,
+             stream: Optional[int] = None) -> None:
+        """``ffs_prog_open``: one entry per slot, and [n, max_cand] candidate tables (rows padded with anything)."""
+        self._open(self.lib.ffs_prog_open, (slot, n_cand, sub_ptr, sub_len, sub_lo, sub_hi, ref_lo, ref_hi, max_offset_samples),
+                   self._OPEN_KINDS, stream)
+
+    def append(self, slot, chunk_ptr, first_bit, n_new, top_k: int, exclusion_samples: int, cand_out, state_out,
+               stream: Optional[int] = None) -> None:
+        """``ffs_prog_append`` into uint8 CUDA tensors of n * max_cand * 160 and n * 64 bytes (asynchronous)."""
+        self._append(self.lib.ffs_prog_append, (slot, chunk_ptr, first_bit, n_new), (np.int32, np.uint64, np.int32, np.int64),
+                     top_k, exclusion_samples, cand_out, state_out, stream)
 
     def reference(self, slot: int) -> Tuple[int, int]:
         """``ffs_prog_reference``: (device address of the plan's bits of the consumed prefix, its length)."""
@@ -1694,26 +1703,15 @@ class ProgPlan(_SidePlan):
     def open_sampled(self, slot, n_cand, sub_ptr, sub_len, sub_lo, sub_hi, ref_lo, ref_hi, max_offset_samples, ref_total,
                      stream: Optional[int] = None) -> None:
         """``ffs_prog_open_sampled``: ``open`` plus the declared reference length of every slot."""
-        kinds = (np.int32, np.int32, np.uint64, np.int64, np.float64, np.float64, np.float64, np.float64, np.int64, np.int64)
-        bufs = [np.ascontiguousarray(a, dtype=t) for a, t in zip(
-            (slot, n_cand, sub_ptr, sub_len, sub_lo, sub_hi, ref_lo, ref_hi, max_offset_samples, ref_total), kinds)]
-        n = bufs[0].size
-        if not all(b.size == (n * self.max_cand if 2 <= i <= 5 else n) for i, b in enumerate(bufs)):
-            raise ValueError("one entry per slot, max_cand candidate entries per slot")
-        check(self.lib.ffs_prog_open_sampled(self.handle, n, *[b.ctypes.data for b in bufs], self._stream(stream)))
+        self._open(self.lib.ffs_prog_open_sampled,
+                   (slot, n_cand, sub_ptr, sub_len, sub_lo, sub_hi, ref_lo, ref_hi, max_offset_samples, ref_total),
+                   self._OPEN_KINDS + (np.int64,), stream)
 
     def append_at(self, slot, chunk_ptr, first_bit, position, n_new, top_k: int, exclusion_samples: int, cand_out, state_out,
                   stream: Optional[int] = None) -> None:
         """``ffs_prog_append_at`` into uint8 CUDA tensors of n * max_cand * 160 and n * 64 bytes (asynchronous)."""
-        kinds = (np.int32, np.uint64, np.int32, np.int64, np.int64)
-        bufs = [np.ascontiguousarray(a, dtype=t) for a, t in zip((slot, chunk_ptr, first_bit, position, n_new), kinds)]
-        n = bufs[0].size
-        if not all(b.size == n for b in bufs):
-            raise ValueError("one entry per slot")
-        if _nbytes(cand_out) < n * self.max_cand * QUALITY_RESULT_BYTES or _nbytes(state_out) < n * PROG_STATE_BYTES:
-            raise ValueError("output buffer too small")
-        check(self.lib.ffs_prog_append_at(self.handle, n, *[b.ctypes.data for b in bufs], int(top_k), int(exclusion_samples),
-                                          cand_out.data_ptr(), state_out.data_ptr(), self._stream(stream)))
+        self._append(self.lib.ffs_prog_append_at, (slot, chunk_ptr, first_bit, position, n_new),
+                     (np.int32, np.uint64, np.int32, np.int64, np.int64), top_k, exclusion_samples, cand_out, state_out, stream)
 
     def known(self, slot: int):
         """``ffs_prog_known``: the merged known intervals of a sampled slot as an int64 array [n, 2], ascending."""

@@ -5368,6 +5368,19 @@ struct ProgSlot {  // what the host knows of a slot: every refusal is decided fr
     int64_t S[ffsa::PROG_MAX_CAND];
     double s0[ffsa::PROG_MAX_CAND], s1[ffsa::PROG_MAX_CAND], r0, r1;  // mapped levels
 };
+
+// index of the first of the n ascending, disjoint intervals iv[2k], iv[2k + 1] that ends at or behind a (n: none)
+int prog_first_ending_at(const int64_t* iv, int n, int64_t a) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) / 2;
+        if (iv[2 * mid + 1] < a)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
+}
 }  // namespace
 
 struct ffs_prog_plan : PlanCore {
@@ -5401,17 +5414,75 @@ struct ffs_prog_plan : PlanCore {
         pre_s = c.take<int32_t>(nc * sw);
     }
 
+    // the rows of one slot, and of one (slot, candidate)
+    uint32_t* ref_row(int s) const { return ref + (int64_t)s * rw; }
+    int32_t* pre_r_row(int s) const { return pre_r + (int64_t)s * rw; }
+    int64_t cand_at(int s, int c) const { return (int64_t)s * max_cand + c; }
+    uint32_t* sub_row(int s, int c) const { return sub + cand_at(s, c) * sw; }
+    int32_t* pre_s_row(int s, int c) const { return pre_s + cand_at(s, c) * sw; }
+    uint32_t* curve_row(int s, int c) const { return curve + cand_at(s, c) * lpad; }
+    double* sc_row(int s, int c) const { return sc + cand_at(s, c) * lpad; }
+    uint32_t* side_row(int s, int c) const { return side + cand_at(s, c) * 3 * lpad; }
+    int64_t* iv_row(int s) { return iv.data() + (size_t)s * FFS_PROG_MAX_INTERVALS * 2; }
+
+    // one slot of a call: in range; `want_open`: and open
+    int check_slot(const char* call, int s, bool want_open) const {
+        if (s < 0 || s >= max_slots) return fail(FFS_E_INVALID, "%s: slot %d outside [0, %d)", call, s, max_slots);
+        if (want_open && !slots[s].open) return fail(FFS_E_INVALID, "%s: slot %d is not open", call, s);
+        return FFS_OK;
+    }
+
     // the slot list of a call: every slot in range and named once; `want_open`: and open
+    // (a slot named twice is reported as that: its first mention has passed the openness check)
     int check_slots(const char* call, int n, const int32_t* slot, bool want_open) {
         std::fill(named.begin(), named.end(), 0);
         for (int i = 0; i < n; ++i) {
             const int s = slot[i];
-            if (s < 0 || s >= max_slots) return fail(FFS_E_INVALID, "%s: slot %d outside [0, %d)", call, s, max_slots);
+            if (int rc = check_slot(call, s, want_open)) return rc;
             if (named[s]) return fail(FFS_E_INVALID, "%s: slot %d named twice", call, s);
             named[s] = 1;
-            if (want_open && !slots[s].open) return fail(FFS_E_INVALID, "%s: slot %d is not open", call, s);
         }
         return FFS_OK;
+    }
+
+    // may [a, a + n) join a sampled slot's known intervals: inside [0, T), disjoint from them, the table not overfull
+    int check_interval(const char* call, int s, int64_t a, int64_t n) {
+        const ProgSlot& ps = slots[s];
+        if (a < 0 || a > ps.T || n > ps.T - a)
+            return fail(FFS_E_INVALID, "%s: slot %d: [%lld, %lld + %lld) outside the reference [0, %lld)", call, s, (long long)a,
+                        (long long)a, (long long)n, (long long)ps.T);
+        if (n == 0) return FFS_OK;
+        const int64_t b = a + n;
+        const int64_t* iv = iv_row(s);
+        // the table is ascending and disjoint: only the first interval that ends at or behind a, and the one after an
+        // abutting one, can meet [a, b) -- a search, so that the host's share of a call does not grow with what is known
+        int joins = 0, k = prog_first_ending_at(iv, ps.n_iv, a);
+        if (k < ps.n_iv && iv[2 * k + 1] == a) ++joins, ++k;
+        if (k < ps.n_iv && iv[2 * k] < b)
+            return fail(FFS_E_INVALID, "%s: slot %d: [%lld, %lld) overlaps the known interval [%lld, %lld)", call, s,
+                        (long long)a, (long long)b, (long long)iv[2 * k], (long long)iv[2 * k + 1]);
+        if (k < ps.n_iv && iv[2 * k] == b) ++joins;
+        if (ps.n_iv + 1 - joins > FFS_PROG_MAX_INTERVALS)
+            return fail(FFS_E_INVALID, "%s: slot %d: more than %d known intervals", call, s, FFS_PROG_MAX_INTERVALS);
+        return FFS_OK;
+    }
+
+    // merge a checked, non-empty [a, b) into a sampled slot's table: it stays ascending
+    void merge_interval(int s, int64_t a, int64_t b) {
+        ProgSlot& ps = slots[s];
+        int64_t* iv = iv_row(s);
+        const int at = prog_first_ending_at(iv, ps.n_iv, a);
+        int last = at;                                    // [at, last): the intervals that abut [a, b)
+        if (last < ps.n_iv && iv[2 * last + 1] == a) a = iv[2 * last++];
+        if (last < ps.n_iv && iv[2 * last] == b) b = iv[2 * last++ + 1];
+        const int removed = last - at;
+        if (removed == 0)
+            memmove(iv + 2 * (at + 1), iv + 2 * at, sizeof(int64_t) * 2 * (size_t)(ps.n_iv - at));
+        else if (removed == 2)
+            memmove(iv + 2 * (at + 1), iv + 2 * (at + 2), sizeof(int64_t) * 2 * (size_t)(ps.n_iv - at - 2));
+        iv[2 * at] = a;
+        iv[2 * at + 1] = b;
+        ps.n_iv += 1 - removed;
     }
 };
 
@@ -5539,24 +5610,24 @@ int prog_open(const char* call, ffs_prog_plan* plan, int n, const int32_t* slot,
         ps.r0 = mapped(ref_lo[i]);
         ps.r1 = mapped(ref_hi[i]);
         for (int c = 0; c < n_cand[i]; ++c) {
-            const int64_t k = (int64_t)i * mc + c, at = (int64_t)slot[i] * mc + c;
+            const int64_t k = (int64_t)i * mc + c;
             ps.S[c] = sub_len[k];
             ps.s0[c] = mapped(sub_lo[k]);
             ps.s1[c] = mapped(sub_hi[k]);
             if (sampled) {
                 ffsa::SampOpenDesc& z = hz[nd];
-                z.side = plan->side + at * 3 * plan->lpad;
-                z.pre_r = c == 0 ? plan->pre_r + (int64_t)slot[i] * plan->rw : nullptr;
+                z.side = plan->side_row(slot[i], c);
+                z.pre_r = c == 0 ? plan->pre_r_row(slot[i]) : nullptr;
                 z.lpad = plan->lpad;
                 z.r_words = plan->rw;
             }
             ffsa::ProgOpenDesc& d = hd[nd++];
             d.src = (const uint32_t*)sub_ptr[k];
-            d.s = plan->sub + at * plan->sw;
-            d.pre_s = plan->pre_s + at * plan->sw;
-            d.curve = plan->curve + at * plan->lpad;
-            d.r = c == 0 ? plan->ref + (int64_t)slot[i] * plan->rw : nullptr;
-            d.pre_r = c == 0 ? plan->pre_r + (int64_t)slot[i] * plan->rw : nullptr;
+            d.s = plan->sub_row(slot[i], c);
+            d.pre_s = plan->pre_s_row(slot[i], c);
+            d.curve = plan->curve_row(slot[i], c);
+            d.r = c == 0 ? plan->ref_row(slot[i]) : nullptr;
+            d.pre_r = c == 0 ? plan->pre_r_row(slot[i]) : nullptr;
             d.S = sub_len[k];
             d.lpad = plan->lpad;
             d.r_words = plan->rw;
@@ -5570,6 +5641,166 @@ int prog_open(const char* call, ffs_prog_plan* plan, int n, const int32_t* slot,
         hipLaunchKernelGGL(ffsa::k_samp_zero, dim3((unsigned)nd), dim3(ffsa::PROG_THREADS), 0, st,
                            (const ffsa::SampOpenDesc*)plan->samp_desc.dev);
     }
+    HIP_TRY(hipGetLastError());
+    return plan->end(st);
+}
+
+// The rest of entry i of an append to prefix slots, in the plan's `desc` (ProgSlotDesc[max_slots], then QualDesc[]): what
+// k_prog_ingest reads into `s`, and one QualDesc per candidate from index nq on.  Returns the next free QualDesc.
+int prog_fill_prefix(ffs_prog_plan* plan, ffsa::ProgSlotDesc& s, int i, int slot, const void* chunk, int first_bit, int nq) {
+    const ProgSlot& ps = plan->slots[slot];
+    ffsa::QualDesc* hq = (ffsa::QualDesc*)((ffsa::ProgSlotDesc*)plan->desc.host + plan->max_slots);
+    s.chunk = (const uint32_t*)chunk;
+    s.r = plan->ref_row(slot);
+    s.pre_r = plan->pre_r_row(slot);
+    s.W = ps.W;
+    s.first_bit = first_bit;
+    s.desc0 = nq;
+    for (int c = 0; c < ps.n_cand; ++c) {
+        ffsa::QualDesc& q = hq[nq++];
+        memset(&q, 0, sizeof q);
+        q.r = s.r;
+        q.s = plan->sub_row(slot, c);
+        q.R = ps.L;
+        q.S = ps.S[c];
+        q.d_lo = -ps.W + 1;
+        q.n_lags = 2 * ps.W;
+        const int64_t clo = std::max(q.d_lo, 1 - q.S), chi = std::min(ps.W, q.R - 1);
+        q.c_lo = clo;
+        q.n_count = chi >= clo ? chi - clo + 1 : 0;
+        q.cd.R = (int32_t)q.R;
+        q.cd.S = (int32_t)q.S;
+        q.cd.s0 = ps.s0[c];
+        q.cd.s1 = ps.s1[c];
+        q.cd.r0 = ps.r0;
+        q.cd.r1 = ps.r1;
+        q.pre_r = s.pre_r;
+        q.pre_s = plan->pre_s_row(slot, c);
+        q.curve = plan->curve_row(slot, c);
+        q.sc = plan->sc_row(slot, c);
+        q.out_row = (int64_t)i * plan->max_cand + c;
+    }
+    return nq;
+}
+
+// The same for sampled slots, in the plan's `samp_desc` (ProgSlotDesc[max_slots], SampSlotDesc[max_slots], then
+// SampDesc[]): entry i's SampSlotDesc for a chunk at `a`, and one SampDesc per candidate.
+int prog_fill_sampled(ffs_prog_plan* plan, int i, int slot, const void* chunk, int first_bit, int64_t a, int64_t n_new,
+                      int nq) {
+    const ProgSlot& ps = plan->slots[slot];
+    ffsa::SampSlotDesc* hs = (ffsa::SampSlotDesc*)((ffsa::ProgSlotDesc*)plan->samp_desc.host + plan->max_slots);
+    ffsa::SampDesc* hq = (ffsa::SampDesc*)(hs + plan->max_slots);
+    ffsa::SampSlotDesc& s = hs[i];
+    memset(&s, 0, sizeof s);
+    s.chunk = (const uint32_t*)chunk;
+    s.r = plan->ref_row(slot);
+    s.pre_r = plan->pre_r_row(slot);
+    s.a = a;
+    s.n_new = n_new;
+    s.T = ps.T;
+    s.W = ps.W;
+    s.first_bit = first_bit;
+    s.n_cand = ps.n_cand;
+    s.desc0 = nq;
+    for (int c = 0; c < ps.n_cand; ++c) {
+        ffsa::SampDesc& q = hq[nq++];
+        memset(&q, 0, sizeof q);
+        q.s = plan->sub_row(slot, c);
+        q.pre_s = plan->pre_s_row(slot, c);
+        q.n11 = plan->curve_row(slot, c);
+        q.side = plan->side_row(slot, c);
+        q.sc = plan->sc_row(slot, c);
+        q.S = ps.S[c];
+        q.lpad = plan->lpad;
+        q.n_lags = 2 * ps.W;
+        q.d_lo = -ps.W + 1;
+        q.out_row = (int64_t)i * plan->max_cand + c;
+        q.s0 = ps.s0[c];
+        q.s1 = ps.s1[c];
+        q.r0 = ps.r0;
+        q.r1 = ps.r1;
+    }
+    return nq;
+}
+
+// ffs_prog_append, and with `position` ffs_prog_append_at: the same checks in the same order, the same begin / stage /
+// upload / end, the same four launches.  The kinds differ in one range check, in the staging block and its fill
+// (above), and in the ingest, counts and peaks kernels.  No slot's state moves before every check of every slot passed.
+int prog_append(const char* call, ffs_prog_plan* plan, int n, const int32_t* slot, const void* const* chunk_dev,
+                const int32_t* first_bit, const int64_t* position, const int64_t* n_new, int top_k,
+                int64_t exclusion_samples, ffs_quality_result* cand_out_dev, ffs_prog_state* state_out_dev, bool sampled,
+                void* hip_stream) {
+    static_assert(sizeof(ffs_prog_state) == sizeof(ffsa::ProgState), "device records must match the header's");
+    if (int rc = check_call(plan, "progressive", n,
+                            !slot || !chunk_dev || !first_bit || (sampled && !position) || !n_new || !cand_out_dev ||
+                                !state_out_dev);
+        rc != CALL_GO_ON)
+        return rc;
+    if (int rc = check_peaks(top_k, exclusion_samples)) return rc;
+    if (((uintptr_t)cand_out_dev | (uintptr_t)state_out_dev) & 7) return fail(FFS_E_INVALID, "misaligned output records");
+    if (n > plan->max_slots) return fail(FFS_E_INVALID, "%s: %d slots exceed the plan's max_slots %d", call, n, plan->max_slots);
+    if (int rc = plan->check_slots(call, n, slot, true)) return rc;
+    for (int i = 0; i < n; ++i) {
+        const ProgSlot& ps = plan->slots[slot[i]];
+        if (ps.sampled != sampled)
+            return sampled ? fail(FFS_E_INVALID, "%s: slot %d is a prefix slot: use ffs_prog_append", call, slot[i])
+                           : fail(FFS_E_INVALID, "%s: slot %d is a sampled slot: use ffs_prog_append_at", call, slot[i]);
+        if (!chunk_dev[i] || ((uintptr_t)chunk_dev[i] & 3))
+            return fail(FFS_E_INVALID, "%s: slot %d: null or misaligned chunk", call, slot[i]);
+        if (first_bit[i] < 0 || first_bit[i] > 31)
+            return fail(FFS_E_INVALID, "%s: slot %d: first_bit=%d outside [0, 32)", call, slot[i], first_bit[i]);
+        if (n_new[i] < 0) return fail(FFS_E_INVALID, "%s: slot %d: n_new=%lld is negative", call, slot[i], (long long)n_new[i]);
+        if (sampled) {
+            if (int rc = plan->check_interval(call, slot[i], position[i], n_new[i])) return rc;
+        } else if (n_new[i] > plan->max_ref - ps.L) {
+            return fail(FFS_E_INVALID, "%s: slot %d: %lld + %lld samples exceed the plan's max_ref_samples %lld", call, slot[i],
+                        (long long)ps.L, (long long)n_new[i], (long long)plan->max_ref);
+        }
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (int rc = plan->begin(st)) return rc;
+    DescStaging& stage = sampled ? plan->samp_desc : plan->desc;
+    if (int rc = stage.wait_free()) return rc;
+    int nq = 0;
+    int64_t max_w = 0;
+    for (int i = 0; i < n; ++i) {
+        ProgSlot& ps = plan->slots[slot[i]];
+        ffsa::ProgSlotDesc& p = ((ffsa::ProgSlotDesc*)stage.host)[i];  // first in either block: all that k_prog_pick reads
+        memset(&p, 0, sizeof p);
+        p.L = ps.L;  // the length (of a sampled slot: |K|) before this append
+        p.n_new = n_new[i];
+        p.n_cand = ps.n_cand;
+        ps.L += n_new[i];
+        if (sampled && n_new[i] > 0) plan->merge_interval(slot[i], position[i], position[i] + n_new[i]);
+        max_w = std::max(max_w, ps.W);
+        nq = sampled ? prog_fill_sampled(plan, i, slot[i], chunk_dev[i], first_bit[i], position[i], n_new[i], nq)
+                     : prog_fill_prefix(plan, p, i, slot[i], chunk_dev[i], first_bit[i], nq);
+    }
+    // one upload of all the arrays (the later ones are at fixed offsets: copy the whole used span)
+    const size_t ms = (size_t)plan->max_slots;
+    const size_t used = sampled ? (sizeof(ffsa::ProgSlotDesc) + sizeof(ffsa::SampSlotDesc)) * ms + sizeof(ffsa::SampDesc) * nq
+                                : sizeof(ffsa::ProgSlotDesc) * ms + sizeof(ffsa::QualDesc) * nq;
+    if (int rc = stage.upload(used, st)) return rc;
+    const int mc = plan->max_cand, n_tiles = (int)((2 * max_w + ffsa::PROG_TILE - 1) / ffsa::PROG_TILE);
+    const dim3 per_slot((unsigned)n), per_tile((unsigned)((int64_t)n * mc * n_tiles)), per_cand((unsigned)nq);
+    const ffsa::ProgSlotDesc* dp = (const ffsa::ProgSlotDesc*)stage.dev;
+    ffsa::QualResult* cand_out = (ffsa::QualResult*)cand_out_dev;
+    if (sampled) {
+        const ffsa::SampSlotDesc* ds = (const ffsa::SampSlotDesc*)(dp + ms);
+        const ffsa::SampDesc* dq = (const ffsa::SampDesc*)(ds + ms);
+        hipLaunchKernelGGL(ffsa::k_samp_ingest, per_slot, dim3(ffsa::PROG_THREADS), 0, st, ds);
+        hipLaunchKernelGGL(ffsa::k_samp_counts, per_tile, dim3(ffsa::PROG_CNT_THREADS), 0, st, ds, dq, n_tiles, mc);
+        hipLaunchKernelGGL(ffsa::k_samp_peaks, per_cand, dim3(ffsa::QUAL_PEAK_THREADS), 0, st, dq, top_k, exclusion_samples,
+                           cand_out);
+    } else {
+        const ffsa::QualDesc* dq = (const ffsa::QualDesc*)(dp + ms);
+        hipLaunchKernelGGL(ffsa::k_prog_ingest, per_slot, dim3(ffsa::PROG_THREADS), 0, st, dp);
+        hipLaunchKernelGGL(ffsa::k_prog_counts, per_tile, dim3(ffsa::PROG_CNT_THREADS), 0, st, dp, dq, n_tiles, mc);
+        hipLaunchKernelGGL(ffsa::k_quality_peaks, per_cand, dim3(ffsa::QUAL_PEAK_THREADS), 0, st, dq, top_k,
+                           exclusion_samples, cand_out);
+    }
+    hipLaunchKernelGGL(ffsa::k_prog_pick, per_slot, dim3(ffsa::PROG_PICK_THREADS), 0, st, dp, mc, cand_out,
+                       (ffsa::ProgState*)state_out_dev);
     HIP_TRY(hipGetLastError());
     return plan->end(st);
 }
@@ -5595,247 +5826,34 @@ int64_t ffs_prog_plan_sampled_bytes(const ffs_prog_plan* plan) { return plan ? p
 int ffs_prog_append(ffs_prog_plan* plan, int n, const int32_t* slot, const void* const* chunk_dev, const int32_t* first_bit,
                     const int64_t* n_new, int top_k, int64_t exclusion_samples, ffs_quality_result* cand_out_dev,
                     ffs_prog_state* state_out_dev, void* hip_stream) {
-    static_assert(sizeof(ffs_prog_state) == sizeof(ffsa::ProgState), "device records must match the header's");
-    if (int rc = check_call(plan, "progressive", n, !slot || !chunk_dev || !first_bit || !n_new || !cand_out_dev || !state_out_dev);
-        rc != CALL_GO_ON)
-        return rc;
-    if (int rc = check_peaks(top_k, exclusion_samples)) return rc;
-    if (((uintptr_t)cand_out_dev | (uintptr_t)state_out_dev) & 7) return fail(FFS_E_INVALID, "misaligned output records");
-    if (n > plan->max_slots) return fail(FFS_E_INVALID, "ffs_prog_append: %d slots exceed the plan's max_slots %d", n, plan->max_slots);
-    if (int rc = plan->check_slots("ffs_prog_append", n, slot, true)) return rc;
-    for (int i = 0; i < n; ++i) {
-        const ProgSlot& ps = plan->slots[slot[i]];
-        if (ps.sampled) return fail(FFS_E_INVALID, "ffs_prog_append: slot %d is a sampled slot: use ffs_prog_append_at", slot[i]);
-        if (!chunk_dev[i] || ((uintptr_t)chunk_dev[i] & 3))
-            return fail(FFS_E_INVALID, "ffs_prog_append: slot %d: null or misaligned chunk", slot[i]);
-        if (first_bit[i] < 0 || first_bit[i] > 31)
-            return fail(FFS_E_INVALID, "ffs_prog_append: slot %d: first_bit=%d outside [0, 32)", slot[i], first_bit[i]);
-        if (n_new[i] < 0) return fail(FFS_E_INVALID, "ffs_prog_append: slot %d: n_new=%lld is negative", slot[i], (long long)n_new[i]);
-        if (n_new[i] > plan->max_ref - ps.L)
-            return fail(FFS_E_INVALID, "ffs_prog_append: slot %d: %lld + %lld samples exceed the plan's max_ref_samples %lld",
-                        slot[i], (long long)ps.L, (long long)n_new[i], (long long)plan->max_ref);
-    }
-    hipStream_t st = (hipStream_t)hip_stream;
-    if (int rc = plan->begin(st)) return rc;
-    if (int rc = plan->desc.wait_free()) return rc;
-    const int mc = plan->max_cand;
-    ffsa::ProgSlotDesc* hs = (ffsa::ProgSlotDesc*)plan->desc.host;
-    ffsa::QualDesc* hq = (ffsa::QualDesc*)(hs + plan->max_slots);
-    const ffsa::ProgSlotDesc* ds = (const ffsa::ProgSlotDesc*)plan->desc.dev;
-    const ffsa::QualDesc* dq = (const ffsa::QualDesc*)(ds + plan->max_slots);
-    int nq = 0;
-    int64_t max_w = 0;
-    for (int i = 0; i < n; ++i) {
-        ProgSlot& ps = plan->slots[slot[i]];
-        ffsa::ProgSlotDesc& s = hs[i];
-        memset(&s, 0, sizeof s);
-        s.chunk = (const uint32_t*)chunk_dev[i];
-        s.r = plan->ref + (int64_t)slot[i] * plan->rw;
-        s.pre_r = plan->pre_r + (int64_t)slot[i] * plan->rw;
-        s.L = ps.L;
-        s.n_new = n_new[i];
-        s.W = ps.W;
-        s.first_bit = first_bit[i];
-        s.n_cand = ps.n_cand;
-        s.desc0 = nq;
-        ps.L += n_new[i];
-        max_w = std::max(max_w, ps.W);
-        for (int c = 0; c < ps.n_cand; ++c) {
-            const int64_t at = (int64_t)slot[i] * mc + c;
-            ffsa::QualDesc& q = hq[nq++];
-            memset(&q, 0, sizeof q);
-            q.r = s.r;
-            q.s = plan->sub + at * plan->sw;
-            q.R = ps.L;
-            q.S = ps.S[c];
-            q.d_lo = -ps.W + 1;
-            q.n_lags = 2 * ps.W;
-            const int64_t clo = std::max(q.d_lo, 1 - q.S), chi = std::min(ps.W, q.R - 1);
-            q.c_lo = clo;
-            q.n_count = chi >= clo ? chi - clo + 1 : 0;
-            q.cd.R = (int32_t)q.R;
-            q.cd.S = (int32_t)q.S;
-            q.cd.s0 = ps.s0[c];
-            q.cd.s1 = ps.s1[c];
-            q.cd.r0 = ps.r0;
-            q.cd.r1 = ps.r1;
-            q.pre_r = s.pre_r;
-            q.pre_s = plan->pre_s + at * plan->sw;
-            q.curve = plan->curve + at * plan->lpad;
-            q.sc = plan->sc + at * plan->lpad;
-            q.out_row = (int64_t)i * mc + c;
-        }
-    }
-    // one upload of both arrays (the QualDesc half is at a fixed offset: copy the whole used span)
-    if (int rc = plan->desc.upload(sizeof(ffsa::ProgSlotDesc) * plan->max_slots + sizeof(ffsa::QualDesc) * nq, st)) return rc;
-    const int n_tiles = (int)((2 * max_w + ffsa::PROG_TILE - 1) / ffsa::PROG_TILE);
-    hipLaunchKernelGGL(ffsa::k_prog_ingest, dim3((unsigned)n), dim3(ffsa::PROG_THREADS), 0, st, ds);
-    hipLaunchKernelGGL(ffsa::k_prog_counts, dim3((unsigned)((int64_t)n * mc * n_tiles)), dim3(ffsa::PROG_CNT_THREADS), 0, st, ds,
-                       dq, n_tiles, mc);
-    hipLaunchKernelGGL(ffsa::k_quality_peaks, dim3((unsigned)nq), dim3(ffsa::QUAL_PEAK_THREADS), 0, st, dq, top_k,
-                       exclusion_samples, (ffsa::QualResult*)cand_out_dev);
-    hipLaunchKernelGGL(ffsa::k_prog_pick, dim3((unsigned)n), dim3(ffsa::PROG_PICK_THREADS), 0, st, ds, mc,
-                       (ffsa::QualResult*)cand_out_dev, (ffsa::ProgState*)state_out_dev);
-    HIP_TRY(hipGetLastError());
-    return plan->end(st);
+    return prog_append("ffs_prog_append", plan, n, slot, chunk_dev, first_bit, nullptr, n_new, top_k, exclusion_samples,
+                       cand_out_dev, state_out_dev, false, hip_stream);
+}
+
+int ffs_prog_append_at(ffs_prog_plan* plan, int n, const int32_t* slot, const void* const* chunk_dev, const int32_t* first_bit,
+                       const int64_t* position, const int64_t* n_new, int top_k, int64_t exclusion_samples,
+                       ffs_quality_result* cand_out_dev, ffs_prog_state* state_out_dev, void* hip_stream) {
+    return prog_append("ffs_prog_append_at", plan, n, slot, chunk_dev, first_bit, position, n_new, top_k, exclusion_samples,
+                       cand_out_dev, state_out_dev, true, hip_stream);
 }
 
 int ffs_prog_reference(ffs_prog_plan* plan, int slot, const uint32_t** bits_dev, int64_t* len) {
     if (!plan) return fail(FFS_E_INVALID, "null progressive plan");
     if (!bits_dev || !len) return fail(FFS_E_INVALID, "null argument");
-    if (slot < 0 || slot >= plan->max_slots) return fail(FFS_E_INVALID, "ffs_prog_reference: slot %d outside [0, %d)", slot, plan->max_slots);
-    if (!plan->slots[slot].open) return fail(FFS_E_INVALID, "ffs_prog_reference: slot %d is not open", slot);
-    *bits_dev = plan->ref + (int64_t)slot * plan->rw;
+    if (int rc = plan->check_slot("ffs_prog_reference", slot, true)) return rc;
+    *bits_dev = plan->ref_row(slot);
     *len = plan->slots[slot].sampled ? plan->slots[slot].T : plan->slots[slot].L;
     return FFS_OK;
-}
-
-namespace {
-// index of the first of the n ascending, disjoint intervals iv[2k], iv[2k + 1] that ends at or behind a (n: none)
-int prog_first_ending_at(const int64_t* iv, int n, int64_t a) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) / 2;
-        if (iv[2 * mid + 1] < a)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-}  // namespace
-
-int ffs_prog_append_at(ffs_prog_plan* plan, int n, const int32_t* slot, const void* const* chunk_dev, const int32_t* first_bit,
-                       const int64_t* position, const int64_t* n_new, int top_k, int64_t exclusion_samples,
-                       ffs_quality_result* cand_out_dev, ffs_prog_state* state_out_dev, void* hip_stream) {
-    if (int rc = check_call(plan, "progressive", n,
-                            !slot || !chunk_dev || !first_bit || !position || !n_new || !cand_out_dev || !state_out_dev);
-        rc != CALL_GO_ON)
-        return rc;
-    if (int rc = check_peaks(top_k, exclusion_samples)) return rc;
-    if (((uintptr_t)cand_out_dev | (uintptr_t)state_out_dev) & 7) return fail(FFS_E_INVALID, "misaligned output records");
-    if (n > plan->max_slots) return fail(FFS_E_INVALID, "ffs_prog_append_at: %d slots exceed the plan's max_slots %d", n, plan->max_slots);
-    if (int rc = plan->check_slots("ffs_prog_append_at", n, slot, true)) return rc;
-    for (int i = 0; i < n; ++i) {
-        const ProgSlot& ps = plan->slots[slot[i]];
-        if (!ps.sampled) return fail(FFS_E_INVALID, "ffs_prog_append_at: slot %d is a prefix slot: use ffs_prog_append", slot[i]);
-        if (!chunk_dev[i] || ((uintptr_t)chunk_dev[i] & 3))
-            return fail(FFS_E_INVALID, "ffs_prog_append_at: slot %d: null or misaligned chunk", slot[i]);
-        if (first_bit[i] < 0 || first_bit[i] > 31)
-            return fail(FFS_E_INVALID, "ffs_prog_append_at: slot %d: first_bit=%d outside [0, 32)", slot[i], first_bit[i]);
-        if (n_new[i] < 0) return fail(FFS_E_INVALID, "ffs_prog_append_at: slot %d: n_new=%lld is negative", slot[i], (long long)n_new[i]);
-        const int64_t a = position[i];
-        if (a < 0 || a > ps.T || n_new[i] > ps.T - a)
-            return fail(FFS_E_INVALID, "ffs_prog_append_at: slot %d: [%lld, %lld + %lld) outside the reference [0, %lld)", slot[i],
-                        (long long)a, (long long)a, (long long)n_new[i], (long long)ps.T);
-        if (n_new[i] == 0) continue;
-        const int64_t b = a + n_new[i];
-        const int64_t* iv = plan->iv.data() + (size_t)slot[i] * FFS_PROG_MAX_INTERVALS * 2;
-        // the table is ascending and disjoint: only the first interval that ends at or behind a, and the one after an
-        // abutting one, can meet [a, b) -- a search, so that the host's share of a call does not grow with what is known
-        int joins = 0, k = prog_first_ending_at(iv, ps.n_iv, a);
-        if (k < ps.n_iv && iv[2 * k + 1] == a) ++joins, ++k;
-        if (k < ps.n_iv && iv[2 * k] < b)
-            return fail(FFS_E_INVALID, "ffs_prog_append_at: slot %d: [%lld, %lld) overlaps the known interval [%lld, %lld)",
-                        slot[i], (long long)a, (long long)b, (long long)iv[2 * k], (long long)iv[2 * k + 1]);
-        if (k < ps.n_iv && iv[2 * k] == b) ++joins;
-        if (ps.n_iv + 1 - joins > FFS_PROG_MAX_INTERVALS)
-            return fail(FFS_E_INVALID, "ffs_prog_append_at: slot %d: more than %d known intervals", slot[i], FFS_PROG_MAX_INTERVALS);
-    }
-    hipStream_t st = (hipStream_t)hip_stream;
-    if (int rc = plan->begin(st)) return rc;
-    if (int rc = plan->samp_desc.wait_free()) return rc;
-    const int mc = plan->max_cand;
-    ffsa::ProgSlotDesc* hp = (ffsa::ProgSlotDesc*)plan->samp_desc.host;
-    ffsa::SampSlotDesc* hs = (ffsa::SampSlotDesc*)(hp + plan->max_slots);
-    ffsa::SampDesc* hq = (ffsa::SampDesc*)(hs + plan->max_slots);
-    const ffsa::ProgSlotDesc* dp = (const ffsa::ProgSlotDesc*)plan->samp_desc.dev;
-    const ffsa::SampSlotDesc* ds = (const ffsa::SampSlotDesc*)(dp + plan->max_slots);
-    const ffsa::SampDesc* dq = (const ffsa::SampDesc*)(ds + plan->max_slots);
-    int nq = 0;
-    int64_t max_w = 0;
-    for (int i = 0; i < n; ++i) {
-        ProgSlot& ps = plan->slots[slot[i]];
-        ffsa::ProgSlotDesc& p = hp[i];  // what k_prog_pick reads: ref_len = |K| after the append, n_cand
-        memset(&p, 0, sizeof p);
-        p.L = ps.L;
-        p.n_new = n_new[i];
-        p.n_cand = ps.n_cand;
-        ffsa::SampSlotDesc& s = hs[i];
-        memset(&s, 0, sizeof s);
-        s.chunk = (const uint32_t*)chunk_dev[i];
-        s.r = plan->ref + (int64_t)slot[i] * plan->rw;
-        s.pre_r = plan->pre_r + (int64_t)slot[i] * plan->rw;
-        s.a = position[i];
-        s.n_new = n_new[i];
-        s.T = ps.T;
-        s.W = ps.W;
-        s.first_bit = first_bit[i];
-        s.n_cand = ps.n_cand;
-        s.desc0 = nq;
-        if (n_new[i] > 0) {  // merge [a, b) into the slot's table: it stays ascending
-            int64_t a = position[i], b = a + n_new[i];
-            int64_t* iv = plan->iv.data() + (size_t)slot[i] * FFS_PROG_MAX_INTERVALS * 2;
-            const int at = prog_first_ending_at(iv, ps.n_iv, a);
-            int last = at;                                    // [at, last): the intervals that abut [a, b)
-            if (last < ps.n_iv && iv[2 * last + 1] == a) a = iv[2 * last++];
-            if (last < ps.n_iv && iv[2 * last] == b) b = iv[2 * last++ + 1];
-            const int removed = last - at;
-            if (removed == 0)
-                memmove(iv + 2 * (at + 1), iv + 2 * at, sizeof(int64_t) * 2 * (size_t)(ps.n_iv - at));
-            else if (removed == 2)
-                memmove(iv + 2 * (at + 1), iv + 2 * (at + 2), sizeof(int64_t) * 2 * (size_t)(ps.n_iv - at - 2));
-            iv[2 * at] = a;
-            iv[2 * at + 1] = b;
-            ps.n_iv += 1 - removed;
-            ps.L += n_new[i];
-        }
-        max_w = std::max(max_w, ps.W);
-        for (int c = 0; c < ps.n_cand; ++c) {
-            const int64_t at = (int64_t)slot[i] * mc + c;
-            ffsa::SampDesc& q = hq[nq++];
-            memset(&q, 0, sizeof q);
-            q.s = plan->sub + at * plan->sw;
-            q.pre_s = plan->pre_s + at * plan->sw;
-            q.n11 = plan->curve + at * plan->lpad;
-            q.side = plan->side + at * 3 * plan->lpad;
-            q.sc = plan->sc + at * plan->lpad;
-            q.S = ps.S[c];
-            q.lpad = plan->lpad;
-            q.n_lags = 2 * ps.W;
-            q.d_lo = -ps.W + 1;
-            q.out_row = (int64_t)i * mc + c;
-            q.s0 = ps.s0[c];
-            q.s1 = ps.s1[c];
-            q.r0 = ps.r0;
-            q.r1 = ps.r1;
-        }
-    }
-    // one upload of the three arrays (the later two are at fixed offsets: copy the whole used span)
-    if (int rc = plan->samp_desc.upload((sizeof(ffsa::ProgSlotDesc) + sizeof(ffsa::SampSlotDesc)) * plan->max_slots +
-                                            sizeof(ffsa::SampDesc) * nq, st))
-        return rc;
-    const int n_tiles = (int)((2 * max_w + ffsa::PROG_TILE - 1) / ffsa::PROG_TILE);
-    hipLaunchKernelGGL(ffsa::k_samp_ingest, dim3((unsigned)n), dim3(ffsa::PROG_THREADS), 0, st, ds);
-    hipLaunchKernelGGL(ffsa::k_samp_counts, dim3((unsigned)((int64_t)n * mc * n_tiles)), dim3(ffsa::PROG_CNT_THREADS), 0, st, ds,
-                       dq, n_tiles, mc);
-    hipLaunchKernelGGL(ffsa::k_samp_peaks, dim3((unsigned)nq), dim3(ffsa::QUAL_PEAK_THREADS), 0, st, dq, top_k,
-                       exclusion_samples, (ffsa::QualResult*)cand_out_dev);
-    hipLaunchKernelGGL(ffsa::k_prog_pick, dim3((unsigned)n), dim3(ffsa::PROG_PICK_THREADS), 0, st, dp, mc,
-                       (ffsa::QualResult*)cand_out_dev, (ffsa::ProgState*)state_out_dev);
-    HIP_TRY(hipGetLastError());
-    return plan->end(st);
 }
 
 int ffs_prog_known(ffs_prog_plan* plan, int slot, int64_t* bounds_out, int cap, int* n_out) {
     if (!plan) return fail(FFS_E_INVALID, "null progressive plan");
     if (!n_out || cap < 0 || (cap > 0 && !bounds_out)) return fail(FFS_E_INVALID, "null argument");
-    if (slot < 0 || slot >= plan->max_slots) return fail(FFS_E_INVALID, "ffs_prog_known: slot %d outside [0, %d)", slot, plan->max_slots);
+    if (int rc = plan->check_slot("ffs_prog_known", slot, false)) return rc;
     const ProgSlot& ps = plan->slots[slot];
     if (!ps.open || !ps.sampled) return fail(FFS_E_INVALID, "ffs_prog_known: slot %d is not an open sampled slot", slot);
     if (ps.n_iv > cap) return fail(FFS_E_INVALID, "ffs_prog_known: %d intervals exceed cap=%d", ps.n_iv, cap);
-    if (ps.n_iv > 0)
-        memcpy(bounds_out, plan->iv.data() + (size_t)slot * FFS_PROG_MAX_INTERVALS * 2, sizeof(int64_t) * 2 * (size_t)ps.n_iv);
+    if (ps.n_iv > 0) memcpy(bounds_out, plan->iv_row(slot), sizeof(int64_t) * 2 * (size_t)ps.n_iv);
     *n_out = ps.n_iv;
     return FFS_OK;
 }

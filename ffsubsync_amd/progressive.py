@@ -255,31 +255,44 @@ class ProgressiveSolve:
                 words = torch.zeros(1, dtype=torch.int32, device=self.device)
         return words
 
+    def _check_open(self, name="ProgressiveSolve") -> None:
+        if self.plan is None:
+            raise ValueError("this %s is closed" % name)
+
+    def _check_file(self, f) -> None:
+        if not isinstance(f, (int, np.integer)) or not 0 <= f < self.n_files:
+            raise ValueError("file %r: need an index in [0, %d)" % (f, self.n_files))
+
     def append(self, chunks: Dict[int, object]) -> Dict[int, ProgressState]:
         """Feed one chunk per named file (index into the tracks): a host 0/1 or bool array, a CUDA label tensor
         (float32: > 0.5 is speech; uint8: != 0), or (int32 CUDA words, first_bit, n).  One native call for all of them."""
-        if self.plan is None:
-            raise ValueError("this ProgressiveSolve is closed")
-        torch = self.torch
+        self._check_open()
         files = list(chunks)
         for f in files:
-            if not isinstance(f, (int, np.integer)) or not 0 <= f < self.n_files:
-                raise ValueError("file %r: need an index in [0, %d)" % (f, self.n_files))
+            self._check_file(f)
         if not files:
             return {}
         checked = [self._chunk(f, chunks[f]) for f in files]  # every ValueError before any native call
-        keep, ptrs = [], []
-        for f, (words, first_bit, n) in zip(files, checked):
-            words = self._device_words(chunks[f], words, n)
-            keep.append(words)
-            ptrs.append(words.data_ptr())
+        return self._append(files, checked, None, [chunks[f] for f in files])
+
+    def _append(self, files, checked, starts, chunks) -> Dict[int, ProgressState]:
+        """``append`` and, with the ``starts`` of the chunks, ``SampledSolve.append_at`` behind their checks: the chunks
+        of ``files`` in their ``checked`` (words or None, first_bit, n) forms onto the device, one native call, the
+        host's books (only once that call has returned), the records read back."""
+        torch = self.torch
+        keep = [self._device_words(chunk, words, n) for chunk, (words, _, n) in zip(chunks, checked)]
+        ptrs, bits, lens = [w.data_ptr() for w in keep], [c[1] for c in checked], [c[2] for c in checked]
         n = len(files)
         cand_out = torch.empty(n * self.n_cand * _native.QUALITY_RESULT_BYTES, dtype=torch.uint8, device=self.device)
         state_out = torch.empty(n * _native.PROG_STATE_BYTES, dtype=torch.uint8, device=self.device)
-        self.plan.append(files, ptrs, [c[1] for c in checked], [c[2] for c in checked], self.top_k, self.exclusion_samples,
-                         cand_out, state_out)
-        for f, c in zip(files, checked):
-            self.consumed[f] += c[2]
+        if starts is None:
+            self.plan.append(files, ptrs, bits, lens, self.top_k, self.exclusion_samples, cand_out, state_out)
+        else:
+            self.plan.append_at(files, ptrs, bits, starts, lens, self.top_k, self.exclusion_samples, cand_out, state_out)
+        for i, f in enumerate(files):
+            self.consumed[f] += lens[i]
+            if starts is not None and lens[i]:
+                self._known[f] = _merged(self._known[f] + [(starts[i], starts[i] + lens[i])])
         recs = cand_out.cpu().numpy().view(_native.QUALITY_RESULT_DTYPE).reshape(n, self.n_cand)
         states = state_out.cpu().numpy().view(_native.PROG_STATE_DTYPE)
         del keep
@@ -292,10 +305,8 @@ class ProgressiveSolve:
         ``split_sync`` / ``drift_sync`` on what was read."""
         from .subtitle_raster import DeviceRaster
 
-        if self.plan is None:
-            raise ValueError("this ProgressiveSolve is closed")
-        if not isinstance(f, (int, np.integer)) or not 0 <= f < self.n_files:
-            raise ValueError("file %r: need an index in [0, %d)" % (f, self.n_files))
+        self._check_open()
+        self._check_file(f)
         torch = self.torch
         ptr, n = self.plan.reference(f)
         if n == 0:
@@ -382,35 +393,61 @@ def progressive_sync(problems, rule: Optional[StopRule] = None, max_offset_secon
     try:
         sources = [p[0] for p in problems]
         iters: List[Optional[Iterable]] = [iter(s) for s in sources]
-        history: List[List[ProgressState]] = [[] for _ in problems]
-        done = [False] * len(problems)
-        while any(it is not None for it in iters):
-            chunks = {}
-            for f, it in enumerate(iters):
-                if it is None:
-                    continue
-                try:
-                    chunks[f] = next(it)
-                except StopIteration:
-                    iters[f] = None
-            for f, st in solve.append(chunks).items():
-                history[f].append(st)
-                if rule.settled(history[f]):
-                    done[f] = True
-                    for obj in (sources[f], iters[f]):  # the caller's own object first: it knows its decoder
-                        close = getattr(obj, "close", None)
-                        if close is not None:
-                            close()
-                            break
-                    iters[f] = None
-        out = []
-        for f, h in enumerate(history):
-            if not h:
-                raise empty_error(0, solve.rasters[f][0].n)
-            st = h[-1]
-            reasons = [] if done[f] else quality.assess(st.quality, rule.min_psr, rule.min_margin)
-            out.append(ProgressiveSyncResult(solve.ratios[st.best_cand], st.best_cand, st.offset, st.score, st.quality,
-                                             st.ratio_margin, st.ref_len, len(h), done[f], reasons))
-        return out
+
+        def rounds():
+            while any(it is not None for it in iters):
+                chunks = {}
+                for f, it in enumerate(iters):
+                    if it is None:
+                        continue
+                    try:
+                        chunks[f] = next(it)
+                    except StopIteration:
+                        iters[f] = None
+                yield chunks
+
+        def settle(f):
+            for obj in (sources[f], iters[f]):  # the caller's own object first: it knows its decoder
+                close = getattr(obj, "close", None)
+                if close is not None:
+                    close()
+                    break
+            iters[f] = None
+
+        return _sync_rounds(solve, rule, solve.append, rounds, settle)
     finally:
         solve.close()
+
+
+def _sync_rounds(solve, rule, append, rounds, settle) -> List[ProgressiveSyncResult]:
+    """The rounds of ``progressive_sync`` and ``sampled_sync`` and their results.  ``rounds()`` yields one round's chunks
+    of the live files at a time, as ``append`` takes them, while any file is live; ``settle(f)`` is told when ``rule``
+    calls file ``f`` settled: it is not to be read again."""
+    history: List[List[ProgressState]] = [[] for _ in range(solve.n_files)]
+    done = [False] * solve.n_files
+    for chunks in rounds():
+        for f, st in append(chunks).items():
+            history[f].append(st)
+            if rule.settled(history[f]):
+                done[f] = True
+                settle(f)
+    out = []
+    for f, h in enumerate(history):
+        if not h:
+            raise empty_error(0, solve.rasters[f][0].n)
+        st = h[-1]
+        reasons = [] if done[f] else quality.assess(st.quality, rule.min_psr, rule.min_margin)
+        out.append(ProgressiveSyncResult(solve.ratios[st.best_cand], st.best_cand, st.offset, st.score, st.quality,
+                                         st.ratio_margin, st.ref_len, len(h), done[f], reasons))
+    return out
+
+
+def _merged(intervals):
+    """Sorted disjoint intervals with abutting neighbours joined (a ``SampledSolve``'s books of what it has fed)."""
+    out: List[List[int]] = []
+    for a, b in sorted(intervals):
+        if out and out[-1][1] == a:
+            out[-1][1] = b
+        else:
+            out.append([a, b])
+    return [(a, b) for a, b in out]

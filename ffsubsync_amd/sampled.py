@@ -19,8 +19,7 @@ import numpy as np
 
 from . import _native, quality
 from .constants import DEFAULT_ENERGY_THRESHOLD_DB, SAMPLE_RATE
-from .progressive import (ProgressiveSolve, ProgressiveSyncResult, ProgressState, StopRule, state_from_records)
-from .side_call import empty_error
+from .progressive import ProgressiveSolve, ProgressiveSyncResult, ProgressState, StopRule, _sync_rounds
 
 MAX_INTERVALS = _native.PROG_MAX_INTERVALS
 # Chosen by profiles/progressive_calibration.py's rule on the CPU model (profiles/sampled_calibration.json):
@@ -120,13 +119,10 @@ class SampledSolve(ProgressiveSolve):
     def append_at(self, chunks: Dict[int, tuple]) -> Dict[int, ProgressState]:
         """Feed one (start_sample, chunk) per named file; ``chunk`` in any form ``ProgressiveSolve.append`` takes.  The
         samples must lie inside [0, duration) and must not have been fed before.  One native call for all of them."""
-        if self.plan is None:
-            raise ValueError("this SampledSolve is closed")
-        torch = self.torch
+        self._check_open("SampledSolve")
         files = list(chunks)
         for f in files:
-            if not isinstance(f, (int, np.integer)) or not 0 <= f < self.n_files:
-                raise ValueError("file %r: need an index in [0, %d)" % (f, self.n_files))
+            self._check_file(f)
             if not isinstance(chunks[f], tuple) or len(chunks[f]) != 2:
                 raise ValueError("file %d: need (start_sample, chunk)" % f)
         if not files:
@@ -137,40 +133,13 @@ class SampledSolve(ProgressiveSolve):
             form = self._chunk_form(chunk)
             starts.append(self._check_interval(f, start, form[2]))
             checked.append(form)
-        keep = [self._device_words(chunks[f][1], words, n) for f, (words, _, n) in zip(files, checked)]
-        n = len(files)
-        cand_out = torch.empty(n * self.n_cand * _native.QUALITY_RESULT_BYTES, dtype=torch.uint8, device=self.device)
-        state_out = torch.empty(n * _native.PROG_STATE_BYTES, dtype=torch.uint8, device=self.device)
-        self.plan.append_at(files, [w.data_ptr() for w in keep], [c[1] for c in checked], starts, [c[2] for c in checked],
-                            self.top_k, self.exclusion_samples, cand_out, state_out)
-        for f, a, c in zip(files, starts, checked):
-            if c[2]:
-                self._known[f] = _merged(self._known[f] + [(a, a + c[2])])
-                self.consumed[f] += c[2]
-        recs = cand_out.cpu().numpy().view(_native.QUALITY_RESULT_DTYPE).reshape(n, self.n_cand)
-        states = state_out.cpu().numpy().view(_native.PROG_STATE_DTYPE)
-        del keep
-        self.last_records = {f: recs[i] for i, f in enumerate(files)}
-        self.last_states = {f: states[i] for i, f in enumerate(files)}
-        return {f: state_from_records(states[i], recs[i]) for i, f in enumerate(files)}
+        return self._append(files, checked, starts, [chunks[f][1] for f in files])
 
     def known(self, f: int) -> List[Tuple[int, int]]:
         """The merged known intervals of file ``f``, ascending (``ffs_prog_known``)."""
-        if self.plan is None:
-            raise ValueError("this SampledSolve is closed")
-        if not isinstance(f, (int, np.integer)) or not 0 <= f < self.n_files:
-            raise ValueError("file %r: need an index in [0, %d)" % (f, self.n_files))
+        self._check_open("SampledSolve")
+        self._check_file(f)
         return [(int(a), int(b)) for a, b in self.plan.known(f)]
-
-
-def _merged(intervals):
-    out: List[List[int]] = []
-    for a, b in sorted(intervals):
-        if out and out[-1][1] == a:
-            out[-1][1] = b
-        else:
-            out.append([a, b])
-    return [(a, b) for a, b in out]
 
 
 def _segment_chunk(data, n_want: int, sample_rate: int, frame_rate: int, energy_threshold_db: float):
@@ -260,38 +229,30 @@ def sampled_sync(problems, rule: Optional[StopRule] = None, segment_seconds: flo
         readers = [p[0] for p in problems]
         at = [0] * len(problems)
         live = [bool(s) for s in schedules]
-        history: List[List[ProgressState]] = [[] for _ in problems]
-        done = [False] * len(problems)
-        while any(live):
-            chunks = {}
-            for f, sched in enumerate(schedules):
-                if not live[f]:
-                    continue
-                a, b = sched[at[f]]
-                at[f] += 1
-                live[f] = at[f] < len(sched)
-                data = readers[f](a / sample_rate, (b - a) / sample_rate)
-                chunk = _segment_chunk(data, b - a, solve.sample_rate, frame_rate, energy_threshold_db)
-                if _chunk_len(chunk) != b - a:
-                    raise ValueError("file %d: read_segment(%r, %r) returned %d samples, the segment has %d"
-                                     % (f, a / sample_rate, (b - a) / sample_rate, _chunk_len(chunk), b - a))
-                chunks[f] = (a, chunk)
-            for f, st in solve.append_at(chunks).items():
-                history[f].append(st)
-                if rule.settled(history[f]):
-                    done[f] = True
-                    live[f] = False
-                    close = getattr(readers[f], "close", None)
-                    if close is not None:
-                        close()
-        out = []
-        for f, h in enumerate(history):
-            if not h:
-                raise empty_error(0, solve.rasters[f][0].n)
-            st = h[-1]
-            reasons = [] if done[f] else quality.assess(st.quality, rule.min_psr, rule.min_margin)
-            out.append(ProgressiveSyncResult(solve.ratios[st.best_cand], st.best_cand, st.offset, st.score, st.quality,
-                                             st.ratio_margin, st.ref_len, len(h), done[f], reasons))
-        return out
+
+        def rounds():
+            while any(live):
+                chunks = {}
+                for f, sched in enumerate(schedules):
+                    if not live[f]:
+                        continue
+                    a, b = sched[at[f]]
+                    at[f] += 1
+                    live[f] = at[f] < len(sched)
+                    data = readers[f](a / sample_rate, (b - a) / sample_rate)
+                    chunk = _segment_chunk(data, b - a, solve.sample_rate, frame_rate, energy_threshold_db)
+                    if _chunk_len(chunk) != b - a:
+                        raise ValueError("file %d: read_segment(%r, %r) returned %d samples, the segment has %d"
+                                         % (f, a / sample_rate, (b - a) / sample_rate, _chunk_len(chunk), b - a))
+                    chunks[f] = (a, chunk)
+                yield chunks
+
+        def settle(f):
+            live[f] = False
+            close = getattr(readers[f], "close", None)
+            if close is not None:
+                close()
+
+        return _sync_rounds(solve, rule, solve.append_at, rounds, settle)
     finally:
         solve.close()

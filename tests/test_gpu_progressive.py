@@ -463,3 +463,61 @@ def test_every_refusal_leaves_state_and_outputs_untouched():
                 _native.ProgPlan(*dims)
     finally:
         plan.close()
+
+
+def test_a_refusal_at_the_second_of_two_slots_leaves_the_first_untouched():
+    """Every per-slot check of every named slot comes before any slot's state changes: a call that names [0, 1] with a
+    good entry for slot 0 and a bad one for slot 1 is refused whole, and slot 0 has not consumed its entry."""
+    import torch
+
+    from ffsubsync_amd import _native
+
+    case = pc.make_case(930, 300, [700, 33], 16)
+    plan = _native.ProgPlan(3, 2, 32, 300, 700)
+    cands = Cands([case])
+    models = [pm.Slot(case["cands"], case["ref_levels"], case["W"]) for _ in range(2)]
+    pos = [0, 0]
+
+    def valid(ns):
+        chunks = [case["ref"][pos[s]:pos[s] + n] for s, n in enumerate(ns)]
+        keep = [_dev(_words(c, 8)) for c in chunks]
+        out = Outputs(2, 2)
+        plan.append([0, 1], [k.data_ptr() for k in keep], [8, 8], ns, 2, 5, *out.views())
+        recs, states = out.read()
+        for s, n in enumerate(ns):
+            pos[s] += n
+            reps, mstate = models[s].append(chunks[s], 2, 5)
+            _check(recs[s], states[s], reps, mstate, 2, 2, ("slot", s, "L", pos[s]))
+
+    try:
+        _open(plan, [0, 1], [case], cands, rows=[0, 0])
+        valid([40, 25])
+        w = _dev(_words(case["ref"][:64], 0))
+        out = Outputs(2, 2)
+        co, so = out.views()
+        bad_second = [dict(ptr=0), dict(ptr=w.data_ptr() + 2), dict(fb=32), dict(n=-1), dict(n=300 - 25 + 1),
+                      dict(other_kind=True)]
+        for bad in bad_second:
+            a = dict(dict(ptr=w.data_ptr(), fb=0, n=5), **bad)
+            if bad.get("other_kind"):  # slot 1 is a sampled slot for this one call
+                _open_sampled_one(plan, case, cands, 1, 300)
+            before = plan.reference(0)[1]
+            with pytest.raises(_native.NativeError) as err:
+                plan.append([0, 1], [w.data_ptr(), a["ptr"]], [0, a["fb"]], [5, a["n"]], 2, 5, co, so)
+            assert err.value.code == -1, bad
+            torch.cuda.synchronize()
+            assert bool((out.cand == 0xA5).all()) and bool((out.state == 0xA5).all()), bad
+            assert plan.reference(0)[1] == before == pos[0], bad
+            if bad.get("other_kind"):  # and a fresh prefix slot again
+                _open(plan, [1], [case], cands, rows=[0])
+                models[1], pos[1] = pm.Slot(case["cands"], case["ref_levels"], case["W"]), 0
+        valid([7, 9])
+    finally:
+        plan.close()
+
+
+def _open_sampled_one(plan, case, cands, slot, total):
+    """``slot`` reopened as a sampled slot on ``case`` with a declared length."""
+    plan.open_sampled([slot], [2], [[cands.ptr(0, 0), cands.ptr(0, 1)]], [[len(s) for s, _ in case["cands"]]],
+                      [[lv[0] for _, lv in case["cands"]]], [[lv[1] for _, lv in case["cands"]]], [case["ref_levels"][0]],
+                      [case["ref_levels"][1]], [case["W"]], [total])

@@ -512,3 +512,55 @@ def test_every_refusal_leaves_state_and_outputs_untouched():
             plan.append_at([0], [w.data_ptr()], [0], [0], [5], 2, 5, co, so)
     finally:
         plan.close()
+
+
+def test_a_refusal_at_the_second_of_two_slots_leaves_the_first_untouched():
+    """Every per-slot check of every named slot comes before any slot's state changes: a call that names [0, 1] with a
+    good entry for slot 0 and a bad one for slot 1 is refused whole, and slot 0 knows no more than before."""
+    import torch
+
+    from ffsubsync_amd import _native
+
+    case = sc.refusal_case()
+    T = case["T"]
+    plan = _native.ProgPlan(3, 2, 32, T, 700)
+    cands = Cands([case])
+    models = [sm.Slot(case["cands"], case["ref_levels"], case["W"], T) for _ in range(2)]
+
+    def valid(starts, ns):
+        chunks = [case["ref"][a:a + n] for a, n in zip(starts, ns)]
+        keep = [_dev(_words(c, 8)) for c in chunks]
+        out = Outputs(2, 2)
+        plan.append_at([0, 1], [k.data_ptr() for k in keep], [8, 8], starts, ns, 2, 5, *out.views())
+        recs, states = out.read()
+        for s in range(2):
+            reps, mstate = models[s].append_at(starts[s], chunks[s], 2, 5)
+            _check(recs[s], states[s], reps, mstate, 2, 2, ("slot", s, "a", starts[s]))
+            assert [tuple(x) for x in plan.known(s)] == models[s].intervals, s
+
+    try:
+        _open_sampled(plan, [0, 1], [case], cands, rows=[0, 0])
+        valid([100, 40], [20, 20])  # slot 1 knows [40, 60)
+        w = _dev(_words(case["ref"][:64], 0))
+        out = Outputs(2, 2)
+        co, so = out.views()
+        bad_second = [dict(ptr=0), dict(ptr=w.data_ptr() + 2), dict(fb=32), dict(n=-1), dict(a=T - 4), dict(a=58),
+                      dict(other_kind=True)]
+        for bad in bad_second:
+            a = dict(dict(ptr=w.data_ptr(), fb=0, a=200, n=5), **bad)
+            if bad.get("other_kind"):  # slot 1 is a prefix slot for this one call
+                _open(plan, [1], [case], cands, rows=[0])
+            before, length = [tuple(x) for x in plan.known(0)], plan.reference(0)[1]
+            with pytest.raises(_native.NativeError) as err:
+                plan.append_at([0, 1], [w.data_ptr(), a["ptr"]], [0, a["fb"]], [0, a["a"]], [5, a["n"]], 2, 5, co, so)
+            assert err.value.code == -1, bad
+            torch.cuda.synchronize()
+            assert bool((out.cand == 0xA5).all()) and bool((out.state == 0xA5).all()), bad
+            assert [tuple(x) for x in plan.known(0)] == before == models[0].intervals, bad
+            assert plan.reference(0)[1] == length == T, bad
+            if bad.get("other_kind"):  # and a fresh sampled slot again
+                _open_sampled(plan, [1], [case], cands, rows=[0])
+                models[1] = sm.Slot(case["cands"], case["ref_levels"], case["W"], T)
+        valid([0, 200], [7, 9])
+    finally:
+        plan.close()
