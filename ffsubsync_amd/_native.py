@@ -195,6 +195,17 @@ VAD_THRESHOLD_DTYPE = np.dtype(
 )
 VAD_THRESHOLD_BYTES = 48
 assert VAD_THRESHOLD_DTYPE.itemsize == VAD_THRESHOLD_BYTES
+# ffs_vad_gate, the record of the steady-run gate (include/ffsubsync_amd.h; static size 48 bytes)
+VAD_GATE_NO_QUIET = 1  # FFS_VAD_GATE_NO_QUIET: threshold - dip_bins <= 0, no frame can close a stretch
+VAD_GATE_ALL_REJECTED = 2  # FFS_VAD_GATE_ALL_REJECTED: active frames, none kept
+VAD_GATE_TOO_LONG = 4  # FFS_VAD_GATE_TOO_LONG: more than VAD_MAX_FRAMES frames, the plain labels
+VAD_GATE_TILE = 4096  # frames of one workgroup of the gate's tile kernels (csrc/ffs_vad_gate.h, GATE_TILE)
+VAD_GATE_DTYPE = np.dtype(
+    [("threshold_bin", "<i4"), ("flags", "<i4"), ("n_stretches", "<i4"), ("n_rejected", "<i4"), ("longest_run", "<i4"),
+     ("reserved", "<i4"), ("n_frames", "<i8"), ("n_active", "<i8"), ("n_kept", "<i8")], align=True
+)
+VAD_GATE_BYTES = 48
+assert VAD_GATE_DTYPE.itemsize == VAD_GATE_BYTES
 # ffs_prog_state (include/ffsubsync_amd.h; static size 64 bytes)
 PROG_STATE_DTYPE = np.dtype(
     [("ref_len", "<i8"), ("offset", "<i8"), ("score", "<f8"), ("mean", "<f8"), ("std", "<f8"), ("runner_up", "<f8"),
@@ -288,6 +299,8 @@ EXPORTED_SYMBOLS = (
     "ffs_vad_level_hist",
     "ffs_vad_pick_threshold",
     "ffs_vad_level_labels",
+    "ffs_vad_steady_gate_workspace_bytes",
+    "ffs_vad_steady_gate",
     "ffs_prog_plan_create",
     "ffs_prog_plan_destroy",
     "ffs_prog_plan_workspace_bytes",
@@ -437,6 +450,11 @@ def load():
         lib.ffs_vad_level_labels.restype = c.c_int
         lib.ffs_vad_level_labels.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int, c.c_float, c.c_void_p, c.c_void_p,
                                              c.c_void_p]
+        lib.ffs_vad_steady_gate_workspace_bytes.restype = c.c_int64
+        lib.ffs_vad_steady_gate_workspace_bytes.argtypes = [c.c_int64]
+        lib.ffs_vad_steady_gate.restype = c.c_int
+        lib.ffs_vad_steady_gate.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int, c.c_int, c.c_int64, c.c_float, c.c_void_p,
+                                            c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p]
         lib.ffs_speech_bounds.restype = c.c_int
         lib.ffs_speech_bounds.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p]
         lib.ffs_raster_length.restype = c.c_int64

@@ -12,10 +12,15 @@ levels, pick one threshold bin from the counts and label the frames with it.
     detect_device_adaptive         the four launches queued on the current stream for PCM resident in HBM
     detect_pinned_stream_adaptive  the same behind ``detect_pinned_stream``'s double-buffered copy loop
     assess                         reasons not to trust a record
+    steady_gate                    ``ffs_vad_steady_gate``: the labels without the stretches of uninterrupted activity
+                                   longer than ``max_run`` frames -- music, hum, hiss
+    detect_device_gated            detect_device_adaptive with the gate behind the pick
+    detect_pinned_stream_gated     detect_pinned_stream_adaptive with the gate behind the pick
+    assess_gate                    what a gate record says about the file
 
-``PCMSpeechTransformer(vad="adaptive")`` runs it behind the pipelined chunk loop.  Nothing existing changes behaviour:
-the fixed rule stays the default everywhere, and every fallback of the pick IS the fixed rule (bin 100 of the default
-table is 50 dB).
+``PCMSpeechTransformer(vad="adaptive")`` runs it behind the pipelined chunk loop, ``vad="gated"`` with the gate.  Nothing
+existing changes behaviour: the fixed rule stays the default everywhere, and every fallback of the pick IS the fixed
+rule (bin 100 of the default table is 50 dB).
 
 What it says and what it does not.  This is the project's own rule with no upstream counterpart (the reference's
 adaptive detector is WebRTC's): parity is against the in-repo model ``tests/adaptive_vad_model.py`` only.  It is still
@@ -286,11 +291,15 @@ def threshold_db(record: ThresholdRecord, edges=None) -> float:
     return math.inf if t > e.size else 10.0 * math.log10(float(e[t - 1]))
 
 
-def _finish(levels, n_bins, non_speech_label, packed, rule, params):
-    """Histogram, pick and labels queued behind pass 1 on the current stream; only the record is read back."""
+def _finish(levels, n_bins, non_speech_label, packed, rule, params, gate=None):
+    """Histogram, pick and labels queued behind pass 1 on the current stream; only the record is read back.  With
+    ``gate`` = (dip_bins, max_run) the labels are :func:`steady_gate`'s and its record is read back too."""
     raw = pick_threshold_device(level_hist(levels, n_bins), rule, **params)
-    labels = level_labels(levels, raw, non_speech_label, packed)
-    return labels, _records(raw, 1)[0]
+    if gate is None:
+        labels = level_labels(levels, raw, non_speech_label, packed)
+        return labels, _records(raw, 1)[0]
+    labels, gate_raw = steady_gate(levels, raw, gate[0], gate[1], non_speech_label, packed)
+    return labels, _records(raw, 1)[0], gate_record_of(gate_raw.cpu().numpy().view(_native.VAD_GATE_DTYPE)[0])
 
 
 def _check_detect(sample_rate, frame_rate, non_speech_label, n_bins, rule, params) -> int:
@@ -322,20 +331,10 @@ def detect_device_adaptive(pcm_dev, sample_rate: int, frame_rate: int, non_speec
     return _finish(levels, n_edges + 1, non_speech_label, packed, rule, params)
 
 
-def detect_pinned_stream_adaptive(pcm_host, sample_rate: int, frame_rate: int, non_speech_label: float,
-                                  rule: str = DEFAULT_RULE, edges=None, staging=None, packed: bool = False, **params):
-    """The adaptive detector behind ``detect_pinned_stream``'s double-buffered copy loop, for decoded s16le PCM in pinned
-    host memory (int16 CPU tensor): pass 1 runs per 100 s buffer while the next one is copied, the histogram, the pick
-    and the labels run once at the end.  Returns what :func:`detect_device_adaptive` returns."""
+def _pinned_levels(pcm_host, frame_len, table, n_edges, staging):
+    """Pass 1 behind ``stream_pinned_buffers``: the level bytes of the whole pinned stream, queued on the current stream."""
     from .speech_transformers import WINDOWS_PER_BUFFER, stream_pinned_buffers
 
-    import torch
-
-    table, n_edges = _edges_checked(edges)
-    frame_len = _check_detect(sample_rate, frame_rate, non_speech_label, n_edges + 1, rule, params)
-    if not (hasattr(pcm_host, "is_cuda") and not pcm_host.is_cuda and pcm_host.dtype == torch.int16 and pcm_host.dim() == 1
-            and pcm_host.is_contiguous()):
-        raise ValueError("pcm: need a contiguous int16 CPU vector (pinned for the copies to overlap)")
     torch = _native.require_gpu()
     table = _edges_dev(table, torch.device("cuda", torch.cuda.current_device()))
     n = int(pcm_host.numel())
@@ -347,6 +346,26 @@ def detect_pinned_stream_adaptive(pcm_host, sample_rate: int, frame_rate: int, n
                                          levels.data_ptr() + o // frame_len, main.cuda_stream))
 
     stream_pinned_buffers(pcm_host, frame_len * WINDOWS_PER_BUFFER, staging, sweep)
+    return levels
+
+
+def _check_pinned(pcm_host) -> None:
+    import torch
+
+    if not (hasattr(pcm_host, "is_cuda") and not pcm_host.is_cuda and pcm_host.dtype == torch.int16 and pcm_host.dim() == 1
+            and pcm_host.is_contiguous()):
+        raise ValueError("pcm: need a contiguous int16 CPU vector (pinned for the copies to overlap)")
+
+
+def detect_pinned_stream_adaptive(pcm_host, sample_rate: int, frame_rate: int, non_speech_label: float,
+                                  rule: str = DEFAULT_RULE, edges=None, staging=None, packed: bool = False, **params):
+    """The adaptive detector behind ``detect_pinned_stream``'s double-buffered copy loop, for decoded s16le PCM in pinned
+    host memory (int16 CPU tensor): pass 1 runs per 100 s buffer while the next one is copied, the histogram, the pick
+    and the labels run once at the end.  Returns what :func:`detect_device_adaptive` returns."""
+    table, n_edges = _edges_checked(edges)
+    frame_len = _check_detect(sample_rate, frame_rate, non_speech_label, n_edges + 1, rule, params)
+    _check_pinned(pcm_host)
+    levels = _pinned_levels(pcm_host, frame_len, table, n_edges, staging)
     return _finish(levels, n_edges + 1, non_speech_label, packed, rule, params)
 
 
@@ -371,4 +390,151 @@ def assess(record: ThresholdRecord, min_eta: Optional[float] = DEFAULT_MIN_ETA) 
         reasons.append("threshold clamped down to bin %d" % record.threshold_bin)
     if min_eta is not None and not f & _native.VAD_THR_FALLBACK and record.eta < min_eta:
         reasons.append("levels do not split into two classes (eta %.2f < %.2f)" % (record.eta, min_eta))
+    return reasons
+
+
+# ---- steady-run gate ---------------------------------------------------------------------------------
+# By the rule of profiles/steady_gate_calibrate.py on the CPU model (profiles/steady_gate_calibration.json; the synthetic
+# 10 min files of the adaptive calibration, SYNTHETIC data only): dip_bins = 0 rejects the least (the kept set shrinks
+# as dip_bins grows) and already takes the music share labelled speech from 1.000 to 0.000, so 0 ships.  max_run is the
+# reference's longest cue, DEFAULT_MAX_SUBTITLE_SECONDS, in frames.
+DEFAULT_DIP_BINS = 0
+
+
+def default_max_run(sample_rate: int = 100) -> int:
+    """The longest cue the reference lets through, in frames of ``sample_rate`` per second: no subtitle can vouch for a
+    longer stretch of uninterrupted activity."""
+    from .constants import DEFAULT_MAX_SUBTITLE_SECONDS
+
+    return int(DEFAULT_MAX_SUBTITLE_SECONDS * sample_rate)
+
+
+DEFAULT_MAX_RUN = default_max_run()
+
+
+@dataclass
+class GateRecord:
+    threshold_bin: int  # the threshold the gate used
+    flags: int  # _native.VAD_GATE_*
+    n_stretches: int
+    n_rejected: int  # stretches longer than max_run
+    longest_run: int  # frames of the longest stretch, 0: none
+    n_frames: int
+    n_active: int  # frames at or above the threshold
+    n_kept: int  # of them, labelled speech
+
+
+def gate_record_of(row) -> GateRecord:
+    """One ``_native.VAD_GATE_DTYPE`` row as Python numbers."""
+    return GateRecord(*(int(row[name]) for name in _native.VAD_GATE_DTYPE.names if name != "reserved"))
+
+
+def _check_gate(dip_bins, max_run):
+    if isinstance(dip_bins, bool) or not isinstance(dip_bins, (int, np.integer)) or not 0 <= dip_bins <= _native.VAD_MAX_EDGES:
+        raise ValueError("dip_bins=%r: need bins in [0, %d]" % (dip_bins, _native.VAD_MAX_EDGES))
+    if isinstance(max_run, bool) or not isinstance(max_run, (int, np.integer)) or not 1 <= max_run <= 2 ** 31 - 1:
+        raise ValueError("max_run=%r: need frames in [1, 2^31 - 1]" % (max_run,))
+    return int(dip_bins), int(max_run)
+
+
+def steady_gate(levels, threshold, dip_bins: int = DEFAULT_DIP_BINS, max_run: int = DEFAULT_MAX_RUN,
+                non_speech_label: float = 0.0, packed: bool = False):
+    """:func:`level_labels` without the stretches of uninterrupted activity longer than ``max_run`` frames
+    (``ffs_vad_steady_gate``): a frame is speech iff level >= threshold and its stretch -- from the first active frame
+    behind a frame below ``threshold - dip_bins`` to the last one in front of the next -- is at most ``max_run`` long.
+    ``threshold``: a bin in [0, 256], a :class:`ThresholdRecord`, or the device tensor of :func:`pick_threshold_device`
+    (read on the device, never read back).  Returns (float32 CUDA labels or with ``packed`` the ``DeviceRaster``, the uint8
+    CUDA tensor of the 48-byte gate record); three launches queued on the current stream, nothing is read back."""
+    import torch
+
+    non_speech_label = _check_label(non_speech_label)
+    dip_bins, max_run = _check_gate(dip_bins, max_run)
+    if isinstance(threshold, ThresholdRecord):
+        threshold = threshold.threshold_bin
+    if hasattr(threshold, "is_cuda"):
+        if not (threshold.is_cuda and threshold.is_contiguous() and _native._nbytes(threshold) >= 4
+                and threshold.dtype in (torch.uint8, torch.int32)):
+            raise ValueError("threshold: a device threshold must be a contiguous uint8 or int32 CUDA tensor of 4 bytes or more")
+        thr_dev, thr_host = threshold.data_ptr(), 0
+    elif isinstance(threshold, bool) or not isinstance(threshold, (int, np.integer)) or not 0 <= threshold <= _native.VAD_MAX_BINS:
+        raise ValueError("threshold=%r: need a bin in [0, %d], a ThresholdRecord or a device tensor" % (threshold, _native.VAD_MAX_BINS))
+    else:
+        thr_dev, thr_host = None, int(threshold)
+    _check_levels(levels)
+    if thr_dev is not None and threshold.device != levels.device:
+        raise ValueError("threshold: a device threshold must be on the levels' device")
+    torch = _native.require_gpu()
+    lib = _native.load()
+    n = int(levels.numel())
+    if packed:
+        out = torch.zeros((n + 31) // 32, dtype=torch.int32, device=levels.device)
+    else:
+        out = torch.empty(n, dtype=torch.float32, device=levels.device)
+    record = torch.empty(_native.VAD_GATE_BYTES, dtype=torch.uint8, device=levels.device)
+    ws_bytes = int(lib.ffs_vad_steady_gate_workspace_bytes(n))
+    workspace = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=levels.device)
+    with torch.cuda.device(levels.device):
+        _native.check(lib.ffs_vad_steady_gate(levels.data_ptr() if n else None, n, thr_dev, thr_host, dip_bins, max_run,
+                                              float(non_speech_label), None if packed or not n else out.data_ptr(),
+                                              out.data_ptr() if packed and n else None, record.data_ptr(), workspace.data_ptr(),
+                                              ws_bytes, _native.current_stream_ptr(torch)))
+    if packed:
+        from .subtitle_raster import DeviceRaster
+
+        return DeviceRaster(out, float(non_speech_label), 1.0, n), record
+    return out, record
+
+
+def _check_detect_gated(sample_rate, dip_bins, max_run):
+    return _check_gate(dip_bins, default_max_run(sample_rate) if max_run is None else max_run)
+
+
+def detect_device_gated(pcm_dev, sample_rate: int, frame_rate: int, non_speech_label: float, rule: str = DEFAULT_RULE,
+                        edges=None, packed: bool = False, dip_bins: int = DEFAULT_DIP_BINS, max_run: Optional[int] = None,
+                        **params):
+    """:func:`detect_device_adaptive` with the steady-run gate behind the pick: (labels or ``DeviceRaster``, the file's
+    ``ThresholdRecord``, its ``GateRecord``).  ``max_run`` defaults to ``default_max_run(sample_rate)``, ten seconds of
+    frames.  Seven launches queued on the current stream; only the two 48-byte records are read back."""
+    table, n_edges = _edges_checked(edges)
+    frame_len = _check_detect(sample_rate, frame_rate, non_speech_label, n_edges + 1, rule, params)
+    gate = _check_detect_gated(sample_rate, dip_bins, max_run)
+    _check_pcm(pcm_dev, frame_len)
+    table = _edges_dev(table, pcm_dev.device)
+    levels = frame_levels(pcm_dev, frame_len, table)
+    return _finish(levels, n_edges + 1, non_speech_label, packed, rule, params, gate)
+
+
+def detect_pinned_stream_gated(pcm_host, sample_rate: int, frame_rate: int, non_speech_label: float,
+                               rule: str = DEFAULT_RULE, edges=None, staging=None, packed: bool = False,
+                               dip_bins: int = DEFAULT_DIP_BINS, max_run: Optional[int] = None, **params):
+    """:func:`detect_pinned_stream_adaptive` with the steady-run gate behind the pick; returns what
+    :func:`detect_device_gated` returns."""
+    table, n_edges = _edges_checked(edges)
+    frame_len = _check_detect(sample_rate, frame_rate, non_speech_label, n_edges + 1, rule, params)
+    gate = _check_detect_gated(sample_rate, dip_bins, max_run)
+    _check_pinned(pcm_host)
+    levels = _pinned_levels(pcm_host, frame_len, table, n_edges, staging)
+    return _finish(levels, n_edges + 1, non_speech_label, packed, rule, params, gate)
+
+
+def assess_gate(record: GateRecord, max_rejected_share: Optional[float] = None) -> List[str]:
+    """What the gate record says about the file ([] = nothing to report): the gate was skipped, no frame could close a
+    stretch, everything active was rejected, and -- only with a ``max_rejected_share``; the calibration ships none --
+    more than that share of the active frames was dropped.  It reports; it decides nothing."""
+    if max_rejected_share is not None and not (isinstance(max_rejected_share, (int, float)) and not isinstance(max_rejected_share, bool)
+                                               and 0.0 <= max_rejected_share <= 1.0):
+        raise ValueError("max_rejected_share=%r: need a share in [0, 1]" % (max_rejected_share,))
+    f, reasons = int(record.flags), []
+    if f & _native.VAD_GATE_TOO_LONG:
+        reasons.append("too many frames for the gate (%d > %d): plain labels" % (record.n_frames, MAX_FRAMES))
+        return reasons
+    if f & _native.VAD_GATE_NO_QUIET:
+        reasons.append("no level lies below threshold bin %d minus the dip: nothing can close a stretch" % record.threshold_bin)
+    if f & _native.VAD_GATE_ALL_REJECTED:
+        reasons.append("all %d active frames lie in stretches longer than the limit (longest %d)" % (record.n_active, record.longest_run))
+    elif max_rejected_share is not None and record.n_active > 0:
+        share = (record.n_active - record.n_kept) / float(record.n_active)
+        if share > max_rejected_share:
+            reasons.append("%.2f of the active frames dropped in %d of %d stretches (limit %.2f)"
+                           % (share, record.n_rejected, record.n_stretches, max_rejected_share))
     return reasons

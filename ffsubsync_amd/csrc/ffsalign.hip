@@ -47,6 +47,7 @@
 #include "ffs_progressive.h"
 #include "ffs_sampled.h"
 #include "ffs_adaptive_vad.h"
+#include "ffs_vad_gate.h"
 
 using namespace ffsa;
 
@@ -3174,6 +3175,59 @@ int ffs_vad_level_labels(const uint8_t* levels_dev, int64_t n_frames, const int3
     if (blocks > LABEL_MAX_BLOCKS) blocks = LABEL_MAX_BLOCKS;
     hipLaunchKernelGGL(k_vad_level_labels, dim3((unsigned)blocks), dim3(LABEL_THREADS), 0, (hipStream_t)hip_stream, levels_dev,
                        (long long)n_frames, (const int*)threshold_dev, threshold_host, non_speech_label, labels_dev, bits_dev);
+    HIP_TRY(hipGetLastError());
+    return FFS_OK;
+}
+
+// ---- steady-run gate behind the adaptive VAD (ffs_vad_gate.h) ---------------------------------------------
+
+int64_t ffs_vad_steady_gate_workspace_bytes(int64_t n_frames) {
+    if (n_frames <= 0 || n_frames > VAD_MAX_FRAMES) return 0;  // nothing to carry: no frames, or the gate is skipped
+    return ((n_frames + GATE_TILE - 1) / GATE_TILE) * (int64_t)GATE_WS_PER_TILE;
+}
+
+int ffs_vad_steady_gate(const uint8_t* levels_dev, int64_t n_frames, const int32_t* threshold_dev, int threshold_host,
+                        int dip_bins, int64_t max_run, float non_speech_label, float* labels_dev, uint8_t* bits_dev,
+                        ffs_vad_gate* record_dev, void* workspace_dev, int64_t workspace_bytes, void* hip_stream) {
+    static_assert(sizeof(ffs_vad_gate) == sizeof(VadGate), "device records must match the header's");
+    if (n_frames < 0) return fail(FFS_E_INVALID, "ffs_vad_steady_gate: n_frames=%lld is negative", (long long)n_frames);
+    if (!threshold_dev && (threshold_host < 0 || threshold_host > VAD_MAX_BINS))
+        return fail(FFS_E_INVALID, "ffs_vad_steady_gate: threshold_host=%d outside [0, %d]", threshold_host, VAD_MAX_BINS);
+    if (dip_bins < 0 || dip_bins > VAD_MAX_EDGES)
+        return fail(FFS_E_INVALID, "ffs_vad_steady_gate: dip_bins=%d outside [0, %d]", dip_bins, VAD_MAX_EDGES);
+    if (max_run < 1 || max_run > 2147483647ll)
+        return fail(FFS_E_INVALID, "ffs_vad_steady_gate: max_run=%lld outside [1, 2^31 - 1]", (long long)max_run);
+    if (!record_dev || (n_frames > 0 && !levels_dev)) return fail(FFS_E_INVALID, "ffs_vad_steady_gate: null levels or record pointer");
+    if ((reinterpret_cast<uintptr_t>(threshold_dev) & 3) || (reinterpret_cast<uintptr_t>(labels_dev) & 3) ||
+        (reinterpret_cast<uintptr_t>(record_dev) & 7) || (reinterpret_cast<uintptr_t>(workspace_dev) & 7))
+        return fail(FFS_E_INVALID, "ffs_vad_steady_gate: misaligned threshold or label (4 bytes), record or workspace (8 bytes) pointer");
+    const int64_t need = ffs_vad_steady_gate_workspace_bytes(n_frames);
+    if (workspace_bytes < need || (need > 0 && !workspace_dev))
+        return fail(FFS_E_INVALID, "ffs_vad_steady_gate: workspace of %lld bytes, %lld needed for %lld frames", (long long)workspace_bytes,
+                    (long long)need, (long long)n_frames);
+    DeviceGuard guard;
+    int rc_dev;
+    if ((rc_dev = guard.enter(record_dev))) return rc_dev;
+    hipStream_t st = (hipStream_t)hip_stream;
+    const int* thr_dev = (const int*)threshold_dev;
+    const bool too_long = n_frames > VAD_MAX_FRAMES;
+    const int n_tiles = too_long ? 0 : (int)((n_frames + GATE_TILE - 1) / GATE_TILE);
+    GateTile* tiles = (GateTile*)workspace_dev;
+    int2* carry = (int2*)(tiles + n_tiles);
+    if (too_long && (labels_dev || bits_dev)) {  // the plain labels, as ffs_vad_level_labels launches them
+        long long blocks = (n_frames + LABEL_THREADS - 1) / LABEL_THREADS;
+        if (blocks > LABEL_MAX_BLOCKS) blocks = LABEL_MAX_BLOCKS;
+        hipLaunchKernelGGL(k_vad_level_labels, dim3((unsigned)blocks), dim3(LABEL_THREADS), 0, st, levels_dev, (long long)n_frames,
+                           thr_dev, threshold_host, non_speech_label, labels_dev, bits_dev);
+    }
+    if (n_tiles)
+        hipLaunchKernelGGL(k_gate_tiles, dim3((unsigned)n_tiles), dim3(GATE_THREADS), 0, st, levels_dev, (long long)n_frames, thr_dev,
+                           threshold_host, dip_bins, (int)max_run, tiles);
+    hipLaunchKernelGGL(k_gate_carry, dim3(1), dim3(GATE_THREADS), 0, st, tiles, n_tiles, (long long)n_frames, thr_dev, threshold_host,
+                       dip_bins, (int)max_run, too_long ? 1 : 0, carry, (VadGate*)record_dev);
+    if (n_tiles && (labels_dev || bits_dev))
+        hipLaunchKernelGGL(k_gate_labels, dim3((unsigned)n_tiles), dim3(GATE_THREADS), 0, st, levels_dev, (long long)n_frames, thr_dev,
+                           threshold_host, dip_bins, (int)max_run, carry, non_speech_label, labels_dev, bits_dev);
     HIP_TRY(hipGetLastError());
     return FFS_OK;
 }

@@ -266,7 +266,8 @@ class PCMSpeechTransformer(TransformerMixin):
         self._non_speech_label = non_speech_label
         self.progress_handler = progress_handler
         self.video_speech_results_: Optional[np.ndarray] = None
-        self.vad_threshold_ = None  # vad="adaptive": the file's adaptive_vad.ThresholdRecord
+        self.vad_threshold_ = None  # vad="adaptive" / "gated": the file's adaptive_vad.ThresholdRecord
+        self.vad_gate_ = None  # vad="gated": the file's adaptive_vad.GateRecord
 
     def _make_detector(self):
         if "fused" in self.vad:  # e.g. "fused" or "fused:intersection" (speech_transformers.py:655-665)
@@ -329,6 +330,25 @@ class PCMSpeechTransformer(TransformerMixin):
         speech = adaptive_vad.level_labels(levels, self.vad_threshold_.threshold_bin, 0.0)
         return [_labels_float64(speech, self._non_speech_label)]
 
+    def _fit_gated_pipelined(self, source, chunk_bytes) -> List[np.ndarray]:
+        """``vad="gated"``: ``vad="adaptive"`` with the steady-run gate of ``adaptive_vad`` behind the pick (stretches
+        of uninterrupted activity longer than ten seconds of frames are dropped: music, hum, hiss).  The pick's record
+        stays on the device for the gate; both records are kept, as ``vad_threshold_`` and ``vad_gate_``."""
+        from . import adaptive_vad
+
+        torch = _native.require_gpu()
+        frame_len = frames_per_window(self.sample_rate, self.frame_rate)
+        max_run = adaptive_vad.default_max_run(self.sample_rate)
+        levels = self._sweep_pipelined(source, chunk_bytes, lambda pcm: adaptive_vad.frame_levels(pcm, frame_len))
+        if not levels:
+            return []
+        levels = torch.cat(levels)
+        raw = adaptive_vad.pick_threshold_device(adaptive_vad.level_hist(levels))
+        speech, gate_raw = adaptive_vad.steady_gate(levels, raw, adaptive_vad.DEFAULT_DIP_BINS, max_run, 0.0)
+        self.vad_threshold_ = adaptive_vad.record_of(raw.cpu().numpy().view(_native.VAD_THRESHOLD_DTYPE)[0])
+        self.vad_gate_ = adaptive_vad.gate_record_of(gate_raw.cpu().numpy().view(_native.VAD_GATE_DTYPE)[0])
+        return [_labels_float64(speech, self._non_speech_label)]
+
     def _sweep_pipelined(self, source, chunk_bytes, sweep) -> list:
         """``sweep(int16 CUDA chunk)`` of every chunk of the stream through the two staging buffers; the device
         tensors it returned, in order."""
@@ -359,7 +379,9 @@ class PCMSpeechTransformer(TransformerMixin):
     def fit(self, source, *_) -> "PCMSpeechTransformer":
         bytes_per_window = BYTES_PER_SAMPLE * self.frame_rate // self.sample_rate  # :683-684
         chunk_bytes = bytes_per_window * WINDOWS_PER_BUFFER
-        if "adaptive" in self.vad:  # tested first: the name holds none of the reference's substrings
+        if "gated" in self.vad:  # tested first: the name holds neither "adaptive" nor any of the reference's substrings
+            media_bstring = self._fit_gated_pipelined(source, chunk_bytes)
+        elif "adaptive" in self.vad:  # tested next: the name holds none of the reference's substrings
             media_bstring = self._fit_adaptive_pipelined(source, chunk_bytes)
         elif "energy" in self.vad and "fused" not in self.vad and "auditok" not in self.vad:
             media_bstring = self._fit_energy_pipelined(source, chunk_bytes)

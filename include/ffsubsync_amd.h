@@ -1445,6 +1445,72 @@ int ffs_vad_pick_threshold(const uint32_t* hist_dev, int n_hist, int n_bins, int
 int ffs_vad_level_labels(const uint8_t* levels_dev, int64_t n_frames, const int32_t* threshold_dev, int threshold_host,
                          float non_speech_label, float* labels_dev, uint8_t* bits_dev, void* hip_stream);
 
+/* ---- steady-run gate behind the adaptive VAD: drop music, hum and hiss by length (csrc/ffs_vad_gate.h) -----------
+ * Replaces: nothing in the reference.  An energy rule labels every loud frame as speech, a music bed, a tone or an
+ * audience included.  A person does not talk for ten seconds without one 10 ms frame falling below the file's threshold,
+ * and the reference clamps every cue to DEFAULT_MAX_SUBTITLE_SECONDS = 10 (constants.py:14, subtitle_parser.py:163), so a
+ * stretch of uninterrupted activity longer than that carries no alignment evidence and is dropped whole, edges
+ * included.  Integers only: pinned bit for bit against tests/steady_gate_model.py.  ffs_vad_level_labels is unchanged.
+ *
+ * Inputs.  level[0 .. n) as ffs_vad_levels writes them; t the threshold bin, read ON THE DEVICE from threshold_dev when
+ * that is not NULL (a record's address works, as for ffs_vad_level_labels; the value is taken as it stands), else
+ * threshold_host in [0, 256]; dip_bins in [0, 255]; max_run in [1, 2^31 - 1] frames.
+ * Classes.  Frame i is ACTIVE iff level[i] >= t, QUIET iff (int)level[i] < t - dip_bins (never when t - dip_bins <= 0),
+ * else a KEEP frame.
+ * State.  s[-1] = quiet; s[i] = the class of the last active or quiet frame at or before i.
+ * Stretches.  A stretch opens at a rise (i active, s[i-1] quiet) and closes at the next fall (i quiet, s[i-1] active)
+ * or at the end of the file.  Its extent is [b, e], b the rise, e the last active frame before the fall (trailing keep
+ * frames do not count); its length is e - b + 1.
+ * Decision.  speech(f) = active(f) and length(stretch(f)) <= max_run.
+ * It follows: max_run >= n gives ffs_vad_level_labels' outputs byte for byte; dip_bins = 0 removes exactly the runs of
+ * ones longer than max_run from them; for fixed t and max_run the kept set shrinks as dip_bins grows.
+ *
+ * Record (one per call, 48 bytes): the t that was used, the flags, the stretches, those longer than max_run, the longest
+ * length (0: none), the frames, the active frames and the active frames kept.  Flags, in order of evaluation:
+ *   FFS_VAD_GATE_TOO_LONG      n_frames > FFS_VAD_MAX_FRAMES: the gate is skipped, the outputs are exactly
+ *                              ffs_vad_level_labels', and of the counts only n_frames is set (the pick's own fallback
+ *                              at this length);
+ *   FFS_VAD_GATE_NO_QUIET      t - dip_bins <= 0: no frame can close a stretch (set beside TOO_LONG too);
+ *   FFS_VAD_GATE_ALL_REJECTED  n_active > 0 and n_kept == 0.
+ *
+ * ffs_vad_steady_gate queues three ordered launches on the stream -- per-tile summaries of 4096 frames, one workgroup
+ * that carries the state over the summaries forward and backward and writes the record, the labels per tile -- and
+ * returns; no workgroup waits for another, nothing is allocated and nothing synchronises.  The carries live in the
+ * caller's workspace_dev: ffs_vad_steady_gate_workspace_bytes(n_frames) bytes (56 per tile; 0 for no frames and for
+ * more than FFS_VAD_MAX_FRAMES, when workspace_dev may be NULL), 8-byte aligned, free again when the stream has passed
+ * the call.  Outputs in ffs_vad_level_labels' two forms, either or both may be NULL: labels_dev[f] = 1.0f /
+ * non_speech_label, bits_dev ceil(n_frames / 8) bytes with the unused high bits of the last byte 0; nothing is written
+ * behind them.  levels_dev may be any byte address (16-byte loads where it is 16-byte aligned).  n_frames == 0 is FFS_OK
+ * and writes the record alone, all counts 0.
+ * FFS_E_INVALID with a message, before any launch: a negative count, threshold_host (without threshold_dev), dip_bins or
+ * max_run outside the ranges above, a null levels_dev (n_frames > 0) or record_dev, a misaligned threshold_dev or
+ * labels_dev (4 bytes), record_dev or workspace_dev (8 bytes), a workspace that is too small.  Stateless. */
+#define FFS_VAD_GATE_NO_QUIET 1     /* t - dip_bins <= 0 */
+#define FFS_VAD_GATE_ALL_REJECTED 2 /* active frames, none kept */
+#define FFS_VAD_GATE_TOO_LONG 4     /* more than FFS_VAD_MAX_FRAMES frames: plain labels */
+
+typedef struct ffs_vad_gate {
+    int32_t threshold_bin;        /* the t that was used */
+    int32_t flags;                /* FFS_VAD_GATE_* */
+    int32_t n_stretches;
+    int32_t n_rejected;           /* stretches longer than max_run */
+    int32_t longest_run;          /* the longest stretch's length, 0: none */
+    int32_t reserved;             /* 0 */
+    int64_t n_frames;
+    int64_t n_active;             /* frames at or above t */
+    int64_t n_kept;               /* of them, labelled speech */
+} ffs_vad_gate;
+#ifdef __cplusplus
+static_assert(sizeof(ffs_vad_gate) == 48, "ffs_vad_gate is 48 bytes");
+#else
+_Static_assert(sizeof(ffs_vad_gate) == 48, "ffs_vad_gate is 48 bytes");
+#endif
+
+int64_t ffs_vad_steady_gate_workspace_bytes(int64_t n_frames);
+int ffs_vad_steady_gate(const uint8_t* levels_dev, int64_t n_frames, const int32_t* threshold_dev, int threshold_host,
+                        int dip_bins, int64_t max_run, float non_speech_label, float* labels_dev, uint8_t* bits_dev,
+                        ffs_vad_gate* record_dev, void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
+
 /* ---- progressive alignment: the quality report of a growing reference prefix (csrc/ffs_progressive.h) -----------
  * Replaces: nothing in the reference (its --multi-segment-sync, speech_transformers.py:760-903, samples eight minutes
  * and hopes they suffice).  Score counts are additive over the reference, so after every appended chunk of reference

@@ -64,11 +64,18 @@ def frame_classes(rng, n_frames, kind, silence):
 
 def class_histograms(seed, duration, kind, silence):
     """{gain: int64 [4, 192]} of one file: the level counts of every class at every gain."""
+    cls, levels = class_levels(seed, duration, kind, silence)
+    return {g: np.stack([np.bincount(levels[g][cls == k], minlength=192) for k in range(4)]).astype(np.int64) for g in GAINS_DB}
+
+
+def class_levels(seed, duration, kind, silence, gains=GAINS_DB):
+    """(class per frame, {gain: uint8 level per frame}) of one file, frame by frame (profiles/steady_gate_calibrate.py
+    needs the order of the frames, not only their counts)."""
     rng = np.random.RandomState(seed)
     n_frames = duration * RATE // FRAME
     cls, burst = frame_classes(rng, n_frames, kind, silence)
     edges = am.default_edges()
-    hists = {g: np.zeros((4, edges.size + 1), np.int64) for g in GAINS_DB}
+    out = {g: np.zeros(n_frames, np.uint8) for g in gains}
     t = np.arange(CHUNK_FRAMES * FRAME, dtype=np.float64) / RATE
     music = sum(np.sin(2 * np.pi * f * t + ph) for f, ph in ((220.0, 0.1), (277.2, 1.3), (329.6, 2.2)))
     music *= 10.0 ** (68.0 / 20.0) / np.sqrt(1.5)
@@ -79,12 +86,10 @@ def class_histograms(seed, duration, kind, silence):
         sigma[c == 3] = 10.0 ** (35.0 / 20.0)  # the noise floor under the music
         x = rng.standard_normal((c.size, FRAME)) * sigma[:, None]
         x[c == 3] += music[:c.size * FRAME].reshape(c.size, FRAME)[c == 3]
-        for g in GAINS_DB:
+        for g in gains:
             pcm = np.clip(np.rint(x * 10.0 ** (g / 20.0)), -32768, 32767).astype(np.int16).ravel()
-            levels = am.frame_levels(pcm, FRAME, edges)
-            for k in range(4):
-                hists[g][k] += np.bincount(levels[c == k], minlength=edges.size + 1)
-    return hists
+            out[g][f0:f0 + c.size] = am.frame_levels(pcm, FRAME, edges)
+    return cls, out
 
 
 def evaluate(class_hist, **pick_args):
