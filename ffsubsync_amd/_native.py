@@ -206,6 +206,17 @@ VAD_GATE_DTYPE = np.dtype(
 )
 VAD_GATE_BYTES = 48
 assert VAD_GATE_DTYPE.itemsize == VAD_GATE_BYTES
+# ffs_vad_centre, the record of the centre gate (include/ffsubsync_amd.h; static size 48 bytes)
+VAD_CENTRE_MONO = 1  # FFS_VAD_CENTRE_MONO: no frame has a side level, the file is dual mono
+VAD_CENTRE_ALL_REJECTED = 2  # FFS_VAD_CENTRE_ALL_REJECTED: active frames, none kept
+VAD_STEREO_MAX_FRAME_VEC = 512  # pairs of the longest frame on the sweep's vector path (csrc/ffs_stereo_vad.h)
+VAD_CENTRE_GRID_FRAMES = 256 * 256  # frames of one trip of the centre gate's capped grid (CENTRE_MAX_BLOCKS * CENTRE_THREADS)
+VAD_CENTRE_DTYPE = np.dtype(
+    [("threshold_bin", "<i4"), ("flags", "<i4"), ("min_contrast_bins", "<i4"), ("max_side", "<i4"), ("n_frames", "<i8"),
+     ("n_active", "<i8"), ("n_kept", "<i8"), ("sum_contrast", "<i8")], align=True
+)
+VAD_CENTRE_BYTES = 48
+assert VAD_CENTRE_DTYPE.itemsize == VAD_CENTRE_BYTES
 # ffs_prog_state (include/ffsubsync_amd.h; static size 64 bytes)
 PROG_STATE_DTYPE = np.dtype(
     [("ref_len", "<i8"), ("offset", "<i8"), ("score", "<f8"), ("mean", "<f8"), ("std", "<f8"), ("runner_up", "<f8"),
@@ -301,6 +312,8 @@ EXPORTED_SYMBOLS = (
     "ffs_vad_level_labels",
     "ffs_vad_steady_gate_workspace_bytes",
     "ffs_vad_steady_gate",
+    "ffs_vad_stereo_levels",
+    "ffs_vad_centre_gate",
     "ffs_prog_plan_create",
     "ffs_prog_plan_destroy",
     "ffs_prog_plan_workspace_bytes",
@@ -455,6 +468,12 @@ def load():
         lib.ffs_vad_steady_gate.restype = c.c_int
         lib.ffs_vad_steady_gate.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_int, c.c_int, c.c_int64, c.c_float, c.c_void_p,
                                             c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p]
+        lib.ffs_vad_stereo_levels.restype = c.c_int
+        lib.ffs_vad_stereo_levels.argtypes = [c.c_void_p, c.c_int64, c.c_int, c.c_void_p, c.c_int, c.c_void_p, c.c_void_p,
+                                              c.c_void_p]
+        lib.ffs_vad_centre_gate.restype = c.c_int
+        lib.ffs_vad_centre_gate.argtypes = [c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p, c.c_int, c.c_int, c.c_void_p,
+                                            c.c_void_p, c.c_void_p]
         lib.ffs_speech_bounds.restype = c.c_int
         lib.ffs_speech_bounds.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p]
         lib.ffs_raster_length.restype = c.c_int64

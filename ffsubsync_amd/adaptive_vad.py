@@ -17,8 +17,17 @@ levels, pick one threshold bin from the counts and label the frames with it.
     detect_device_gated            detect_device_adaptive with the gate behind the pick
     detect_pinned_stream_gated     detect_pinned_stream_adaptive with the gate behind the pick
     assess_gate                    what a gate record says about the file
+    stereo_levels                  ``ffs_vad_stereo_levels``: mid (L + R) and side (L - R) level per frame of interleaved
+                                   stereo PCM
+    centre_gate                    ``ffs_vad_centre_gate``: the mid levels with every frame zeroed whose mid level does not
+                                   stand ``min_contrast_bins`` above its side level -- wide music, ambience, audiences
+    detect_device_centre           stereo sweep, histogram and pick of the mid levels, centre gate, labels (or, with
+                                   ``steady``, the steady-run gate on the centre gate's output)
+    detect_pinned_stream_centre    the same behind ``detect_pinned_stream``'s double-buffered copy loop
+    assess_centre                  what a centre record says about the file
 
-``PCMSpeechTransformer(vad="adaptive")`` runs it behind the pipelined chunk loop, ``vad="gated"`` with the gate.  Nothing
+``PCMSpeechTransformer(vad="adaptive")`` runs it behind the pipelined chunk loop, ``vad="gated"`` with the gate,
+``vad="centre"`` and ``vad="centre_steady"`` the centre-channel path on two interleaved channels.  Nothing
 existing changes behaviour: the fixed rule stays the default everywhere, and every fallback of the pick IS the fixed
 rule (bin 100 of the default table is 50 dB).
 
@@ -291,15 +300,26 @@ def threshold_db(record: ThresholdRecord, edges=None) -> float:
     return math.inf if t > e.size else 10.0 * math.log10(float(e[t - 1]))
 
 
-def _finish(levels, n_bins, non_speech_label, packed, rule, params, gate=None):
+def _finish(levels, n_bins, non_speech_label, packed, rule, params, gate=None, centre=None):
     """Histogram, pick and labels queued behind pass 1 on the current stream; only the record is read back.  With
-    ``gate`` = (dip_bins, max_run) the labels are :func:`steady_gate`'s and its record is read back too."""
+    ``gate`` = (dip_bins, max_run) the labels are :func:`steady_gate`'s and its record is read back too.  With ``centre``
+    = (side levels, min_contrast_bins) ``levels`` are the mid levels: the pick runs on their histogram, the labels (or
+    the steady-run gate) on :func:`centre_gate`'s output, and the centre record follows the threshold's."""
     raw = pick_threshold_device(level_hist(levels, n_bins), rule, **params)
+    records = ()
+    if centre is not None:
+        levels, centre_raw = centre_gate(levels, centre[0], raw, centre[1])
+        records = (centre_raw,)
     if gate is None:
         labels = level_labels(levels, raw, non_speech_label, packed)
-        return labels, _records(raw, 1)[0]
-    labels, gate_raw = steady_gate(levels, raw, gate[0], gate[1], non_speech_label, packed)
-    return labels, _records(raw, 1)[0], gate_record_of(gate_raw.cpu().numpy().view(_native.VAD_GATE_DTYPE)[0])
+    else:
+        labels, gate_raw = steady_gate(levels, raw, gate[0], gate[1], non_speech_label, packed)
+    out = (labels, _records(raw, 1)[0])
+    if centre is not None:
+        out += (centre_record_of(records[0].cpu().numpy().view(_native.VAD_CENTRE_DTYPE)[0]),)
+    if gate is not None:
+        out += (gate_record_of(gate_raw.cpu().numpy().view(_native.VAD_GATE_DTYPE)[0]),)
+    return out
 
 
 def _check_detect(sample_rate, frame_rate, non_speech_label, n_bins, rule, params) -> int:
@@ -537,4 +557,201 @@ def assess_gate(record: GateRecord, max_rejected_share: Optional[float] = None) 
         if share > max_rejected_share:
             reasons.append("%.2f of the active frames dropped in %d of %d stretches (limit %.2f)"
                            % (share, record.n_rejected, record.n_stretches, max_rejected_share))
+    return reasons
+
+
+# ---- centre-channel VAD: mid / side contrast of stereo PCM -------------------------------------------
+# The project's own rule with no upstream counterpart: parity is against the in-repo model tests/stereo_vad_model.py only.
+# By the rule of profiles/centre_gate_calibrate.py on the CPU model (profiles/centre_gate_calibration.json; the synthetic
+# 10 min "mixed" files of the adaptive calibration made stereo, SYNTHETIC data only): the largest candidate of 0, 6, 12,
+# 18, 24 bins that keeps at least 0.99 of the speech frames c = 0 keeps on every file where the pick finds the speech.
+# Speech over a wide bed 10 dB below its mean level loses 1.7 % of its frames at c = 6 already (16 % at 12: the quietest
+# frames of a burst lie below the bed), so no candidate above 0 qualifies and 0 SHIPS: a frame is rejected only when its
+# side level exceeds its mid level.  That takes the share of uncorrelated (rho = 0) music labelled speech from 1.00 to
+# 0.76 only; c = 6 takes it to 0.00 and c = 12 does the same up to rho = 0.5 (0.02) while keeping 1.00 of plain speech
+# and of speech over a bed 20 dB down.  A caller who knows the beds pass ``min_contrast_bins`` (``vad="centre:12"``).
+DEFAULT_MIN_CONTRAST_BINS = 0
+
+
+@dataclass
+class CentreRecord:
+    threshold_bin: int  # the threshold the gate used
+    flags: int  # _native.VAD_CENTRE_*
+    min_contrast_bins: int  # the contrast the gate asked for
+    max_side: int  # the largest side level, 0: none (dual mono)
+    n_frames: int
+    n_active: int  # frames whose mid level reaches the threshold
+    n_kept: int  # of them, with mid - side >= min_contrast_bins
+    sum_contrast: int  # signed sum of mid - side over the active frames
+
+
+def centre_record_of(row) -> CentreRecord:
+    """One ``_native.VAD_CENTRE_DTYPE`` row as Python numbers."""
+    return CentreRecord(*(int(row[name]) for name in _native.VAD_CENTRE_DTYPE.names))
+
+
+def _check_contrast(min_contrast_bins) -> int:
+    if isinstance(min_contrast_bins, bool) or not isinstance(min_contrast_bins, (int, np.integer)) \
+            or not 0 <= min_contrast_bins <= _native.VAD_MAX_EDGES:
+        raise ValueError("min_contrast_bins=%r: need bins in [0, %d]" % (min_contrast_bins, _native.VAD_MAX_EDGES))
+    return int(min_contrast_bins)
+
+
+def _check_stereo_pcm(pcm_dev, frame_len) -> int:
+    frame_len = _check_pcm(pcm_dev, frame_len)
+    if int(pcm_dev.numel()) % 2:
+        raise ValueError("pcm: %d int16 values are not interleaved (L, R) pairs" % int(pcm_dev.numel()))
+    return frame_len
+
+
+def stereo_levels(pcm_dev, frame_len: int, edges=None, out=None):
+    """(mid, side): uint8 CUDA levels per frame of an int16 CUDA vector of interleaved (L, R) pairs, ``frame_len`` pairs a
+    frame: the number of ``edges`` (default :func:`default_edges`) that sum (L + R)^2 / (4 n) and sum (L - R)^2 / (4 n)
+    reach.  For L == R mid is :func:`frame_levels` of one channel and side is all zero.  ``out``: a pair of contiguous
+    uint8 CUDA vectors to write into (any offset will do)."""
+    table, n_edges = _edges_checked(edges)
+    frame_len = _check_stereo_pcm(pcm_dev, frame_len)
+    n = int(pcm_dev.numel()) // 2
+    n_frames = (n + frame_len - 1) // frame_len
+    if out is not None:
+        if not (isinstance(out, (tuple, list)) and len(out) == 2):
+            raise ValueError("out: need a pair of level vectors (mid, side)")
+        for o in out:
+            _check_levels(o)
+            if o.numel() < n_frames or o.device != pcm_dev.device:
+                raise ValueError("out: need %d level bytes on the PCM's device" % n_frames)
+    torch = _native.require_gpu()
+    table = _edges_dev(table, pcm_dev.device)
+    if out is None:
+        both = torch.empty((2, n_frames), dtype=torch.uint8, device=pcm_dev.device)
+        mid, side = both[0], both[1]
+    else:
+        mid, side = out
+    if n:
+        _native.check(_native.load().ffs_vad_stereo_levels(pcm_dev.data_ptr(), n, frame_len, table.data_ptr(), n_edges,
+                                                           mid.data_ptr(), side.data_ptr(), _native.current_stream_ptr(torch)))
+    return mid[:n_frames], side[:n_frames]
+
+
+def centre_gate(mid, side, threshold, min_contrast_bins: int = DEFAULT_MIN_CONTRAST_BINS, out=None):
+    """The mid levels with every frame zeroed whose mid level stands less than ``min_contrast_bins`` above its side level
+    (``ffs_vad_centre_gate``): :func:`level_labels` and :func:`steady_gate` run on the result unchanged.  ``threshold``
+    (it only counts: a frame is active iff mid >= threshold): a bin in [0, 256], a :class:`ThresholdRecord`, or the device
+    tensor of :func:`pick_threshold_device` (read on the device, never read back).  Returns (uint8 CUDA levels, the uint8
+    CUDA tensor of the 48-byte centre record); two launches queued on the current stream, nothing is read back."""
+    import torch
+
+    c = _check_contrast(min_contrast_bins)
+    if isinstance(threshold, ThresholdRecord):
+        threshold = threshold.threshold_bin
+    if hasattr(threshold, "is_cuda"):
+        if not (threshold.is_cuda and threshold.is_contiguous() and _native._nbytes(threshold) >= 4
+                and threshold.dtype in (torch.uint8, torch.int32)):
+            raise ValueError("threshold: a device threshold must be a contiguous uint8 or int32 CUDA tensor of 4 bytes or more")
+        thr_dev, thr_host = threshold.data_ptr(), 0
+    elif isinstance(threshold, bool) or not isinstance(threshold, (int, np.integer)) or not 0 <= threshold <= _native.VAD_MAX_BINS:
+        raise ValueError("threshold=%r: need a bin in [0, %d], a ThresholdRecord or a device tensor" % (threshold, _native.VAD_MAX_BINS))
+    else:
+        thr_dev, thr_host = None, int(threshold)
+    _check_levels(mid)
+    _check_levels(side)
+    n = int(mid.numel())
+    if int(side.numel()) != n or side.device != mid.device:
+        raise ValueError("side: need %d level bytes on the mid levels' device" % n)
+    if thr_dev is not None and threshold.device != mid.device:
+        raise ValueError("threshold: a device threshold must be on the levels' device")
+    if out is not None:
+        _check_levels(out)
+        if out.numel() < n or out.device != mid.device:
+            raise ValueError("out: need %d level bytes on the levels' device" % n)
+        lo, hi = out.data_ptr(), out.data_ptr() + n
+        if n and any(lo < t.data_ptr() + n and t.data_ptr() < hi for t in (mid, side)):
+            raise ValueError("out: must not overlap mid or side")
+    torch = _native.require_gpu()
+    if out is None:
+        out = torch.empty(n, dtype=torch.uint8, device=mid.device)
+    record = torch.empty(_native.VAD_CENTRE_BYTES, dtype=torch.uint8, device=mid.device)
+    with torch.cuda.device(mid.device):
+        _native.check(_native.load().ffs_vad_centre_gate(mid.data_ptr() if n else None, side.data_ptr() if n else None, n,
+                                                         thr_dev, thr_host, c, out.data_ptr() if n else None,
+                                                         record.data_ptr(), _native.current_stream_ptr(torch)))
+    return out[:n], record
+
+
+def _check_detect_centre(sample_rate, min_contrast_bins, steady, dip_bins, max_run):
+    if not isinstance(steady, bool):
+        raise ValueError("steady=%r: need True or False" % (steady,))
+    c = _check_contrast(min_contrast_bins)
+    gate = _check_detect_gated(sample_rate, dip_bins, max_run)
+    return c, (gate if steady else None)
+
+
+def detect_device_centre(pcm_dev, sample_rate: int, frame_rate: int, non_speech_label: float, rule: str = DEFAULT_RULE,
+                         edges=None, packed: bool = False, min_contrast_bins: int = DEFAULT_MIN_CONTRAST_BINS,
+                         steady: bool = False, dip_bins: int = DEFAULT_DIP_BINS, max_run: Optional[int] = None, **params):
+    """The centre-channel detector for stereo PCM resident in HBM (int16 CUDA vector of interleaved (L, R) pairs,
+    ``frame_rate`` pairs a second): (labels or ``DeviceRaster``, the file's ``ThresholdRecord`` -- picked on the histogram
+    of the mid levels of all frames --, its ``CentreRecord``) and, with ``steady``, the ``GateRecord`` of the steady-run
+    gate run on the centre gate's output.  Everything is queued on the current stream; only the records are read back."""
+    table, n_edges = _edges_checked(edges)
+    frame_len = _check_detect(sample_rate, frame_rate, non_speech_label, n_edges + 1, rule, params)
+    c, gate = _check_detect_centre(sample_rate, min_contrast_bins, steady, dip_bins, max_run)
+    _check_stereo_pcm(pcm_dev, frame_len)
+    table = _edges_dev(table, pcm_dev.device)
+    mid, side = stereo_levels(pcm_dev, frame_len, table)
+    return _finish(mid, n_edges + 1, non_speech_label, packed, rule, params, gate, (side, c))
+
+
+def _pinned_stereo_levels(pcm_host, frame_len, table, n_edges, staging):
+    """The stereo pass 1 behind ``stream_pinned_buffers``: buffers of WINDOWS_PER_BUFFER frames of pairs."""
+    from .speech_transformers import WINDOWS_PER_BUFFER, stream_pinned_buffers
+
+    torch = _native.require_gpu()
+    table = _edges_dev(table, torch.device("cuda", torch.cuda.current_device()))
+    n = int(pcm_host.numel()) // 2
+    both = torch.empty((2, (n + frame_len - 1) // frame_len), dtype=torch.uint8, device="cuda")
+    lib = _native.load()
+
+    def sweep(buf, m, o, main):  # m, o in int16 values: two a pair
+        first = o // (2 * frame_len)
+        _native.check(lib.ffs_vad_stereo_levels(buf.data_ptr(), m // 2, frame_len, table.data_ptr(), n_edges,
+                                                both[0].data_ptr() + first, both[1].data_ptr() + first, main.cuda_stream))
+
+    stream_pinned_buffers(pcm_host, 2 * frame_len * WINDOWS_PER_BUFFER, staging, sweep)
+    return both[0], both[1]
+
+
+def detect_pinned_stream_centre(pcm_host, sample_rate: int, frame_rate: int, non_speech_label: float,
+                                rule: str = DEFAULT_RULE, edges=None, staging=None, packed: bool = False,
+                                min_contrast_bins: int = DEFAULT_MIN_CONTRAST_BINS, steady: bool = False,
+                                dip_bins: int = DEFAULT_DIP_BINS, max_run: Optional[int] = None, **params):
+    """:func:`detect_device_centre` behind ``detect_pinned_stream``'s double-buffered copy loop, for decoded two-channel
+    s16le PCM in pinned host memory (int16 CPU tensor of interleaved pairs; staging buffers of their own hold
+    2 * frame_len * WINDOWS_PER_BUFFER values)."""
+    table, n_edges = _edges_checked(edges)
+    frame_len = _check_detect(sample_rate, frame_rate, non_speech_label, n_edges + 1, rule, params)
+    c, gate = _check_detect_centre(sample_rate, min_contrast_bins, steady, dip_bins, max_run)
+    _check_pinned(pcm_host)
+    if int(pcm_host.numel()) % 2:
+        raise ValueError("pcm: %d int16 values are not interleaved (L, R) pairs" % int(pcm_host.numel()))
+    mid, side = _pinned_stereo_levels(pcm_host, frame_len, table, n_edges, staging)
+    return _finish(mid, n_edges + 1, non_speech_label, packed, rule, params, gate, (side, c))
+
+
+def assess_centre(record: CentreRecord, max_rejected_share: Optional[float] = None) -> List[str]:
+    """What the centre record says about the file ([] = nothing to report): it is dual mono (no frame has a side level,
+    the gate decided nothing), every active frame was rejected, and -- only with a ``max_rejected_share``; the
+    calibration ships none -- more than that share of the active frames was dropped.  It reports; it decides nothing."""
+    if max_rejected_share is not None and not (isinstance(max_rejected_share, (int, float)) and not isinstance(max_rejected_share, bool)
+                                               and 0.0 <= max_rejected_share <= 1.0):
+        raise ValueError("max_rejected_share=%r: need a share in [0, 1]" % (max_rejected_share,))
+    f, reasons = int(record.flags), []
+    if f & _native.VAD_CENTRE_MONO:
+        reasons.append("no frame has a side level: the file is dual mono, the centre gate decides nothing")
+    if f & _native.VAD_CENTRE_ALL_REJECTED:
+        reasons.append("all %d active frames stand less than %d bins above their side level" % (record.n_active, record.min_contrast_bins))
+    elif max_rejected_share is not None and record.n_active > 0:
+        share = (record.n_active - record.n_kept) / float(record.n_active)
+        if share > max_rejected_share:
+            reasons.append("%.2f of the active frames rejected by the centre gate (limit %.2f)" % (share, max_rejected_share))
     return reasons

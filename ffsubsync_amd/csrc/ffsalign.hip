@@ -48,6 +48,7 @@
 #include "ffs_sampled.h"
 #include "ffs_adaptive_vad.h"
 #include "ffs_vad_gate.h"
+#include "ffs_stereo_vad.h"
 
 using namespace ffsa;
 
@@ -3228,6 +3229,67 @@ int ffs_vad_steady_gate(const uint8_t* levels_dev, int64_t n_frames, const int32
     if (n_tiles && (labels_dev || bits_dev))
         hipLaunchKernelGGL(k_gate_labels, dim3((unsigned)n_tiles), dim3(GATE_THREADS), 0, st, levels_dev, (long long)n_frames, thr_dev,
                            threshold_host, dip_bins, (int)max_run, carry, non_speech_label, labels_dev, bits_dev);
+    HIP_TRY(hipGetLastError());
+    return FFS_OK;
+}
+
+// ---- centre-channel VAD: mid / side levels of stereo PCM and the centre gate (ffs_stereo_vad.h) -----------
+
+int ffs_vad_stereo_levels(const int16_t* pcm_dev, int64_t n_pairs, int frame_len, const double* edges_dev, int n_edges,
+                          uint8_t* mid_levels_dev, uint8_t* side_levels_dev, void* hip_stream) {
+    if (n_pairs < 0 || frame_len < 1)
+        return fail(FFS_E_INVALID, "ffs_vad_stereo_levels: bad n_pairs=%lld / frame_len=%d", (long long)n_pairs, frame_len);
+    if (n_edges < 1 || n_edges > VAD_MAX_EDGES)
+        return fail(FFS_E_INVALID, "ffs_vad_stereo_levels: n_edges=%d outside [1, %d]", n_edges, VAD_MAX_EDGES);
+    if (n_pairs == 0) return FFS_OK;
+    if (!pcm_dev || !edges_dev || !mid_levels_dev || !side_levels_dev)
+        return fail(FFS_E_INVALID, "ffs_vad_stereo_levels: null device pointer");
+    if ((reinterpret_cast<uintptr_t>(pcm_dev) & 1) || (reinterpret_cast<uintptr_t>(edges_dev) & 7))
+        return fail(FFS_E_INVALID, "ffs_vad_stereo_levels: misaligned PCM (2 bytes) or edge table (8 bytes)");
+    DeviceGuard guard;
+    int rc_dev;
+    if ((rc_dev = guard.enter(mid_levels_dev))) return rc_dev;
+    const long long n_frames = (n_pairs + frame_len - 1) / frame_len;
+    long long blocks = ((n_frames + VAD_FPT - 1) / VAD_FPT + 3) / 4;  // k_vad_levels' grid: a wave per VAD_FPT frames
+    if (blocks > 256 * 64) blocks = 256 * 64;
+    hipLaunchKernelGGL(k_vad_stereo_levels, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)hip_stream, pcm_dev,
+                       (long long)n_pairs, frame_len, n_frames, edges_dev, n_edges, mid_levels_dev, side_levels_dev);
+    HIP_TRY(hipGetLastError());
+    return FFS_OK;
+}
+
+int ffs_vad_centre_gate(const uint8_t* mid_dev, const uint8_t* side_dev, int64_t n_frames, const int32_t* threshold_dev,
+                        int threshold_host, int min_contrast_bins, uint8_t* out_levels_dev, ffs_vad_centre* record_dev,
+                        void* hip_stream) {
+    static_assert(sizeof(ffs_vad_centre) == sizeof(VadCentre), "device records must match the header's");
+    if (n_frames < 0) return fail(FFS_E_INVALID, "ffs_vad_centre_gate: n_frames=%lld is negative", (long long)n_frames);
+    if (!threshold_dev && (threshold_host < 0 || threshold_host > VAD_MAX_BINS))
+        return fail(FFS_E_INVALID, "ffs_vad_centre_gate: threshold_host=%d outside [0, %d]", threshold_host, VAD_MAX_BINS);
+    if (min_contrast_bins < 0 || min_contrast_bins > VAD_MAX_EDGES)
+        return fail(FFS_E_INVALID, "ffs_vad_centre_gate: min_contrast_bins=%d outside [0, %d]", min_contrast_bins, VAD_MAX_EDGES);
+    if (!record_dev || (n_frames > 0 && (!mid_dev || !side_dev)))
+        return fail(FFS_E_INVALID, "ffs_vad_centre_gate: null mid, side or record pointer");
+    if ((reinterpret_cast<uintptr_t>(threshold_dev) & 3) || (reinterpret_cast<uintptr_t>(record_dev) & 7))
+        return fail(FFS_E_INVALID, "ffs_vad_centre_gate: misaligned threshold (4 bytes) or record (8 bytes) pointer");
+    if (out_levels_dev && n_frames > 0) {  // the n_frames output bytes may not overlap either input's
+        const uintptr_t o = reinterpret_cast<uintptr_t>(out_levels_dev), n = (uintptr_t)n_frames;
+        const uintptr_t m = reinterpret_cast<uintptr_t>(mid_dev), s = reinterpret_cast<uintptr_t>(side_dev);
+        if ((o < m + n && m < o + n) || (o < s + n && s < o + n))
+            return fail(FFS_E_INVALID, "ffs_vad_centre_gate: out_levels_dev overlaps an input");
+    }
+    DeviceGuard guard;
+    int rc_dev;
+    if ((rc_dev = guard.enter(record_dev))) return rc_dev;
+    hipStream_t st = (hipStream_t)hip_stream;
+    HIP_TRY(hipMemsetAsync(record_dev, 0, sizeof(ffs_vad_centre), st));
+    if (n_frames > 0) {
+        long long blocks = (n_frames + CENTRE_THREADS - 1) / CENTRE_THREADS;
+        if (blocks > CENTRE_MAX_BLOCKS) blocks = CENTRE_MAX_BLOCKS;
+        hipLaunchKernelGGL(k_centre_gate, dim3((unsigned)blocks), dim3(CENTRE_THREADS), 0, st, mid_dev, side_dev, (long long)n_frames,
+                           (const int*)threshold_dev, threshold_host, min_contrast_bins, out_levels_dev, (VadCentre*)record_dev);
+    }
+    hipLaunchKernelGGL(k_centre_finish, dim3(1), dim3(64), 0, st, (long long)n_frames, (const int*)threshold_dev, threshold_host,
+                       min_contrast_bins, (VadCentre*)record_dev);
     HIP_TRY(hipGetLastError());
     return FFS_OK;
 }

@@ -253,6 +253,9 @@ class ComputeSpeechFrameBoundariesMixin:
 class PCMSpeechTransformer(TransformerMixin):
     """The VAD leg of ``VideoSpeechTransformer`` (speech_transformers.py:320-351, 635-757) for an
     already-decoded s16le mono stream: read 100 s chunks, run the detector on each, concatenate.
+    ``vad="centre"`` and ``vad="centre_steady"`` (``adaptive_vad``) take s16le with TWO interleaved
+    channels instead (``ffmpeg ... -ac 2 -f s16le``); a trailing incomplete pair is dropped.  ``"centre:12"`` /
+    ``"centre_steady:12"`` pass ``min_contrast_bins`` (default ``adaptive_vad.DEFAULT_MIN_CONTRAST_BINS``).
 
     ``fit(source)`` accepts a binary file object (e.g. ``subprocess.Popen(...).stdout``), bytes or
     an int16 array.  The fitted ``video_speech_results_`` is a float64 ndarray as in the reference.
@@ -266,8 +269,9 @@ class PCMSpeechTransformer(TransformerMixin):
         self._non_speech_label = non_speech_label
         self.progress_handler = progress_handler
         self.video_speech_results_: Optional[np.ndarray] = None
-        self.vad_threshold_ = None  # vad="adaptive" / "gated": the file's adaptive_vad.ThresholdRecord
-        self.vad_gate_ = None  # vad="gated": the file's adaptive_vad.GateRecord
+        self.vad_threshold_ = None  # vad="adaptive" / "gated" / "centre" / "centre_steady": the file's adaptive_vad.ThresholdRecord
+        self.vad_gate_ = None  # vad="gated" / "centre_steady": the file's adaptive_vad.GateRecord
+        self.vad_centre_ = None  # vad="centre" / "centre_steady": the file's adaptive_vad.CentreRecord
 
     def _make_detector(self):
         if "fused" in self.vad:  # e.g. "fused" or "fused:intersection" (speech_transformers.py:655-665)
@@ -349,9 +353,42 @@ class PCMSpeechTransformer(TransformerMixin):
         self.vad_gate_ = adaptive_vad.gate_record_of(gate_raw.cpu().numpy().view(_native.VAD_GATE_DTYPE)[0])
         return [_labels_float64(speech, self._non_speech_label)]
 
-    def _sweep_pipelined(self, source, chunk_bytes, sweep) -> list:
+    def _fit_centre_pipelined(self, source, chunk_bytes, steady) -> List[np.ndarray]:
+        """``vad="centre"``: two interleaved channels; the stereo sweep of ``adaptive_vad`` is pass 1 (``chunk_bytes``
+        holds whole frames of pairs), the pick runs on the histogram of the mid levels, the centre gate zeroes the frames
+        that are not centred and the labels -- with ``steady`` (``vad="centre_steady"``) the steady-run gate -- run on
+        its output.  The records are kept as ``vad_threshold_``, ``vad_centre_`` and ``vad_gate_``."""
+        from . import adaptive_vad
+
+        contrast = adaptive_vad.DEFAULT_MIN_CONTRAST_BINS
+        if ":" in self.vad:  # "centre:12": the contrast in bins, as "fused:intersection" carries its strategy
+            tail = self.vad.split(":", 1)[1]
+            if not tail.isdigit():
+                raise ValueError("vad=%r: need min_contrast_bins as an integer behind the colon" % (self.vad,))
+            contrast = adaptive_vad._check_contrast(int(tail))
+        torch = _native.require_gpu()
+        frame_len = frames_per_window(self.sample_rate, self.frame_rate)
+        pairs = self._sweep_pipelined(source, chunk_bytes, lambda pcm: adaptive_vad.stereo_levels(pcm, frame_len),
+                                      unit=2 * BYTES_PER_SAMPLE)
+        if not pairs:
+            return []
+        mid, side = torch.cat([m for m, _ in pairs]), torch.cat([s for _, s in pairs])
+        raw = adaptive_vad.pick_threshold_device(adaptive_vad.level_hist(mid))
+        levels, centre_raw = adaptive_vad.centre_gate(mid, side, raw, contrast)
+        if steady:
+            speech, gate_raw = adaptive_vad.steady_gate(levels, raw, adaptive_vad.DEFAULT_DIP_BINS,
+                                                        adaptive_vad.default_max_run(self.sample_rate), 0.0)
+            self.vad_gate_ = adaptive_vad.gate_record_of(gate_raw.cpu().numpy().view(_native.VAD_GATE_DTYPE)[0])
+        else:
+            speech = adaptive_vad.level_labels(levels, raw, 0.0)
+        self.vad_threshold_ = adaptive_vad.record_of(raw.cpu().numpy().view(_native.VAD_THRESHOLD_DTYPE)[0])
+        self.vad_centre_ = adaptive_vad.centre_record_of(centre_raw.cpu().numpy().view(_native.VAD_CENTRE_DTYPE)[0])
+        return [_labels_float64(speech, self._non_speech_label)]
+
+    def _sweep_pipelined(self, source, chunk_bytes, sweep, unit: int = BYTES_PER_SAMPLE) -> list:
         """``sweep(int16 CUDA chunk)`` of every chunk of the stream through the two staging buffers; the device
-        tensors it returned, in order."""
+        tensors it returned, in order.  ``unit``: bytes of one sample of all channels; a chunk's trailing part of one is
+        dropped."""
         torch = _native.require_gpu()
         pinned = [torch.empty(chunk_bytes, dtype=torch.uint8).pin_memory() for _ in range(2)]
         device = [torch.empty(chunk_bytes, dtype=torch.uint8, device="cuda") for _ in range(2)]
@@ -360,8 +397,8 @@ class PCMSpeechTransformer(TransformerMixin):
         processed = 0.0
         for i, in_bytes in enumerate(self._chunks(source, chunk_bytes)):
             k = i % 2
-            n = in_bytes.size // BYTES_PER_SAMPLE * BYTES_PER_SAMPLE
-            processed += len(in_bytes) / float(BYTES_PER_SAMPLE) / self.frame_rate
+            n = in_bytes.size // unit * unit
+            processed += len(in_bytes) / float(unit) / self.frame_rate
             self._progress(processed)
             if n == 0:
                 labels.append(sweep(device[k][:0].view(torch.int16)))
@@ -379,7 +416,11 @@ class PCMSpeechTransformer(TransformerMixin):
     def fit(self, source, *_) -> "PCMSpeechTransformer":
         bytes_per_window = BYTES_PER_SAMPLE * self.frame_rate // self.sample_rate  # :683-684
         chunk_bytes = bytes_per_window * WINDOWS_PER_BUFFER
-        if "gated" in self.vad:  # tested first: the name holds neither "adaptive" nor any of the reference's substrings
+        if "centre_steady" in self.vad:  # tested first, then "centre": neither name holds "gated", "adaptive" or any of
+            media_bstring = self._fit_centre_pipelined(source, 2 * chunk_bytes, True)  # the reference's substrings
+        elif "centre" in self.vad:  # two interleaved channels: twice the bytes per chunk, still whole frames
+            media_bstring = self._fit_centre_pipelined(source, 2 * chunk_bytes, False)
+        elif "gated" in self.vad:  # tested next: the name holds neither "adaptive" nor any of the reference's substrings
             media_bstring = self._fit_gated_pipelined(source, chunk_bytes)
         elif "adaptive" in self.vad:  # tested next: the name holds none of the reference's substrings
             media_bstring = self._fit_adaptive_pipelined(source, chunk_bytes)

@@ -1511,6 +1511,72 @@ int ffs_vad_steady_gate(const uint8_t* levels_dev, int64_t n_frames, const int32
                         int dip_bins, int64_t max_run, float non_speech_label, float* labels_dev, uint8_t* bits_dev,
                         ffs_vad_gate* record_dev, void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
 
+/* ---- centre-channel VAD: speech from stereo PCM by mid / side contrast (csrc/ffs_stereo_vad.h) -----------------------
+ * Replaces: nothing in the reference (it asks ffmpeg for -ac 1, speech_transformers.py:551, and so discards the cue).
+ * Dialogue is mixed to the centre, L ~ R; music, ambience, audiences and effects are mixed wide.  The mid signal L + R
+ * holds the centre, the side signal L - R only what differs between the channels, so a frame whose mid level does not
+ * stand min_contrast_bins above its side level is not dialogue, however loud, and speech over a wide bed still is.
+ * The project's own rule: a numpy / integer model (tests/stereo_vad_model.py) is its only reference, and its shipped
+ * default comes from SYNTHETIC data (profiles/centre_gate_calibration.json).
+ *
+ * ffs_vad_stereo_levels.  pcm_dev holds n_pairs interleaved (L, R) int16 pairs at any 2-byte aligned address; frame_len
+ * >= 1 counts PAIRS per frame; n_frames = ceil(n_pairs / frame_len), the last frame may be short (n_f pairs).  In exact
+ * 64-bit integers
+ *   M_f = sum (L_i + R_i)^2,   S_f = sum (L_i - R_i)^2
+ *   mid[f]  = #{k : (double)M_f >= edges[k] * (double)(4 n_f)}
+ *   side[f] = #{k : (double)S_f >= edges[k] * (double)(4 n_f)}
+ * edges and n_edges as for ffs_vad_levels.  The factor 4 (exact on both sides of the compare) makes a dual-mono file
+ * (L == R) give mid equal to ffs_vad_levels of one channel byte for byte and side all zero.  Exactly n_frames bytes are
+ * written to each output, each at any byte address, nothing behind them.  One pass over the PCM: 16-byte loads when
+ * frame_len is a multiple of 4 and at most 512 pairs and pcm_dev is 16-byte aligned, a pair per lane otherwise (and for
+ * the last frames of the buffer).  Stateless, no atomics, no allocation; can be called chunk by chunk like
+ * ffs_vad_levels.  n_pairs == 0 is FFS_OK with nothing written.
+ *
+ * ffs_vad_centre_gate.  t is read ON THE DEVICE from threshold_dev when that is not NULL (a pick record's address works,
+ * as for ffs_vad_level_labels; the value is taken as it stands), else it is threshold_host in [0, 256];
+ * c = min_contrast_bins in [0, 255].
+ *   out[f] = mid[f] if (int)mid[f] - (int)side[f] >= c, else 0          (does not depend on t)
+ *   active(f) = mid[f] >= t;   kept(f) = active(f) and mid[f] - side[f] >= c
+ * It follows: ffs_vad_level_labels(out, t) labels exactly the kept frames (for t >= 1), ffs_vad_steady_gate(out, t, ...)
+ * sees a rejected frame as level 0, and for L == R and c <= t the labels are the mono path's byte for byte.
+ * Record (one per call, 48 bytes, 8-byte aligned): the t and the c that were used, max_side the largest side level
+ * (0 for no frames), the frames, the active and the kept frames, sum_contrast the signed sum of mid - side over the
+ * active frames.  Flags:
+ *   FFS_VAD_CENTRE_MONO          n_frames > 0 and max_side == 0: the file is dual mono, the gate decides nothing;
+ *   FFS_VAD_CENTRE_ALL_REJECTED  n_active > 0 and n_kept == 0.
+ * out_levels_dev may be NULL (the record alone) and may not overlap an input; n_frames == 0 writes the record alone.
+ * Nothing is written behind out[n_frames - 1] or around the record.  The record is zeroed on the stream, a capped grid
+ * adds each workgroup's integer sums into it with integer atomics (add, max: order-independent), one more wave writes
+ * t, c, n_frames and the flags; no workgroup waits for another, nothing is allocated, nothing synchronises.
+ * FFS_E_INVALID with a message that starts with the export's name, before any launch: a negative count, frame_len < 1,
+ * n_edges outside [1, 255], threshold_host (without threshold_dev) or min_contrast_bins outside the ranges above, a null
+ * pointer, PCM not 2-byte, edges or record not 8-byte, threshold_dev not 4-byte aligned, an output that overlaps an
+ * input.  Stateless. */
+#define FFS_VAD_CENTRE_MONO 1         /* no frame has a side level: dual mono */
+#define FFS_VAD_CENTRE_ALL_REJECTED 2 /* active frames, none kept */
+
+typedef struct ffs_vad_centre {
+    int32_t threshold_bin;        /* the t that was used */
+    int32_t flags;                /* FFS_VAD_CENTRE_* */
+    int32_t min_contrast_bins;    /* the c that was used */
+    int32_t max_side;             /* the largest side level, 0 for no frames */
+    int64_t n_frames;
+    int64_t n_active;             /* frames with mid >= t */
+    int64_t n_kept;               /* of them, with mid - side >= c */
+    int64_t sum_contrast;         /* signed sum of mid - side over the active frames */
+} ffs_vad_centre;
+#ifdef __cplusplus
+static_assert(sizeof(ffs_vad_centre) == 48, "ffs_vad_centre is 48 bytes");
+#else
+_Static_assert(sizeof(ffs_vad_centre) == 48, "ffs_vad_centre is 48 bytes");
+#endif
+
+int ffs_vad_stereo_levels(const int16_t* pcm_dev, int64_t n_pairs, int frame_len, const double* edges_dev, int n_edges,
+                          uint8_t* mid_levels_dev, uint8_t* side_levels_dev, void* hip_stream);
+int ffs_vad_centre_gate(const uint8_t* mid_dev, const uint8_t* side_dev, int64_t n_frames, const int32_t* threshold_dev,
+                        int threshold_host, int min_contrast_bins, uint8_t* out_levels_dev, ffs_vad_centre* record_dev,
+                        void* hip_stream);
+
 /* ---- progressive alignment: the quality report of a growing reference prefix (csrc/ffs_progressive.h) -----------
  * Replaces: nothing in the reference (its --multi-segment-sync, speech_transformers.py:760-903, samples eight minutes
  * and hopes they suffice).  Score counts are additive over the reference, so after every appended chunk of reference
